@@ -9,7 +9,15 @@ dqn vocabulary [56,135,18,87,18,25]) on synthetic (B, T=1024, 7-field) compound-
 bf16 activations / MFMA GEMMs, f32 scan state + statistics + master weights, dropout 0.1 live.
 One step = forward + backward + (DP gradient all-reduce) + clip_grad_norm_(3) + Adam, i.e. the body of
 the reference's loop at dqn_policy/agent_pretrain.py:546-565 -- inputs already resident in HBM.
-Prints ONE JSON line (rank 0).  `value` = CW tokens/s of the whole job.
+Prints ONE JSON line (rank 0).  `value` = CW tokens/s of the whole job, `ms_per_step` = one timed step.
+
+A plain run does only what that headline needs: set up, warm up, time --steps steps, print the line.  Everything else
+the benchmark measures or checks runs with --full only: the per-kernel `kernels` table and `roofline*` entries (HIP
+events on every 10th timed step), the PPO env-steps/s block, the CPU baselines and, under data parallelism, the
+replica checksum spread.  --no-kernel-timer / --no-ppo / --no-cpu-baseline drop single parts of --full.
+
+    --dump-outputs DIR   after the timed steps, write what the last one computed as float32 .npy files
+                         (dump_outputs(); same arguments -> same inputs, so two builds can be compared file by file)
 """
 import argparse
 import json
@@ -138,6 +146,42 @@ def cpu_baseline(seconds_budget=30.0):
     dt = (time.perf_counter() - t0) / n
     return {"value": round(1024 / dt, 2), "unit": "CW-tokens/s", "cores": cores, "kind": "port",
             "sample": "%d steps of B=1 x T=1024 (fwd+bwd+clip+Adam, fp32, dropout 0.1), oracle/cw_model.py" % n}
+
+
+DUMP_SAMPLE = 1 << 20                            # elements of the parameter / gradient samples of --dump-outputs
+DUMP_SEED = 20261016
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, params, losses, grad_norm, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs: what the step handed back, as float32 .npy files in out_dir.
+      losses.npy        the six per-field losses (train_step's return) and, last, their mean (the step's loss)
+      grad_norm.npy     the total gradient norm before clipping (clip_grad_norm_'s return)
+      params_sample.npy the updated parameters, grads_sample.npy their clipped gradients: the same fixed, seeded
+                        sample of `sample` elements of all parameters flattened in registration order (the whole
+                        tensors are 156 MB each at repo dims), in ascending flat index
+    -> {name: shape}."""
+    import numpy as np
+    params = list(params)
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                        for p in params])
+    n = flat_p.numel()
+    if n > sample:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:sample].sort().values
+        idx = idx.to(flat_p.device)
+        flat_p, flat_g = flat_p[idx], flat_g[idx]
+    ls = torch.stack([l.detach().float().reshape(()) for l in losses])
+    arrays = {"losses": torch.cat([ls, ls.mean().reshape(1)]), "grad_norm": grad_norm.detach().float().reshape(1),
+              "params_sample": flat_p, "grads_sample": flat_g}
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: a.shape for k, a in arrays.items()}
 
 
 def roofline_entry(name, kind, achieved, avg_ms, share, work_per_launch, traffic=None):
@@ -282,7 +326,7 @@ def run_ppo_block(run, group, nranks, device, log, *a, **kw):
         group //= 2
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="ranks = GPUs of this node; N > 1 outside a launcher starts torch.distributed.run itself")
@@ -292,15 +336,24 @@ def main():
     ap.add_argument("--batch", type=int, default=512, help="sequences per GPU")
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel table / roofline, the PPO block, the CPU baselines and the replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's losses, gradient norm and parameter / gradient samples as .npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="with --full: skip the per-kernel table")
     ap.add_argument("--tune-gemms", action="store_true", help="re-tune the hipBLASLt/rocBLAS table (GPU box)")
     ap.add_argument("--no-tuned-gemms", action="store_true")
-    ap.add_argument("--no-ppo", action="store_true", help="skip the PPO env-steps/s block (BASELINE's second metric)")
+    ap.add_argument("--no-ppo", action="store_true",
+                    help="with --full: skip the PPO env-steps/s block (BASELINE's second metric)")
     ap.add_argument("--ppo-rollouts", type=int, default=64)
     ap.add_argument("--ppo-window", type=int, default=1024)
     ap.add_argument("--ppo-steps", type=int, default=10)
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
 
     import rlmg_amd  # noqa: F401
     from rlmg_amd import dist as rdist, gemm_tuning, ops
@@ -340,9 +393,9 @@ def main():
         loss = (losses[0] + losses[1] + losses[2] + losses[3] + losses[4] + losses[5]) / 6
         loss.backward()
         sync.finish()
-        sync.clip_grad_norm_(3.0)
+        norm = sync.clip_grad_norm_(3.0)
         opt.step()
-        return loss
+        return loss, losses, norm
 
     def fence():
         if world > 1:
@@ -362,7 +415,7 @@ def main():
     # A pair of HIP timing events around every C-ABI call (~190 calls per step) makes the GPU drain between kernels:
     # measured +25 ms on a 106 ms step.  The per-kernel durations therefore come from every 10th timed step only
     # (step 0 of the default 10): still live, inside the timed region, on the launch stream; cost ~2 % of `value`.
-    timing = rank == 0 and not args.no_kernel_timer
+    timing = rank == 0 and args.full and not args.no_kernel_timer
     ops.KernelTimer.reset(False)
     if timing:
         ops.KernelTimer.reserve(512 * len([i for i in range(args.steps) if i % 10 == 0]))
@@ -370,7 +423,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         ops.KernelTimer.enabled = timing and i % 10 == 0
-        loss = step()
+        loss, losses, norm = step()
     fence()
     dt = time.perf_counter() - t0
     ops.KernelTimer.enabled = False
@@ -386,7 +439,11 @@ def main():
     ops.KernelTimer.reset(False)
     final_loss = round(float(loss.item()), 4)
     hbm_peak = round(torch.cuda.max_memory_allocated() / 1e9, 1)
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, net.parameters(), losses, norm)
+        log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, shapes))
+    del losses, norm
+    if world > 1 and args.full:
         # data-parallel sanity (outside the timed region): every rank must hold the same parameters after the
         # all-reduced steps; spread = max over ranks - min over ranks of a parameter checksum
         chk = torch.stack([p.detach().double().sum() for p in net.parameters()]).sum().reshape(1)
@@ -397,7 +454,7 @@ def main():
         log("replica parameter checksum spread: %.3e" % replica_spread)
 
     ppo = None
-    if not args.no_ppo:
+    if args.full and not args.no_ppo:
         # BASELINE.json's second metric (PPO env-steps/s, configs[2]: 64 rollouts x window 1024 per GPU), measured in
         # the same driver-run process after the pretrain region; the pretrain model and its optimizer are released first
         del net, opt, sync, x, y, mask, loss
@@ -418,7 +475,7 @@ def main():
         out = report(args, kt, B, T, s, world, ms_per_step, tokens_per_s, final_loss, replica_spread, tuned, hbm_peak)
         if ppo is not None:
             out["ppo"] = ppo_report(args, ppo, world)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline()
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = round(tokens_per_s / cb["value"], 1)

@@ -46,6 +46,9 @@ def _worker(rank, world, port, out):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
+    # gloo on the host whatever the box has: with a GPU visible, init_from_env would pick RCCL and bind rank i to
+    # device i, which a one-GPU box does not have
+    torch.cuda.is_available = lambda: False
     import rlmg_amd  # noqa: F401
     from rlmg_amd import dist as rdist
     r, _, w = rdist.init_from_env()
