@@ -359,6 +359,32 @@ int cwlt_recurrent_cla_step(const void* q, const void* k, const void* v, float* 
                             int N, int H, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                             float eps, int dtype, void* stream);
 
+/* ---- prompt prefill: the chunked scan started from, and handing back, the recurrent state ----------------------
+ * The state a prompt of len tokens leaves behind, and its attention rows, in ONE pass per (sequence, head) instead of
+ * len calls of cwlt_recurrent_cla_step (same values up to the order of the f32 sums): the generation-time
+ * continuation of a prompt (the reference's write_midi(..., prompt_path=...), ppo_policy/utils.py:219,308, and its
+ * prompt loop over `init`, dqn_policy/testing-no-type-cp.py:135-152).
+ * q, k, v, out: (N, L, H, head_dim) as cwlt_causal_linear_fwd (row strides ld*, multiples of 4, 16-byte aligned q, k,
+ * v).  S (N, H, 64, 64) f32 key-feature-major (S[n,h,d,m]) and Z (N, H, 64) f32 -- cwlt_recurrent_cla_step's state --
+ * are read as the starting state and overwritten in place with the state after the sequence's last valid token:
+ *   out_l = phi(q_l) . (S0 + sum_{j<=l} phi(k_j) (x) v_j) / (phi(q_l) . (Z0 + sum_{j<=l} phi(k_j)) + eps).
+ * lengths: DEVICE int32 (N) or NULL (= all L); rows t >= lengths[n] add nothing and their out rows are not written, a
+ * length of 0 leaves that sequence's S and Z bit-for-bit unchanged (lengths are clamped to [0, L]).
+ * f32 only (CWLT_ERR_DTYPE otherwise); head_dim != 64 is CWLT_ERR_ARG.
+ * Few streams (one song is N * H = 8 workgroups on 256 CUs): `segments` > 1 cuts every sequence into runs of whole
+ * 32-token chunks, one workgroup each -- a first pass reduces each run to its state increment, a second turns the
+ * increments into starting states (S0, Z0 included), the scan proper starts every run from its state and the run
+ * holding a sequence's last chunk writes the final state.  cwlt_prefill_segments() is the library's choice (1 once
+ * the streams fill the chip); seg_ws: cwlt_prefill_seg_floats(N, H, segments) floats, NULL when segments == 1.  A run
+ * owns ceil(chunks / segments) chunks (chunks = ceil(L / 32)) and every run must own at least one
+ * ((segments - 1) * ceil(chunks / segments) < chunks), else CWLT_ERR_ARG. */
+int cwlt_prefill_segments(int N, int H, int L);
+int64_t cwlt_prefill_seg_floats(int N, int H, int segments);
+int cwlt_causal_linear_fwd_state(const void* q, const void* k, const void* v, void* out, float* S, float* Z,
+                                 const int* lengths, int N, int H, int L, int head_dim, int64_t ldq, int64_t ldk,
+                                 int64_t ldv, int64_t ldo, float eps, int segments, float* seg_ws, int dtype,
+                                 void* stream);
+
 /* ---- generation: one CW token through the whole recurrent-form model (f32) --------------------------
  * Replaces the per-token body of the reference's generation loop: `forward_hidden(input_, memory,
  * is_training=False)` (dqn_policy/testing-no-type-cp.py:150,166 -> dqn_policy/model.py:200-238 -> the

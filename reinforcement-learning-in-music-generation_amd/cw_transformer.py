@@ -165,6 +165,30 @@ class CWTrunk(nn.Module):
         pos_emb = self.pos_emb(emb_linear).squeeze(0)
         return self.transformer_encoder(pos_emb, memory=memory)
 
+    def prefill_hidden(self, tokens, memory, lengths=None):
+        """A whole prompt through the recurrent encoder in one pass: tokens (N, L, 6) int64 on the GPU, memory the
+        per-layer [S, Zs] state (advanced IN PLACE as L calls of forward_hidden(..., is_training=False) would), lengths
+        a host sequence of N prompt lengths in [1, L] (None = all L).  Every prompt row gets pe[0], as on the recurrent
+        path (forward_hidden squeezes a length-1 sequence).  -> (N, d_model): each sequence's row lengths[n] - 1,
+        what forward_hidden returns for its last prompt token (final norm applied)."""
+        if not self._recurrent:
+            raise RuntimeError("prefill needs a model built with is_training=False (recurrent encoder)")
+        if self.compute_dtype != torch.float32:
+            raise RuntimeError("prefill computes in f32; this model's activations are %s" % self.compute_dtype)
+        N, L, _ = tokens.shape
+        idx = torch.full((N,), L - 1, dtype=torch.int64)
+        dev_len = None
+        if lengths is not None:
+            idx = torch.as_tensor(np.asarray(lengths, dtype=np.int64).reshape(-1)) - 1
+            if idx.numel() != N or (idx < 0).any() or (idx >= L).any():
+                raise ValueError("prompt lengths must be %d values in [1, %d], got %s" % (N, L, list(idx + 1)))
+            dev_len = (idx + 1).to(torch.int32).to(tokens.device)
+        D = self.d_model
+        x = self.embed(tokens).reshape(N * L, D)
+        x = ops.posenc_dropout(x, self.pos_emb.pe.reshape(-1, D), 1).view(N, L, D)      # x + pe[0] on every row
+        h = self.transformer_encoder.prefill(x, memory, dev_len)
+        return h[torch.arange(N, device=h.device), idx.to(h.device)]
+
     def _losses(self, h, target, loss_mask):
         logits = self.fused_logits(h)
         return ops.heads_ce(logits, target, loss_mask, self.n_token)

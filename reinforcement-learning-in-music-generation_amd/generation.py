@@ -176,15 +176,18 @@ class DecodeSession:
                 self._plan.refresh()
         self.n_steps = 0
 
+    def _fused_plan(self):
+        if self._plan is None:
+            with torch.no_grad():
+                self._plan = _FusedPlan(self.model, self.memory, self.n_songs)
+            self._plan.tag = self._weights_tag()
+        return self._plan
+
     def _device_step(self):
         """testing-no-type-cp.py:150 / :166 (`forward_hidden(input_, memory, is_training=False)`) followed by the six
         head projections of forward_output_sampling (dqn_policy/model.py:273-278) as one fused GEMV."""
         if self.fused:
-            if self._plan is None:
-                with torch.no_grad():
-                    self._plan = _FusedPlan(self.model, self.memory, self.n_songs)
-                self._plan.tag = self._weights_tag()
-            out = self._plan.step(self.tok)
+            out = self._fused_plan().step(self.tok)
             self.hidden = self._plan.hidden
             return out
         h, mem = self.model.forward_hidden(self.tok, self.memory, is_training=False)
@@ -232,6 +235,63 @@ class DecodeSession:
         res = self._host_logits.numpy()
         return res[0] if self.n_songs == 1 else res
 
+    def _prefill(self, tokens, lengths=None):
+        """prefill() without the host copy: -> (n_songs, sum n_token) f32 device logits."""
+        if self.model.training:
+            raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
+        if self.model.compute_dtype != torch.float32:
+            raise RuntimeError("prefill computes in f32: this session's model runs %s activations (step() one token "
+                               "at a time instead)" % self.model.compute_dtype)
+        toks = np.asarray(tokens, dtype=np.int64)
+        if toks.ndim == 2:
+            toks = toks[None]
+        A = len(self.n_token)
+        if toks.ndim != 3 or toks.shape[0] != self.n_songs or toks.shape[2] != A or toks.shape[1] == 0:
+            raise ValueError("prompt tokens must be (P, %d) or (n_songs=%d, P, %d) with P >= 1, got %s"
+                             % (A, self.n_songs, A, np.shape(tokens)))
+        P = toks.shape[1]
+        lens = np.full(self.n_songs, P) if lengths is None else np.asarray(lengths, dtype=np.int64).reshape(-1)
+        if lens.shape != (self.n_songs,) or (lens < 1).any() or (lens > P).any():
+            raise ValueError("prompt lengths must be %d values in [1, %d], got %s" % (self.n_songs, P, list(lens)))
+        for i, n in enumerate(lens):
+            bad = (toks[i, :n] < 0) | (toks[i, :n] >= np.asarray(self.n_token))
+            if bad.any():
+                t, a = np.argwhere(bad)[0]
+                raise ValueError("prompt %d, token %d: id %d out of range for attribute %d (%d classes)"
+                                 % (i, t, toks[i, t, a], a, self.n_token[a]))
+        heads = self.model._heads()
+        with torch.no_grad():
+            h = self.model.prefill_hidden(torch.as_tensor(toks).to(self.dev), self.memory,
+                                          None if lengths is None else lens)
+            # h already carries the final norm: the stacked heads are a plain GEMV (no LayerNorm prologue)
+            logits = ops.decode_gemv(torch.cat([m.weight.float() for m in heads], 0),
+                                     torch.cat([m.bias.float() for m in heads], 0), h)
+        if self.fused:
+            hid = self._fused_plan().hidden
+            hid.copy_(h)
+            self.hidden = hid
+        elif self._graph is not None:
+            self.hidden.copy_(h)            # the captured step's output buffer: every later replay refreshes it
+        else:
+            self.hidden = h
+        self.n_steps += int(lens.max())
+        return logits
+
+    def prefill(self, tokens, lengths=None):
+        """Feed a whole prompt in one parallel pass per layer: leaves the state exactly as feeding the prompt's
+        tokens through step() one by one would (within f32 rounding), starting from whatever state the session holds
+        (reset(), earlier steps or an earlier prefill), and returns what the last of those step() calls would: the
+        next-token logits (host numpy) and `hidden`.  tokens: (P, 6) for one song, (n_songs, P, 6) for several;
+        ragged prompts pass `lengths` (n_songs values in [1, P]; rows past a song's length are ignored).  The state is
+        updated in the session's own buffers, so a captured step graph stays valid.  f32 sessions in eval() mode.
+        n_steps advances by the longest prompt: with ragged prompts song i has then been fed
+        n_steps - (max(lengths) - lengths[i]) tokens in total."""
+        out = self._prefill(tokens, lengths)
+        self._host_logits.copy_(out, non_blocking=True)
+        torch.cuda.current_stream(self.dev).synchronize()
+        res = self._host_logits.numpy()
+        return res[0] if self.n_songs == 1 else res
+
     def split(self, logits):
         outs, o = [], 0
         for n in self.n_token:
@@ -266,6 +326,18 @@ class _DeviceLoop:
                                temperature=self.temperature, top_p=self.top_p)
         self.count.add_(1)
 
+    def start(self, logits):
+        """Draw the first token from logits the session already holds on the device (a prefill's), as `_one` draws
+        every later one: into the step's token buffer and row 0 of the song, keyed by the counter."""
+        if self.enqueued:
+            raise RuntimeError("start() draws the loop's first token")
+        s = self.sess
+        with torch.no_grad():
+            ops.sample_categorical(logits, s.n_token, s.tok.view(1, self.A), self.seed, counter=self.count,
+                                   song=self.song, temperature=self.temperature, top_p=self.top_p)
+            self.count.add_(1)
+        self.enqueued = 1
+
     def run(self, n):
         """Enqueue n more tokens (no host sync)."""
         n = min(n, self.capacity - self.enqueued)
@@ -293,16 +365,33 @@ class _DeviceLoop:
         return self.song[start:stop, 0].cpu().numpy()
 
 
-def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None):
+def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
     """ppo_policy/inference.py:78-160 (`testing()`): start from the all-zero token, per step run the recurrent-form
     actor on the PREVIOUS token only -- the reference passes `memory=None` on every call (:106), so no state is
     carried; `carry_memory=True` is the evident intent -- and draw each attribute from Categorical(softmax(logits))
     (:121-133).  Everything stays on the device (`_DeviceLoop`); ONE host sync at the end.  Same distribution as the
-    reference's torch.distributions draws, not the same random stream.  -> (token_count, 6) int64 numpy."""
+    reference's torch.distributions draws, not the same random stream.  -> (token_count, 6) int64 numpy.
+
+    prompt: a (P, 6) CW token array to continue (e.g. a slice of a dataset song): it is prefilled in one pass
+    (DecodeSession.prefill), the first token is drawn from its logits on the device, and the result is the prompt
+    followed by token_count drawn tokens.  Needs carry_memory=True: with the reference's fresh state per token the
+    prompt would be thrown away after its last token."""
+    if prompt is not None and not carry_memory:
+        raise ValueError("a prompt needs carry_memory=True: the reference's memory=None per step would discard it")
+    if prompt is not None and init is not None:
+        raise ValueError("pass a prompt or an initial token, not both")
     sess = DecodeSession(model, graph=False)
     if sess.model.training:
         raise RuntimeError("generation runs in eval() mode (ppo_policy/inference.py:96)")
     A = len(sess.n_token)
+    if prompt is not None:
+        prompt = np.asarray(prompt, dtype=np.int64).reshape(-1, A)
+        logits = sess._prefill(prompt)
+        loop = _DeviceLoop(sess, token_count, carry_memory=True, graph=graph)
+        if token_count > 0:
+            loop.start(logits)
+            loop.run(token_count - 1)
+        return np.concatenate([prompt, loop.tokens(0, token_count)])
     sess.tok.copy_(torch.as_tensor(np.zeros(A) if init is None else np.asarray(init), dtype=torch.int64)
                    .view(1, 1, A).to(sess.dev))
     loop = _DeviceLoop(sess, token_count, carry_memory=carry_memory, graph=graph)
@@ -374,18 +463,89 @@ def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=Non
     return np.concatenate(final_res)
 
 
+def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, log=None, session=None,
+                          device_sampling=False, chunk=128):
+    """Continue a piece: `prompt` ((P, 6) CW tokens, e.g. a slice of a dataset song or an earlier song's .npy) is
+    prefilled in one pass (DecodeSession.prefill) and the reference's sampling loop runs on from its logits.  The
+    result is the prompt followed by the continuation.  The bar rule is the reference's, applied as if the prompt's
+    tokens had been drawn by the loop: the count starts at 1 and counts the Bar tokens of prompt[1:], so a prompt that
+    already reaches `bar_cond` is refused.  `max_tokens` caps the whole song, prompt included.
+    prompt = INIT_CW reproduces inference_from_scratch.
+
+    device_sampling=False: the reference's numpy samplers on the host, the first token drawn from the prefill logits.
+    device_sampling=True: every token, the first included, drawn on the device (`cwlt_sample_categorical`, keyed by
+    the loop's counter), with no host round trip between the prefill and the loop."""
+    classes = list(word2event.keys())
+    prompt = np.asarray(prompt, dtype=np.int64).reshape(-1, len(classes))
+    if len(prompt) == 0:
+        raise ValueError("empty prompt")
+    cnt_bar = 1 + sum(word2event["bar-beat"][int(r[2])] == "Bar" for r in prompt[1:])
+    if cnt_bar >= bar_cond:
+        raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (cnt_bar, bar_cond))
+    if max_tokens is not None and max_tokens <= len(prompt):
+        raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(prompt)))
+    sess = session or DecodeSession(model)
+    sess.reset()
+
+    def show(cp, prefix=""):
+        if log is not None:
+            log(prefix + " | ".join("{:15s}".format(str(word2event[k][int(cp[i])])) for i, k in enumerate(classes)))
+
+    final_res = []
+    for row in prompt:
+        show(row)
+        final_res.append(row[None, ...])
+    if device_sampling:
+        cap = max_tokens - len(prompt) if max_tokens is not None else 16384
+        logits = sess._prefill(prompt)
+        loop = _DeviceLoop(sess, cap, temperature=DQN_TEMPERATURE, top_p=DQN_TOP_P, carry_memory=True,
+                           graph=sess.use_graph)
+        loop.start(logits)
+        done = 0
+        while done < cap:
+            stop = min(cap, done + chunk)
+            loop.run(stop - loop.enqueued)
+            for next_arr in loop.tokens(done, stop):
+                final_res.append(next_arr[None, ...])
+                show(next_arr, "bar: %d  ==" % cnt_bar)
+                if word2event["bar-beat"][int(next_arr[2])] == "Bar":
+                    cnt_bar += 1
+                if cnt_bar == bar_cond:
+                    return np.concatenate(final_res)
+            done = stop
+        return np.concatenate(final_res)
+    logits = sess.prefill(prompt)
+    while True:
+        next_arr = sample_cw(sess.split(logits))
+        final_res.append(next_arr[None, ...])
+        show(next_arr, "bar: %d  ==" % cnt_bar)
+        logits = sess.step(next_arr)
+        if word2event["bar-beat"][int(next_arr[2])] == "Bar":
+            cnt_bar += 1
+        if cnt_bar == bar_cond:
+            break
+        if max_tokens is not None and len(final_res) >= max_tokens:
+            break
+    return np.concatenate(final_res)
+
+
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
-             max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False):
+             max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
-    (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy."""
+    (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
+    prompt: a (P, 6) CW token array every song continues (inference_from_prompt); None starts from scratch."""
     os.makedirs(path_gendir, exist_ok=True)
     sess = DecodeSession(model)
     song_time_list, words_len_list = [], []
     for sidx in range(n_songs):
         start = time.time()
-        res = inference_from_scratch(model, word2event, bar_cond, max_tokens=max_tokens, session=sess,
-                                     device_sampling=device_sampling)
+        if prompt is None:
+            res = inference_from_scratch(model, word2event, bar_cond, max_tokens=max_tokens, session=sess,
+                                         device_sampling=device_sampling)
+        else:
+            res = inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=max_tokens, session=sess,
+                                        device_sampling=device_sampling)
         if write_midi is not None:
             write_midi(res, os.path.join(path_gendir, "get_%d.mid" % sidx), word2event)
         else:

@@ -1439,6 +1439,45 @@ def recurrent_cla_step(qkv, S, Z, H, eps=CLA_EPS):
     return out
 
 
+def cla_fwd_state(q, k, v, S, Z, lengths=None, eps=CLA_EPS, out=None, segments=None):
+    """The prompt form of recurrent_cla_step (csrc/prefill.hip): q, k, v (N, L, H, 64) views (row-strided ok) of a
+    whole prompt per sequence; S (N, H, 64, 64), Z (N, H, 64) f32 recurrent states, read as the starting state and
+    updated IN PLACE to the state after each sequence's last token; lengths: (N) int32 device tensor (or None = all
+    L) -- rows t >= lengths[n] add nothing and stay unwritten in `out` (a dense (N, L, H, 64) buffer to write into,
+    or None for a fresh one).  segments: runs per sequence of the few-stream form (None = the library's choice,
+    cwlt_prefill_segments; 1 = one workgroup per (sequence, head)).  -> out."""
+    N, L, H, D = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("cla_fwd_state needs q, k, v of one shape (N, L, H, D)")
+    if q.dtype != k.dtype or q.dtype != v.dtype:
+        raise TypeError("q, k, v dtypes differ")
+    if S.shape != (N, H, D, D) or Z.shape != (N, H, D):
+        raise ValueError("state shapes %s / %s do not match (N, H, D, D) / (N, H, D) = %s"
+                         % (tuple(S.shape), tuple(Z.shape), (N, H, D, D)))
+    if S.dtype != torch.float32 or Z.dtype != torch.float32 or not S.is_contiguous() or not Z.is_contiguous():
+        raise TypeError("the recurrent state is dense f32 (it is updated in place)")
+    if lengths is not None:
+        if lengths.shape != (N,) or lengths.dtype != torch.int32 or not lengths.is_contiguous():
+            raise ValueError("lengths must be a dense (N,) int32 tensor")
+    for name, t in (("k", k), ("v", v), ("S", S), ("Z", Z), ("lengths", lengths)):
+        if t is not None and t.device != q.device:
+            raise ValueError("%s is on %s, q on %s" % (name, t.device, q.device))
+    q, ldq = _as_rows(q)
+    k, ldk = _as_rows(k)
+    v, ldv = _as_rows(v)
+    if out is None:
+        out = torch.empty((N, L, H, D), dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
+        raise ValueError("out must be a dense (N, L, H, D) tensor of q's dtype and device")
+    lib = _lib.load()
+    P = lib.cwlt_prefill_segments(N, H, L) if segments is None else int(segments)
+    ws = torch.empty(int(lib.cwlt_prefill_seg_floats(N, H, P)), dtype=torch.float32, device=q.device) if P > 1 else None
+    _call("cwlt_causal_linear_fwd_state", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
+          _lib.dev(S, "S"), _lib.dev(Z, "Z"), _lib.opt(lengths), N, H, L, D, ldq, ldk, ldv, H * D, float(eps), P,
+          _lib.opt(ws), _lib.dtype_code(q.dtype), _lib.stream_ptr())
+    return out
+
+
 def sqrt_width(w):
     return math.sqrt(w)
 

@@ -27,7 +27,9 @@ Pretrain_CKPT = "./ckpt/actor_pretrain.pt"
 Output_File_Path = "./gen_midi/ppo_song.npy"
 
 
-def testing(token_count=None, carry_memory=False, log=print):
+def testing(token_count=None, carry_memory=False, log=print, prompt=None):
+    """prompt: optional (P, 6) CW token array (a slice of a dataset song, an earlier ppo_song.npy) to continue;
+    needs carry_memory=True.  The saved song is then the prompt followed by the drawn tokens."""
     os.makedirs(os.path.dirname(Output_File_Path) or ".", exist_ok=True)
     dictionary, _ = cwdata.load_ppo(datapath["path_dictionary"], datapath["path_train_data"], n_seq=1, T=64)
     event2word, word2event = dictionary
@@ -40,7 +42,7 @@ def testing(token_count=None, carry_memory=False, log=print):
         log("[*] %s not found: sampling from freshly initialised weights" % Pretrain_CKPT)
     model.eval()
     song = generation.categorical_rollout(model, TOKEN_COUNT if token_count is None else token_count,
-                                          carry_memory=carry_memory)
+                                          carry_memory=carry_memory, prompt=prompt)
     np.save(Output_File_Path, song)
     log("====== Finish ====== ")
     return song

@@ -54,6 +54,35 @@ class RecurrentTransformerEncoderLayer(nn.Module):
                                      ops.next_seed() if p > 0 else 0, save_s=False)
         return x2, [S, Zs]
 
+    def prefill(self, x, state, lengths=None):
+        """A whole prompt per sequence in one pass: x (N, L, D); state [S (N, H, 64, 64), Zs (N, H, 64)] advanced IN
+        PLACE as L calls of forward() would (only the first lengths[n] rows of sequence n count).  The row-wise ops are
+        forward()'s own, on N*L rows; only the per-token attention step becomes ops.cla_fwd_state.  -> (N, L, D)."""
+        at = self.attention
+        N, L, D = x.shape
+        H = at.n_heads
+        if self.training:
+            raise RuntimeError("prefill runs in eval() mode")
+        S, Zs = state
+        with torch.no_grad():
+            wqkv = torch.cat([at.query_projection.weight, at.key_projection.weight, at.value_projection.weight], 0)
+            bqkv = torch.cat([at.query_projection.bias, at.key_projection.bias, at.value_projection.bias], 0)
+            x = x.reshape(N * L, D).contiguous()
+            qkv = torch.addmm(bqkv.to(x.dtype), x, wqkv.to(x.dtype).t()).view(N, L, 3, H, D // H)
+            # padded rows are never written by the scan: zero them so that everything downstream stays finite
+            a = (torch.zeros if lengths is not None else torch.empty)((N, L, H, D // H), dtype=x.dtype,
+                                                                      device=x.device)
+            ops.cla_fwd_state(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], S, Zs, lengths, out=a)
+            o = at.out_projection(a.view(N * L, D))
+            _, x1, _, _ = ops.ln_fwd(x, o, ops._f32(self.norm1.weight), ops._f32(self.norm1.bias), self.norm1.eps,
+                                     0.0, 0, save_s=False)
+            h = torch.mm(x1, self.linear1.weight.to(x.dtype).t())
+            g = ops.gelu_fwd(h, ops._f32(self.linear1.bias))
+            y = self.linear2(g)
+            _, x2, _, _ = ops.ln_fwd(x1, y, ops._f32(self.norm2.weight), ops._f32(self.norm2.bias), self.norm2.eps,
+                                     0.0, 0, save_s=False)
+        return x2.view(N, L, D)
+
 
 class RecurrentTransformerEncoder(nn.Module):
     def __init__(self, layers, norm_layer=None):
@@ -75,3 +104,30 @@ class RecurrentTransformerEncoder(nn.Module):
             with torch.no_grad():
                 x = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return x, state
+
+    def prefill(self, x, state, lengths=None):
+        """x (N, L, D) prompt rows (embedded, positional row added) -> (N, L, D) final-norm outputs; `state` (a list of
+        [S, Zs] per layer, as forward() takes it) advanced IN PLACE over each sequence's first lengths[n] rows
+        (lengths: (N) int32 device tensor, None = all L).  f32 only: the result is what L calls of forward() return,
+        row by row, so the projections run in full f32 (no TF32 / XF32)."""
+        if not x.is_cuda:
+            raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
+        if x.dtype != torch.float32:
+            raise RuntimeError("prefill computes in f32 (got %s activations)" % x.dtype)
+        if state is None or len(state) != len(self.layers) or any(s is None for s in state):
+            raise ValueError("prefill needs one [S, Zs] state per layer, updated in place")
+        N = x.shape[0]
+        for S, Zs in state:
+            if len(S) != N or len(Zs) != N:
+                raise ValueError("state holds %d sequences, the prompt batch %d" % (len(S), N))
+        tf32 = torch.backends.cuda.matmul.allow_tf32
+        torch.backends.cuda.matmul.allow_tf32 = False
+        try:
+            for layer, st in zip(self.layers, state):
+                x = layer.prefill(x, st, lengths)
+            if self.norm is not None:
+                with torch.no_grad():
+                    x = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
+        finally:
+            torch.backends.cuda.matmul.allow_tf32 = tf32
+        return x
