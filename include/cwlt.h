@@ -430,6 +430,25 @@ int cwlt_decode_gemv(const float* W, const float* bias, const float* xin, const 
                      const float* res, float* out, float* x_out, int n_out, int K, int act, int n_songs,
                      int64_t ld_x, int64_t ld_res, int64_t ld_out, int64_t ld_xo, void* stream);
 
+/* ---- generation: the same token step for many songs at once, projections as f32 MFMA GEMMs (csrc/decode_gemm.hip)
+ * cwlt_decode_gemm: cwlt_decode_gemv's product, prologue and epilogue for n_songs rows (1..4096), each weight read
+ * once per 64 songs.  Exact f32 (v_mfma_f32_16x16x4_f32) and batch invariant: a row's result is bitwise the same
+ * whatever n_songs, its position or the other rows.  K % 16 == 0, 16 <= K <= 2048, n_out <= 4096, ld_x (and ld_xo
+ * with a prologue) multiples of 4.  scratch: cwlt_decode_gemm_scratch_floats(n_out, K, n_songs) f32 (16-byte aligned),
+ * the split-K partials and, when a prologue has no x_out, the normalised rows; -1 for an unsupported shape. */
+int64_t cwlt_decode_gemm_scratch_floats(int n_out, int K, int n_songs);
+int cwlt_decode_gemm(const float* W, const float* bias, const float* xin, const float* ln_w,
+                     const float* ln_b, const float* ln2_w, const float* ln2_b, float eps,
+                     const float* res, float* out, float* x_out, int n_out, int K, int act, int n_songs,
+                     int64_t ld_x, int64_t ld_res, int64_t ld_out, int64_t ld_xo, float* scratch, void* stream);
+/* cwlt_decode_step's arguments and outputs, its projections on cwlt_decode_gemm.  work: the per-song rows of
+ * cwlt_decode_step (n_songs * cwlt_decode_workspace_floats(m)) followed by the GEMMs' scratch,
+ * cwlt_decode_rows_workspace_floats(m, n_songs) floats in all (-1: unsupported model or n_songs outside 1..4096;
+ * the model also needs d_model, d_ff and emb_width multiples of 16). */
+int64_t cwlt_decode_rows_workspace_floats(const cwlt_decode_model* m, int n_songs);
+int cwlt_decode_step_rows(const cwlt_decode_model* m, const int64_t* tokens, float* work, float* hidden,
+                          float* logits, int n_songs, void* stream);
+
 /* Device-side sampling of the next CW token: for each of `rows` songs and each attribute a, draw from
  * Categorical(softmax(logits[row, off_a : off_a + n_class[a]] / temperature[a])) and store the class id in
  * tokens[row, a] (and in song[counter, row, a] when song != NULL and *counter < song_rows).  Replaces the six
@@ -444,6 +463,13 @@ int cwlt_sample_categorical(const float* logits, const int* n_class, const float
                             const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
                             const int64_t* counter, int64_t* tokens, int64_t* song, int64_t song_rows,
                             void* stream);
+/* The same draw keyed by (seed, *counter, song row, attribute) independently of `rows`: song n's tokens are the same
+ * whatever the number of songs in the launch (cwlt_sample_categorical mixes `rows` into the key; both give the same
+ * keys when rows == 1).  Used by many-song generation, whose songs must not depend on the batch size; *counter < 2^40. */
+int cwlt_sample_categorical_slots(const float* logits, const int* n_class, const float* temperature,
+                                  const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                  const int64_t* counter, int64_t* tokens, int64_t* song, int64_t song_rows,
+                                  void* stream);
 
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass

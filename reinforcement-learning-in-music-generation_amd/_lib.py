@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -117,7 +117,13 @@ _SIGNATURES = {
     "cwlt_decode_workspace_floats": [ctypes.POINTER(DecodeModel)],
     "cwlt_decode_step": [ctypes.POINTER(DecodeModel), _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
     "cwlt_decode_gemv": [_ptr] * 7 + [_c_f32] + [_ptr] * 3 + [_c_int] * 4 + [_c_i64] * 4 + [_ptr],
+    "cwlt_decode_gemm_scratch_floats": [_c_int, _c_int, _c_int],
+    "cwlt_decode_gemm": [_ptr] * 7 + [_c_f32] + [_ptr] * 3 + [_c_int] * 4 + [_c_i64] * 4 + [_ptr, _ptr],
+    "cwlt_decode_rows_workspace_floats": [ctypes.POINTER(DecodeModel), _c_int],
+    "cwlt_decode_step_rows": [ctypes.POINTER(DecodeModel), _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
     "cwlt_sample_categorical": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64, _ptr, _ptr, _ptr, _c_i64, _ptr],
+    "cwlt_sample_categorical_slots": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64, _ptr, _ptr, _ptr, _c_i64,
+                                      _ptr],
     "cwlt_heads_blocks": [_c_i64],
     "cwlt_heads_fwd": [_ptr, _ptr, _c_int] + [_ptr] * 7 + [_c_i64, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_heads_ce_bwd": [_ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr],
@@ -156,7 +162,8 @@ def load():
         fn = getattr(lib, name)  # AttributeError if the .so is stale
         fn.argtypes = argtypes
         fn.restype = _c_i64 if name in ("cwlt_decode_workspace_floats", "cwlt_gemm_nt_tiles", "cwlt_scan_seg_floats",
-                                         "cwlt_scan_final_state_floats", "cwlt_prefill_seg_floats") else _c_int
+                                         "cwlt_scan_final_state_floats", "cwlt_prefill_seg_floats",
+                                         "cwlt_decode_gemm_scratch_floats", "cwlt_decode_rows_workspace_floats") else _c_int
     got = lib.cwlt_abi_version()
     if got != ABI_VERSION:
         raise ImportError("libcwlt.so ABI version %d, binding expects %d -- rebuild" % (got, ABI_VERSION))

@@ -30,7 +30,8 @@ struct SampleArgs {
 
 __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
-    const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows) {
+    const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
+    int slot_keyed) {
     __shared__ float e_s[CWLT_MAX_ATTR][256];
     const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
     if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
@@ -89,7 +90,9 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     }
     const float before = inc - run;
     const float total = lane_value(inc, 63);
-    const uint32_t r = rng_pair(seed, ((uint64_t)step * gridDim.x + n) * CWLT_MAX_ATTR + a);
+    // slot-keyed: song n's draws do not depend on how many songs share the launch (the same keys at n = 0)
+    const uint64_t key = slot_keyed ? ((uint64_t)n << 40) + (uint64_t)step : (uint64_t)step * gridDim.x + n;
+    const uint32_t r = rng_pair(seed, key * CWLT_MAX_ATTR + a);
     const float u = (float)(r >> 8) * (1.0f / 16777216.0f);      // [0, 1)
     const float target = u * total;
     int pick = INT_MAX;
@@ -117,9 +120,9 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
 
 }  // namespace cwlt
 
-extern "C" int cwlt_sample_categorical(const float* logits, const int* n_class, const float* temperature,
-                                       const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter,
-                                       int64_t* tokens, int64_t* song, int64_t song_rows, void* stream) {
+static int sample(const float* logits, const int* n_class, const float* temperature, const float* top_p, int n_attr,
+                  int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter, int64_t* tokens, int64_t* song,
+                  int64_t song_rows, int slot_keyed, void* stream) {
     using namespace cwlt;
     if (!logits || !n_class || !tokens || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0) return CWLT_ERR_ARG;
     SampleArgs A;
@@ -136,6 +139,22 @@ extern "C" int cwlt_sample_categorical(const float* logits, const int* n_class, 
     }
     if (ld < off) return CWLT_ERR_ARG;
     hipLaunchKernelGGL(sample_categorical_kernel, dim3((unsigned)rows), dim3(64 * n_attr), 0, (hipStream_t)stream, logits,
-                       (long)ld, A, n_attr, seed, counter, tokens, song, (long)song_rows);
+                       (long)ld, A, n_attr, seed, counter, tokens, song, (long)song_rows, slot_keyed);
     return (int)hipGetLastError();
+}
+
+extern "C" int cwlt_sample_categorical(const float* logits, const int* n_class, const float* temperature,
+                                       const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter,
+                                       int64_t* tokens, int64_t* song, int64_t song_rows, void* stream) {
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, counter, tokens, song, song_rows, 0,
+                  stream);
+}
+
+extern "C" int cwlt_sample_categorical_slots(const float* logits, const int* n_class, const float* temperature,
+                                             const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                             const int64_t* counter, int64_t* tokens, int64_t* song,
+                                             int64_t song_rows, void* stream) {
+    if (rows > (1L << 20)) return CWLT_ERR_ARG;             // row << 40 stays clear of the attribute factor
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, counter, tokens, song, song_rows, 1,
+                  stream);
 }

@@ -33,9 +33,10 @@ class _FusedPlan:
     """Host description of the model for `cwlt_decode_step` (include/cwlt.h: cwlt_decode_model): stacked
     QKV / head weights, device pointers of every parameter, the per-song state and workspace.  Holds references
     to every tensor whose pointer it hands out.  Built once per song (`DecodeSession.reset` rebuilds it, so
-    weights loaded between songs are picked up)."""
+    weights loaded between songs are picked up).  kernel="gemm": the step is `cwlt_decode_step_rows`
+    (csrc/decode_gemm.hip), whose workspace also holds its GEMMs' split-K scratch."""
 
-    def __init__(self, model, memory, n_songs):
+    def __init__(self, model, memory, n_songs, kernel="gemv"):
         from . import _lib
         lib = _lib.load()
         enc = model.transformer_encoder
@@ -97,8 +98,15 @@ class _FusedPlan:
         if per_song <= 0:
             raise RuntimeError("cwlt_decode_step does not support this model shape (d_model %d, d_ff %d)"
                                % (m.d_model, m.d_ff))
+        floats = n_songs * per_song
+        if kernel == "gemm":
+            floats = lib.cwlt_decode_rows_workspace_floats(ctypes.byref(m), n_songs)
+            if floats <= 0:
+                raise RuntimeError("cwlt_decode_step_rows does not support this model shape or batch (d_model %d, "
+                                   "d_ff %d, %d songs)" % (m.d_model, m.d_ff, n_songs))
+        self.entry = "cwlt_decode_step_rows" if kernel == "gemm" else "cwlt_decode_step"
         dev = memory[0][0].device
-        self.work = torch.zeros(n_songs * per_song, dtype=torch.float32, device=dev)
+        self.work = torch.zeros(floats, dtype=torch.float32, device=dev)
         self.hidden = torch.zeros((n_songs, m.d_model), dtype=torch.float32, device=dev)
         self.logits = torch.zeros((n_songs, m.n_logits), dtype=torch.float32, device=dev)
         self.n_songs = n_songs
@@ -111,10 +119,10 @@ class _FusedPlan:
 
     def step(self, tok):
         from . import _lib
-        st = _lib.load().cwlt_decode_step(ctypes.byref(self.model), _lib.dev(tok), _lib.dev(self.work),
-                                          _lib.dev(self.hidden), _lib.dev(self.logits), self.n_songs,
-                                          _lib.stream_ptr())
-        _lib.check(st, "cwlt_decode_step")
+        st = getattr(_lib.load(), self.entry)(ctypes.byref(self.model), _lib.dev(tok), _lib.dev(self.work),
+                                              _lib.dev(self.hidden), _lib.dev(self.logits), self.n_songs,
+                                              _lib.stream_ptr())
+        _lib.check(st, self.entry)
         return self.logits
 
 
@@ -123,9 +131,12 @@ class DecodeSession:
     `step(ids) -> (sum n_token,) f32 numpy logits` (or (n_songs, sum n_token) when n_songs > 1).
 
     fused=True (default for f32 models): the step is `cwlt_decode_step` (csrc/decode.hip, 5 launches per layer);
-    fused=False: the layer-by-layer module path (recurrent.py), the only one for bf16 activations."""
+    fused=False: the layer-by-layer module path (recurrent.py), the only one for bf16 activations.
+    kernel="gemm" (fused f32 only): the step is `cwlt_decode_step_rows` (csrc/decode_gemm.hip), its projections f32
+    MFMA GEMMs that read each weight once per 64 songs -- the step for many songs in lock-step; "gemv" (default):
+    `cwlt_decode_step`, one weight stream per song."""
 
-    def __init__(self, model, graph=None, fused=None, n_songs=1):
+    def __init__(self, model, graph=None, fused=None, n_songs=1, kernel="gemv"):
         if not getattr(model, "_recurrent", False):
             raise RuntimeError("generation needs a model built with is_training=False (recurrent encoder)")
         p = next(model.parameters())
@@ -141,7 +152,12 @@ class DecodeSession:
             raise RuntimeError("the fused decode step computes in f32; use fused=False for bf16 activations")
         if not fused and self.n_songs != 1:
             raise RuntimeError("the module-by-module decode path generates one song at a time (as the reference)")
+        if kernel not in ("gemv", "gemm"):
+            raise ValueError("kernel must be 'gemv' or 'gemm', got %r" % (kernel,))
+        if kernel == "gemm" and not fused:
+            raise RuntimeError("the GEMM decode step is the fused f32 step: it needs fused=True and f32 activations")
         self.fused = bool(fused)
+        self.kernel = kernel
         enc = model.transformer_encoder
         H = enc.layers[0].attention.n_heads
         d = model.d_model // H
@@ -179,7 +195,7 @@ class DecodeSession:
     def _fused_plan(self):
         if self._plan is None:
             with torch.no_grad():
-                self._plan = _FusedPlan(self.model, self.memory, self.n_songs)
+                self._plan = _FusedPlan(self.model, self.memory, self.n_songs, self.kernel)
             self._plan.tag = self._weights_tag()
         return self._plan
 
@@ -302,40 +318,52 @@ class DecodeSession:
 
 class _DeviceLoop:
     """Generation loop that never returns to the host: per token the decode step, ONE sampling kernel
-    (csrc/sample.hip) that writes the drawn ids into the step's token buffer and into row `count` of `song`, and
-    the counter increment -- eager for the first two tokens, then one captured hipGraph replayed per token."""
+    (csrc/sample.hip) that writes the drawn ids of every song into the step's token buffer and into row `count` of
+    `song` (capacity, n_songs, 6), and the counter increment -- eager for the first two tokens, then one captured
+    hipGraph replayed per token.
 
-    def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None):
-        if sess.n_songs != 1:
-            raise RuntimeError("device-side generation loops run one song per session")
+    ring=R: `song` holds only the last R rows (row t of the stream in slot t % R) so that many songs with a large cap
+    do not need capacity x n_songs rows; read each R-row stretch before the next R tokens overwrite it.  The draws are
+    the same either way (they are keyed by the counter)."""
+
+    def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
-        self.A = len(sess.n_token)
-        self.song = torch.zeros((self.capacity, 1, self.A), dtype=torch.int64, device=sess.dev)
+        self.A, self.N = len(sess.n_token), sess.n_songs
+        self.ring = None if ring is None or int(ring) >= self.capacity else int(ring)
+        rows = self.capacity if self.ring is None else self.ring
+        self.song = torch.zeros((rows, self.N, self.A), dtype=torch.int64, device=sess.dev)
         self.count = torch.zeros(1, dtype=torch.int64, device=sess.dev)
+        if self.ring is not None:
+            self.slot = torch.zeros(1, dtype=torch.int64, device=sess.dev)       # count % ring
         self.temperature, self.top_p = temperature, top_p
         self.seed = ops.next_seed()                       # keyed from torch.manual_seed, like the dropout seeds
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
         self._graph, self.enqueued = None, 0
 
+    def _draw(self, logits):
+        s = self.sess
+        tok = s.tok.view(self.N, self.A)
+        ops.sample_categorical(logits, s.n_token, tok, self.seed, counter=self.count,
+                               song=self.song if self.ring is None else None, temperature=self.temperature,
+                               top_p=self.top_p, slot_keys=True)
+        if self.ring is not None:
+            self.song.index_copy_(0, self.slot, tok.view(1, self.N, self.A))
+            self.slot.add_(1).remainder_(self.ring)
+        self.count.add_(1)
+
     def _one(self):
         s = self.sess
         if not self.carry:
             s._state.zero_()
-        logits = s._device_step()
-        ops.sample_categorical(logits, s.n_token, s.tok.view(1, self.A), self.seed, counter=self.count, song=self.song,
-                               temperature=self.temperature, top_p=self.top_p)
-        self.count.add_(1)
+        self._draw(s._device_step())
 
     def start(self, logits):
         """Draw the first token from logits the session already holds on the device (a prefill's), as `_one` draws
         every later one: into the step's token buffer and row 0 of the song, keyed by the counter."""
         if self.enqueued:
             raise RuntimeError("start() draws the loop's first token")
-        s = self.sess
         with torch.no_grad():
-            ops.sample_categorical(logits, s.n_token, s.tok.view(1, self.A), self.seed, counter=self.count,
-                                   song=self.song, temperature=self.temperature, top_p=self.top_p)
-            self.count.add_(1)
+            self._draw(logits)
         self.enqueued = 1
 
     def run(self, n):
@@ -359,10 +387,16 @@ class _DeviceLoop:
         return n
 
     def tokens(self, start, stop):
-        """Rows [start, stop) of the song as host numpy (syncs)."""
-        if int(self.count.item()) < stop:
-            raise RuntimeError("device generation loop produced %d of %d tokens" % (int(self.count.item()), stop))
-        return self.song[start:stop, 0].cpu().numpy()
+        """Rows [start, stop) of the songs as host numpy (rows, n_songs, 6) (syncs)."""
+        count = int(self.count.item())
+        if count < stop:
+            raise RuntimeError("device generation loop produced %d of %d tokens" % (count, stop))
+        if self.ring is None:
+            return self.song[start:stop].cpu().numpy()
+        if count - start > self.ring:
+            raise RuntimeError("rows from %d on were overwritten: the loop's ring holds the last %d" % (start, self.ring))
+        idx = torch.arange(start, stop, device=self.song.device) % self.ring
+        return self.song.index_select(0, idx).cpu().numpy()
 
 
 def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
@@ -391,12 +425,12 @@ def categorical_rollout(model, token_count, init=None, carry_memory=False, graph
         if token_count > 0:
             loop.start(logits)
             loop.run(token_count - 1)
-        return np.concatenate([prompt, loop.tokens(0, token_count)])
+        return np.concatenate([prompt, loop.tokens(0, token_count)[:, 0]])
     sess.tok.copy_(torch.as_tensor(np.zeros(A) if init is None else np.asarray(init), dtype=torch.int64)
                    .view(1, 1, A).to(sess.dev))
     loop = _DeviceLoop(sess, token_count, carry_memory=carry_memory, graph=graph)
     loop.run(token_count)
-    return loop.tokens(0, token_count)
+    return loop.tokens(0, token_count)[:, 0]
 
 
 # per-attribute sampler settings of forward_output_sampling (dqn_policy/model.py:281-286), attribute order
@@ -435,7 +469,7 @@ def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=Non
         done = 0
         while done < cap:
             n = loop.run(chunk)
-            for next_arr in loop.tokens(done, done + n):
+            for next_arr in loop.tokens(done, done + n)[:, 0]:
                 final_res.append(next_arr[None, ...])
                 show(next_arr, "bar: %d  ==" % cnt_bar)
                 if word2event["bar-beat"][int(next_arr[2])] == "Bar":
@@ -505,7 +539,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
         while done < cap:
             stop = min(cap, done + chunk)
             loop.run(stop - loop.enqueued)
-            for next_arr in loop.tokens(done, stop):
+            for next_arr in loop.tokens(done, stop)[:, 0]:
                 final_res.append(next_arr[None, ...])
                 show(next_arr, "bar: %d  ==" % cnt_bar)
                 if word2event["bar-beat"][int(next_arr[2])] == "Bar":
@@ -529,30 +563,138 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
     return np.concatenate(final_res)
 
 
+def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
+                   log=None):
+    """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
+    projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
+    token for all songs.  -> list of N (L_i, 6) int64 arrays.
+
+    prompts=None: every song starts from INIT_CW (inference_from_scratch(device_sampling=True)); one (P, 6) array: every
+    song continues it; a list of N arrays of any lengths: song i continues prompts[i] (prefilled in one ragged pass).
+    The first token after a prompt is drawn on the device from the prefill logits.
+    sampler="dqn": the per-attribute temperature / nucleus settings of forward_output_sampling; "categorical": the PPO
+    side's plain draw.  Every `chunk` tokens the host cuts each song by the reference's bar rule (the count starts at 1
+    and counts the Bar tokens of the prompt's rows after the first, the song ends WITH the token that opens bar
+    `bar_cond`), or at `max_tokens` rows, prompt included.  Finished songs keep stepping until the batch ends; their
+    extra rows are discarded.  The draws are keyed by (torch seed, step, song slot): song i of a batch from scratch
+    is the same whatever the batch size."""
+    if sampler not in ("dqn", "categorical"):
+        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
+    if model.training:
+        raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
+    if model.compute_dtype != torch.float32:
+        raise RuntimeError("the GEMM decode step computes in f32: this model runs %s activations (generate one song at "
+                           "a time with fused=False instead)" % model.compute_dtype)
+    n_songs, chunk = int(n_songs), int(chunk)
+    if n_songs < 1 or chunk < 1:
+        raise ValueError("n_songs and chunk must be >= 1")
+    classes = list(word2event.keys())
+    A = len(classes)
+    is_bar = lambda row: word2event["bar-beat"][int(row[2])] == "Bar"
+    if prompts is None:
+        heads = [INIT_CW[0].astype(np.int64)[None]] * n_songs
+    elif isinstance(prompts, (list, tuple)):
+        if len(prompts) != n_songs:
+            raise ValueError("prompts: %d arrays for %d songs" % (len(prompts), n_songs))
+        heads = [np.asarray(p, dtype=np.int64).reshape(-1, A) for p in prompts]
+    else:
+        heads = [np.asarray(prompts, dtype=np.int64).reshape(-1, A)] * n_songs
+    cnt_bar = []
+    for p in heads:
+        if len(p) == 0:
+            raise ValueError("empty prompt")
+        cnt = 1 + sum(is_bar(r) for r in p[1:])
+        if cnt >= bar_cond:
+            raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (cnt, bar_cond))
+        if max_tokens is not None and max_tokens <= len(p):
+            raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(p)))
+        cnt_bar.append(cnt)
+    caps = [16384 if max_tokens is None else max_tokens - len(p) for p in heads]     # drawn tokens per song
+    cap = max(caps)
+    sess = DecodeSession(model, n_songs=n_songs, kernel="gemm")
+    sess.reset()
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
+                       ring=chunk)
+    if prompts is None:
+        sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
+                       .view(n_songs, 1, A).to(sess.dev))
+    else:
+        P = max(len(p) for p in heads)
+        toks = np.zeros((n_songs, P, A), dtype=np.int64)
+        for i, p in enumerate(heads):
+            toks[i, :len(p)] = p
+        lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
+        loop.start(sess._prefill(toks, lengths))
+    drawn = [[] for _ in range(n_songs)]
+    live = set(range(n_songs))
+    done = 0
+    while done < cap and live:
+        stop = min(cap, done + chunk)
+        loop.run(stop - loop.enqueued)
+        rows = loop.tokens(done, stop)                                # (stop - done, N, 6)
+        for i in sorted(live):
+            for t in range(min(stop, caps[i]) - done):
+                row = rows[t, i]
+                drawn[i].append(row)
+                if is_bar(row):
+                    cnt_bar[i] += 1
+                if cnt_bar[i] == bar_cond:
+                    break
+            if cnt_bar[i] == bar_cond or len(drawn[i]) >= caps[i]:
+                live.discard(i)
+        done = stop
+    songs = [np.concatenate([p, np.asarray(d, dtype=np.int64).reshape(-1, A)]) for p, d in zip(heads, drawn)]
+    if log is not None:
+        log("batch of %d songs: %d tokens, %d steps" % (n_songs, sum(len(x) for x in songs), done))
+    return songs
+
+
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
-             max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None):
+             max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
+             batch_size=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
-    prompt: a (P, 6) CW token array every song continues (inference_from_prompt); None starts from scratch."""
+    prompt: a (P, 6) CW token array every song continues (inference_from_prompt); None starts from scratch.
+    batch_size: make the songs `batch_size` at a time with generate_batch (device sampling, one GEMM-step session per
+    group); a song's time is then its group's wall time divided by the group's size.  None: one song at a time."""
     os.makedirs(path_gendir, exist_ok=True)
-    sess = DecodeSession(model)
     song_time_list, words_len_list = [], []
-    for sidx in range(n_songs):
-        start = time.time()
-        if prompt is None:
-            res = inference_from_scratch(model, word2event, bar_cond, max_tokens=max_tokens, session=sess,
-                                         device_sampling=device_sampling)
-        else:
-            res = inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=max_tokens, session=sess,
-                                        device_sampling=device_sampling)
+
+    def save(sidx, res):
         if write_midi is not None:
             write_midi(res, os.path.join(path_gendir, "get_%d.mid" % sidx), word2event)
         else:
             np.save(os.path.join(path_gendir, "get_%d.npy" % sidx), res)
-        song_time_list.append(time.time() - start)
-        words_len_list.append(len(res))
-        log("song %d: %d tokens in %.3f s" % (sidx, len(res), song_time_list[-1]))
+
+    if batch_size is not None:
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        for first in range(0, n_songs, int(batch_size)):
+            group = min(int(batch_size), n_songs - first)
+            start = time.time()
+            songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens, prompts=prompt)
+            wall = time.time() - start
+            for j, res in enumerate(songs):
+                save(first + j, res)
+                song_time_list.append(wall / group)
+                words_len_list.append(len(res))
+                log("song %d: %d tokens in %.3f s (batch of %d)" % (first + j, len(res), song_time_list[-1], group))
+    else:
+        sess = DecodeSession(model)
+        for sidx in range(n_songs):
+            start = time.time()
+            if prompt is None:
+                res = inference_from_scratch(model, word2event, bar_cond, max_tokens=max_tokens, session=sess,
+                                             device_sampling=device_sampling)
+            else:
+                res = inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=max_tokens, session=sess,
+                                            device_sampling=device_sampling)
+            save(sidx, res)
+            song_time_list.append(time.time() - start)
+            words_len_list.append(len(res))
+            log("song %d: %d tokens in %.3f s" % (sidx, len(res), song_time_list[-1]))
     result = {"song_time": song_time_list, "words_len_list": words_len_list,
               "ave token time:": sum(words_len_list) / sum(song_time_list),
               "ave song time": float(np.mean(song_time_list))}

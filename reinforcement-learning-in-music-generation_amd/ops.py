@@ -1504,11 +1504,40 @@ def decode_gemv(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
     return (out, xn) if want_normed else out
 
 
-def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, temperature=None, top_p=None):
+def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, want_normed=False):
+    """decode_gemv's product for many rows at once (csrc/decode_gemm.hip: f32 MFMA, each weight read once per 64 rows,
+    bitwise batch invariant).  x (n, K) f32 with a row stride that is a multiple of 4, w (n_out, K) f32, K % 16 == 0
+    -> (n, n_out) f32 [, the normalised x]."""
+    if x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise TypeError("decode_gemm computes in f32")
+    n, K = x.shape
+    n_out = w.shape[0]
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+        x = x.contiguous()
+    w = w.contiguous()
+    out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
+    xn = torch.empty((n, K), dtype=torch.float32, device=x.device) if (want_normed and ln is not None) else None
+    if res is not None and res.stride(1) != 1:
+        res = res.contiguous()
+    lib = _lib.load()
+    need = lib.cwlt_decode_gemm_scratch_floats(n_out, K, n)
+    if need < 0:
+        raise ValueError("decode_gemm: unsupported shape n=%d, K=%d, n_out=%d" % (n, K, n_out))
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+    p = lambda pair, i: _lib.opt(None if pair is None else pair[i].contiguous())
+    _call("cwlt_decode_gemm", _lib.dev(w, "w"), _lib.opt(bias), _lib.dev(x, "x"), p(ln, 0), p(ln, 1), p(ln2, 0),
+          p(ln2, 1), float(eps), _lib.opt(res), _lib.dev(out), _lib.opt(xn), n_out, K, 1 if act == "gelu" else 0, n,
+          x.stride(0), 0 if res is None else res.stride(0), n_out, K, _lib.dev(scratch), _lib.stream_ptr())
+    return (out, xn) if want_normed else out
+
+
+def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, temperature=None, top_p=None,
+                       slot_keys=False):
     """tokens[row, a] ~ Categorical(softmax(logits[row, segment a] / temperature[a])) on the device
     (csrc/sample.hip; ppo_policy/inference.py:115-141).  logits (rows, >= sum n_class) f32; tokens (rows, A) int64
     written in place; counter: device int64 scalar tensor that keys the draw (and indexes `song` (T, rows, A));
-    top_p[a] < 1 (or None = off) samples attribute a from its nucleus (dqn_policy/model.py:33-47)."""
+    top_p[a] < 1 (or None = off) samples attribute a from its nucleus (dqn_policy/model.py:33-47).
+    slot_keys=True: the draw of row n does not depend on `rows` (cwlt_sample_categorical_slots; same draws at rows == 1)."""
     if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
         raise TypeError("sample_categorical takes f32 logits and int64 tokens")
     rows, A = logits.shape[0], len(n_class)
@@ -1518,7 +1547,7 @@ def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, t
         logits = logits.contiguous()
     temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
     topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    _call("cwlt_sample_categorical", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+    _call("cwlt_sample_categorical_slots" if slot_keys else "cwlt_sample_categorical", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
           logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.dev(tokens, "tokens"), _lib.opt(song),
           0 if song is None else song.shape[0], _lib.stream_ptr())
     return tokens
