@@ -470,6 +470,35 @@ int cwlt_sample_categorical_slots(const float* logits, const int* n_class, const
                                   const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
                                   const int64_t* counter, int64_t* tokens, int64_t* song, int64_t song_rows,
                                   void* stream);
+/* The slot-keyed draw with per-row keys (DEVICE int64 arrays): row n draws what cwlt_sample_categorical_slots draws for
+ * row key[n] at counter step[n] (key[n] < 2^20, step[n] < 2^40).  Continuous batching keys a slot's draw by (song index,
+ * position in song), so a song's tokens do not depend on the slot it runs in or on when it started. */
+int cwlt_sample_categorical_keyed(const float* logits, const int* n_class, const float* temperature,
+                                  const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                  const int64_t* key, const int64_t* step, int64_t* tokens, void* stream);
+
+/* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
+ * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,
+ * cwlt_stream_refill, cwlt_sample_categorical_keyed and cwlt_stream_advance.
+ *
+ * cwlt_stream_refill: for every slot s with fresh[s] != 0 (DEVICE int64, `slots` flags), copy the one-slot snapshot
+ * into slot s of `state` and snap_logits (n_logits floats) into logits row s (row stride ld_logits).  state holds
+ * n_layer blocks, each the S rows of all slots (slots x s_floats) then their Z rows (slots x z_floats); snap_state is
+ * the same layout for one slot.  s_floats, z_floats multiples of 4, both state pointers 16-byte aligned.  Other slots'
+ * bytes are not written.
+ * cwlt_stream_advance (one workgroup): per slot, write (song[s], tokens[s, 0..n_attr), end bit) into row ctl[0] %
+ * ring_rows of ring (ring_rows, slots, n_attr + 2) int64; for a slot with song[s] >= 0 advance pos[s] and bar[s] (+1 when
+ * bar_mask[tokens[s, bar_attr]], an int array of bar_classes flags) and end the song when bar[s] reaches bar_cond or
+ * pos[s] reaches cap.  Ended slots take the next song indices ctl[1], ctl[1] + 1, ... in slot order (song -1 once all
+ * n_songs are assigned), get pos 0 and bar bar0, and are flagged fresh; every other slot's flag is cleared.
+ * ctl (DEVICE int64 x 3) = {tokens advanced, songs assigned, songs finished}.  n_songs <= 2^20, bar0 < bar_cond. */
+int cwlt_stream_refill(float* state, const float* snap_state, int n_layer, int64_t s_floats, int64_t z_floats,
+                       float* logits, const float* snap_logits, int64_t n_logits, int64_t ld_logits,
+                       const int64_t* fresh, int64_t slots, void* stream);
+int cwlt_stream_advance(const int64_t* tokens, int n_attr, int64_t slots, int bar_attr, const int* bar_mask,
+                        int bar_classes, int64_t bar_cond, int64_t bar0, int64_t cap, int64_t n_songs, int64_t* song,
+                        int64_t* pos, int64_t* bar, int64_t* fresh, int64_t* ctl, int64_t* ring, int64_t ring_rows,
+                        void* stream);
 
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass

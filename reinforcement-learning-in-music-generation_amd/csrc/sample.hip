@@ -31,13 +31,14 @@ struct SampleArgs {
 __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
     const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
-    int slot_keyed) {
+    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step) {
     __shared__ float e_s[CWLT_MAX_ATTR][256];
     const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
     if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
     const int nc = A.n[a];
     const float* x = logits + (long)n * ld + A.off[a];
-    const long step = counter ? *counter : 0;
+    // keyed by row: row n draws what the slot-keyed launch draws for row row_key[n] at counter row_step[n]
+    const long step = row_step ? row_step[n] : counter ? *counter : 0;
     float v[4];
     float m = -INFINITY;
 #pragma unroll
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float before = inc - run;
     const float total = lane_value(inc, 63);
     // slot-keyed: song n's draws do not depend on how many songs share the launch (the same keys at n = 0)
-    const uint64_t key = slot_keyed ? ((uint64_t)n << 40) + (uint64_t)step : (uint64_t)step * gridDim.x + n;
+    const uint64_t slot = row_key ? (uint64_t)row_key[n] : (uint64_t)n;
+    const uint64_t key = slot_keyed ? (slot << 40) + (uint64_t)step : (uint64_t)step * gridDim.x + n;
     const uint32_t r = rng_pair(seed, key * CWLT_MAX_ATTR + a);
     const float u = (float)(r >> 8) * (1.0f / 16777216.0f);      // [0, 1)
     const float target = u * total;
@@ -122,7 +124,8 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
 
 static int sample(const float* logits, const int* n_class, const float* temperature, const float* top_p, int n_attr,
                   int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter, int64_t* tokens, int64_t* song,
-                  int64_t song_rows, int slot_keyed, void* stream) {
+                  int64_t song_rows, int slot_keyed, void* stream, const int64_t* row_key = nullptr,
+                  const int64_t* row_step = nullptr) {
     using namespace cwlt;
     if (!logits || !n_class || !tokens || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0) return CWLT_ERR_ARG;
     SampleArgs A;
@@ -139,7 +142,7 @@ static int sample(const float* logits, const int* n_class, const float* temperat
     }
     if (ld < off) return CWLT_ERR_ARG;
     hipLaunchKernelGGL(sample_categorical_kernel, dim3((unsigned)rows), dim3(64 * n_attr), 0, (hipStream_t)stream, logits,
-                       (long)ld, A, n_attr, seed, counter, tokens, song, (long)song_rows, slot_keyed);
+                       (long)ld, A, n_attr, seed, counter, tokens, song, (long)song_rows, slot_keyed, row_key, row_step);
     return (int)hipGetLastError();
 }
 
@@ -157,4 +160,12 @@ extern "C" int cwlt_sample_categorical_slots(const float* logits, const int* n_c
     if (rows > (1L << 20)) return CWLT_ERR_ARG;             // row << 40 stays clear of the attribute factor
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, counter, tokens, song, song_rows, 1,
                   stream);
+}
+
+extern "C" int cwlt_sample_categorical_keyed(const float* logits, const int* n_class, const float* temperature,
+                                             const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                             const int64_t* key, const int64_t* step, int64_t* tokens, void* stream) {
+    if (!key || !step || rows > (1L << 20)) return CWLT_ERR_ARG;
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, nullptr, tokens, nullptr, 0, 1, stream,
+                  key, step);
 }

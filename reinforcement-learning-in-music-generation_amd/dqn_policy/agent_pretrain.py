@@ -120,10 +120,12 @@ num_songs = 5
 bar_production = 50                               # testing-no-type-cp.py:35
 
 
-def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sampling=False, batch_size=None):
+def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sampling=False, batch_size=None,
+             slots=None):
     """agent_pretrain.py:636-706 / testing-no-type-cp.py:182-260: build the recurrent-form net, load
     ./ckpt/_params.pt when present, sample `num_songs` songs, write get_<i>.mid + runtime_stats.json.
-    batch_size: make the songs that many at a time in lock-step (generation.generate_batch)."""
+    batch_size: make the songs that many at a time in lock-step (generation.generate_batch).
+    slots: make the songs by continuous batching on that many decode slots (generation.generate_stream)."""
     from rlmg_amd import generation, midi
     dictionary, _ = cwdata.load_dqn(path_train_data, path_dictionary, n_seq=1, T=64)
     event2word, word2event = ({k: v for k, v in d.items() if k != "type"} for d in dictionary)
@@ -141,7 +143,7 @@ def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sam
     return generation.generate(net, word2event, n_songs=num_songs if n_songs is None else n_songs,
                                bar_cond=bar_production if bar_cond is None else bar_cond, path_gendir=path_gendir,
                                write_midi=midi.write_midi, max_tokens=max_tokens, log=log,
-                               device_sampling=device_sampling, batch_size=batch_size)
+                               device_sampling=device_sampling, batch_size=batch_size, slots=slots)
 
 
 if __name__ == "__main__":

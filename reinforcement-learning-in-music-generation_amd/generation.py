@@ -399,6 +399,195 @@ class _DeviceLoop:
         return self.song.index_select(0, idx).cpu().numpy()
 
 
+class _StreamLoop:
+    """Continuous batching on the device: `sess` (DecodeSession(n_songs=slots, kernel="gemm")) is a pool of decode slots
+    that runs `n_songs` songs, each slot starting the next song as soon as its own one ends.  Per token, one fixed
+    sequence of launches (captured as one hipGraph after two eager tokens):
+      the GEMM decode step on every slot;
+      cwlt_stream_refill: slots flagged fresh get the snapshot's state and logits (the state every song starts from);
+      cwlt_sample_categorical_keyed: each slot's draw keyed by (song index, position in song);
+      cwlt_stream_advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count
+        advanced, the song's end detected, finished slots handed the next song indices in slot order.
+    The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host."""
+
+    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
+                 temperature=None, top_p=None, graph=None):
+        self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
+        self.S, self.A = sess.n_songs, len(sess.n_token)
+        dev = sess.dev
+        self.snap_state, self.snap_logits = snap_state, snap_logits.reshape(-1)
+        self.n_layer = len(sess.memory)
+        self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
+        self.z_floats = sess.memory[0][1][0].numel()             # one slot's Z (H x d)
+        self.seed, self.temperature, self.top_p = seed, temperature, top_p
+        self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
+        self.bar_cond, self.bar0, self.cap = int(bar_cond), int(bar0), int(cap)
+        slot = torch.arange(self.S, dtype=torch.int64, device=dev)
+        self.song = torch.where(slot < self.n_songs, slot, torch.full_like(slot, -1))
+        self.pos = torch.zeros(self.S, dtype=torch.int64, device=dev)
+        self.bar = torch.full((self.S,), self.bar0, dtype=torch.int64, device=dev)
+        self.fresh = torch.ones(self.S, dtype=torch.int64, device=dev)     # every slot starts from the snapshot
+        self.ctl = torch.tensor([0, min(self.S, self.n_songs), 0], dtype=torch.int64, device=dev)
+        self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
+        self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._host_ctl = [torch.zeros(3, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._events = [torch.cuda.Event(), torch.cuda.Event()]
+        self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
+        self._graph, self.enqueued = None, 0
+        self.wait_s = 0.0                                          # host time spent waiting on the device
+
+    def _one(self):
+        s = self.sess
+        tok = s.tok.view(self.S, self.A)
+        logits = s._device_step()
+        ops.stream_refill(s._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
+                          self.snap_logits, self.fresh)
+        ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
+                                     temperature=self.temperature, top_p=self.top_p)
+        ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
+                           self.pos, self.bar, self.fresh, self.ctl, self.ring)
+
+    def _enqueue_chunk(self):
+        """Enqueue `chunk` tokens and the copy of their ring half (and the counters) to pinned host memory."""
+        with torch.no_grad():
+            for _ in range(self.chunk):
+                if not self.use_graph or self.enqueued < 2:
+                    self._one()
+                else:
+                    if self._graph is None:
+                        torch.cuda.synchronize(self.sess.dev)
+                        self._graph = ops.capture_hip_graph(self._one, torch.no_grad, "stream step")[0]  # recorded,
+                        if self._graph is None:                                                     # not executed
+                            self.use_graph = False
+                            self._one()
+                            self.enqueued += 1
+                            continue
+                    self._graph.replay()
+                self.enqueued += 1
+        k = self.enqueued // self.chunk - 1
+        h = k % 2
+        self._host[h].copy_(self.ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
+        self._host_ctl[h].copy_(self.ctl, non_blocking=True)
+        self._events[h].record()
+        return h
+
+    def run(self):
+        """Run until the device's finished counter reaches n_songs -> (rows (n, A + 2) of every song, time-ordered)."""
+        parts = []
+        limit = -(-self.n_songs // self.S) * (self.cap + 1) + 2 * self.chunk     # every slot's songs, one by one
+        h = self._enqueue_chunk()
+        while True:
+            nxt = self._enqueue_chunk()
+            t = time.perf_counter()
+            self._events[h].synchronize()
+            self.wait_s += time.perf_counter() - t
+            rows = self._host[h].numpy().reshape(-1, self.A + 2)
+            parts.append(rows[rows[:, 0] >= 0])                   # boolean indexing copies: the buffer is reused
+            if int(self._host_ctl[h][2]) >= self.n_songs:
+                break
+            if self.enqueued > limit:
+                raise RuntimeError("stream did not finish %d songs in %d steps" % (self.n_songs, self.enqueued))
+            h = nxt
+        t = time.perf_counter()
+        self._events[nxt].synchronize()                           # the one chunk enqueued past the end
+        self.wait_s += time.perf_counter() - t
+        return np.concatenate(parts)
+
+
+def _stream_snapshot(model, prompt, A):
+    """The state and logits every song of a stream starts from, on a one-slot GEMM session: one step of INIT_CW from
+    zero state (bitwise any row of the many-slot step, by batch invariance), or a one-row prefill of the prompt."""
+    snap = DecodeSession(model, n_songs=1, kernel="gemm", graph=False)
+    snap.reset()
+    with torch.no_grad():
+        if prompt is None:
+            snap.tok.copy_(torch.as_tensor(INIT_CW[0], dtype=torch.int64).view(1, 1, A).to(snap.dev))
+            logits = snap._device_step()
+        else:
+            logits = snap._prefill(prompt)
+    return snap._state.clone(), logits.reshape(-1).clone()
+
+
+def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
+                     chunk=128, log=None):
+    """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
+    wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph."""
+    if sampler not in ("dqn", "categorical"):
+        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
+    if model.training:
+        raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
+    if model.compute_dtype != torch.float32:
+        raise RuntimeError("the GEMM decode step computes in f32: this model runs %s activations (generate one song at "
+                           "a time with fused=False instead)" % model.compute_dtype)
+    n_songs, slots, chunk = int(n_songs), int(slots), int(chunk)
+    if n_songs < 1 or chunk < 1:
+        raise ValueError("n_songs and chunk must be >= 1")
+    if n_songs > 1 << 20:
+        raise ValueError("n_songs must be <= 2**20 (the sampler's key layout), got %d" % n_songs)
+    if slots < 1:
+        raise ValueError("slots must be >= 1, got %d" % slots)
+    if isinstance(prompt, (list, tuple)):
+        raise ValueError("generate_stream takes one shared (P, 6) prompt: ragged per-song prompts are not supported "
+                         "in a stream (use generate_batch)")
+    classes = list(word2event.keys())
+    A = len(classes)
+    bar_names = word2event["bar-beat"]
+    is_bar = lambda row: bar_names[int(row[2])] == "Bar"
+    head = INIT_CW[0].astype(np.int64)[None] if prompt is None else np.asarray(prompt, dtype=np.int64).reshape(-1, A)
+    if len(head) == 0:
+        raise ValueError("empty prompt")
+    bar0 = 1 + sum(is_bar(r) for r in head[1:])
+    if bar0 >= bar_cond:
+        raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (bar0, bar_cond))
+    if max_tokens is not None and max_tokens <= len(head):
+        raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(head)))
+    cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
+    start = time.perf_counter()
+    sess = DecodeSession(model, n_songs=slots, kernel="gemm")
+    sess.reset()
+    seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
+    snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else head, A)
+    bar_mask = [int(bar_names[i] == "Bar") for i in range(sess.n_token[2])]      # every class named "Bar", not one id
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
+                       temperature=temperature, top_p=top_p, graph=sess.use_graph)
+    rows = loop.run()
+    # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
+    order = np.argsort(rows[:, 0], kind="stable")
+    rows = rows[order]
+    counts = np.bincount(rows[:, 0], minlength=n_songs)
+    ends = np.cumsum(counts)
+    if len(counts) != n_songs or (counts == 0).any() or rows[:, -1].sum() != n_songs or \
+            not rows[ends - 1, -1].all():
+        raise RuntimeError("stream output is inconsistent: %d rows, %d end bits for %d songs"
+                           % (len(rows), int(rows[:, -1].sum()), n_songs))
+    songs = [np.concatenate([head, d]) for d in np.split(rows[:, 1:1 + A], ends[:-1])]
+    seconds = time.perf_counter() - start
+    stats = {"steps": loop.enqueued, "tokens": int(sum(len(x) for x in songs)), "drawn": int(len(rows)),
+             "slot_steps": loop.enqueued * slots, "seconds": seconds, "wait_seconds": loop.wait_s,
+             "graph": loop._graph is not None}
+    if log is not None:
+        log("stream of %d songs on %d slots: %d tokens, %d steps" % (n_songs, slots, stats["tokens"], loop.enqueued))
+    return songs, stats
+
+
+def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
+                    chunk=128, log=None):
+    """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
+    a slot starts the next song on the token after its song ends, and the device decides when a song ends.
+    -> list of n_songs (L_i, 6) int64 arrays, in song order.
+
+    Song k is bitwise the song k of generate_batch(model, word2event, n_songs, bar_cond, max_tokens, sampler=...) after
+    the same torch.manual_seed, whatever `slots`: the GEMM step is batch invariant, every song starts from the same
+    snapshot, and each draw is keyed by (torch seed, position in song, song index) -- generate_batch's (seed, step,
+    song slot).  The bar rule is generate_batch's: the count starts at 1 and counts the Bar tokens of the prompt's rows
+    after the first, a song ends WITH the token that opens bar `bar_cond`, or at `max_tokens` rows, prompt included
+    (16384 drawn tokens without a cap).  prompt: None (INIT_CW) or one (P, 6) array every song continues.
+    sampler: "dqn" or "categorical", as in generate_batch.  The host reads the songs every `chunk` tokens."""
+    return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
+                            prompt=prompt, sampler=sampler, chunk=chunk, log=log)[0]
+
+
 def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
     """ppo_policy/inference.py:78-160 (`testing()`): start from the all-zero token, per step run the recurrent-form
     actor on the PREVIOUS token only -- the reference passes `memory=None` on every call (:106), so no state is
@@ -652,13 +841,17 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None):
+             batch_size=None, slots=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
     prompt: a (P, 6) CW token array every song continues (inference_from_prompt); None starts from scratch.
     batch_size: make the songs `batch_size` at a time with generate_batch (device sampling, one GEMM-step session per
-    group); a song's time is then its group's wall time divided by the group's size.  None: one song at a time."""
+    group); a song's time is then its group's wall time divided by the group's size.  None: one song at a time.
+    slots: make the songs by continuous batching on that many decode slots (generate_stream); a song's time is then
+    the stream's wall time divided by n_songs.  Not together with batch_size."""
+    if batch_size is not None and slots is not None:
+        raise ValueError("pass batch_size or slots, not both")
     os.makedirs(path_gendir, exist_ok=True)
     song_time_list, words_len_list = [], []
 
@@ -668,7 +861,17 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         else:
             np.save(os.path.join(path_gendir, "get_%d.npy" % sidx), res)
 
-    if batch_size is not None:
+    if slots is not None:
+        start = time.time()
+        songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
+                                prompt=prompt)
+        wall = time.time() - start
+        for sidx, res in enumerate(songs):
+            save(sidx, res)
+            song_time_list.append(wall / n_songs)
+            words_len_list.append(len(res))
+            log("song %d: %d tokens in %.3f s (stream on %d slots)" % (sidx, len(res), song_time_list[-1], int(slots)))
+    elif batch_size is not None:
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
         for first in range(0, n_songs, int(batch_size)):

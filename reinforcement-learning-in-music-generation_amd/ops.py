@@ -1552,3 +1552,60 @@ def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, t
           0 if song is None else song.shape[0], _lib.stream_ptr())
     return tokens
 
+
+
+# --------------------------------------------------------------------------------------------------
+# continuous batching (csrc/stream.hip, csrc/sample.hip): the per-token launches of generation.generate_stream
+# --------------------------------------------------------------------------------------------------
+def sample_categorical_keyed(logits, n_class, tokens, seed, key, step, temperature=None, top_p=None):
+    """sample_categorical with per-row keys: row n draws what slot_keys=True draws for row key[n] at counter step[n]
+    (cwlt_sample_categorical_keyed).  key, step: (rows,) int64 device tensors (song index < 2^20, position < 2^40)."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
+        raise TypeError("sample_categorical_keyed takes f32 logits and int64 tokens")
+    rows, A = logits.shape[0], len(n_class)
+    if tokens.numel() != rows * A or not tokens.is_contiguous():
+        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
+    for t in (key, step):
+        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    _call("cwlt_sample_categorical_keyed", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.dev(key, "key"), _lib.dev(step, "step"),
+          _lib.dev(tokens, "tokens"), _lib.stream_ptr())
+    return tokens
+
+
+def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):
+    """Copy the one-slot snapshot (state, logits) into every slot whose fresh flag is set (cwlt_stream_refill).
+    state: flat f32 of n_layer x [S (slots, s_floats), Z (slots, z_floats)] (DecodeSession._state); snap_state: the same
+    for one slot; logits (slots, >= n) f32 with snap_logits (n,) f32; fresh (slots,) int64."""
+    slots = fresh.numel()
+    per = s_floats + z_floats
+    if state.dtype != torch.float32 or snap_state.dtype != torch.float32 or fresh.dtype != torch.int64:
+        raise TypeError("stream_refill takes f32 state / logits and int64 flags")
+    if state.numel() != n_layer * slots * per or snap_state.numel() != n_layer * per:
+        raise ValueError("stream_refill: state holds %d floats, snapshot %d, for %d layers x %d slots x %d"
+                         % (state.numel(), snap_state.numel(), n_layer, slots, per))
+    if logits.shape[0] != slots or logits.stride(-1) != 1 or snap_logits.numel() > logits.shape[1]:
+        raise ValueError("stream_refill: logits must be (slots, >= n_logits) with unit column stride")
+    _call("cwlt_stream_refill", _lib.dev(state, "state"), _lib.dev(snap_state.contiguous(), "snap_state"), int(n_layer),
+          int(s_floats), int(z_floats), _lib.dev(logits, "logits"), _lib.dev(snap_logits.contiguous(), "snap_logits"),
+          snap_logits.numel(), logits.stride(0), _lib.dev(fresh, "fresh"), slots, _lib.stream_ptr())
+
+
+def stream_advance(tokens, bar_attr, bar_mask, bar_cond, bar0, cap, n_songs, song, pos, bar, fresh, ctl, ring):
+    """One token of the stream's slot bookkeeping (cwlt_stream_advance): tokens (slots, A) int64 just drawn; bar_mask
+    (n_class[bar_attr],) int32; song / pos / bar / fresh (slots,) int64; ctl (3,) int64; ring (R, slots, A + 2) int64."""
+    slots, A = song.numel(), tokens.shape[-1]
+    for t in (song, pos, bar, fresh, ctl, ring, tokens):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError("stream_advance takes contiguous int64 slot arrays")
+    if bar_mask.dtype != torch.int32 or tokens.numel() != slots * A or ring.shape[1:] != (slots, A + 2) or \
+            ctl.numel() != 3 or not all(t.numel() == slots for t in (pos, bar, fresh)):
+        raise ValueError("stream_advance: inconsistent slot array shapes")
+    _call("cwlt_stream_advance", _lib.dev(tokens, "tokens"), A, slots, int(bar_attr), _lib.dev(bar_mask, "bar_mask"),
+          bar_mask.numel(), int(bar_cond), int(bar0), int(cap), int(n_songs), _lib.dev(song), _lib.dev(pos),
+          _lib.dev(bar), _lib.dev(fresh), _lib.dev(ctl), _lib.dev(ring), ring.shape[0], _lib.stream_ptr())
