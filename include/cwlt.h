@@ -499,6 +499,27 @@ int cwlt_stream_advance(const int64_t* tokens, int n_attr, int64_t slots, int ba
                         int bar_classes, int64_t bar_cond, int64_t bar0, int64_t cap, int64_t n_songs, int64_t* song,
                         int64_t* pos, int64_t* bar, int64_t* fresh, int64_t* ctl, int64_t* ring, int64_t ring_rows,
                         void* stream);
+/* Per-song prompts: every song starts from its own prefilled state, held in a device bank of `bank` entries (song k in
+ * entry k % bank; the host prefills blocks of songs into it while the stream runs).
+ * cwlt_stream_refill_bank: cwlt_stream_refill with the source of a fresh slot s the bank entry song[s] % bank (slots
+ * with song[s] < 0 are skipped).  bank_state holds n_layer blocks, each the S rows of all entries (bank x s_floats)
+ * then their Z rows (bank x z_floats); bank_logits (bank, >= n_logits) with row stride ld_bank_logits.
+ * cwlt_stream_advance_bank: cwlt_stream_advance with these changes.  ctl (DEVICE int64 x 4) = {tokens advanced, songs
+ * assigned, songs finished, songs ready}: the host raises ctl[3] (with a write enqueued after the prefill) once the
+ * entries of songs below it are written.  A slot whose song ended, and a slot already WAITING, is a candidate; the
+ * candidates are ranked in slot order and take the next song indices only while they are below min(ready, n_songs).
+ * A candidate past that waits (song[s] = -2) while songs remain unassigned and goes idle (-1) once all are; a waiting
+ * or idle slot writes song -1 into its ring row, its pos and bar do not move, and it is not counted as finished.  A slot
+ * handed song k gets pos 0, bar bank_bar0[k % bank] and cap[s] = bank_cap[k % bank] (its own cap, kept per slot since
+ * the entry is reused later) and is flagged fresh; every other slot's flag is cleared.  bar_cond >= 1. */
+int cwlt_stream_refill_bank(float* state, const float* bank_state, int64_t bank, int n_layer, int64_t s_floats,
+                            int64_t z_floats, float* logits, const float* bank_logits, int64_t n_logits,
+                            int64_t ld_logits, int64_t ld_bank_logits, const int64_t* fresh, const int64_t* song,
+                            int64_t slots, void* stream);
+int cwlt_stream_advance_bank(const int64_t* tokens, int n_attr, int64_t slots, int bar_attr, const int* bar_mask,
+                             int bar_classes, int64_t bar_cond, const int64_t* bank_bar0, const int64_t* bank_cap,
+                             int64_t bank, int64_t n_songs, int64_t* song, int64_t* pos, int64_t* bar, int64_t* cap,
+                             int64_t* fresh, int64_t* ctl, int64_t* ring, int64_t ring_rows, void* stream);
 
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass

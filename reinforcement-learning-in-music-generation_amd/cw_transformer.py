@@ -165,12 +165,21 @@ class CWTrunk(nn.Module):
         pos_emb = self.pos_emb(emb_linear).squeeze(0)
         return self.transformer_encoder(pos_emb, memory=memory)
 
-    def prefill_hidden(self, tokens, memory, lengths=None):
+    def prefill_hidden(self, tokens, memory, lengths=None, kernel="blas", logits=False, rows=None):
         """A whole prompt through the recurrent encoder in one pass: tokens (N, L, 6) int64 on the GPU, memory the
         per-layer [S, Zs] state (advanced IN PLACE as L calls of forward_hidden(..., is_training=False) would), lengths
         a host sequence of N prompt lengths in [1, L] (None = all L).  Every prompt row gets pe[0], as on the recurrent
         path (forward_hidden squeezes a length-1 sequence).  -> (N, d_model): each sequence's row lengths[n] - 1,
-        what forward_hidden returns for its last prompt token (final norm applied)."""
+        what forward_hidden returns for its last prompt token (final norm applied).
+
+        kernel="gemm": the batch-invariant prefill (RecurrentTransformerEncoder.prefill(kernel="gemm")): in_linear is a
+        cwlt_decode_gemm too (pe[0] added in its epilogue), at most `rows` rows per call, and sequence n's state, hidden
+        row and logits are bitwise independent of the other sequences, of L and of `rows`.  logits=True (gemm only):
+        -> (hidden, logits (N, sum n_token)), the heads run as the GEMM decode step runs them."""
+        if kernel not in ("blas", "gemm"):
+            raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
+        if logits and kernel != "gemm":
+            raise ValueError("logits=True needs kernel='gemm'")
         if not self._recurrent:
             raise RuntimeError("prefill needs a model built with is_training=False (recurrent encoder)")
         if self.compute_dtype != torch.float32:
@@ -184,10 +193,36 @@ class CWTrunk(nn.Module):
                 raise ValueError("prompt lengths must be %d values in [1, %d], got %s" % (N, L, list(idx + 1)))
             dev_len = (idx + 1).to(torch.int32).to(tokens.device)
         D = self.d_model
+        if kernel == "gemm":
+            h, lg = self._prefill_gemm(tokens, memory, dev_len, idx.to(tokens.device), rows)
+            return (h, lg) if logits else h
         x = self.embed(tokens).reshape(N * L, D)
         x = ops.posenc_dropout(x, self.pos_emb.pe.reshape(-1, D), 1).view(N, L, D)      # x + pe[0] on every row
         h = self.transformer_encoder.prefill(x, memory, dev_len)
         return h[torch.arange(N, device=h.device), idx.to(h.device)]
+
+    def _prefill_gemm(self, tokens, memory, lengths, last, rows=None):
+        """prefill_hidden(kernel="gemm", logits=True) on device arguments only (no host sync, so it can be enqueued
+        between the replays of a running stream): tokens (N, L, 6) int64, lengths (N) int32 or None, last (N) int64 =
+        lengths - 1, all on the GPU.  -> (hidden (N, D), logits (N, sum n_token))."""
+        rows = 4096 if rows is None else int(rows)
+        if not 1 <= rows <= 4096:
+            raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
+        N, L, _ = tokens.shape
+        D = self.d_model
+        with torch.no_grad():
+            emb = ops.cw_embed(tokens, self._tables(), torch.float32).reshape(N * L, -1)
+            x = torch.empty((N * L, D), dtype=torch.float32, device=tokens.device)
+            pe = self.pos_emb.pe.reshape(-1, D)[0].float().expand(min(rows, N * L), D).contiguous()   # pe[0] rows
+            w, b = ops._f32(self.in_linear.weight), ops._f32(self.in_linear.bias)
+            for a in range(0, N * L, rows):
+                z = min(N * L, a + rows)
+                ops.decode_gemm(w, b, emb[a:z], res=pe[:z - a], out=x[a:z])
+            heads = self._heads()
+            hw = torch.cat([ops._f32(m.weight) for m in heads], 0)
+            hb = torch.cat([ops._f32(m.bias) for m in heads], 0)
+            return self.transformer_encoder.prefill(x.view(N, L, D), memory, lengths, kernel="gemm", last=last,
+                                                    heads=(hw, hb), rows=rows)
 
     def _losses(self, h, target, loss_mask):
         logits = self.fused_logits(h)

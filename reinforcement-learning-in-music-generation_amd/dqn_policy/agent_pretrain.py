@@ -121,12 +121,22 @@ bar_production = 50                               # testing-no-type-cp.py:35
 
 
 def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sampling=False, batch_size=None,
-             slots=None):
+             slots=None, prompts=None, prompt_bars=None):
     """agent_pretrain.py:636-706 / testing-no-type-cp.py:182-260: build the recurrent-form net, load
     ./ckpt/_params.pt when present, sample `num_songs` songs, write get_<i>.mid + runtime_stats.json.
     batch_size: make the songs that many at a time in lock-step (generation.generate_batch).
-    slots: make the songs by continuous batching on that many decode slots (generation.generate_stream)."""
+    slots: make the songs by continuous batching on that many decode slots (generation.generate_stream).
+    prompts: one (P_i, 6) array per song to continue.  prompt_bars: instead, song i continues the first prompt_bars
+    bars of the loaded dataset song i (generation.dataset_prompts)."""
     from rlmg_amd import generation, midi
+    if prompts is not None and prompt_bars is not None:
+        raise ValueError("pass prompts or prompt_bars, not both")
+    n_songs = num_songs if n_songs is None else n_songs
+    if prompt_bars is not None:
+        dictionary, data = cwdata.load_dqn(path_train_data, path_dictionary)
+        x = np.concatenate((data["x"][:, :, :3], data["x"][:, :, 4:]), axis=2)       # the training inputs' 6 attributes
+        word2event = {k: v for k, v in dictionary[1].items() if k != "type"}
+        prompts = generation.dataset_prompts(x, word2event, prompt_bars, n_songs, mask=data["mask"])
     dictionary, _ = cwdata.load_dqn(path_train_data, path_dictionary, n_seq=1, T=64)
     event2word, word2event = ({k: v for k, v in d.items() if k != "type"} for d in dictionary)
     n_class = [len(event2word[k]) for k in event2word.keys()]
@@ -140,10 +150,11 @@ def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sam
         net.load_state_dict(sd.get("model_state_dict", sd))
     else:
         log("[*] %s not found: sampling from freshly initialised weights" % path_saved_ckpt)
-    return generation.generate(net, word2event, n_songs=num_songs if n_songs is None else n_songs,
+    return generation.generate(net, word2event, n_songs=n_songs,
                                bar_cond=bar_production if bar_cond is None else bar_cond, path_gendir=path_gendir,
                                write_midi=midi.write_midi, max_tokens=max_tokens, log=log,
-                               device_sampling=device_sampling, batch_size=batch_size, slots=slots)
+                               device_sampling=device_sampling, batch_size=batch_size, slots=slots,
+                               prompts=prompts)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,76 @@ from . import ops
 from .sampling import sample_cw
 
 INIT_CW = np.array([[0, 0, 1, 0, 0, 0]])          # "Bar" token, testing-no-type-cp.py:135-137
+PREFILL_ROWS = 32768        # default token-row budget of one gemm prefill block (prompts x the block's longest prompt)
+
+
+def cut_prompt(song, word2event, prompt_bars):
+    """The first `prompt_bars` bars of a CW token song (T, 6): the rows before the Bar token that opens bar
+    prompt_bars + 1, by the generation bar rule (the count starts at 1 and counts the Bar tokens after the first row).
+    A song with fewer bars is returned whole.  -> (P, 6) int64."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1, len(word2event))
+    if int(prompt_bars) < 1:
+        raise ValueError("prompt_bars must be >= 1, got %r" % (prompt_bars,))
+    names = word2event["bar-beat"]
+    cnt = 1 + np.cumsum([names[int(r[2])] == "Bar" for r in song[1:]])
+    past = np.nonzero(cnt > int(prompt_bars))[0]
+    return song if len(past) == 0 else song[:past[0] + 1]
+
+
+def dataset_prompts(x, word2event, prompt_bars, n_songs, mask=None):
+    """One prompt per song from dataset songs x (n_seq, T, 6) (mask (n_seq, T): rows > 0 are the song's own, the
+    rest padding): song i continues the first `prompt_bars` bars of dataset song i % n_seq (cut_prompt)."""
+    x = np.asarray(x)
+    if len(x) == 0:
+        raise ValueError("no dataset songs to take prompts from")
+    out = []
+    for i in range(int(n_songs)):
+        s = x[i % len(x)]
+        if mask is not None:
+            s = s[:int((np.asarray(mask[i % len(x)]) > 0).sum())]
+        p = cut_prompt(s, word2event, prompt_bars)
+        if len(p) == 0:
+            raise ValueError("dataset song %d is empty" % (i % len(x)))
+        out.append(p)
+    return out
+
+
+def stream_bank_plan(prompt_lengths, slots, prefill_rows=None, bank=None, entry_bytes=0, free_bytes=None):
+    """Block size B and bank entries of generate_stream(prompts=...) -> (B, bank).
+    B = prefill_rows // the longest prompt (at least 1, at most n_songs): every block's prefill stays within the row
+    budget.  bank (None): the smallest multiple of B that holds max(2 B, 2 slots) entries -- slots never wait for a
+    prefill while a second batch of songs is queued -- at most the songs rounded up to whole blocks, and at most a
+    quarter of free_bytes at entry_bytes per entry (never below two blocks).  A given bank must be a multiple of B (B is
+    lowered to bank when bank < B)."""
+    lens = [int(n) for n in prompt_lengths]
+    n = len(lens)
+    if n < 1 or min(lens) < 1:
+        raise ValueError("stream_bank_plan needs at least one prompt, each of at least one row")
+    rows = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
+    if rows < 1:
+        raise ValueError("prefill_rows must be >= 1, got %d" % rows)
+    B = max(1, min(n, rows // max(lens)))
+    blocks = -(-n // B)
+    if bank is not None:
+        bank = int(bank)
+        if bank < 1:
+            raise ValueError("bank must be >= 1, got %d" % bank)
+        B = min(B, bank)
+        if bank % B:
+            raise ValueError("bank (%d) must be a multiple of the prefill block (%d songs)" % (bank, B))
+        return B, bank
+    nb = max(2, -(-2 * int(slots) // B))
+    if free_bytes is not None and entry_bytes > 0:
+        nb = min(nb, max(2, int(free_bytes) // 4 // (int(entry_bytes) * B)))
+    return B, min(nb, blocks) * B
+
+
+def bank_may_prefill(j, B, bank, assigned):
+    """Reuse rule of the bank: block j (songs [j B, (j + 1) B), entries [(j % nb) B, ...) with nb = bank // B) may be
+    written once the block that held those entries before it, j - nb, has all its songs assigned to slots (`assigned`:
+    the device's assigned counter, as copied back one chunk behind)."""
+    nb = bank // B
+    return j < nb or int(assigned) >= (j - nb + 1) * B
 
 
 class _FusedPlan:
@@ -251,8 +321,10 @@ class DecodeSession:
         res = self._host_logits.numpy()
         return res[0] if self.n_songs == 1 else res
 
-    def _prefill(self, tokens, lengths=None):
+    def _prefill(self, tokens, lengths=None, kernel="blas", prefill_rows=None):
         """prefill() without the host copy: -> (n_songs, sum n_token) f32 device logits."""
+        if kernel not in ("blas", "gemm"):
+            raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
         if self.model.training:
             raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
         if self.model.compute_dtype != torch.float32:
@@ -277,11 +349,23 @@ class DecodeSession:
                                  % (i, t, toks[i, t, a], a, self.n_token[a]))
         heads = self.model._heads()
         with torch.no_grad():
-            h = self.model.prefill_hidden(torch.as_tensor(toks).to(self.dev), self.memory,
-                                          None if lengths is None else lens)
-            # h already carries the final norm: the stacked heads are a plain GEMV (no LayerNorm prologue)
-            logits = ops.decode_gemv(torch.cat([m.weight.float() for m in heads], 0),
-                                     torch.cat([m.bias.float() for m in heads], 0), h)
+            if kernel == "gemm":
+                # batch invariant: blocks of whole songs under the row budget give the bits of one call
+                per = max(1, (PREFILL_ROWS if prefill_rows is None else int(prefill_rows)) // P)
+                h = torch.empty((self.n_songs, self.model.d_model), dtype=torch.float32, device=self.dev)
+                logits = torch.empty((self.n_songs, self.width), dtype=torch.float32, device=self.dev)
+                for a in range(0, self.n_songs, per):
+                    z = min(self.n_songs, a + per)
+                    Pb = int(lens[a:z].max())
+                    h[a:z], logits[a:z] = self.model.prefill_hidden(
+                        torch.as_tensor(toks[a:z, :Pb]).to(self.dev), [[S[a:z], Z[a:z]] for S, Z in self.memory],
+                        lens[a:z], kernel="gemm", logits=True)
+            else:
+                h = self.model.prefill_hidden(torch.as_tensor(toks).to(self.dev), self.memory,
+                                              None if lengths is None else lens)
+                # h already carries the final norm: the stacked heads are a plain GEMV (no LayerNorm prologue)
+                logits = ops.decode_gemv(torch.cat([m.weight.float() for m in heads], 0),
+                                         torch.cat([m.bias.float() for m in heads], 0), h)
         if self.fused:
             hid = self._fused_plan().hidden
             hid.copy_(h)
@@ -293,7 +377,7 @@ class DecodeSession:
         self.n_steps += int(lens.max())
         return logits
 
-    def prefill(self, tokens, lengths=None):
+    def prefill(self, tokens, lengths=None, kernel="blas", prefill_rows=None):
         """Feed a whole prompt in one parallel pass per layer: leaves the state exactly as feeding the prompt's
         tokens through step() one by one would (within f32 rounding), starting from whatever state the session holds
         (reset(), earlier steps or an earlier prefill), and returns what the last of those step() calls would: the
@@ -301,8 +385,13 @@ class DecodeSession:
         ragged prompts pass `lengths` (n_songs values in [1, P]; rows past a song's length are ignored).  The state is
         updated in the session's own buffers, so a captured step graph stays valid.  f32 sessions in eval() mode.
         n_steps advances by the longest prompt: with ragged prompts song i has then been fed
-        n_steps - (max(lengths) - lengths[i]) tokens in total."""
-        out = self._prefill(tokens, lengths)
+        n_steps - (max(lengths) - lengths[i]) tokens in total.
+
+        kernel="blas" (default): the projections on hipBLASLt.  kernel="gemm": the batch-invariant prefill
+        (CWTrunk.prefill_hidden(kernel="gemm"), every projection a cwlt_decode_gemm): song i's state, hidden row and
+        logits are bitwise the same whatever the other prompts, their lengths and order; songs go through in blocks of
+        at most prefill_rows // P (default PREFILL_ROWS) prompts, which changes no bits."""
+        out = self._prefill(tokens, lengths, kernel, prefill_rows)
         self._host_logits.copy_(out, non_blocking=True)
         torch.cuda.current_stream(self.dev).synchronize()
         res = self._host_logits.numpy()
@@ -494,6 +583,152 @@ class _StreamLoop:
         return np.concatenate(parts)
 
 
+class _BankStreamLoop(_StreamLoop):
+    """_StreamLoop with a prompt of its own for every song.  Song k starts from entry k % bank of a device bank laid out
+    like a `bank`-slot DecodeSession._state (per layer the S rows of all entries, then their Z rows), with its next-token
+    logits, bar count and cap beside it.  Blocks of B consecutive songs are prefilled (CWTrunk._prefill_gemm, batch
+    invariant) straight into their entries between chunks, on the stream's own stream, each followed by a device write
+    of ctl[3] = songs ready.  Per token: the GEMM decode step, cwlt_stream_refill_bank, the keyed sampler,
+    cwlt_stream_advance_bank (a slot takes a song only below ctl[3], otherwise it waits)."""
+
+    def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
+                 top_p=None, graph=None, prefill_rows=None):
+        self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
+        self.S, self.A = sess.n_songs, len(sess.n_token)
+        dev = sess.dev
+        self.B, self.bank = int(B), int(bank)
+        self.nb = self.bank // self.B
+        self.n_blocks = -(-self.n_songs // self.B)
+        self.n_layer = len(sess.memory)
+        H, d = sess.memory[0][1].shape[1:]
+        self.s_floats, self.z_floats = H * d * d, H * d
+        self.seed, self.temperature, self.top_p = seed, temperature, top_p
+        self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
+        self.bar_cond = int(bar_cond)
+        per = self.bank * (self.s_floats + self.z_floats)
+        self.bank_state = torch.zeros(per * self.n_layer, dtype=torch.float32, device=dev)
+        self.bank_mem = [[self.bank_state[i * per:i * per + self.bank * self.s_floats].view(self.bank, H, d, d),
+                          self.bank_state[i * per + self.bank * self.s_floats:(i + 1) * per].view(self.bank, H, d)]
+                         for i in range(self.n_layer)]
+        self.bank_logits = torch.zeros((self.bank, sess.width), dtype=torch.float32, device=dev)
+        self.bank_bar0 = torch.zeros(self.bank, dtype=torch.int64, device=dev)
+        self.bank_cap = torch.ones(self.bank, dtype=torch.int64, device=dev)
+        # every prompt on the device once, padded to the longest: no host copy (and no sync) inside the stream
+        lens = np.array([len(h) for h in heads], dtype=np.int64)
+        self.lens = lens
+        toks = np.zeros((self.n_songs, int(lens.max()), self.A), dtype=np.int64)
+        for i, h in enumerate(heads):
+            toks[i, :len(h)] = h
+        self.toks = torch.as_tensor(toks).to(dev)
+        self.dev_len = torch.as_tensor(lens.astype(np.int32)).to(dev)
+        self.bar0_all = torch.as_tensor(np.asarray(bar0s, dtype=np.int64)).to(dev)
+        self.cap_all = torch.as_tensor(np.asarray(caps, dtype=np.int64)).to(dev)
+        self.prefill_rows = prefill_rows
+        self.song = torch.full((self.S,), -1, dtype=torch.int64, device=dev)
+        self.pos = torch.zeros(self.S, dtype=torch.int64, device=dev)
+        self.bar = torch.zeros(self.S, dtype=torch.int64, device=dev)
+        self.cap = torch.ones(self.S, dtype=torch.int64, device=dev)
+        self.fresh = torch.zeros(self.S, dtype=torch.int64, device=dev)
+        self.ctl = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
+        self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._host_ctl = [torch.zeros(4, dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._events = [torch.cuda.Event(), torch.cuda.Event()]
+        self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
+        self._graph, self.enqueued = None, 0
+        self.wait_s = 0.0
+        self.next_block = 0                                        # blocks prefilled so far
+        self.prefill_events = []                                   # (start, stop) CUDA events of every block
+        self.gated_chunks = 0                                      # chunks that ended with every ready song assigned
+
+    def _prefill_block(self):
+        """Enqueue block next_block's prefill into its bank entries, then ctl[3] = its last song + 1."""
+        j = self.next_block
+        a, z = j * self.B, min(self.n_songs, (j + 1) * self.B)
+        e0 = (j % self.nb) * self.B
+        e1 = e0 + (z - a)
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        ev[0].record()
+        mem = [[S[e0:e1], Z[e0:e1]] for S, Z in self.bank_mem]
+        with torch.no_grad():
+            for S, Z in mem:
+                S.zero_()
+                Z.zero_()
+            P = int(self.lens[a:z].max())
+            dl = self.dev_len[a:z]
+            _, logits = self.sess.model._prefill_gemm(self.toks[a:z, :P].contiguous(), mem, dl, dl.to(torch.int64) - 1)
+            self.bank_logits[e0:e1].copy_(logits)
+            self.bank_bar0[e0:e1].copy_(self.bar0_all[a:z])
+            self.bank_cap[e0:e1].copy_(self.cap_all[a:z])
+            self.ctl[3:4].fill_(z)                                 # ordered after the block's writes: same stream
+        ev[1].record()
+        self.prefill_events.append(ev)
+        self.next_block += 1
+
+    def _prefill_allowed(self, assigned):
+        """Prefill every block the reuse rule allows (bank_may_prefill) given the copied assigned counter."""
+        while self.next_block < self.n_blocks and bank_may_prefill(self.next_block, self.B, self.bank, assigned):
+            self._prefill_block()
+
+    def start(self):
+        """Before the first token: prefill the first nb blocks and hand the ready songs to slots 0, 1, ... in order
+        (slots past them wait while songs remain, or idle)."""
+        self._prefill_allowed(0)
+        ready = min(self.n_songs, self.next_block * self.B)
+        first = min(self.S, ready)
+        slot = torch.arange(self.S, dtype=torch.int64, device=self.sess.dev)
+        wait = torch.where(slot < self.n_songs, torch.full_like(slot, -2), torch.full_like(slot, -1))
+        self.song.copy_(torch.where(slot < first, slot, wait))
+        idx = slot[:first]
+        self.fresh.copy_((slot < first).to(torch.int64))
+        self.bar[:first] = self.bar0_all[idx]
+        self.cap[:first] = self.cap_all[idx]
+        self.ctl.copy_(torch.tensor([0, first, 0, ready], dtype=torch.int64))
+
+    def _one(self):
+        s = self.sess
+        tok = s.tok.view(self.S, self.A)
+        logits = s._device_step()
+        ops.stream_refill_bank(s._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
+                               self.bank_logits, self.fresh, self.song)
+        ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
+                                     temperature=self.temperature, top_p=self.top_p)
+        ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
+                                self.song, self.pos, self.bar, self.cap, self.fresh, self.ctl, self.ring)
+
+    def run(self, max_cap):
+        """Run until the device's finished counter reaches n_songs -> rows (n, A + 2) of every song, time-ordered.
+        Between chunks the host prefills every block the reuse rule allows by the counters of the chunk it just read."""
+        parts = []
+        self.start()
+        limit = -(-self.n_songs // self.S) * (int(max_cap) + 1) + 2 * self.chunk
+        h = self._enqueue_chunk()
+        while True:
+            nxt = self._enqueue_chunk()
+            t = time.perf_counter()
+            self._events[h].synchronize()
+            self.wait_s += time.perf_counter() - t
+            rows = self._host[h].numpy().reshape(-1, self.A + 2)
+            parts.append(rows[rows[:, 0] >= 0])
+            ctl = self._host_ctl[h].numpy().copy()
+            if ctl[2] >= self.n_songs:
+                break
+            if ctl[1] < self.n_songs and ctl[1] >= ctl[3]:
+                self.gated_chunks += 1                             # slots may have waited for a prefill: more steps
+            if self.enqueued > limit + self.gated_chunks * self.chunk:
+                raise RuntimeError("stream did not finish %d songs in %d steps" % (self.n_songs, self.enqueued))
+            self._prefill_allowed(int(ctl[1]))
+            h = nxt
+        t = time.perf_counter()
+        self._events[nxt].synchronize()
+        self.wait_s += time.perf_counter() - t
+        return np.concatenate(parts)
+
+    def prefill_seconds(self):
+        """GPU time of the block prefills (after run())."""
+        return sum(a.elapsed_time(b) for a, b in self.prefill_events) / 1e3
+
+
 def _stream_snapshot(model, prompt, A):
     """The state and logits every song of a stream starts from, on a one-slot GEMM session: one step of INIT_CW from
     zero state (bitwise any row of the many-slot step, by batch invariance), or a one-row prefill of the prompt."""
@@ -508,10 +743,59 @@ def _stream_snapshot(model, prompt, A):
     return snap._state.clone(), logits.reshape(-1).clone()
 
 
+def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
+    """generate_batch's refusals for a list of per-song prompts -> (heads, bar0s, caps)."""
+    A = len(n_token)
+    if len(prompts) != n_songs:
+        raise ValueError("prompts: %d arrays for %d songs" % (len(prompts), n_songs))
+    names = word2event["bar-beat"]
+    heads, bar0s, caps = [], [], []
+    for i, p in enumerate(prompts):
+        p = np.asarray(p, dtype=np.int64).reshape(-1, A)
+        if len(p) == 0:
+            raise ValueError("empty prompt (song %d)" % i)
+        bad = (p < 0) | (p >= np.asarray(n_token))
+        if bad.any():
+            t, a = np.argwhere(bad)[0]
+            raise ValueError("prompt %d, token %d: id %d out of range for attribute %d (%d classes)"
+                             % (i, t, p[t, a], a, n_token[a]))
+        cnt = 1 + sum(names[int(r[2])] == "Bar" for r in p[1:])
+        if cnt >= bar_cond:
+            raise ValueError("the prompt of song %d already reaches bar %d of bar_cond=%d" % (i, cnt, bar_cond))
+        if max_tokens is not None and max_tokens <= len(p):
+            raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(p)))
+        heads.append(p)
+        bar0s.append(cnt)
+        caps.append(16384 if max_tokens is None else max_tokens - len(p))
+    return heads, bar0s, caps
+
+
+def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_tokens, prompts, sampler, chunk, bank,
+                             prefill_rows, log):
+    start = time.perf_counter()
+    n_token = list(model.n_token)
+    heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
+    sess = DecodeSession(model, n_songs=slots, kernel="gemm")
+    sess.reset()
+    seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
+    per_entry = 4 * (sess._state.numel() // slots + sess.width + 2)
+    B, bank = stream_bank_plan([len(h) for h in heads], slots, prefill_rows, bank, per_entry,
+                               torch.cuda.mem_get_info(sess.dev)[0])
+    names = word2event["bar-beat"]
+    bar_mask = [int(names[i] == "Bar") for i in range(sess.n_token[2])]
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
+                           temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows)
+    rows = loop.run(max(caps))
+    return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
+                                      "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
+
+
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                     chunk=128, log=None):
+                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
-    wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph."""
+    wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
+    prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if model.training:
@@ -527,31 +811,42 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if slots < 1:
         raise ValueError("slots must be >= 1, got %d" % slots)
     if isinstance(prompt, (list, tuple)):
-        raise ValueError("generate_stream takes one shared (P, 6) prompt: ragged per-song prompts are not supported "
-                         "in a stream (use generate_batch)")
+        raise ValueError("generate_stream takes one shared (P, 6) prompt: ragged per-song prompts go in prompts=[...]")
+    if prompt is not None and prompts is not None:
+        raise ValueError("pass one shared prompt or per-song prompts, not both")
     classes = list(word2event.keys())
     A = len(classes)
-    bar_names = word2event["bar-beat"]
-    is_bar = lambda row: bar_names[int(row[2])] == "Bar"
-    head = INIT_CW[0].astype(np.int64)[None] if prompt is None else np.asarray(prompt, dtype=np.int64).reshape(-1, A)
-    if len(head) == 0:
-        raise ValueError("empty prompt")
-    bar0 = 1 + sum(is_bar(r) for r in head[1:])
-    if bar0 >= bar_cond:
-        raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (bar0, bar_cond))
-    if max_tokens is not None and max_tokens <= len(head):
-        raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(head)))
-    cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
-    start = time.perf_counter()
-    sess = DecodeSession(model, n_songs=slots, kernel="gemm")
-    sess.reset()
-    seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
-    snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else head, A)
-    bar_mask = [int(bar_names[i] == "Bar") for i in range(sess.n_token[2])]      # every class named "Bar", not one id
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-    loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                       temperature=temperature, top_p=top_p, graph=sess.use_graph)
-    rows = loop.run()
+    extra = {}
+    if prompts is not None:
+        heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
+                                                                   max_tokens, prompts, sampler, chunk, bank,
+                                                                   prefill_rows, log)
+    else:
+        if bank is not None or prefill_rows is not None:
+            raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
+        bar_names = word2event["bar-beat"]
+        is_bar = lambda row: bar_names[int(row[2])] == "Bar"
+        head = INIT_CW[0].astype(np.int64)[None] if prompt is None else \
+            np.asarray(prompt, dtype=np.int64).reshape(-1, A)
+        if len(head) == 0:
+            raise ValueError("empty prompt")
+        bar0 = 1 + sum(is_bar(r) for r in head[1:])
+        if bar0 >= bar_cond:
+            raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (bar0, bar_cond))
+        if max_tokens is not None and max_tokens <= len(head):
+            raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(head)))
+        cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
+        start = time.perf_counter()
+        sess = DecodeSession(model, n_songs=slots, kernel="gemm")
+        sess.reset()
+        seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
+        snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else head, A)
+        bar_mask = [int(bar_names[i] == "Bar") for i in range(sess.n_token[2])]   # every class named "Bar", not one id
+        temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+        loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
+                           temperature=temperature, top_p=top_p, graph=sess.use_graph)
+        rows = loop.run()
+        heads = [head] * n_songs
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
     order = np.argsort(rows[:, 0], kind="stable")
     rows = rows[order]
@@ -561,18 +856,19 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
             not rows[ends - 1, -1].all():
         raise RuntimeError("stream output is inconsistent: %d rows, %d end bits for %d songs"
                            % (len(rows), int(rows[:, -1].sum()), n_songs))
-    songs = [np.concatenate([head, d]) for d in np.split(rows[:, 1:1 + A], ends[:-1])]
+    songs = [np.concatenate([h, d]) for h, d in zip(heads, np.split(rows[:, 1:1 + A], ends[:-1]))]
     seconds = time.perf_counter() - start
     stats = {"steps": loop.enqueued, "tokens": int(sum(len(x) for x in songs)), "drawn": int(len(rows)),
              "slot_steps": loop.enqueued * slots, "seconds": seconds, "wait_seconds": loop.wait_s,
              "graph": loop._graph is not None}
+    stats.update(extra)
     if log is not None:
         log("stream of %d songs on %d slots: %d tokens, %d steps" % (n_songs, slots, stats["tokens"], loop.enqueued))
     return songs, stats
 
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                    chunk=128, log=None):
+                    chunk=128, log=None, prompts=None, bank=None, prefill_rows=None):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -583,9 +879,19 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     song slot).  The bar rule is generate_batch's: the count starts at 1 and counts the Bar tokens of the prompt's rows
     after the first, a song ends WITH the token that opens bar `bar_cond`, or at `max_tokens` rows, prompt included
     (16384 drawn tokens without a cap).  prompt: None (INIT_CW) or one (P, 6) array every song continues.
-    sampler: "dqn" or "categorical", as in generate_batch.  The host reads the songs every `chunk` tokens."""
+    sampler: "dqn" or "categorical", as in generate_batch.  The host reads the songs every `chunk` tokens.
+
+    prompts: a list of n_songs (P_i, 6) arrays, song k continues prompts[k] (_BankStreamLoop).  Song k is then bitwise
+    song k of generate_batch(..., prompts=prompts, prefill="gemm"): each prompt is prefilled by the batch-invariant
+    prefill into a device bank, in blocks of B consecutive songs, between chunks; a slot takes song k once its entry is
+    written.  The bar count of song k starts from prompts[k] and its cap is max_tokens - len(prompts[k]).
+    Defaults (stream_bank_plan): B = prefill_rows // the longest prompt, prefill_rows = PREFILL_ROWS (32768 token rows,
+    about 0.8 GB of prefill activations at d_model 512); bank = the smallest multiple of B with max(2 B, 2 slots)
+    entries, capped by the songs and a quarter of free device memory (one entry at d_model 512 / 12 layers / 8 heads
+    is 12 x 8 x 64 x 65 x 4 B = 1.6 MB).  `bank` (a multiple of B) overrides the bank size."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
-                            prompt=prompt, sampler=sampler, chunk=chunk, log=log)[0]
+                            prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
+                            prefill_rows=prefill_rows)[0]
 
 
 def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
@@ -753,7 +1059,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
-                   log=None):
+                   log=None, prefill="blas"):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -766,9 +1072,13 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     and counts the Bar tokens of the prompt's rows after the first, the song ends WITH the token that opens bar
     `bar_cond`), or at `max_tokens` rows, prompt included.  Finished songs keep stepping until the batch ends; their
     extra rows are discarded.  The draws are keyed by (torch seed, step, song slot): song i of a batch from scratch
-    is the same whatever the batch size."""
+    is the same whatever the batch size.  prefill: the prompt prefill's kernel, DecodeSession.prefill's "blas"
+    (default) or "gemm" (batch invariant: song i's start depends on prompts[i] alone -- generate_stream(prompts=...)
+    gives the same songs)."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
+    if prefill not in ("blas", "gemm"):
+        raise ValueError("prefill must be 'blas' or 'gemm', got %r" % (prefill,))
     if model.training:
         raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
     if model.compute_dtype != torch.float32:
@@ -814,7 +1124,7 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         for i, p in enumerate(heads):
             toks[i, :len(p)] = p
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
-        loop.start(sess._prefill(toks, lengths))
+        loop.start(sess._prefill(toks, lengths, kernel=prefill))
     drawn = [[] for _ in range(n_songs)]
     live = set(range(n_songs))
     done = 0
@@ -841,7 +1151,7 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None, slots=None):
+             batch_size=None, slots=None, prompts=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -849,9 +1159,17 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     batch_size: make the songs `batch_size` at a time with generate_batch (device sampling, one GEMM-step session per
     group); a song's time is then its group's wall time divided by the group's size.  None: one song at a time.
     slots: make the songs by continuous batching on that many decode slots (generate_stream); a song's time is then
-    the stream's wall time divided by n_songs.  Not together with batch_size."""
+    the stream's wall time divided by n_songs.  Not together with batch_size.
+    prompts: a list of n_songs (P_i, 6) arrays, song i continues prompts[i] (not together with prompt): on the stream
+    with slots, each batch_size group with its own slice of the list, or one song at a time."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if prompts is not None:
+        if prompt is not None:
+            raise ValueError("pass one shared prompt or per-song prompts, not both")
+        if len(prompts) != n_songs:
+            raise ValueError("prompts: %d arrays for %d songs" % (len(prompts), n_songs))
+    song_prompt = (lambda i: prompt) if prompts is None else (lambda i: prompts[i])
     os.makedirs(path_gendir, exist_ok=True)
     song_time_list, words_len_list = [], []
 
@@ -864,7 +1182,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     if slots is not None:
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
-                                prompt=prompt)
+                                prompt=prompt, prompts=None if prompts is None else list(prompts))
         wall = time.time() - start
         for sidx, res in enumerate(songs):
             save(sidx, res)
@@ -877,7 +1195,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         for first in range(0, n_songs, int(batch_size)):
             group = min(int(batch_size), n_songs - first)
             start = time.time()
-            songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens, prompts=prompt)
+            songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens,
+                                   prompts=prompt if prompts is None else list(prompts[first:first + group]))
             wall = time.time() - start
             for j, res in enumerate(songs):
                 save(first + j, res)
@@ -888,12 +1207,12 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         sess = DecodeSession(model)
         for sidx in range(n_songs):
             start = time.time()
-            if prompt is None:
+            if song_prompt(sidx) is None:
                 res = inference_from_scratch(model, word2event, bar_cond, max_tokens=max_tokens, session=sess,
                                              device_sampling=device_sampling)
             else:
-                res = inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=max_tokens, session=sess,
-                                            device_sampling=device_sampling)
+                res = inference_from_prompt(model, word2event, song_prompt(sidx), bar_cond, max_tokens=max_tokens,
+                                            session=sess, device_sampling=device_sampling)
             save(sidx, res)
             song_time_list.append(time.time() - start)
             words_len_list.append(len(res))

@@ -1504,10 +1504,12 @@ def decode_gemv(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
     return (out, xn) if want_normed else out
 
 
-def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, want_normed=False):
+def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, want_normed=False, out=None,
+                normed=None):
     """decode_gemv's product for many rows at once (csrc/decode_gemm.hip: f32 MFMA, each weight read once per 64 rows,
     bitwise batch invariant).  x (n, K) f32 with a row stride that is a multiple of 4, w (n_out, K) f32, K % 16 == 0
-    -> (n, n_out) f32 [, the normalised x]."""
+    -> (n, n_out) f32 [, the normalised x].  out / normed: row-strided (n, n_out) / (n, K) f32 views to write the
+    result / the normalised x into (normed implies want_normed; its row stride a multiple of 4)."""
     if x.dtype != torch.float32 or w.dtype != torch.float32:
         raise TypeError("decode_gemm computes in f32")
     n, K = x.shape
@@ -1515,8 +1517,18 @@ def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
     if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
         x = x.contiguous()
     w = w.contiguous()
-    out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
-    xn = torch.empty((n, K), dtype=torch.float32, device=x.device) if (want_normed and ln is not None) else None
+    if out is None:
+        out = torch.empty((n, n_out), dtype=torch.float32, device=x.device)
+    elif out.shape != (n, n_out) or out.dtype != torch.float32 or out.stride(1) != 1 or out.device != x.device:
+        raise ValueError("decode_gemm: out must be an f32 (%d, %d) view with unit column stride" % (n, n_out))
+    if normed is not None:
+        if ln is None or normed.shape != (n, K) or normed.dtype != torch.float32 or normed.stride(1) != 1 or \
+                normed.stride(0) % 4 or normed.device != x.device:
+            raise ValueError("decode_gemm: normed needs a LayerNorm prologue and an f32 (%d, %d) view, row stride % 4"
+                             % (n, K))
+        want_normed = True
+    xn = normed if normed is not None else \
+        (torch.empty((n, K), dtype=torch.float32, device=x.device) if (want_normed and ln is not None) else None)
     if res is not None and res.stride(1) != 1:
         res = res.contiguous()
     lib = _lib.load()
@@ -1527,7 +1539,8 @@ def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
     p = lambda pair, i: _lib.opt(None if pair is None else pair[i].contiguous())
     _call("cwlt_decode_gemm", _lib.dev(w, "w"), _lib.opt(bias), _lib.dev(x, "x"), p(ln, 0), p(ln, 1), p(ln2, 0),
           p(ln2, 1), float(eps), _lib.opt(res), _lib.dev(out), _lib.opt(xn), n_out, K, 1 if act == "gelu" else 0, n,
-          x.stride(0), 0 if res is None else res.stride(0), n_out, K, _lib.dev(scratch), _lib.stream_ptr())
+          x.stride(0), 0 if res is None else res.stride(0), out.stride(0), K if xn is None else xn.stride(0),
+          _lib.dev(scratch), _lib.stream_ptr())
     return (out, xn) if want_normed else out
 
 
@@ -1609,3 +1622,45 @@ def stream_advance(tokens, bar_attr, bar_mask, bar_cond, bar0, cap, n_songs, son
     _call("cwlt_stream_advance", _lib.dev(tokens, "tokens"), A, slots, int(bar_attr), _lib.dev(bar_mask, "bar_mask"),
           bar_mask.numel(), int(bar_cond), int(bar0), int(cap), int(n_songs), _lib.dev(song), _lib.dev(pos),
           _lib.dev(bar), _lib.dev(fresh), _lib.dev(ctl), _lib.dev(ring), ring.shape[0], _lib.stream_ptr())
+
+
+def stream_refill_bank(state, bank_state, n_layer, s_floats, z_floats, logits, bank_logits, fresh, song):
+    """Copy each fresh slot's start from the bank (cwlt_stream_refill_bank): slot s with fresh[s] and song[s] >= 0 gets
+    entry song[s] % bank.  state: flat f32 n_layer x [S (slots, s_floats), Z (slots, z_floats)]; bank_state the same
+    for `bank` entries; logits (slots, >= n) and bank_logits (bank, n) f32; fresh, song (slots,) int64."""
+    slots, per = fresh.numel(), s_floats + z_floats
+    bank = bank_logits.shape[0]
+    if state.dtype != torch.float32 or bank_state.dtype != torch.float32 or bank_logits.dtype != torch.float32:
+        raise TypeError("stream_refill_bank takes f32 state / logits")
+    if fresh.dtype != torch.int64 or song.dtype != torch.int64 or song.numel() != slots:
+        raise TypeError("stream_refill_bank takes (slots,) int64 fresh flags and songs")
+    if state.numel() != n_layer * slots * per or bank_state.numel() != n_layer * bank * per:
+        raise ValueError("stream_refill_bank: state holds %d floats, bank %d, for %d layers x %d slots / %d entries x %d"
+                         % (state.numel(), bank_state.numel(), n_layer, slots, bank, per))
+    if logits.shape[0] != slots or logits.stride(-1) != 1 or bank_logits.stride(-1) != 1 or \
+            bank_logits.shape[1] > logits.shape[1]:
+        raise ValueError("stream_refill_bank: logits must be (slots, >= n_logits), bank_logits (bank, n_logits), unit "
+                         "column strides")
+    _call("cwlt_stream_refill_bank", _lib.dev(state, "state"), _lib.dev(bank_state, "bank_state"), bank, int(n_layer),
+          int(s_floats), int(z_floats), _lib.dev(logits, "logits"), _lib.dev(bank_logits, "bank_logits"),
+          bank_logits.shape[1], logits.stride(0), bank_logits.stride(0), _lib.dev(fresh, "fresh"),
+          _lib.dev(song, "song"), slots, _lib.stream_ptr())
+
+
+def stream_advance_bank(tokens, bar_attr, bar_mask, bar_cond, bank_bar0, bank_cap, n_songs, song, pos, bar, cap, fresh,
+                        ctl, ring):
+    """stream_advance with per-song bar0 / cap from the bank and the ready gate (cwlt_stream_advance_bank): bank_bar0,
+    bank_cap (bank,) int64; cap (slots,) int64 the slots' own caps; ctl (4,) int64 {tokens, assigned, finished, ready};
+    a waiting slot holds song -2."""
+    slots, A = song.numel(), tokens.shape[-1]
+    for t in (song, pos, bar, cap, fresh, ctl, ring, tokens, bank_bar0, bank_cap):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise TypeError("stream_advance_bank takes contiguous int64 slot and bank arrays")
+    if bar_mask.dtype != torch.int32 or tokens.numel() != slots * A or ring.shape[1:] != (slots, A + 2) or \
+            ctl.numel() != 4 or not all(t.numel() == slots for t in (pos, bar, cap, fresh)) or \
+            bank_cap.numel() != bank_bar0.numel():
+        raise ValueError("stream_advance_bank: inconsistent slot or bank array shapes")
+    _call("cwlt_stream_advance_bank", _lib.dev(tokens, "tokens"), A, slots, int(bar_attr),
+          _lib.dev(bar_mask, "bar_mask"), bar_mask.numel(), int(bar_cond), _lib.dev(bank_bar0), _lib.dev(bank_cap),
+          bank_bar0.numel(), int(n_songs), _lib.dev(song), _lib.dev(pos), _lib.dev(bar), _lib.dev(cap),
+          _lib.dev(fresh), _lib.dev(ctl), _lib.dev(ring), ring.shape[0], _lib.stream_ptr())

@@ -105,11 +105,28 @@ class RecurrentTransformerEncoder(nn.Module):
                 x = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return x, state
 
-    def prefill(self, x, state, lengths=None):
+    def prefill(self, x, state, lengths=None, kernel="blas", last=None, heads=None, rows=None):
         """x (N, L, D) prompt rows (embedded, positional row added) -> (N, L, D) final-norm outputs; `state` (a list of
         [S, Zs] per layer, as forward() takes it) advanced IN PLACE over each sequence's first lengths[n] rows
         (lengths: (N) int32 device tensor, None = all L).  f32 only: the result is what L calls of forward() return,
-        row by row, so the projections run in full f32 (no TF32 / XF32)."""
+        row by row, so the projections run in full f32 (no TF32 / XF32).
+
+        kernel="gemm": batch invariant -- sequence n's state and outputs are bitwise the same whatever the other
+        sequences, their lengths, L and `rows`.  Every projection is a cwlt_decode_gemm chained as the GEMM decode step
+        chains it (cwlt_decode_step_rows: a layer's norm2 is the LayerNorm prologue of the next layer's QKV, norm1 that of
+        linear1; residual and GELU in the epilogue), at most `rows` (<= 4096, default 4096) rows per call, and the scan
+        is one workgroup per (sequence, head) over the sequence's own chunks (segments=1).  Only row last[n] ((N) int64
+        device tensor, None = all L - 1) of each sequence goes through the final norms, as the prologue of the stacked
+        heads GEMM heads = (w (n_out, D), b (n_out)).  -> (hidden (N, D), logits (N, n_out))."""
+        if kernel not in ("blas", "gemm"):
+            raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
+        if kernel == "gemm":
+            self._check_prefill(x, state)
+            if heads is None:
+                raise ValueError("the gemm prefill ends in the heads GEMM: pass heads=(weight, bias)")
+            return self._prefill_gemm(x, state, lengths, last, heads, 4096 if rows is None else int(rows))
+        if last is not None or heads is not None or rows is not None:
+            raise ValueError("last, heads and rows belong to kernel='gemm'")
         if not x.is_cuda:
             raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
         if x.dtype != torch.float32:
@@ -131,3 +148,69 @@ class RecurrentTransformerEncoder(nn.Module):
         finally:
             torch.backends.cuda.matmul.allow_tf32 = tf32
         return x
+
+    def _check_prefill(self, x, state):
+        if not x.is_cuda:
+            raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
+        if x.dtype != torch.float32:
+            raise RuntimeError("prefill computes in f32 (got %s activations)" % x.dtype)
+        if state is None or len(state) != len(self.layers) or any(s is None for s in state):
+            raise ValueError("prefill needs one [S, Zs] state per layer, updated in place")
+        for S, Zs in state:
+            if len(S) != x.shape[0] or len(Zs) != x.shape[0]:
+                raise ValueError("state holds %d sequences, the prompt batch %d" % (len(S), x.shape[0]))
+
+    def _prefill_gemm(self, x, state, lengths, last, heads, rows):
+        if not 1 <= rows <= 4096:
+            raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
+        N, L, D = x.shape
+        M = N * L
+        H = self.layers[0].attention.n_heads
+        d = D // H
+        F = self.layers[0].linear1.out_features
+        eps = self.layers[0].norm1.eps
+        for layer in self.layers:
+            if layer.norm1.eps != eps or layer.norm2.eps != eps or (self.norm is not None and self.norm.eps != eps):
+                raise RuntimeError("the gemm prefill needs one LayerNorm eps for the whole encoder")
+        f = ops._f32
+        pair = lambda nrm: (f(nrm.weight), f(nrm.bias))
+
+        def gemm(w, b, src, dst, ln=None, res=None, act=None, normed=None):
+            for a in range(0, M, rows):
+                z = min(M, a + rows)
+                ops.decode_gemm(w, b, src[a:z], ln=ln, eps=eps, res=None if res is None else res[a:z], act=act,
+                                out=dst[a:z], normed=None if normed is None else normed[a:z])
+
+        dev = x.device
+        new = lambda n: torch.empty((M, n), dtype=torch.float32, device=dev)
+        x0 = x.reshape(M, D).contiguous()
+        xn, qkv, s1, x1, hh, s2 = new(D), new(3 * D), new(D), new(D), new(F), new(D)
+        a = torch.zeros((N, L, H, d), dtype=torch.float32, device=dev)    # padded rows stay zero: never written
+        with torch.no_grad():
+            for i, (layer, (S, Zs)) in enumerate(zip(self.layers, state)):
+                at = layer.attention
+                wqkv = torch.cat([f(at.query_projection.weight), f(at.key_projection.weight),
+                                  f(at.value_projection.weight)], 0)
+                bqkv = torch.cat([f(at.query_projection.bias), f(at.key_projection.bias), f(at.value_projection.bias)])
+                prev = self.layers[i - 1] if i else None
+                gemm(wqkv, bqkv, s2 if prev else x0, qkv, ln=pair(prev.norm2) if prev else None,
+                     normed=xn if prev else None)
+                q = qkv.view(N, L, 3, H, d)
+                ops.cla_fwd_state(q[:, :, 0], q[:, :, 1], q[:, :, 2], S, Zs, lengths, out=a, segments=1)
+                gemm(f(at.out_projection.weight), f(at.out_projection.bias), a.view(M, D), s1,
+                     res=xn if prev else x0)
+                gemm(f(layer.linear1.weight), f(layer.linear1.bias), s1, hh, ln=pair(layer.norm1), act="gelu",
+                     normed=x1)
+                gemm(f(layer.linear2.weight), f(layer.linear2.bias), hh, s2, res=x1)
+            if last is None:
+                last = torch.full((N,), L - 1, dtype=torch.int64, device=dev)
+            top = s2.view(N, L, D)[torch.arange(N, device=dev), last]          # (N, D): a gather, exact
+            ln2 = pair(self.norm) if self.norm is not None else None
+            w, b = f(heads[0]), f(heads[1])
+            logits = torch.empty((N, w.shape[0]), dtype=torch.float32, device=dev)
+            hidden = torch.empty((N, D), dtype=torch.float32, device=dev)
+            for a in range(0, N, rows):
+                z = min(N, a + rows)
+                ops.decode_gemm(w, b, top[a:z], ln=pair(self.layers[-1].norm2), ln2=ln2, eps=eps, out=logits[a:z],
+                                normed=hidden[a:z])
+        return hidden, logits
