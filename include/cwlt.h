@@ -476,6 +476,25 @@ int cwlt_sample_categorical_slots(const float* logits, const int* n_class, const
 int cwlt_sample_categorical_keyed(const float* logits, const int* n_class, const float* temperature,
                                   const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
                                   const int64_t* key, const int64_t* step, int64_t* tokens, void* stream);
+/* Constrained draw (generation.Constraint): the slot-keyed draw with disallowed classes removed.  Keyed as
+ * cwlt_sample_categorical_keyed when key and step are given (song k = key[n]), otherwise as
+ * cwlt_sample_categorical_slots at *counter (song k = n).  Row n uses mask row sched[2k] + min(bar[n] - 1,
+ * sched[2k + 1] - 1) of `masks` (mask_rows x mask_words uint32, class c of attribute a is bit off[a] + c with off the
+ * running sum of n_class); bar (DEVICE int64 x rows) is the song's bar count before this row, sched (DEVICE int64,
+ * n_sched x {first row, rows}).  Disallowed classes are -inf logits before the temperature, the max, the softmax and
+ * the nucleus (top_p over the renormalised allowed mass).  With every bit set the draw is bitwise the unmasked one.
+ * Rows with k < 0 or k >= n_sched, songs with a 0-row schedule, and mask rows outside [0, mask_rows) draw unmasked.
+ * Refused: null bar / sched / masks, key without step (or neither key nor counter), mask_words * 32 < sum n_class,
+ * rows > 2^20. */
+int cwlt_sample_categorical_masked(const float* logits, const int* n_class, const float* temperature,
+                                   const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                   const int64_t* counter, const int64_t* key, const int64_t* step, const int64_t* bar,
+                                   const int64_t* sched, int64_t n_sched, const uint32_t* masks, int64_t mask_rows,
+                                   int mask_words, int64_t* tokens, void* stream);
+/* The batch loop's bar count in constrained mode, enqueued after each draw: bar[n] += 1 (DEVICE int64 x rows) when
+ * tokens[n, bar_attr] is a class c < bar_classes with bar_mask[c] != 0 (DEVICE int32).  rows <= 2^20. */
+int cwlt_count_bars(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* bar_mask,
+                    int bar_classes, int64_t* bar, void* stream);
 
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,

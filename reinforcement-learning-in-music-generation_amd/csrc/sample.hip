@@ -28,10 +28,26 @@ struct SampleArgs {
     float top_p[CWLT_MAX_ATTR];                      // nucleus mass per attribute; >= 1: plain categorical
 };
 
+// Allowed-class table of the masked draw (cwlt_sample_categorical_masked): the song of row n is k (row_key[n], or n
+// when slot-keyed by the counter); its mask row is sched[2k] + min(bar[n] - 1, sched[2k + 1] - 1), `words` uint32 per
+// row, class c of attribute a allowed when bit off[a] + c is set.  k < 0 (idle / waiting slots), k >= n_sched, a
+// schedule of length 0 and a row outside [0, rows) all draw unmasked.
+struct MaskArgs {
+    const int64_t* bar;
+    const int64_t* sched;
+    const uint32_t* masks;
+    long n_sched, rows;
+    int words;
+};
+
+// MASKED = false is the plain draw of the three unmasked entry points (M unused).  MASKED = true: disallowed classes
+// get -inf logits before the temperature, the max, the softmax and the nucleus, so the draw is over the renormalised
+// allowed distribution; with every bit set it is bitwise the plain draw.
+template <bool MASKED>
 __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
     const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
-    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step) {
+    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step, MaskArgs M) {
     __shared__ float e_s[CWLT_MAX_ATTR][256];
     const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
     if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
@@ -39,18 +55,36 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float* x = logits + (long)n * ld + A.off[a];
     // keyed by row: row n draws what the slot-keyed launch draws for row row_key[n] at counter row_step[n]
     const long step = row_step ? row_step[n] : counter ? *counter : 0;
+    bool ok[4] = {true, true, true, true};
+    if constexpr (MASKED) {
+        const long k = row_key ? row_key[n] : (long)n;
+        if (k >= 0 && k < M.n_sched) {
+            const long first = M.sched[2 * k], len = M.sched[2 * k + 1];
+            long b = M.bar[n] - 1;
+            b = b < 0 ? 0 : b < len - 1 ? b : len - 1;
+            const long r = first + b;
+            if (len > 0 && r >= 0 && r < M.rows) {
+                const uint32_t* w = M.masks + r * M.words;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int bit = A.off[a] + lane * 4 + j;         // < sum n_class <= 32 * words: inside the row
+                    ok[j] = lane * 4 + j < nc ? ((w[bit >> 5] >> (bit & 31)) & 1u) != 0 : false;
+                }
+            }
+        }
+    }
     float v[4];
     float m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int c = lane * 4 + j;
-        v[j] = c < nc ? x[c] * A.inv_t[a] : -INFINITY;
+        v[j] = c < nc && ok[j] ? x[c] * A.inv_t[a] : -INFINITY;
         m = fmaxf(m, v[j]);
     }
     m = wave_max(m);
     float e[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) e[j] = lane * 4 + j < nc ? expf(v[j] - m) : 0.f;
+    for (int j = 0; j < 4; ++j) e[j] = lane * 4 + j < nc && ok[j] ? expf(v[j] - m) : 0.f;
     if (A.top_p[a] < 1.0f) {
         // nucleus (dqn_policy/model.py:33-47): in descending-probability order keep every class whose PRECEDING
         // mass is <= p (the class that crosses p is kept); probabilities there are exp/(sum + 1e-5).  The mass
@@ -125,7 +159,7 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
 static int sample(const float* logits, const int* n_class, const float* temperature, const float* top_p, int n_attr,
                   int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter, int64_t* tokens, int64_t* song,
                   int64_t song_rows, int slot_keyed, void* stream, const int64_t* row_key = nullptr,
-                  const int64_t* row_step = nullptr) {
+                  const int64_t* row_step = nullptr, const cwlt::MaskArgs* mask = nullptr) {
     using namespace cwlt;
     if (!logits || !n_class || !tokens || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0) return CWLT_ERR_ARG;
     SampleArgs A;
@@ -141,8 +175,16 @@ static int sample(const float* logits, const int* n_class, const float* temperat
         off += n_class[a];
     }
     if (ld < off) return CWLT_ERR_ARG;
-    hipLaunchKernelGGL(sample_categorical_kernel, dim3((unsigned)rows), dim3(64 * n_attr), 0, (hipStream_t)stream, logits,
-                       (long)ld, A, n_attr, seed, counter, tokens, song, (long)song_rows, slot_keyed, row_key, row_step);
+    if (mask) {
+        if ((int64_t)mask->words * 32 < off) return CWLT_ERR_ARG;
+        hipLaunchKernelGGL(sample_categorical_kernel<true>, dim3((unsigned)rows), dim3(64 * n_attr), 0,
+                           (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
+                           (long)song_rows, slot_keyed, row_key, row_step, *mask);
+    } else {
+        hipLaunchKernelGGL(sample_categorical_kernel<false>, dim3((unsigned)rows), dim3(64 * n_attr), 0,
+                           (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
+                           (long)song_rows, slot_keyed, row_key, row_step, MaskArgs{});
+    }
     return (int)hipGetLastError();
 }
 
@@ -168,4 +210,45 @@ extern "C" int cwlt_sample_categorical_keyed(const float* logits, const int* n_c
     if (!key || !step || rows > (1L << 20)) return CWLT_ERR_ARG;
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, nullptr, tokens, nullptr, 0, 1, stream,
                   key, step);
+}
+
+extern "C" int cwlt_sample_categorical_masked(const float* logits, const int* n_class, const float* temperature,
+                                              const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                              const int64_t* counter, const int64_t* key, const int64_t* step,
+                                              const int64_t* bar, const int64_t* sched, int64_t n_sched,
+                                              const uint32_t* masks, int64_t mask_rows, int mask_words,
+                                              int64_t* tokens, void* stream) {
+    using namespace cwlt;
+    if (!bar || !sched || !masks || rows > (1L << 20)) return CWLT_ERR_ARG;
+    if (!key != !step || (!key && !counter)) return CWLT_ERR_ARG;    // keyed per row, or by slot and counter
+    if (n_sched < 1 || mask_rows < 1 || mask_words < 1) return CWLT_ERR_ARG;
+    const MaskArgs M{bar, sched, masks, (long)n_sched, (long)mask_rows, mask_words};
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
+                  0, 1, stream, key, step, &M);
+}
+
+namespace cwlt {
+
+// Bar count of the batch loop's constrained mode, after each draw: bar[n] += 1 when row n's bar-beat class is a Bar.
+__global__ __launch_bounds__(256) void count_bars_kernel(const int64_t* __restrict__ tokens, long rows, int n_attr,
+                                                         int bar_attr, const int* __restrict__ bar_mask,
+                                                         int bar_classes, int64_t* __restrict__ bar) {
+    const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= rows) return;
+    const int64_t tk = tokens[n * n_attr + bar_attr];
+    if (tk >= 0 && tk < bar_classes && bar_mask[tk]) bar[n] += 1;
+}
+
+}  // namespace cwlt
+
+extern "C" int cwlt_count_bars(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* bar_mask,
+                               int bar_classes, int64_t* bar, void* stream) {
+    using namespace cwlt;
+    if (!tokens || !bar_mask || !bar) return CWLT_ERR_ARG;
+    if (rows < 1 || rows > (1L << 20) || n_attr < 1 || n_attr > CWLT_MAX_ATTR || bar_attr < 0 || bar_attr >= n_attr ||
+        bar_classes < 1)
+        return CWLT_ERR_ARG;
+    hipLaunchKernelGGL(count_bars_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       tokens, (long)rows, n_attr, bar_attr, bar_mask, bar_classes, bar);
+    return (int)hipGetLastError();
 }

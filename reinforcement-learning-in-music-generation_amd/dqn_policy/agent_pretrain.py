@@ -121,13 +121,15 @@ bar_production = 50                               # testing-no-type-cp.py:35
 
 
 def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sampling=False, batch_size=None,
-             slots=None, prompts=None, prompt_bars=None):
+             slots=None, prompts=None, prompt_bars=None, constraints=None):
     """agent_pretrain.py:636-706 / testing-no-type-cp.py:182-260: build the recurrent-form net, load
     ./ckpt/_params.pt when present, sample `num_songs` songs, write get_<i>.mid + runtime_stats.json.
     batch_size: make the songs that many at a time in lock-step (generation.generate_batch).
     slots: make the songs by continuous batching on that many decode slots (generation.generate_stream).
     prompts: one (P_i, 6) array per song to continue.  prompt_bars: instead, song i continues the first prompt_bars
-    bars of the loaded dataset song i (generation.dataset_prompts)."""
+    bars of the loaded dataset song i (generation.dataset_prompts).
+    constraints: a generation.Constraint (built on the dictionary's word2event) or a list of n_songs of them (None
+    entries unconstrained), with batch_size or slots (generation.generate)."""
     from rlmg_amd import generation, midi
     if prompts is not None and prompt_bars is not None:
         raise ValueError("pass prompts or prompt_bars, not both")
@@ -154,7 +156,7 @@ def generate(n_songs=None, bar_cond=None, max_tokens=None, log=print, device_sam
                                bar_cond=bar_production if bar_cond is None else bar_cond, path_gendir=path_gendir,
                                write_midi=midi.write_midi, max_tokens=max_tokens, log=log,
                                device_sampling=device_sampling, batch_size=batch_size, slots=slots,
-                               prompts=prompts)
+                               prompts=prompts, constraints=constraints)
 
 
 if __name__ == "__main__":

@@ -99,6 +99,183 @@ def bank_may_prefill(j, B, bank, assigned):
     return j < nb or int(assigned) >= (j - nb + 1) * B
 
 
+class Constraint:
+    """What a song may contain, attribute by attribute, enforced inside the device sampler
+    (cwlt_sample_categorical_masked).  generate_batch / generate_stream / generate(batch_size=... | slots=...) take it
+    as `constraints=`.
+
+    allow: {attribute name (a key of word2event, e.g. "pitch"): events}, a static allowed set for every bar.
+    per_bar: {attribute name: [events, events, ...]}, a schedule whose entry i applies to bar i + 1.
+    Events are event names (values of word2event[attribute]) or class ids; a single name or id is one event.
+    Bars follow the generation bar rule: the count starts at 1 and counts the Bar tokens of the prompt's rows after the
+    first; a drawn row is constrained by the entry for the count BEFORE that row, and the count goes up after a row
+    whose bar-beat class is a Bar class -- so the Bar token that opens bar c + 1 is still drawn under bar c's entry.
+    Past the end of a schedule its last entry holds; cycle=True repeats the schedule instead.
+    keep_neutral=True: in every attribute the constraint restricts, class 0 and every class named "CONTI" stay allowed
+    (note rows carry 0 in tempo / chord / bar-beat, metrical rows 0 in pitch / duration / velocity and often CONTI in
+    tempo / chord), so a pitch range or a chord set does not force every row to be a note or a beat.
+    The draw: disallowed classes are -inf logits before the temperature, the max, the softmax and the nucleus (top_p is
+    taken over the renormalised allowed distribution).  Draw keys are unchanged, so a constraint that allows every
+    class gives bitwise the unconstrained songs.  Prompt rows are never constrained.
+    Refused (ValueError): unknown attribute or event names, ids out of range, an empty allowed set, an attribute in both
+    allow and per_bar."""
+
+    def __init__(self, word2event, allow=None, per_bar=None, cycle=False, keep_neutral=True):
+        self.keys = list(word2event.keys())
+        self.n_class = [len(word2event[k]) for k in self.keys]
+        self.cycle, self.keep_neutral = bool(cycle), bool(keep_neutral)
+        allow = {} if allow is None else dict(allow)
+        per_bar = {} if per_bar is None else dict(per_bar)
+        both = sorted(set(allow) & set(per_bar))
+        if both:
+            raise ValueError("attribute %r is in both allow and per_bar" % both[0])
+        self.static = {self._attr(name): self._allowed(word2event, name, ev) for name, ev in allow.items()}
+        self.schedule = {}
+        for name, entries in per_bar.items():
+            a = self._attr(name)
+            if isinstance(entries, (str, bytes)) or not hasattr(entries, "__len__") or len(entries) == 0:
+                raise ValueError("per_bar[%r] must be a non-empty list with one collection of events per bar" % (name,))
+            self.schedule[a] = [self._allowed(word2event, name, ev, i) for i, ev in enumerate(entries)]
+        self.bar_attr = self.keys.index("bar-beat") if "bar-beat" in self.keys else None
+        self.bar_ids = [] if self.bar_attr is None else \
+            [i for i, e in word2event["bar-beat"].items() if e == "Bar"]
+
+    def _attr(self, name):
+        if name not in self.keys:
+            raise ValueError("unknown attribute %r (attributes: %s)" % (name, ", ".join(map(str, self.keys))))
+        return self.keys.index(name)
+
+    def _allowed(self, word2event, name, events, bar=None):
+        where = "%r" % (name,) if bar is None else "%r, bar %d" % (name, bar + 1)
+        names = word2event[name]
+        n = len(names)
+        if isinstance(events, (str, bytes, int, np.integer)):
+            events = [events]
+        keep = np.zeros(n, dtype=bool)
+        count = 0
+        for ev in events:
+            count += 1
+            if isinstance(ev, (int, np.integer)) and not isinstance(ev, bool):
+                if not 0 <= int(ev) < n:
+                    raise ValueError("%s: class id %d out of range (%d classes)" % (where, int(ev), n))
+                keep[int(ev)] = True
+                continue
+            ids = [i for i, e in names.items() if e == ev]
+            if not ids:
+                raise ValueError("%s: unknown event %r" % (where, ev))
+            keep[ids] = True
+        if count == 0:
+            raise ValueError("%s: the allowed set is empty" % where)
+        if self.keep_neutral:
+            keep[0] = True
+            keep[[i for i, e in names.items() if e == "CONTI"]] = True
+        return keep
+
+    def allowed(self, bar):
+        """Per attribute, the (n_class,) bool array of classes allowed in bar `bar` (the count before the row)."""
+        out = []
+        i = max(int(bar) - 1, 0)
+        for a, n in enumerate(self.n_class):
+            if a in self.static:
+                out.append(self.static[a])
+            elif a in self.schedule:
+                sch = self.schedule[a]
+                out.append(sch[i % len(sch)] if self.cycle else sch[min(i, len(sch) - 1)])
+            else:
+                out.append(np.ones(n, dtype=bool))
+        return out
+
+    def mask_rows(self, bar_cond):
+        """The device table of this constraint for songs that end at bar `bar_cond` -> (R, ceil(sum n_class / 32))
+        uint32: row i is bar i + 1, class c of attribute a is bit sum(n_class[:a]) + c.  Without a schedule R = 1;
+        cycle=True expands the schedule to bar_cond - 1 rows (no kept row is drawn at a count >= bar_cond); otherwise R
+        is the longest schedule, cut at bar_cond - 1.  The device clamps to the last row."""
+        last = max(1, int(bar_cond) - 1)
+        if not self.schedule:
+            R = 1
+        elif self.cycle:
+            R = last
+        else:
+            R = min(max(len(v) for v in self.schedule.values()), last)
+        W = -(-sum(self.n_class) // 32)
+        bits = np.zeros((R, W * 32), dtype=bool)
+        for i in range(R):
+            row = np.concatenate(self.allowed(i + 1))
+            bits[i, :len(row)] = row
+        return np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(R, W)
+
+    def can_end(self, bar0, bar_cond):
+        """False when some bar in [bar0, bar_cond) allows no Bar class: a song there could never reach bar_cond."""
+        if self.bar_attr is None or (self.bar_attr not in self.static and self.bar_attr not in self.schedule):
+            return True
+        for b in range(int(bar0), int(bar_cond)):
+            if not self.allowed(b)[self.bar_attr][self.bar_ids].any():
+                return False
+        return True
+
+    def violations(self, song, bar0=1):
+        """Indices of the rows of `song` ((L, 6) drawn rows, e.g. generated[len(prompt):]) that break the constraint,
+        the first row drawn at bar count bar0 (1 from scratch; a prompt's own count after a prompt)."""
+        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
+        bad, b = [], int(bar0)
+        bar_ids = set(self.bar_ids)
+        for t, row in enumerate(song):
+            ok = self.allowed(b)
+            if any(not (0 <= int(c) < n and ok[a][int(c)]) for a, (c, n) in enumerate(zip(row, self.n_class))):
+                bad.append(t)
+            if self.bar_attr is not None and int(row[self.bar_attr]) in bar_ids:
+                b += 1
+        return bad
+
+
+def compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens):
+    """The device table of `constraints` (one Constraint for every song, or a list of n_songs entries, None =
+    unconstrained) -> None when no song is constrained, else (sched (n_songs, 2) int64 {first row, rows}, masks (R, W)
+    uint32).  One Constraint object's rows are shared by all songs that use it; an unconstrained song has 0 rows.
+    bar0s: each song's bar count before its first drawn row.  Without max_tokens a song whose bar-beat restriction
+    allows no Bar class in some bar it can reach would never end: refused."""
+    if isinstance(constraints, Constraint):
+        constraints = [constraints] * n_songs
+    elif isinstance(constraints, (list, tuple)):
+        if len(constraints) != n_songs:
+            raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
+    else:
+        raise ValueError("constraints must be a Constraint or a list of n_songs Constraint / None entries, got %s"
+                         % type(constraints).__name__)
+    if all(c is None for c in constraints):
+        return None
+    sched = np.zeros((n_songs, 2), dtype=np.int64)
+    parts, rows, ends, total = [], {}, {}, 0
+    for k, c in enumerate(constraints):
+        if c is None:
+            continue
+        if not isinstance(c, Constraint):
+            raise ValueError("constraints[%d] is a %s, not a Constraint or None" % (k, type(c).__name__))
+        if list(c.n_class) != list(n_token):
+            raise ValueError("constraints[%d] was built for classes %s, the model draws %s" % (k, c.n_class,
+                                                                                            list(n_token)))
+        if id(c) not in rows:
+            parts.append(c.mask_rows(bar_cond))
+            rows[id(c)] = (total, len(parts[-1]))
+            total += len(parts[-1])
+        sched[k] = rows[id(c)]
+        if max_tokens is None:
+            key = (id(c), int(bar0s[k]))
+            if key not in ends:
+                ends[key] = c.can_end(bar0s[k], bar_cond)
+            if not ends[key]:
+                raise ValueError("constraints[%d] allows no Bar in some bar before bar_cond=%d: the song could never "
+                                 "end (pass max_tokens, or allow a Bar class in every bar)" % (k, bar_cond))
+    return sched, np.concatenate(parts)
+
+
+def _device_constraints(table, dev):
+    """compile_constraints' table on the device: {"sched", "masks"} (int32 view of the mask words)."""
+    sched, masks = table
+    return {"sched": torch.as_tensor(sched).to(dev),
+            "masks": torch.as_tensor(np.ascontiguousarray(masks).view(np.int32)).to(dev)}
+
+
 class _FusedPlan:
     """Host description of the model for `cwlt_decode_step` (include/cwlt.h: cwlt_decode_model): stacked
     QKV / head weights, device pointers of every parameter, the per-song state and workspace.  Holds references
@@ -413,10 +590,16 @@ class _DeviceLoop:
 
     ring=R: `song` holds only the last R rows (row t of the stream in slot t % R) so that many songs with a large cap
     do not need capacity x n_songs rows; read each R-row stretch before the next R tokens overwrite it.  The draws are
-    the same either way (they are keyed by the counter)."""
+    the same either way (they are keyed by the counter).
 
-    def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None):
+    mask: constrained mode, {"sched", "masks"} (_device_constraints) and "bar" ((n_songs,) int64 device bar counts
+    before the next row), "bar_mask" ((n_class[2],) int32 Bar classes): the draw is cwlt_sample_categorical_masked,
+    then cwlt_count_bars advances the bar counts, both inside the captured token."""
+
+    def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None,
+                 mask=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
+        self.mask = mask
         self.A, self.N = len(sess.n_token), sess.n_songs
         self.ring = None if ring is None or int(ring) >= self.capacity else int(ring)
         rows = self.capacity if self.ring is None else self.ring
@@ -432,9 +615,17 @@ class _DeviceLoop:
     def _draw(self, logits):
         s = self.sess
         tok = s.tok.view(self.N, self.A)
-        ops.sample_categorical(logits, s.n_token, tok, self.seed, counter=self.count,
-                               song=self.song if self.ring is None else None, temperature=self.temperature,
-                               top_p=self.top_p, slot_keys=True)
+        if self.mask is None:
+            ops.sample_categorical(logits, s.n_token, tok, self.seed, counter=self.count,
+                                   song=self.song if self.ring is None else None, temperature=self.temperature,
+                                   top_p=self.top_p, slot_keys=True)
+        else:
+            m = self.mask
+            ops.sample_categorical_masked(logits, s.n_token, tok, self.seed, m["bar"], m["sched"], m["masks"],
+                                          counter=self.count, temperature=self.temperature, top_p=self.top_p)
+            ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
+            if self.ring is None:
+                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
         if self.ring is not None:
             self.song.index_copy_(0, self.slot, tok.view(1, self.N, self.A))
             self.slot.add_(1).remainder_(self.ring)
@@ -500,8 +691,9 @@ class _StreamLoop:
     The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host."""
 
     def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 temperature=None, top_p=None, graph=None):
+                 temperature=None, top_p=None, graph=None, mask=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
+        self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
         self.snap_state, self.snap_logits = snap_state, snap_logits.reshape(-1)
@@ -531,10 +723,21 @@ class _StreamLoop:
         logits = s._device_step()
         ops.stream_refill(s._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
                           self.snap_logits, self.fresh)
-        ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
-                                     temperature=self.temperature, top_p=self.top_p)
+        self._sample(logits, tok)
         ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
                            self.pos, self.bar, self.fresh, self.ctl, self.ring)
+
+    def _sample(self, logits, tok):
+        """Each slot's draw keyed by (song index, position in song); constrained (mask: _device_constraints) by the
+        song's mask row for the slot's bar count."""
+        s = self.sess
+        if self.mask is None:
+            ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
+                                         temperature=self.temperature, top_p=self.top_p)
+        else:
+            ops.sample_categorical_masked(logits, s.n_token, tok, self.seed, self.bar, self.mask["sched"],
+                                          self.mask["masks"], key=self.song, step=self.pos,
+                                          temperature=self.temperature, top_p=self.top_p)
 
     def _enqueue_chunk(self):
         """Enqueue `chunk` tokens and the copy of their ring half (and the counters) to pinned host memory."""
@@ -592,8 +795,9 @@ class _BankStreamLoop(_StreamLoop):
     cwlt_stream_advance_bank (a slot takes a song only below ctl[3], otherwise it waits)."""
 
     def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
-                 top_p=None, graph=None, prefill_rows=None):
+                 top_p=None, graph=None, prefill_rows=None, mask=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
+        self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
         self.B, self.bank = int(B), int(bank)
@@ -691,8 +895,7 @@ class _BankStreamLoop(_StreamLoop):
         logits = s._device_step()
         ops.stream_refill_bank(s._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
                                self.bank_logits, self.fresh, self.song)
-        ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
-                                     temperature=self.temperature, top_p=self.top_p)
+        self._sample(logits, tok)
         ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
                                 self.song, self.pos, self.bar, self.cap, self.fresh, self.ctl, self.ring)
 
@@ -771,10 +974,12 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 
 def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_tokens, prompts, sampler, chunk, bank,
-                             prefill_rows, log):
+                             prefill_rows, log, constraints=None):
     start = time.perf_counter()
     n_token = list(model.n_token)
     heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
+    table = None if constraints is None else \
+        compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens)
     sess = DecodeSession(model, n_songs=slots, kernel="gemm")
     sess.reset()
     seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
@@ -785,14 +990,15 @@ def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_to
     bar_mask = [int(names[i] == "Bar") for i in range(sess.n_token[2])]
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
     loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
-                           temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows)
+                           temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows,
+                           mask=None if table is None else _device_constraints(table, sess.dev))
     rows = loop.run(max(caps))
     return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
                                       "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
 
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None):
+                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks."""
@@ -820,7 +1026,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompts is not None:
         heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
                                                                    max_tokens, prompts, sampler, chunk, bank,
-                                                                   prefill_rows, log)
+                                                                   prefill_rows, log, constraints)
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
@@ -836,6 +1042,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         if max_tokens is not None and max_tokens <= len(head):
             raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(head)))
         cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
+        table = None if constraints is None else \
+            compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, [bar0] * n_songs, max_tokens)
         start = time.perf_counter()
         sess = DecodeSession(model, n_songs=slots, kernel="gemm")
         sess.reset()
@@ -844,7 +1052,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         bar_mask = [int(bar_names[i] == "Bar") for i in range(sess.n_token[2])]   # every class named "Bar", not one id
         temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
         loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                           temperature=temperature, top_p=top_p, graph=sess.use_graph)
+                           temperature=temperature, top_p=top_p, graph=sess.use_graph,
+                           mask=None if table is None else _device_constraints(table, sess.dev))
         rows = loop.run()
         heads = [head] * n_songs
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
@@ -868,7 +1077,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
 
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                    chunk=128, log=None, prompts=None, bank=None, prefill_rows=None):
+                    chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -888,10 +1097,15 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     Defaults (stream_bank_plan): B = prefill_rows // the longest prompt, prefill_rows = PREFILL_ROWS (32768 token rows,
     about 0.8 GB of prefill activations at d_model 512); bank = the smallest multiple of B with max(2 B, 2 slots)
     entries, capped by the songs and a quarter of free device memory (one entry at d_model 512 / 12 layers / 8 heads
-    is 12 x 8 x 64 x 65 x 4 B = 1.6 MB).  `bank` (a multiple of B) overrides the bank size."""
+    is 12 x 8 x 64 x 65 x 4 B = 1.6 MB).  `bank` (a multiple of B) overrides the bank size.
+
+    constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained).
+    The host compiles them into one device table before the first token (compile_constraints) and each slot's draw
+    is masked by its song's row for the slot's bar count (cwlt_sample_categorical_masked); song k is still bitwise
+    song k of generate_batch(..., constraints=constraints)."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
-                            prefill_rows=prefill_rows)[0]
+                            prefill_rows=prefill_rows, constraints=constraints)[0]
 
 
 def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
@@ -1059,7 +1273,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
-                   log=None, prefill="blas"):
+                   log=None, prefill="blas", constraints=None):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -1074,7 +1288,12 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     extra rows are discarded.  The draws are keyed by (torch seed, step, song slot): song i of a batch from scratch
     is the same whatever the batch size.  prefill: the prompt prefill's kernel, DecodeSession.prefill's "blas"
     (default) or "gemm" (batch invariant: song i's start depends on prompts[i] alone -- generate_stream(prompts=...)
-    gives the same songs)."""
+    gives the same songs).
+
+    constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained),
+    compiled into one device table before the first token.  The loop then keeps each song's bar count on the device
+    (from its prompt's count; cwlt_count_bars after every draw) and masks each draw by the song's row for that count
+    (cwlt_sample_categorical_masked).  None: the unconstrained sampler, unchanged."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if prefill not in ("blas", "gemm"):
@@ -1110,11 +1329,20 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         cnt_bar.append(cnt)
     caps = [16384 if max_tokens is None else max_tokens - len(p) for p in heads]     # drawn tokens per song
     cap = max(caps)
+    table = None if constraints is None else \
+        compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, cnt_bar, max_tokens)
     sess = DecodeSession(model, n_songs=n_songs, kernel="gemm")
     sess.reset()
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    mask = None
+    if table is not None:
+        mask = _device_constraints(table, sess.dev)
+        mask["bar"] = torch.as_tensor(np.asarray(cnt_bar, dtype=np.int64)).to(sess.dev)
+        names = word2event["bar-beat"]
+        mask["bar_mask"] = torch.as_tensor(np.array([names[i] == "Bar" for i in range(sess.n_token[2])],
+                                                    dtype=np.int32)).to(sess.dev)
     loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
-                       ring=chunk)
+                       ring=chunk, mask=mask)
     if prompts is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
                        .view(n_songs, 1, A).to(sess.dev))
@@ -1151,7 +1379,7 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None, slots=None, prompts=None):
+             batch_size=None, slots=None, prompts=None, constraints=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1161,9 +1389,17 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     slots: make the songs by continuous batching on that many decode slots (generate_stream); a song's time is then
     the stream's wall time divided by n_songs.  Not together with batch_size.
     prompts: a list of n_songs (P_i, 6) arrays, song i continues prompts[i] (not together with prompt): on the stream
-    with slots, each batch_size group with its own slice of the list, or one song at a time."""
+    with slots, each batch_size group with its own slice of the list, or one song at a time.
+    constraints: one Constraint for every song or a list of n_songs Constraint / None entries (generate_batch,
+    generate_stream), with slots or batch_size only: the one-song path samples on the host."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if constraints is not None:
+        if batch_size is None and slots is None:
+            raise ValueError("constraints run in the device samplers of generate_batch / generate_stream: pass "
+                             "batch_size or slots (one song: generate_batch(n_songs=1, constraints=...))")
+        if isinstance(constraints, (list, tuple)) and len(constraints) != n_songs:
+            raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
     if prompts is not None:
         if prompt is not None:
             raise ValueError("pass one shared prompt or per-song prompts, not both")
@@ -1182,7 +1418,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     if slots is not None:
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
-                                prompt=prompt, prompts=None if prompts is None else list(prompts))
+                                prompt=prompt, prompts=None if prompts is None else list(prompts),
+                                constraints=constraints)
         wall = time.time() - start
         for sidx, res in enumerate(songs):
             save(sidx, res)
@@ -1196,7 +1433,9 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
             group = min(int(batch_size), n_songs - first)
             start = time.time()
             songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens,
-                                   prompts=prompt if prompts is None else list(prompts[first:first + group]))
+                                   prompts=prompt if prompts is None else list(prompts[first:first + group]),
+                                   constraints=list(constraints[first:first + group])
+                                   if isinstance(constraints, (list, tuple)) else constraints)
             wall = time.time() - start
             for j, res in enumerate(songs):
                 save(first + j, res)

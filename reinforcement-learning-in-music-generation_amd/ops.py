@@ -1591,6 +1591,55 @@ def sample_categorical_keyed(logits, n_class, tokens, seed, key, step, temperatu
     return tokens
 
 
+def sample_categorical_masked(logits, n_class, tokens, seed, bar, sched, masks, counter=None, key=None, step=None,
+                              temperature=None, top_p=None):
+    """The constrained draw (cwlt_sample_categorical_masked): sample_categorical(slot_keys=True) at `counter` (song k =
+    row n) or sample_categorical_keyed with per-row key / step (song k = key[n]), with every class whose bit is clear
+    in the song's mask row treated as a -inf logit.  bar (rows,) int64: the song's bar count before this row; sched
+    (n_sched, 2) int64: per song index {first mask row, rows}, row used first + min(bar - 1, rows - 1); masks
+    (mask_rows, mask_words) int32 / uint32 bits, class c of attribute a at bit sum(n_class[:a]) + c.  Songs k < 0 or
+    >= n_sched and 0-row schedules draw unmasked.  All device tensors."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
+        raise TypeError("sample_categorical_masked takes f32 logits and int64 tokens")
+    rows, A = logits.shape[0], len(n_class)
+    if tokens.numel() != rows * A or not tokens.is_contiguous():
+        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
+    if (key is None) != (step is None) or (key is None and counter is None):
+        raise ValueError("sample_categorical_masked is keyed by key and step, or by the slot and a counter")
+    for t in [bar] + ([] if key is None else [key, step]):
+        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+            raise ValueError("bar, key and step must be contiguous (rows,) int64 tensors")
+    if sched.dtype != torch.int64 or sched.dim() != 2 or sched.shape[1] != 2 or not sched.is_contiguous():
+        raise ValueError("sched must be a contiguous (n_songs, 2) int64 tensor")
+    if masks.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or masks.dim() != 2 or not masks.is_contiguous():
+        raise ValueError("masks must be a contiguous (rows, words) 32-bit tensor")
+    if masks.shape[1] * 32 < sum(n_class):
+        raise ValueError("masks: %d words per row hold fewer than the %d classes" % (masks.shape[1], sum(n_class)))
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    _call("cwlt_sample_categorical_masked", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step),
+          _lib.dev(bar, "bar"), _lib.dev(sched, "sched"), sched.shape[0], _lib.dev(masks, "masks"), masks.shape[0],
+          masks.shape[1], _lib.dev(tokens, "tokens"), _lib.stream_ptr())
+    return tokens
+
+
+def count_bars(tokens, bar_attr, bar_mask, bar):
+    """bar[n] += 1 where row n of tokens (rows, A) int64 has a Bar class in attribute bar_attr (bar_mask
+    (n_class[bar_attr],) int32) -- cwlt_count_bars, the batch loop's bar count in constrained mode."""
+    rows, A = bar.numel(), tokens.shape[-1]
+    if tokens.dtype != torch.int64 or bar.dtype != torch.int64 or not tokens.is_contiguous() or \
+            not bar.is_contiguous():
+        raise TypeError("count_bars takes contiguous int64 tokens and bar")
+    if bar_mask.dtype != torch.int32 or tokens.numel() != rows * A:
+        raise ValueError("count_bars: tokens must be (rows, A) for %d bar counts, bar_mask int32" % rows)
+    _call("cwlt_count_bars", _lib.dev(tokens, "tokens"), rows, A, int(bar_attr), _lib.dev(bar_mask, "bar_mask"),
+          bar_mask.numel(), _lib.dev(bar, "bar"), _lib.stream_ptr())
+    return bar
+
+
 def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):
     """Copy the one-slot snapshot (state, logits) into every slot whose fresh flag is set (cwlt_stream_refill).
     state: flat f32 of n_layer x [S (slots, s_floats), Z (slots, z_floats)] (DecodeSession._state); snap_state: the same
