@@ -491,6 +491,32 @@ int cwlt_sample_categorical_masked(const float* logits, const int* n_class, cons
                                    const int64_t* counter, const int64_t* key, const int64_t* step, const int64_t* bar,
                                    const int64_t* sched, int64_t n_sched, const uint32_t* masks, int64_t mask_rows,
                                    int mask_words, int64_t* tokens, void* stream);
+/* Draw with log-probabilities: the slot-keyed draw at *counter (key = step = NULL), or keyed per row by
+ * key / step, as cwlt_sample_categorical_slots / _keyed; masked as cwlt_sample_categorical_masked when bar, sched and
+ * masks are given (all three, or none).  Tokens are those entries' tokens, bit for bit.  For the drawn class c of row
+ * n, attribute a, it also writes the f32 pair {lp_model, lp_sampler} to logp[((o * rows + n) * n_attr + a) * 2] with
+ * o = *out_counter % out_rows (out_counter: DEVICE int64, e.g. the counter the caller advances after the draw; NULL
+ * needs out_rows == 1).  lp_model = log_softmax(raw logits)[c]; lp_sampler = log q(c), q the distribution of the draw:
+ * tempered logits v, disallowed classes -inf, the nucleus kept set, renormalised: (v_c - m) - log(sum over kept e).
+ * Refused: null logp, key without step (or neither key nor counter), a partial mask table, out_rows < 1,
+ * rows > 2^20, and what cwlt_sample_categorical refuses. */
+int cwlt_sample_categorical_logp(const float* logits, const int* n_class, const float* temperature,
+                                 const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                 const int64_t* counter, const int64_t* key, const int64_t* step, const int64_t* bar,
+                                 const int64_t* sched, int64_t n_sched, const uint32_t* masks, int64_t mask_rows,
+                                 int mask_words, int64_t* tokens, float* logp, const int64_t* out_counter,
+                                 int64_t out_rows, void* stream);
+/* Score given classes: the pair cwlt_sample_categorical_logp writes, for class targets[n * n_attr + a] (DEVICE int64,
+ * rows x n_attr) of row n of logits (rows x ld f32), into logp[(n * n_attr + a) * 2] (rows x n_attr x 2 f32).  The
+ * same kernel body as the draw: the logits a draw came from, scored at the class it drew, give its pair bitwise.
+ * Masked when bar (the bar count of row n), sched and masks are given, with song key[n] (NULL: n) as in
+ * cwlt_sample_categorical_masked.  A negative target (padding) leaves its pair unwritten; a target >= n_class[a]
+ * gets {-inf, -inf}.  Refused: null targets / logp, a partial mask table, rows > 2^20, what cwlt_sample_categorical
+ * refuses. */
+int cwlt_score_categorical(const float* logits, const int* n_class, const float* temperature, const float* top_p,
+                           int n_attr, int64_t rows, int64_t ld, const int64_t* targets, const int64_t* key,
+                           const int64_t* bar, const int64_t* sched, int64_t n_sched, const uint32_t* masks,
+                           int64_t mask_rows, int mask_words, float* logp, void* stream);
 /* The batch loop's bar count in constrained mode, enqueued after each draw: bar[n] += 1 (DEVICE int64 x rows) when
  * tokens[n, bar_attr] is a class c < bar_classes with bar_mask[c] != 0 (DEVICE int32).  rows <= 2^20. */
 int cwlt_count_bars(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* bar_mask,

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -126,6 +126,10 @@ _SIGNATURES = {
                                       _ptr],
     "cwlt_sample_categorical_keyed": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64, _ptr, _ptr, _ptr, _ptr],
     "cwlt_sample_categorical_masked": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64] + [_ptr] * 5
+    + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr],
+    "cwlt_sample_categorical_logp": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64] + [_ptr] * 5
+    + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr],
+    "cwlt_score_categorical": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64] + [_ptr] * 4
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr],
     "cwlt_count_bars": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr],
     "cwlt_stream_refill": [_ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr],

@@ -13,6 +13,11 @@
 // The draw counter is a device int64 read by the kernel: a captured hipGraph draws fresh numbers on every replay.
 // Same distribution as the reference's sampler, not the same stream (torch's Philox stream is device- and
 // version-specific anyway).
+//
+// Log-probabilities: the LOGP instantiations also write, per drawn class c, the pair (log_softmax of the
+// raw logits at c, log q(c)) with q the distribution the draw was made from (temperature, mask, nucleus kept set,
+// renormalised); the FORCED instantiations take c from a target array instead of drawing it and compute the same pair,
+// through the same body, so scoring the logits a draw came from at the class it drew gives the sampler's bits.
 #include "cwlt_common.h"
 
 #include <climits>
@@ -40,22 +45,45 @@ struct MaskArgs {
     int words;
 };
 
+// Log-prob output of the LOGP / FORCED instantiations (unused otherwise; it is the last kernel argument, so the
+// other arguments keep their offsets).  The pair of row n, attribute a goes to logp[((o * rows + n) * n_attr + a) * 2]
+// with o = *out_counter % out_rows (o = 0 without a counter).  FORCED: the class is targets[n * n_attr + a]; a negative
+// target (padding) leaves the pair unwritten.
+struct LogpArgs {
+    float* logp;
+    const int64_t* out_counter;
+    long out_rows;
+    const int64_t* targets;
+};
+
 // MASKED = false is the plain draw of the three unmasked entry points (M unused).  MASKED = true: disallowed classes
 // get -inf logits before the temperature, the max, the softmax and the nucleus, so the draw is over the renormalised
 // allowed distribution; with every bit set it is bitwise the plain draw.
-template <bool MASKED>
+// LOGP: after the draw, write (lp_model, lp_sampler) of the drawn class (LogpArgs).  FORCED (implies LOGP): no draw, no
+// RNG, no token write; the class is the target's.  lp_sampler = (v_c - m) - log(sum of e over the kept classes), -inf
+// outside the mask or the nucleus kept set; lp_model = (x_c - mx) - log(sum exp(x - mx)) over the raw logits (its max
+// and sum are the sampler's own when inv_t == 1 and no mask row applies).
+template <bool MASKED, bool LOGP = false, bool FORCED = false>
 __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
     const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
-    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step, MaskArgs M) {
+    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step, MaskArgs M,
+    LogpArgs L) {
+    static_assert(LOGP || !FORCED, "FORCED writes log-probs");
     __shared__ float e_s[CWLT_MAX_ATTR][256];
     const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
     if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
     const int nc = A.n[a];
     const float* x = logits + (long)n * ld + A.off[a];
+    long forced = 0;
+    if constexpr (FORCED) {
+        forced = L.targets[(long)n * n_attr + a];
+        if (forced < 0) return;                      // padding row: wave-uniform, nothing written
+    }
     // keyed by row: row n draws what the slot-keyed launch draws for row row_key[n] at counter row_step[n]
-    const long step = row_step ? row_step[n] : counter ? *counter : 0;
+    const long step = FORCED ? 0 : row_step ? row_step[n] : counter ? *counter : 0;
     bool ok[4] = {true, true, true, true};
+    bool row_masked = false;
     if constexpr (MASKED) {
         const long k = row_key ? row_key[n] : (long)n;
         if (k >= 0 && k < M.n_sched) {
@@ -64,6 +92,7 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
             b = b < 0 ? 0 : b < len - 1 ? b : len - 1;
             const long r = first + b;
             if (len > 0 && r >= 0 && r < M.rows) {
+                row_masked = true;
                 const uint32_t* w = M.masks + r * M.words;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -85,6 +114,10 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     float e[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) e[j] = lane * 4 + j < nc && ok[j] ? expf(v[j] - m) : 0.f;
+    bool keep[4];                                    // the support of q: allowed, and inside the nucleus
+#pragma unroll
+    for (int j = 0; j < 4; ++j) keep[j] = lane * 4 + j < nc && ok[j];
+    float tot_all = 0.f;                             // sum of e before the nucleus cut (nucleus rows only)
     if (A.top_p[a] < 1.0f) {
         // nucleus (dqn_policy/model.py:33-47): in descending-probability order keep every class whose PRECEDING
         // mass is <= p (the class that crosses p is kept); probabilities there are exp/(sum + 1e-5).  The mass
@@ -109,6 +142,11 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
         const float limit = A.top_p[a] * (tot * (1.0f + 1e-5f));
 #pragma unroll
         for (int j = 0; j < 4; ++j) e[j] = ahead[j] <= limit ? e[j] : 0.f;
+        if constexpr (LOGP) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) keep[j] = keep[j] && ahead[j] <= limit;
+            tot_all = tot;
+        }
     }
     float run = 0.f, cum[4];
 #pragma unroll
@@ -125,43 +163,92 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
     }
     const float before = inc - run;
     const float total = lane_value(inc, 63);
-    // slot-keyed: song n's draws do not depend on how many songs share the launch (the same keys at n = 0)
-    const uint64_t slot = row_key ? (uint64_t)row_key[n] : (uint64_t)n;
-    const uint64_t key = slot_keyed ? (slot << 40) + (uint64_t)step : (uint64_t)step * gridDim.x + n;
-    const uint32_t r = rng_pair(seed, key * CWLT_MAX_ATTR + a);
-    const float u = (float)(r >> 8) * (1.0f / 16777216.0f);      // [0, 1)
-    const float target = u * total;
     int pick = INT_MAX;
+    if constexpr (FORCED) {
+        pick = forced < nc ? (int)forced : INT_MAX;  // a class outside the attribute: both log-probs -inf
+    } else {
+        // slot-keyed: song n's draws do not depend on how many songs share the launch (the same keys at n = 0)
+        const uint64_t slot = row_key ? (uint64_t)row_key[n] : (uint64_t)n;
+        const uint64_t key = slot_keyed ? (slot << 40) + (uint64_t)step : (uint64_t)step * gridDim.x + n;
+        const uint32_t r = rng_pair(seed, key * CWLT_MAX_ATTR + a);
+        const float u = (float)(r >> 8) * (1.0f / 16777216.0f);      // [0, 1)
+        const float target = u * total;
 #pragma unroll
-    for (int j = 3; j >= 0; --j) {
-        const int c = lane * 4 + j;
-        if (c < nc && e[j] > 0.f && before + cum[j] > target) pick = c;
+        for (int j = 3; j >= 0; --j) {
+            const int c = lane * 4 + j;
+            if (c < nc && e[j] > 0.f && before + cum[j] > target) pick = c;
+        }
+        // the first lane (lowest classes) whose cumulative mass passes the target wins
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) pick = min(pick, __shfl_xor(pick, d, 64));
+        if (pick == INT_MAX) {                       // u * total rounded past the last kept class: take that class
+            int last = -1;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) last = e[j] > 0.f ? lane * 4 + j : last;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) last = max(last, __shfl_xor(last, d, 64));
+            pick = last < 0 ? 0 : last;
+        }
+        if (lane == 0) {
+            tokens[(long)n * n_attr + a] = pick;
+            if (song && step < song_rows) song[((long)step * gridDim.x + n) * n_attr + a] = pick;
+        }
     }
-    // the first lane (lowest classes) whose cumulative mass passes the target wins
+    if constexpr (LOGP) {
+        // model log-prob: the raw logits' max and sum, or the sampler's own when they are the same numbers
+        float mx = m, sx;
+        if (A.inv_t[a] == 1.0f && !row_masked) {
+            sx = A.top_p[a] < 1.0f ? tot_all : total;
+        } else {
+            float w[4];
+            mx = -INFINITY;
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) pick = min(pick, __shfl_xor(pick, d, 64));
-    if (pick == INT_MAX) {                           // u * total rounded past the last kept class: take that class
-        int last = -1;
+            for (int j = 0; j < 4; ++j) {
+                w[j] = lane * 4 + j < nc ? x[lane * 4 + j] : -INFINITY;
+                mx = fmaxf(mx, w[j]);
+            }
+            mx = wave_max(mx);
+            float s4 = 0.f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) last = e[j] > 0.f ? lane * 4 + j : last;
+            for (int j = 0; j < 4; ++j) s4 += lane * 4 + j < nc ? expf(w[j] - mx) : 0.f;
+            sx = wave_sum(s4);
+        }
+        // the picked class's lane holds its tempered logit and kept bit; one bpermute brings them to every lane
+        float lq = -INFINITY;
 #pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) last = max(last, __shfl_xor(last, d, 64));
-        pick = last < 0 ? 0 : last;
-    }
-    if (lane == 0) {
-        tokens[(long)n * n_attr + a] = pick;
-        if (song && step < song_rows) song[((long)step * gridDim.x + n) * n_attr + a] = pick;
+        for (int j = 0; j < 4; ++j)
+            if (lane * 4 + j == pick && keep[j]) lq = (v[j] - m) - logf(total);
+        const int owner = pick < nc ? pick >> 2 : 0;
+        lq = __shfl(lq, owner, 64);
+        if (lane == 0) {
+            const float lm = pick < nc ? (x[pick] - mx) - logf(sx) : -INFINITY;
+            const long o = L.out_counter ? ((*L.out_counter % L.out_rows) + L.out_rows) % L.out_rows : 0;
+            *reinterpret_cast<float2*>(L.logp + ((o * gridDim.x + n) * n_attr + a) * 2) = make_float2(lm, lq);
+        }
     }
 }
 
 }  // namespace cwlt
 
+template <bool MASKED, bool LOGP, bool FORCED>
+static void launch_sample(int64_t rows, int n_attr, void* stream, const float* logits, int64_t ld,
+                          const cwlt::SampleArgs& A, uint64_t seed, const int64_t* counter, int64_t* tokens,
+                          int64_t* song, int64_t song_rows, int slot_keyed, const int64_t* row_key,
+                          const int64_t* row_step, const cwlt::MaskArgs& M, const cwlt::LogpArgs& L) {
+    hipLaunchKernelGGL((cwlt::sample_categorical_kernel<MASKED, LOGP, FORCED>), dim3((unsigned)rows), dim3(64 * n_attr),
+                       0, (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
+                       (long)song_rows, slot_keyed, row_key, row_step, M, L);
+}
+
+// lp: the log-prob output (LOGP instantiations); forced: score lp->targets instead of drawing (FORCED).
 static int sample(const float* logits, const int* n_class, const float* temperature, const float* top_p, int n_attr,
                   int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter, int64_t* tokens, int64_t* song,
                   int64_t song_rows, int slot_keyed, void* stream, const int64_t* row_key = nullptr,
-                  const int64_t* row_step = nullptr, const cwlt::MaskArgs* mask = nullptr) {
+                  const int64_t* row_step = nullptr, const cwlt::MaskArgs* mask = nullptr,
+                  const cwlt::LogpArgs* lp = nullptr, bool forced = false) {
     using namespace cwlt;
-    if (!logits || !n_class || !tokens || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0) return CWLT_ERR_ARG;
+    if (!logits || !n_class || (!tokens && !forced) || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0)
+        return CWLT_ERR_ARG;
     SampleArgs A;
     int off = 0;
     for (int a = 0; a < n_attr; ++a) {
@@ -175,16 +262,21 @@ static int sample(const float* logits, const int* n_class, const float* temperat
         off += n_class[a];
     }
     if (ld < off) return CWLT_ERR_ARG;
-    if (mask) {
-        if ((int64_t)mask->words * 32 < off) return CWLT_ERR_ARG;
-        hipLaunchKernelGGL(sample_categorical_kernel<true>, dim3((unsigned)rows), dim3(64 * n_attr), 0,
-                           (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
-                           (long)song_rows, slot_keyed, row_key, row_step, *mask);
-    } else {
-        hipLaunchKernelGGL(sample_categorical_kernel<false>, dim3((unsigned)rows), dim3(64 * n_attr), 0,
-                           (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
-                           (long)song_rows, slot_keyed, row_key, row_step, MaskArgs{});
-    }
+    if (mask && (int64_t)mask->words * 32 < off) return CWLT_ERR_ARG;
+    const MaskArgs M = mask ? *mask : MaskArgs{};
+    const LogpArgs L = lp ? *lp : LogpArgs{};
+    if (!lp)
+        (mask ? launch_sample<true, false, false> : launch_sample<false, false, false>)(
+            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
+            M, L);
+    else if (!forced)
+        (mask ? launch_sample<true, true, false> : launch_sample<false, true, false>)(
+            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
+            M, L);
+    else
+        (mask ? launch_sample<true, true, true> : launch_sample<false, true, true>)(
+            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
+            M, L);
     return (int)hipGetLastError();
 }
 
@@ -225,6 +317,49 @@ extern "C" int cwlt_sample_categorical_masked(const float* logits, const int* n_
     const MaskArgs M{bar, sched, masks, (long)n_sched, (long)mask_rows, mask_words};
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
                   0, 1, stream, key, step, &M);
+}
+
+// Mask table arguments shared by the log-prob entries: all three pointers, or none (unmasked).  -> 0 ok, 1 refused.
+static int logp_mask(const int64_t* bar, const int64_t* sched, int64_t n_sched, const uint32_t* masks,
+                     int64_t mask_rows, int mask_words, cwlt::MaskArgs* M, bool* masked) {
+    *masked = bar || sched || masks;
+    if (!*masked) return 0;
+    if (!bar || !sched || !masks || n_sched < 1 || mask_rows < 1 || mask_words < 1) return 1;
+    *M = cwlt::MaskArgs{bar, sched, masks, (long)n_sched, (long)mask_rows, mask_words};
+    return 0;
+}
+
+extern "C" int cwlt_sample_categorical_logp(const float* logits, const int* n_class, const float* temperature,
+                                            const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                            const int64_t* counter, const int64_t* key, const int64_t* step,
+                                            const int64_t* bar, const int64_t* sched, int64_t n_sched,
+                                            const uint32_t* masks, int64_t mask_rows, int mask_words,
+                                            int64_t* tokens, float* logp, const int64_t* out_counter,
+                                            int64_t out_rows, void* stream) {
+    using namespace cwlt;
+    if (!logp || rows > (1L << 20) || out_rows < 1 || (out_counter == nullptr && out_rows != 1)) return CWLT_ERR_ARG;
+    if (!key != !step || (!key && !counter)) return CWLT_ERR_ARG;    // keyed per row, or by slot and counter
+    MaskArgs M{};
+    bool masked = false;
+    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    const LogpArgs L{logp, out_counter, (long)out_rows, nullptr};
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
+                  0, 1, stream, key, step, masked ? &M : nullptr, &L);
+}
+
+extern "C" int cwlt_score_categorical(const float* logits, const int* n_class, const float* temperature,
+                                      const float* top_p, int n_attr, int64_t rows, int64_t ld, const int64_t* targets,
+                                      const int64_t* key, const int64_t* bar, const int64_t* sched, int64_t n_sched,
+                                      const uint32_t* masks, int64_t mask_rows, int mask_words, float* logp,
+                                      void* stream) {
+    using namespace cwlt;
+    if (!logp || !targets || rows > (1L << 20)) return CWLT_ERR_ARG;
+    MaskArgs M{};
+    bool masked = false;
+    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    const LogpArgs L{logp, nullptr, 1, targets};
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, 0, nullptr, nullptr, nullptr, 0, 1, stream,
+                  key, nullptr, masked ? &M : nullptr, &L, true);
 }
 
 namespace cwlt {

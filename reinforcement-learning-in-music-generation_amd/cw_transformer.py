@@ -175,10 +175,18 @@ class CWTrunk(nn.Module):
         kernel="gemm": the batch-invariant prefill (RecurrentTransformerEncoder.prefill(kernel="gemm")): in_linear is a
         cwlt_decode_gemm too (pe[0] added in its epilogue), at most `rows` rows per call, and sequence n's state, hidden
         row and logits are bitwise independent of the other sequences, of L and of `rows`.  logits=True (gemm only):
-        -> (hidden, logits (N, sum n_token)), the heads run as the GEMM decode step runs them."""
+        -> (hidden, logits (N, sum n_token)), the heads run as the GEMM decode step runs them.
+
+        logits="all": the heads on EVERY row -> (N, L, sum n_token) f32 logits, row t the next-token logits after
+        tokens[n, :t + 1] on the recurrent form (pe[0] on every row), what step(tokens[n, t]) returns there; rows at or
+        past lengths[n] are padding.  gemm: the stacked heads as one more cwlt_decode_gemm over all N * L rows (the last
+        norm2 and the final norm as its prologue, at most `rows` rows per call), bitwise independent of the other
+        sequences, of L and of `rows`.  blas: the encoder's rows through an f32 heads GEMM with TF32 off."""
         if kernel not in ("blas", "gemm"):
             raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
-        if logits and kernel != "gemm":
+        if logits not in (False, True, "all"):
+            raise ValueError("logits must be False, True or 'all', got %r" % (logits,))
+        if logits is True and kernel != "gemm":
             raise ValueError("logits=True needs kernel='gemm'")
         if not self._recurrent:
             raise RuntimeError("prefill needs a model built with is_training=False (recurrent encoder)")
@@ -194,17 +202,29 @@ class CWTrunk(nn.Module):
             dev_len = (idx + 1).to(torch.int32).to(tokens.device)
         D = self.d_model
         if kernel == "gemm":
-            h, lg = self._prefill_gemm(tokens, memory, dev_len, idx.to(tokens.device), rows)
-            return (h, lg) if logits else h
+            h, lg = self._prefill_gemm(tokens, memory, dev_len, idx.to(tokens.device), rows, all_rows=logits == "all")
+            return lg if logits == "all" else (h, lg) if logits else h
         x = self.embed(tokens).reshape(N * L, D)
         x = ops.posenc_dropout(x, self.pos_emb.pe.reshape(-1, D), 1).view(N, L, D)      # x + pe[0] on every row
         h = self.transformer_encoder.prefill(x, memory, dev_len)
+        if logits == "all":
+            heads = self._heads()
+            hw = torch.cat([ops._f32(m.weight) for m in heads], 0)
+            hb = torch.cat([ops._f32(m.bias) for m in heads], 0)
+            tf32 = torch.backends.cuda.matmul.allow_tf32
+            torch.backends.cuda.matmul.allow_tf32 = False
+            try:
+                with torch.no_grad():
+                    return torch.addmm(hb, h.reshape(N * L, D), hw.t()).view(N, L, -1)
+            finally:
+                torch.backends.cuda.matmul.allow_tf32 = tf32
         return h[torch.arange(N, device=h.device), idx.to(h.device)]
 
-    def _prefill_gemm(self, tokens, memory, lengths, last, rows=None):
+    def _prefill_gemm(self, tokens, memory, lengths, last, rows=None, all_rows=False):
         """prefill_hidden(kernel="gemm", logits=True) on device arguments only (no host sync, so it can be enqueued
         between the replays of a running stream): tokens (N, L, 6) int64, lengths (N) int32 or None, last (N) int64 =
-        lengths - 1, all on the GPU.  -> (hidden (N, D), logits (N, sum n_token))."""
+        lengths - 1, all on the GPU.  -> (hidden (N, D), logits (N, sum n_token)); all_rows=True: (None, logits (N, L,
+        sum n_token)), the heads on every row (prefill_hidden(logits="all"))."""
         rows = 4096 if rows is None else int(rows)
         if not 1 <= rows <= 4096:
             raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
@@ -222,7 +242,7 @@ class CWTrunk(nn.Module):
             hw = torch.cat([ops._f32(m.weight) for m in heads], 0)
             hb = torch.cat([ops._f32(m.bias) for m in heads], 0)
             return self.transformer_encoder.prefill(x.view(N, L, D), memory, lengths, kernel="gemm", last=last,
-                                                    heads=(hw, hb), rows=rows)
+                                                    heads=(hw, hb), rows=rows, all_rows=all_rows)
 
     def _losses(self, h, target, loss_mask):
         logits = self.fused_logits(h)

@@ -594,16 +594,20 @@ class _DeviceLoop:
 
     mask: constrained mode, {"sched", "masks"} (_device_constraints) and "bar" ((n_songs,) int64 device bar counts
     before the next row), "bar_mask" ((n_class[2],) int32 Bar classes): the draw is cwlt_sample_categorical_masked,
-    then cwlt_count_bars advances the bar counts, both inside the captured token."""
+    then cwlt_count_bars advances the bar counts, both inside the captured token.
+
+    logprobs=True: the draw is cwlt_sample_categorical_logp (the same tokens), which also writes each drawn class's
+    (model, sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects."""
 
     def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None,
-                 mask=None):
+                 mask=None, logprobs=False):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
         self.mask = mask
         self.A, self.N = len(sess.n_token), sess.n_songs
         self.ring = None if ring is None or int(ring) >= self.capacity else int(ring)
         rows = self.capacity if self.ring is None else self.ring
         self.song = torch.zeros((rows, self.N, self.A), dtype=torch.int64, device=sess.dev)
+        self.logp = torch.zeros((rows, self.N, self.A, 2), dtype=torch.float32, device=sess.dev) if logprobs else None
         self.count = torch.zeros(1, dtype=torch.int64, device=sess.dev)
         if self.ring is not None:
             self.slot = torch.zeros(1, dtype=torch.int64, device=sess.dev)       # count % ring
@@ -615,7 +619,16 @@ class _DeviceLoop:
     def _draw(self, logits):
         s = self.sess
         tok = s.tok.view(self.N, self.A)
-        if self.mask is None:
+        if self.logp is not None:
+            m = {} if self.mask is None else self.mask
+            ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.logp, counter=self.count,
+                                        bar=m.get("bar"), sched=m.get("sched"), masks=m.get("masks"),
+                                        out_counter=self.count, temperature=self.temperature, top_p=self.top_p)
+            if self.mask is not None:
+                ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
+            if self.ring is None:
+                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
+        elif self.mask is None:
             ops.sample_categorical(logits, s.n_token, tok, self.seed, counter=self.count,
                                    song=self.song if self.ring is None else None, temperature=self.temperature,
                                    top_p=self.top_p, slot_keys=True)
@@ -678,6 +691,16 @@ class _DeviceLoop:
         idx = torch.arange(start, stop, device=self.song.device) % self.ring
         return self.song.index_select(0, idx).cpu().numpy()
 
+    def logprobs(self, start, stop):
+        """The log-probs of rows [start, stop) as host numpy (rows, n_songs, 6, 2) (logprobs=True; syncs)."""
+        if self.logp is None:
+            raise RuntimeError("this loop was built without logprobs=True")
+        self.tokens(start, stop)                                     # the same checks (and sync)
+        if self.ring is None:
+            return self.logp[start:stop].cpu().numpy()
+        idx = torch.arange(start, stop, device=self.logp.device) % self.ring
+        return self.logp.index_select(0, idx).cpu().numpy()
+
 
 class _StreamLoop:
     """Continuous batching on the device: `sess` (DecodeSession(n_songs=slots, kernel="gemm")) is a pool of decode slots
@@ -688,10 +711,13 @@ class _StreamLoop:
       cwlt_sample_categorical_keyed: each slot's draw keyed by (song index, position in song);
       cwlt_stream_advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count
         advanced, the song's end detected, finished slots handed the next song indices in slot order.
-    The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host."""
+    The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host.
+    logprobs=True: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
+    log-probs into `lp_ring` (2 chunk, slots, A, 2) at the row ctl[0] selects -- the row of `ring` the advance writes --
+    copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`)."""
 
     def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 temperature=None, top_p=None, graph=None, mask=None):
+                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
@@ -711,6 +737,7 @@ class _StreamLoop:
         self.ctl = torch.tensor([0, min(self.S, self.n_songs), 0], dtype=torch.int64, device=dev)
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._init_logprobs(logprobs)
         self._host_ctl = [torch.zeros(3, dtype=torch.int64).pin_memory() for _ in range(2)]
         self._events = [torch.cuda.Event(), torch.cuda.Event()]
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
@@ -727,11 +754,32 @@ class _StreamLoop:
         ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
                            self.pos, self.bar, self.fresh, self.ctl, self.ring)
 
+    def _init_logprobs(self, logprobs):
+        dev = self.sess.dev
+        self.lp_ring = torch.zeros((2 * self.chunk, self.S, self.A, 2), dtype=torch.float32, device=dev) \
+            if logprobs else None
+        self._host_lp = [torch.zeros((self.chunk, self.S, self.A, 2), dtype=torch.float32).pin_memory()
+                         for _ in range(2)] if logprobs else None
+        self.lp_parts = []
+
+    def _read(self, h):
+        """The rows of ring half h that belong to songs (waiting and idle slots write song < 0), and their log-probs
+        into lp_parts by the same mask.  Boolean indexing copies: the pinned buffers are reused."""
+        rows = self._host[h].numpy().reshape(-1, self.A + 2)
+        keep = rows[:, 0] >= 0
+        if self.lp_ring is not None:
+            self.lp_parts.append(self._host_lp[h].numpy().reshape(-1, self.A, 2)[keep])
+        return rows[keep]
+
     def _sample(self, logits, tok):
         """Each slot's draw keyed by (song index, position in song); constrained (mask: _device_constraints) by the
         song's mask row for the slot's bar count."""
         s = self.sess
-        if self.mask is None:
+        if self.lp_ring is not None:
+            m = {} if self.mask is None else {"bar": self.bar, "sched": self.mask["sched"], "masks": self.mask["masks"]}
+            ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.lp_ring, key=self.song, step=self.pos,
+                                        out_counter=self.ctl, temperature=self.temperature, top_p=self.top_p, **m)
+        elif self.mask is None:
             ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
                                          temperature=self.temperature, top_p=self.top_p)
         else:
@@ -759,6 +807,8 @@ class _StreamLoop:
         k = self.enqueued // self.chunk - 1
         h = k % 2
         self._host[h].copy_(self.ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
+        if self.lp_ring is not None:
+            self._host_lp[h].copy_(self.lp_ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
         self._host_ctl[h].copy_(self.ctl, non_blocking=True)
         self._events[h].record()
         return h
@@ -773,8 +823,7 @@ class _StreamLoop:
             t = time.perf_counter()
             self._events[h].synchronize()
             self.wait_s += time.perf_counter() - t
-            rows = self._host[h].numpy().reshape(-1, self.A + 2)
-            parts.append(rows[rows[:, 0] >= 0])                   # boolean indexing copies: the buffer is reused
+            parts.append(self._read(h))
             if int(self._host_ctl[h][2]) >= self.n_songs:
                 break
             if self.enqueued > limit:
@@ -795,7 +844,7 @@ class _BankStreamLoop(_StreamLoop):
     cwlt_stream_advance_bank (a slot takes a song only below ctl[3], otherwise it waits)."""
 
     def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
-                 top_p=None, graph=None, prefill_rows=None, mask=None):
+                 top_p=None, graph=None, prefill_rows=None, mask=None, logprobs=False):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
@@ -836,6 +885,7 @@ class _BankStreamLoop(_StreamLoop):
         self.ctl = torch.zeros(4, dtype=torch.int64, device=dev)
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._init_logprobs(logprobs)
         self._host_ctl = [torch.zeros(4, dtype=torch.int64).pin_memory() for _ in range(2)]
         self._events = [torch.cuda.Event(), torch.cuda.Event()]
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
@@ -911,8 +961,7 @@ class _BankStreamLoop(_StreamLoop):
             t = time.perf_counter()
             self._events[h].synchronize()
             self.wait_s += time.perf_counter() - t
-            rows = self._host[h].numpy().reshape(-1, self.A + 2)
-            parts.append(rows[rows[:, 0] >= 0])
+            parts.append(self._read(h))
             ctl = self._host_ctl[h].numpy().copy()
             if ctl[2] >= self.n_songs:
                 break
@@ -974,7 +1023,7 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 
 def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_tokens, prompts, sampler, chunk, bank,
-                             prefill_rows, log, constraints=None):
+                             prefill_rows, log, constraints=None, logprobs=False):
     start = time.perf_counter()
     n_token = list(model.n_token)
     heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
@@ -991,17 +1040,19 @@ def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_to
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
     loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
                            temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows,
-                           mask=None if table is None else _device_constraints(table, sess.dev))
+                           mask=None if table is None else _device_constraints(table, sess.dev), logprobs=logprobs)
     rows = loop.run(max(caps))
     return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
                                       "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
 
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None):
+                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
+                     return_logprobs=False):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
-    prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks."""
+    prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
+    return_logprobs=True: -> ((songs, logprobs), stats)."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if model.training:
@@ -1026,7 +1077,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompts is not None:
         heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
                                                                    max_tokens, prompts, sampler, chunk, bank,
-                                                                   prefill_rows, log, constraints)
+                                                                   prefill_rows, log, constraints, return_logprobs)
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
@@ -1053,7 +1104,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
         loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
                            temperature=temperature, top_p=top_p, graph=sess.use_graph,
-                           mask=None if table is None else _device_constraints(table, sess.dev))
+                           mask=None if table is None else _device_constraints(table, sess.dev),
+                           logprobs=return_logprobs)
         rows = loop.run()
         heads = [head] * n_songs
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
@@ -1073,11 +1125,14 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     stats.update(extra)
     if log is not None:
         log("stream of %d songs on %d slots: %d tokens, %d steps" % (n_songs, slots, stats["tokens"], loop.enqueued))
+    if return_logprobs:            # filtered by the same mask as the rows, in the same order: the same sort applies
+        return (songs, np.split(np.concatenate(loop.lp_parts)[order], ends[:-1])), stats
     return songs, stats
 
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
-                    chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None):
+                    chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
+                    return_logprobs=False):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -1102,13 +1157,25 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained).
     The host compiles them into one device table before the first token (compile_constraints) and each slot's draw
     is masked by its song's row for the slot's bar count (cwlt_sample_categorical_masked); song k is still bitwise
-    song k of generate_batch(..., constraints=constraints)."""
+    song k of generate_batch(..., constraints=constraints).
+
+    return_logprobs=True: -> (songs, logprobs), logprobs[k] the (L_k - P_k, 6, 2) f32 log-probs of song k's drawn rows
+    (P_k its prompt's length), [..., 0] the model's and [..., 1] the sampler's (score_songs' layout), as
+    the device sampler wrote them (cwlt_sample_categorical_logp): bitwise those of generate_batch(...,
+    return_logprobs=True).  The songs are the same as without the flag."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
-                            prefill_rows=prefill_rows, constraints=constraints)[0]
+                            prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs)[0]
 
 
-def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None):
+def _refuse_logprobs(return_logprobs, where):
+    if return_logprobs:
+        raise ValueError("%s samples one song on the host or its one-song loop: log-probs come from the device samplers "
+                         "of generate_batch / generate_stream (return_logprobs=True), or score_songs()" % where)
+
+
+def categorical_rollout(model, token_count, init=None, carry_memory=False, graph=None, prompt=None,
+                        return_logprobs=False):
     """ppo_policy/inference.py:78-160 (`testing()`): start from the all-zero token, per step run the recurrent-form
     actor on the PREVIOUS token only -- the reference passes `memory=None` on every call (:106), so no state is
     carried; `carry_memory=True` is the evident intent -- and draw each attribute from Categorical(softmax(logits))
@@ -1118,7 +1185,8 @@ def categorical_rollout(model, token_count, init=None, carry_memory=False, graph
     prompt: a (P, 6) CW token array to continue (e.g. a slice of a dataset song): it is prefilled in one pass
     (DecodeSession.prefill), the first token is drawn from its logits on the device, and the result is the prompt
     followed by token_count drawn tokens.  Needs carry_memory=True: with the reference's fresh state per token the
-    prompt would be thrown away after its last token."""
+    prompt would be thrown away after its last token.  return_logprobs=True is refused (score_songs scores a song)."""
+    _refuse_logprobs(return_logprobs, "categorical_rollout")
     if prompt is not None and not carry_memory:
         raise ValueError("a prompt needs carry_memory=True: the reference's memory=None per step would discard it")
     if prompt is not None and init is not None:
@@ -1148,14 +1216,16 @@ DQN_TOP_P = (0.9, 0.99, None, 0.9, 0.9, None)
 
 
 def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=None, session=None,
-                           device_sampling=False, chunk=128):
+                           device_sampling=False, chunk=128, return_logprobs=False):
     """testing-no-type-cp.py:126-179: start from the Bar token, sample until `bar_cond` bars have begun.
     `max_tokens` (not in the reference, whose loop is unbounded) caps the song length.
 
     device_sampling=False: the reference's numpy samplers on the host (a seeded np.random reproduces its stream).
     device_sampling=True: the same per-attribute temperature / nucleus settings drawn on the device
     (`cwlt_sample_categorical`); the host only looks at the song every `chunk` tokens to count bars, and cuts it
-    where the reference's loop would have stopped.  Same distribution, different random stream, ~1.2x faster (no host round trip per token)."""
+    where the reference's loop would have stopped.  Same distribution, different random stream, ~1.2x faster (no host round trip per token).
+    return_logprobs=True is refused (score_songs scores a song)."""
+    _refuse_logprobs(return_logprobs, "inference_from_scratch")
     classes = list(word2event.keys())
     sess = session or DecodeSession(model)
     sess.reset()
@@ -1207,7 +1277,7 @@ def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=Non
 
 
 def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, log=None, session=None,
-                          device_sampling=False, chunk=128):
+                          device_sampling=False, chunk=128, return_logprobs=False):
     """Continue a piece: `prompt` ((P, 6) CW tokens, e.g. a slice of a dataset song or an earlier song's .npy) is
     prefilled in one pass (DecodeSession.prefill) and the reference's sampling loop runs on from its logits.  The
     result is the prompt followed by the continuation.  The bar rule is the reference's, applied as if the prompt's
@@ -1217,7 +1287,9 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
     device_sampling=False: the reference's numpy samplers on the host, the first token drawn from the prefill logits.
     device_sampling=True: every token, the first included, drawn on the device (`cwlt_sample_categorical`, keyed by
-    the loop's counter), with no host round trip between the prefill and the loop."""
+    the loop's counter), with no host round trip between the prefill and the loop.
+    return_logprobs=True is refused (score_songs scores a song)."""
+    _refuse_logprobs(return_logprobs, "inference_from_prompt")
     classes = list(word2event.keys())
     prompt = np.asarray(prompt, dtype=np.int64).reshape(-1, len(classes))
     if len(prompt) == 0:
@@ -1273,7 +1345,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
-                   log=None, prefill="blas", constraints=None):
+                   log=None, prefill="blas", constraints=None, return_logprobs=False):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -1293,7 +1365,12 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained),
     compiled into one device table before the first token.  The loop then keeps each song's bar count on the device
     (from its prompt's count; cwlt_count_bars after every draw) and masks each draw by the song's row for that count
-    (cwlt_sample_categorical_masked).  None: the unconstrained sampler, unchanged."""
+    (cwlt_sample_categorical_masked).  None: the unconstrained sampler, unchanged.
+
+    return_logprobs=True: -> (songs, logprobs), logprobs[i] the (L_i - P_i, 6, 2) f32 log-probs of song i's drawn rows
+    (P_i its prompt's length; [..., 0] model, [..., 1] sampler, score_songs' layout), written by the
+    device sampler itself (cwlt_sample_categorical_logp, into a float ring beside the token ring).  The songs are
+    bitwise those drawn without the flag."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if prefill not in ("blas", "gemm"):
@@ -1342,7 +1419,7 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         mask["bar_mask"] = torch.as_tensor(np.array([names[i] == "Bar" for i in range(sess.n_token[2])],
                                                     dtype=np.int32)).to(sess.dev)
     loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
-                       ring=chunk, mask=mask)
+                       ring=chunk, mask=mask, logprobs=return_logprobs)
     if prompts is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
                        .view(n_songs, 1, A).to(sess.dev))
@@ -1354,16 +1431,20 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
         loop.start(sess._prefill(toks, lengths, kernel=prefill))
     drawn = [[] for _ in range(n_songs)]
+    lp_drawn = [[] for _ in range(n_songs)] if return_logprobs else None
     live = set(range(n_songs))
     done = 0
     while done < cap and live:
         stop = min(cap, done + chunk)
         loop.run(stop - loop.enqueued)
         rows = loop.tokens(done, stop)                                # (stop - done, N, 6)
+        lps = loop.logprobs(done, stop) if return_logprobs else None  # (stop - done, N, 6, 2)
         for i in sorted(live):
             for t in range(min(stop, caps[i]) - done):
                 row = rows[t, i]
                 drawn[i].append(row)
+                if lp_drawn is not None:
+                    lp_drawn[i].append(lps[t, i])
                 if is_bar(row):
                     cnt_bar[i] += 1
                 if cnt_bar[i] == bar_cond:
@@ -1374,12 +1455,139 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     songs = [np.concatenate([p, np.asarray(d, dtype=np.int64).reshape(-1, A)]) for p, d in zip(heads, drawn)]
     if log is not None:
         log("batch of %d songs: %d tokens, %d steps" % (n_songs, sum(len(x) for x in songs), done))
+    if return_logprobs:
+        return songs, [np.asarray(l, dtype=np.float32).reshape(-1, A, 2) for l in lp_drawn]
     return songs
+
+
+SCORE_BLOCK_SONGS = 1024    # most songs in one score_songs block: bounds its scratch decode state (1.6 MB a song at repo dims)
+
+
+def song_bar_counts(song, word2event):
+    """The bar count each row after the first of `song` ((L, 6) CW tokens) is drawn under, by the generation bar rule
+    -> (L - 1,) int64: entry t (row t + 1) is 1 + the Bar tokens of song[1:t + 1], the count the prompt song[:t + 1]
+    leaves (cut_prompt, generate_batch) -- the Bar token that opens a bar is drawn under the bar before it."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1, len(word2event))
+    if len(song) < 2:
+        return np.zeros(0, dtype=np.int64)
+    names = word2event["bar-beat"]
+    bars = np.array([names[int(r[2])] == "Bar" for r in song[1:-1]], dtype=np.int64)
+    return 1 + np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(bars)])
+
+
+def _score_inputs(songs, mask, n_token):
+    """score_songs' song forms -> list of (L_i, A) int64 arrays, checked as prefill checks a prompt."""
+    A = len(n_token)
+    if isinstance(songs, (np.ndarray, torch.Tensor)) and np.ndim(songs) == 3:
+        x = np.asarray(songs.cpu() if isinstance(songs, torch.Tensor) else songs, dtype=np.int64)
+        if mask is None:
+            out = list(x)
+        else:
+            m = np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask)
+            if m.shape != x.shape[:2]:
+                raise ValueError("mask must be (n_seq, T) = %s, got %s" % (x.shape[:2], m.shape))
+            out = [x[i][:int((m[i] > 0).sum())] for i in range(len(x))]
+    else:
+        if mask is not None:
+            raise ValueError("mask belongs to the dataset-array form (songs (n_seq, T, 6))")
+        out = [np.asarray(s, dtype=np.int64).reshape(-1, A) for s in songs]
+    for i, s in enumerate(out):
+        if s.ndim != 2 or s.shape[1] != A:
+            raise ValueError("song %d must be (L, %d), got %s" % (i, A, s.shape))
+        if len(s) == 0:
+            raise ValueError("song %d is empty" % i)
+        bad = (s < 0) | (s >= np.asarray(n_token))
+        if bad.any():
+            t, a = np.argwhere(bad)[0]
+            raise ValueError("song %d, token %d: id %d out of range for attribute %d (%d classes)"
+                             % (i, t, s[t, a], a, n_token[a]))
+    return out
+
+
+def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
+                prefill_rows=None):
+    """Log-likelihoods of given songs under the recurrent form, as generation samples them.
+    -> list of (L_i - 1, 6, 2) float32 arrays; row t is about song[t + 1] given song[:t + 1] (pe[0] on every row, as
+    DecodeSession.step and prefill compute it): [..., 0] the model log-prob log_softmax(logits_t[a])[song[t + 1, a]]
+    (temperature 1, no mask, no nucleus), [..., 1] the sampler log-prob log q(song[t + 1, a]) with q what the device
+    sampler draws from: the tempered logits, the constraint mask, the nucleus kept set, renormalised; -inf outside the
+    kept set or the mask.  A generated song with a P-row prompt has drawn rows song[P:]: their log-probs are rows
+    P - 1 ... L - 2, what generate_batch / generate_stream(return_logprobs=True) return for it.
+
+    songs: a list of (L_i, 6) arrays, or a dataset array (n_seq, T, 6) with mask (n_seq, T) (rows > 0 are the song).
+    sampler: "dqn" (forward_output_sampling's temperature / nucleus settings) or "categorical", as in generate_batch.
+    constraints: as in generate_batch; row t + 1 is masked by the song's entry for bar count song_bar_counts()[t].
+    The table is compiled for the largest bar count among the songs; a constraint that could never end is not refused
+    (the songs are given, not drawn).
+    kernel="gemm": the batch-invariant prefill with the heads on every row (prefill_hidden(logits="all")) -- song k's
+    scores are bitwise the same whatever the other songs, their order and lengths, and prefill_rows.  "blas": the
+    hipBLASLt prefill, faster and not batch invariant.  Songs go in blocks of whole songs under prefill_rows token rows
+    (default PREFILL_ROWS; at most SCORE_BLOCK_SONGS songs), each block on a fresh scratch state: no session is
+    touched.  The logits are scored by cwlt_score_categorical, the sampler's own kernel body, so the logits a draw came
+    from, scored at the class it drew, give the sampler's pair bitwise.
+    Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range."""
+    if sampler not in ("dqn", "categorical"):
+        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
+    if kernel not in ("blas", "gemm"):
+        raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
+    if not getattr(model, "_recurrent", False):
+        raise RuntimeError("scoring needs a model built with is_training=False (recurrent encoder)")
+    if model.training:
+        raise RuntimeError("scoring runs in eval() mode (agent_pretrain.py:657)")
+    if model.compute_dtype != torch.float32:
+        raise RuntimeError("scoring computes in f32: this model runs %s activations" % model.compute_dtype)
+    n_token = list(model.n_token)
+    A = len(n_token)
+    songs = _score_inputs(songs, mask, n_token)
+    n = len(songs)
+    if n == 0:
+        return []
+    rows_budget = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
+    if rows_budget < 1:
+        raise ValueError("prefill_rows must be >= 1, got %d" % rows_budget)
+    dev = next(model.parameters()).device
+    bars = [song_bar_counts(x, word2event) for x in songs]
+    dmask = None
+    if constraints is not None:
+        top = max([int(b.max()) for b in bars if len(b)] + [1])
+        # max_tokens = the longest song: every song ends, so compile_constraints' "could never end" check is skipped
+        table = compile_constraints(constraints, n, n_token, top + 1, [1] * n, max(len(x) for x in songs))
+        dmask = None if table is None else _device_constraints(table, dev)
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    enc = model.transformer_encoder
+    H = enc.layers[0].attention.n_heads
+    d = model.d_model // H
+    per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
+    out = []
+    for a0 in range(0, n, per):
+        blk = songs[a0:a0 + per]
+        nb, Lb = len(blk), max(len(x) for x in blk)
+        toks = np.zeros((nb, Lb, A), dtype=np.int64)
+        tgt = np.full((nb, Lb, A), -1, dtype=np.int64)          # the last row of a song and padding: not scored
+        bar = np.ones((nb, Lb), dtype=np.int64)
+        for i, x in enumerate(blk):
+            toks[i, :len(x)] = x
+            tgt[i, :len(x) - 1] = x[1:]
+            bar[i, :len(x) - 1] = bars[a0 + i]
+        memory = [[torch.zeros((nb, H, d, d), dtype=torch.float32, device=dev),
+                   torch.zeros((nb, H, d), dtype=torch.float32, device=dev)] for _ in enc.layers]
+        with torch.no_grad():
+            lg = model.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
+                                      logits="all")
+            m = {}
+            if dmask is not None:
+                m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
+                     "bar": torch.as_tensor(bar.reshape(-1)).to(dev), "sched": dmask["sched"], "masks": dmask["masks"]}
+            lp = ops.score_categorical(lg.reshape(nb * Lb, -1), n_token, torch.as_tensor(tgt.reshape(-1, A)).to(dev),
+                                       temperature=temperature, top_p=top_p, **m)
+        lp = lp.view(nb, Lb, A, 2).cpu().numpy()
+        out.extend(lp[i, :len(x) - 1].copy() for i, x in enumerate(blk))
+    return out
 
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None, slots=None, prompts=None, constraints=None):
+             batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1391,9 +1599,14 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     prompts: a list of n_songs (P_i, 6) arrays, song i continues prompts[i] (not together with prompt): on the stream
     with slots, each batch_size group with its own slice of the list, or one song at a time.
     constraints: one Constraint for every song or a list of n_songs Constraint / None entries (generate_batch,
-    generate_stream), with slots or batch_size only: the one-song path samples on the host."""
+    generate_stream), with slots or batch_size only: the one-song path samples on the host.
+    logprobs=True (with slots or batch_size only): save each song's drawn-row log-probs (return_logprobs of
+    generate_stream / generate_batch) as get_<i>_logp.npy next to the song."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if logprobs and batch_size is None and slots is None:
+        raise ValueError("log-probs come from the device samplers of generate_batch / generate_stream: pass batch_size "
+                         "or slots (or score the songs with score_songs)")
     if constraints is not None:
         if batch_size is None and slots is None:
             raise ValueError("constraints run in the device samplers of generate_batch / generate_stream: pass "
@@ -1410,6 +1623,9 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     song_time_list, words_len_list = [], []
 
     def save(sidx, res):
+        if logprobs:
+            res, lp = res
+            np.save(os.path.join(path_gendir, "get_%d_logp.npy" % sidx), lp)
         if write_midi is not None:
             write_midi(res, os.path.join(path_gendir, "get_%d.mid" % sidx), word2event)
         else:
@@ -1419,10 +1635,13 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                 prompt=prompt, prompts=None if prompts is None else list(prompts),
-                                constraints=constraints)
+                                constraints=constraints, return_logprobs=logprobs)
         wall = time.time() - start
+        if logprobs:
+            songs = list(zip(*songs))
         for sidx, res in enumerate(songs):
             save(sidx, res)
+            res = res[0] if logprobs else res
             song_time_list.append(wall / n_songs)
             words_len_list.append(len(res))
             log("song %d: %d tokens in %.3f s (stream on %d slots)" % (sidx, len(res), song_time_list[-1], int(slots)))
@@ -1435,10 +1654,14 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
             songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens,
                                    prompts=prompt if prompts is None else list(prompts[first:first + group]),
                                    constraints=list(constraints[first:first + group])
-                                   if isinstance(constraints, (list, tuple)) else constraints)
+                                   if isinstance(constraints, (list, tuple)) else constraints,
+                                   return_logprobs=logprobs)
             wall = time.time() - start
+            if logprobs:
+                songs = list(zip(*songs))
             for j, res in enumerate(songs):
                 save(first + j, res)
+                res = res[0] if logprobs else res
                 song_time_list.append(wall / group)
                 words_len_list.append(len(res))
                 log("song %d: %d tokens in %.3f s (batch of %d)" % (first + j, len(res), song_time_list[-1], group))

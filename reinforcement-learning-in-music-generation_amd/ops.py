@@ -1626,6 +1626,94 @@ def sample_categorical_masked(logits, n_class, tokens, seed, bar, sched, masks, 
     return tokens
 
 
+def _mask_table(n_class, rows, bar, sched, masks, key=None):
+    """Checks of the optional constraint table shared by the log-prob entries -> (bar, sched, n_sched, masks, rows,
+    words) ctypes arguments (all NULL / 0 when unmasked)."""
+    if bar is None and sched is None and masks is None:
+        return None, None, 0, None, 0, 0
+    if bar is None or sched is None or masks is None:
+        raise ValueError("the constraint table needs bar, sched and masks together")
+    for t in [bar] + ([] if key is None else [key]):
+        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+            raise ValueError("bar and key must be contiguous (rows,) int64 tensors")
+    if sched.dtype != torch.int64 or sched.dim() != 2 or sched.shape[1] != 2 or not sched.is_contiguous():
+        raise ValueError("sched must be a contiguous (n_songs, 2) int64 tensor")
+    if masks.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or masks.dim() != 2 or \
+            not masks.is_contiguous():
+        raise ValueError("masks must be a contiguous (rows, words) 32-bit tensor")
+    if masks.shape[1] * 32 < sum(n_class):
+        raise ValueError("masks: %d words per row hold fewer than the %d classes" % (masks.shape[1], sum(n_class)))
+    return (_lib.dev(bar, "bar"), _lib.dev(sched, "sched"), sched.shape[0], _lib.dev(masks, "masks"), masks.shape[0],
+            masks.shape[1])
+
+
+def sample_categorical_logp(logits, n_class, tokens, seed, logp, counter=None, key=None, step=None, bar=None,
+                            sched=None, masks=None, out_counter=None, temperature=None, top_p=None):
+    """The draw of sample_categorical(slot_keys=True) at `counter`, or of sample_categorical_keyed with key / step,
+    masked as sample_categorical_masked when bar / sched / masks are given -- the same tokens -- that also writes the
+    (model, sampler) log-probs of each drawn class (cwlt_sample_categorical_logp).  logp: (R, rows, A, 2)
+    f32 device ring; the pair of row n, attribute a goes to logp[*out_counter % R, n, a] (out_counter: device int64,
+    e.g. the counter the loop advances after the draw; None needs R == 1)."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
+        raise TypeError("sample_categorical_logp takes f32 logits and int64 tokens")
+    rows, A = logits.shape[0], len(n_class)
+    if tokens.numel() != rows * A or not tokens.is_contiguous():
+        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
+    if (key is None) != (step is None) or (key is None and counter is None):
+        raise ValueError("sample_categorical_logp is keyed by key and step, or by the slot and a counter")
+    for t in ([] if key is None else [key, step]):
+        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
+    if logp.dtype != torch.float32 or logp.dim() != 4 or tuple(logp.shape[1:]) != (rows, A, 2) or \
+            not logp.is_contiguous():
+        raise ValueError("logp must be a contiguous (R, %d, %d, 2) f32 ring" % (rows, A))
+    if out_counter is None and logp.shape[0] != 1:
+        raise ValueError("a logp ring of %d rows needs out_counter" % logp.shape[0])
+    table = _mask_table(n_class, rows, bar, sched, masks)
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    _call("cwlt_sample_categorical_logp", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
+          _lib.dev(tokens, "tokens"), _lib.dev(logp, "logp"), _lib.opt(out_counter), logp.shape[0],
+          _lib.stream_ptr())
+    return tokens
+
+
+def score_categorical(logits, n_class, targets, temperature=None, top_p=None, key=None, bar=None, sched=None,
+                      masks=None, out=None):
+    """(model, sampler) log-probs of given classes (cwlt_score_categorical): logits (rows, >= sum n_class)
+    f32, targets (rows, A) int64 (negative: padding, left unwritten) -> (rows, A, 2) f32.  Masked when bar / sched /
+    masks are given, song key[n] (None: n).  Bitwise the pairs sample_categorical_logp writes for the same logits,
+    settings and classes.  Rows go through in launches of at most 2^20."""
+    if logits.dtype != torch.float32 or targets.dtype != torch.int64:
+        raise TypeError("score_categorical takes f32 logits and int64 targets")
+    rows, A = logits.shape[0], len(n_class)
+    if targets.numel() != rows * A or not targets.is_contiguous():
+        raise ValueError("targets must be a contiguous (rows, n_attr) int64 tensor")
+    if key is not None and bar is None:
+        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
+    _mask_table(n_class, rows, bar, sched, masks, key)
+    if out is None:
+        out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    tv = targets.view(rows, A)
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        sl = lambda t: None if t is None else t[a:z]
+        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
+        _call("cwlt_score_categorical", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
+              logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, _lib.dev(out[a:z], "logp"),
+              _lib.stream_ptr())
+    return out
+
+
 def count_bars(tokens, bar_attr, bar_mask, bar):
     """bar[n] += 1 where row n of tokens (rows, A) int64 has a Bar class in attribute bar_attr (bar_mask
     (n_class[bar_attr],) int32) -- cwlt_count_bars, the batch loop's bar count in constrained mode."""

@@ -105,7 +105,7 @@ class RecurrentTransformerEncoder(nn.Module):
                 x = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return x, state
 
-    def prefill(self, x, state, lengths=None, kernel="blas", last=None, heads=None, rows=None):
+    def prefill(self, x, state, lengths=None, kernel="blas", last=None, heads=None, rows=None, all_rows=False):
         """x (N, L, D) prompt rows (embedded, positional row added) -> (N, L, D) final-norm outputs; `state` (a list of
         [S, Zs] per layer, as forward() takes it) advanced IN PLACE over each sequence's first lengths[n] rows
         (lengths: (N) int32 device tensor, None = all L).  f32 only: the result is what L calls of forward() return,
@@ -117,16 +117,18 @@ class RecurrentTransformerEncoder(nn.Module):
         linear1; residual and GELU in the epilogue), at most `rows` (<= 4096, default 4096) rows per call, and the scan
         is one workgroup per (sequence, head) over the sequence's own chunks (segments=1).  Only row last[n] ((N) int64
         device tensor, None = all L - 1) of each sequence goes through the final norms, as the prologue of the stacked
-        heads GEMM heads = (w (n_out, D), b (n_out)).  -> (hidden (N, D), logits (N, n_out))."""
+        heads GEMM heads = (w (n_out, D), b (n_out)).  -> (hidden (N, D), logits (N, n_out)).
+        all_rows=True (gemm): the heads GEMM, with the same two LayerNorms as its prologue, runs on every row of every
+        sequence instead (padded rows included; `last` is ignored) -> (None, logits (N, L, n_out))."""
         if kernel not in ("blas", "gemm"):
             raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
         if kernel == "gemm":
             self._check_prefill(x, state)
             if heads is None:
                 raise ValueError("the gemm prefill ends in the heads GEMM: pass heads=(weight, bias)")
-            return self._prefill_gemm(x, state, lengths, last, heads, 4096 if rows is None else int(rows))
-        if last is not None or heads is not None or rows is not None:
-            raise ValueError("last, heads and rows belong to kernel='gemm'")
+            return self._prefill_gemm(x, state, lengths, last, heads, 4096 if rows is None else int(rows), all_rows)
+        if last is not None or heads is not None or rows is not None or all_rows:
+            raise ValueError("last, heads, rows and all_rows belong to kernel='gemm'")
         if not x.is_cuda:
             raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
         if x.dtype != torch.float32:
@@ -160,7 +162,7 @@ class RecurrentTransformerEncoder(nn.Module):
             if len(S) != x.shape[0] or len(Zs) != x.shape[0]:
                 raise ValueError("state holds %d sequences, the prompt batch %d" % (len(S), x.shape[0]))
 
-    def _prefill_gemm(self, x, state, lengths, last, heads, rows):
+    def _prefill_gemm(self, x, state, lengths, last, heads, rows, all_rows=False):
         if not 1 <= rows <= 4096:
             raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
         N, L, D = x.shape
@@ -175,11 +177,11 @@ class RecurrentTransformerEncoder(nn.Module):
         f = ops._f32
         pair = lambda nrm: (f(nrm.weight), f(nrm.bias))
 
-        def gemm(w, b, src, dst, ln=None, res=None, act=None, normed=None):
+        def gemm(w, b, src, dst, ln=None, res=None, act=None, normed=None, ln2=None):
             for a in range(0, M, rows):
                 z = min(M, a + rows)
-                ops.decode_gemm(w, b, src[a:z], ln=ln, eps=eps, res=None if res is None else res[a:z], act=act,
-                                out=dst[a:z], normed=None if normed is None else normed[a:z])
+                ops.decode_gemm(w, b, src[a:z], ln=ln, ln2=ln2, eps=eps, res=None if res is None else res[a:z],
+                                act=act, out=dst[a:z], normed=None if normed is None else normed[a:z])
 
         dev = x.device
         new = lambda n: torch.empty((M, n), dtype=torch.float32, device=dev)
@@ -202,6 +204,12 @@ class RecurrentTransformerEncoder(nn.Module):
                 gemm(f(layer.linear1.weight), f(layer.linear1.bias), s1, hh, ln=pair(layer.norm1), act="gelu",
                      normed=x1)
                 gemm(f(layer.linear2.weight), f(layer.linear2.bias), hh, s2, res=x1)
+            if all_rows:
+                w, b = f(heads[0]), f(heads[1])
+                logits = torch.empty((M, w.shape[0]), dtype=torch.float32, device=dev)
+                gemm(w, b, s2, logits, ln=pair(self.layers[-1].norm2),
+                     ln2=pair(self.norm) if self.norm is not None else None)
+                return None, logits.view(N, L, w.shape[0])
             if last is None:
                 last = torch.full((N,), L - 1, dtype=torch.int64, device=dev)
             top = s2.view(N, L, D)[torch.arange(N, device=dev), last]          # (N, D): a gather, exact

@@ -71,3 +71,32 @@ def sample_cw(y):
     duration = sampling(y[4], t=2, p=0.9)
     velocity = sampling(y[5], t=5)
     return np.array([tempo, chord, barbeat, pitch, duration, velocity])
+
+
+def logprobs_f64(logits, target, temperature=1.0, top_p=None, allowed=None):
+    """Float64 restatement of the device sampler's log-probs for one attribute: logits (n,), the class
+    `target` -> (model log-prob, sampler log-prob).  The model log-prob is log_softmax(logits)[target].  The sampler's
+    q: logits / temperature, classes outside `allowed` ((n,) bool, None = all) removed, then the nucleus kept set of
+    `nucleus` above (top_p None or >= 1: every allowed class): classes ranked by probability (ties: the larger index
+    first, as argsort()[::-1] orders them), a class kept when the mass ranked ahead of it is <= top_p in units of
+    probs / (sum + 1e-5); renormalised over the kept classes.  -inf outside the kept set."""
+    x = np.asarray(logits, dtype=np.float64)
+    n = len(x)
+    target = int(target)
+    mx = x.max()
+    lm = x[target] - mx - np.log(np.exp(x - mx).sum())
+    ok = np.ones(n, dtype=bool) if allowed is None else np.asarray(allowed, dtype=bool)
+    if not ok[target]:
+        return lm, -np.inf
+    v = x / float(temperature)
+    m = v[ok].max()
+    e = np.where(ok, np.exp(np.where(ok, v, m) - m), 0.0)
+    keep = ok.copy()
+    if top_p is not None and top_p < 1.0:
+        order = np.lexsort((-np.arange(n), -e))                  # probability descending, ties: larger index first
+        ahead = np.empty(n)
+        ahead[order] = np.concatenate([[0.0], np.cumsum(e[order])[:-1]])
+        keep &= ahead / e.sum() / (1.0 + 1e-5) <= top_p
+    if not keep[target]:
+        return lm, -np.inf
+    return lm, (v[target] - m) - np.log(e[keep].sum())
