@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 from fill import fill_params  # noqa: E402
 
 import rlmg_amd  # noqa: E402,F401
+from rlmg_amd import ops  # noqa: E402
 from oracle import cw_model  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -138,7 +139,6 @@ def test_repo_dims_train_step_grads_match_oracle(cuda):
 
 def test_greedy_ids_bit_exact_vs_oracle(cuda):
     """Greedy (softmax -> argmax) token ids from the GPU path equal the CPU oracle's."""
-    from rlmg_amd import ops
     n_class = [56, 135, 18, 87, 18, 25]
     net = _dqn_model((512, 12, 8), n_class, 41, cuda)
     ref = fill_params(cw_model.CWLinearTransformer(n_class, 512, 12, 8, variant="dqn"), seed=41).eval()
@@ -173,11 +173,29 @@ _ORACLE_CACHE = {}
 def test_repo_dims_bf16_train_step_grads_match_fp32_oracle(cuda, monkeypatch, schedule):
     """BASELINE configs[1]'s own shapes in the benched dtype: repo dims, T = 1024, B = 2, bf16 storage; losses and
     EVERY parameter gradient against the fp32 CPU oracle on the same tokens (dropout off so both are deterministic).
-    "library": what the library picks for 16 (sequence, head) streams -- segmented scans, the dkdv + dq backward pair;
-    "bench": whole-sequence scans as at B = 512 -- the forward's final-state hand-over and the one-sweep backward.
-    Both run the one-kernel FFN forward and the fused FFN backward."""
+    "library": what the library picks for 2 048 token rows -- the whole stack as one host call (csrc/layer.hip), whose
+    scans cut the 16 (sequence, head) streams into segments (the dkdv + dq backward pair);
+    "bench": the per-op layer the bench runs (one-call layers off) with whole-sequence scans forced as at B = 512 -- the
+    forward's final-state hand-over and the one-sweep backward, the one-kernel FFN forward and the fused FFN backward.
+    CWLT_SCAN_SEGMENTS is read by ops.scan_segments only, so it reaches the per-op path and not the one-call layer."""
+    calls = {"stack": 0, "fin": []}
+    real_stack, real_bwd = ops.encoder_fwd, ops.cla_bwd
+
+    def encoder_fwd(arr, n):
+        calls["stack"] += 1
+        return real_stack(arr, n)
+
+    def cla_bwd(*a, **kw):
+        calls["fin"].append(kw.get("final_state") is not None)
+        return real_bwd(*a, **kw)
+
+    monkeypatch.setattr(ops, "encoder_fwd", encoder_fwd)
+    monkeypatch.setattr(ops, "cla_bwd", cla_bwd)
     if schedule == "bench":
+        monkeypatch.setattr(ops, "LAYER_C", False)
         monkeypatch.setenv("CWLT_SCAN_SEGMENTS", "1")
+    else:
+        assert ops.scan_segments(2, 8, 1024, torch.bfloat16) > 1      # the library's choice: segmented scans
     n_class = [56, 135, 18, 87, 18, 25]
     net = _dqn_model((512, 12, 8), n_class, 51, cuda)
     B, T = 2, 1024
@@ -196,6 +214,10 @@ def test_repo_dims_bf16_train_step_grads_match_fp32_oracle(cuda, monkeypatch, sc
     net.compute_dtype = torch.bfloat16
     lg = net.train_step(x.to(cuda), y.to(cuda), mask.to(cuda))
     (sum(lg) / 6).backward()
+    if schedule == "bench":
+        assert calls["stack"] == 0 and calls["fin"] == [True] * 12     # per-op layers, one-sweep scan backward
+    else:
+        assert calls["stack"] == 1 and calls["fin"] == []              # the one-call stack
     l16, l32 = np.array([l.item() for l in lg]), np.array([l.item() for l in lr])
     # a loss is a mean over 2 000 tokens of nll values that each carry the logits' relative error
     assert np.abs(l16 - l32).max() <= BF16_GRAD_REL * np.abs(l32).max(), (l16, l32)
