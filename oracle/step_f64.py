@@ -32,9 +32,11 @@ LN_EPS = 1e-5
 ATTRS = ("tempo", "chord", "barbeat", "pitch", "duration", "velocity")
 
 
-def layer_forward(x, P, pre, n_heads, p, seeds, row0=0, drop=dropout.dropout, taps=None):
+def layer_forward(x, P, pre, n_heads, p, seeds, row0=0, drop=dropout.dropout, taps=None, attn=cla.cla_reference,
+                  act=F.gelu):
     """One post-LN encoder layer: x (n, L, D) -> (n, L, D).  P[pre + name]: the layer's parameters; seeds: its 3 sites'.
-    taps: a list that receives (q, k, attention output), their gradients retained (normaliser_gains)."""
+    taps: a list that receives (q, k, attention output), their gradients retained (normaliser_gains).
+    attn(q, k, v, eps) and act(h): the attention and the FFN activation (oracle/decode_f64.py hands in others)."""
     n, L, D = x.shape
     x2 = x.reshape(n * L, D)
     at = pre + "attention."
@@ -44,7 +46,7 @@ def layer_forward(x, P, pre, n_heads, p, seeds, row0=0, drop=dropout.dropout, ta
 
     q, k, v = (proj(nm, x2).view(n, L, n_heads, D // n_heads)
                for nm in ("query_projection", "key_projection", "value_projection"))
-    a = cla.cla_reference(q, k, v, cla.EPS)
+    a = attn(q, k, v, cla.EPS)
     if taps is not None:
         for t in (q, k, a):
             t.retain_grad()
@@ -52,15 +54,18 @@ def layer_forward(x, P, pre, n_heads, p, seeds, row0=0, drop=dropout.dropout, ta
     a = a.reshape(n * L, D)
     s1 = x2 + drop(proj("out_projection", a), p, seeds[0], row0)
     x1 = F.layer_norm(s1, (D,), P[pre + "norm1.weight"], P[pre + "norm1.bias"], LN_EPS)
-    g = drop(F.gelu(F.linear(x1, P[pre + "linear1.weight"], P[pre + "linear1.bias"])), p, seeds[1], row0)
+    g = drop(act(F.linear(x1, P[pre + "linear1.weight"], P[pre + "linear1.bias"])), p, seeds[1], row0)
     s2 = x1 + drop(F.linear(g, P[pre + "linear2.weight"], P[pre + "linear2.bias"]), p, seeds[2], row0)
     return F.layer_norm(s2, (D,), P[pre + "norm2.weight"], P[pre + "norm2.bias"], LN_EPS).view(n, L, D)
 
 
-def encoder_forward(x, P, n_layers, n_heads, p, seeds, row0=0, pre="", drop=dropout.dropout, taps=None):
-    """The layers (seeds[3i:3i + 3] for layer i) and the final norm."""
+def encoder_forward(x, P, n_layers, n_heads, p, seeds, row0=0, pre="", drop=dropout.dropout, taps=None, attn=None,
+                    act=F.gelu):
+    """The layers (seeds[3i:3i + 3] for layer i) and the final norm.  attn: None (cla.cla_reference) or layer index ->
+    that layer's attention(q, k, v, eps); act: the FFN activation."""
     for i in range(n_layers):
-        x = layer_forward(x, P, "%slayers.%d." % (pre, i), n_heads, p, seeds[3 * i:3 * i + 3], row0, drop, taps)
+        x = layer_forward(x, P, "%slayers.%d." % (pre, i), n_heads, p, seeds[3 * i:3 * i + 3], row0, drop, taps,
+                          cla.cla_reference if attn is None else attn(i), act)
     D = x.shape[-1]
     return F.layer_norm(x, (D,), P[pre + "norm.weight"], P[pre + "norm.bias"], LN_EPS)
 
