@@ -1,4 +1,5 @@
-"""Parity of the HIP causal-linear-attention kernels (through the C-ABI) against the CPU oracle."""
+"""Parity of the HIP causal-linear-attention kernels (through the C-ABI) against the CPU oracle.
+Row-by-row bounds for every form of the scan: tests/test_cla_f64_gpu.py."""
 import pytest
 import torch
 

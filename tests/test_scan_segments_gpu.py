@@ -1,7 +1,8 @@
 """GPU: the few-stream (segmented, "T-split") schedule of the bf16 scan kernels -- every sequence cut into runs of
 whole chunks, one workgroup each, with a state-increment pass and a prefix pass in front -- against the one-pass
 schedule and the f64 oracle.  The reference reaches this kernel with 4 sequences x 8 heads = 32 streams
-(dqn_policy/agent_pretrain.py:48,524-526: batch 4, T = 3584)."""
+(dqn_policy/agent_pretrain.py:48,524-526: batch 4, T = 3584).
+Per-row bounds of the segmented schedule against f64: tests/test_cla_f64_gpu.py."""
 import pytest
 import torch
 

@@ -1,7 +1,8 @@
 """GPU: the one-sweep backward of the bf16 scan (cwlt_causal_linear_bwd_sweep) -- dQ, dK, dV from a single reverse pass
 that takes the dQ scan's prefix state from the forward's final state by subtraction -- against the f64 oracle, the
 dkdv + dq kernel pair, and itself across batch sizes.  Reference: the backward of fast_transformers'
-causal_dot_product reached from dqn_policy/model.py:128-137."""
+causal_dot_product reached from dqn_policy/model.py:128-137.
+Per-row bounds, final state and column sums against f64: tests/test_cla_f64_gpu.py."""
 import pytest
 import torch
 
