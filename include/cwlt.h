@@ -522,6 +522,45 @@ int cwlt_score_categorical(const float* logits, const int* n_class, const float*
 int cwlt_count_bars(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* bar_mask,
                     int bar_classes, int64_t* bar, void* stream);
 
+/* Row grammar (generation.Grammar): the draw of cwlt_sample_categorical_logp -- slot-keyed at *counter or
+ * keyed per row by key / step, masked when bar, sched and masks are given (all three, or none) -- in which the
+ * attributes of a row depend on one another.  Attribute bar_attr (bar-beat) is drawn first, under the mask row AND the
+ * position rule: with b = beat[n] (DEVICE int64 x rows: -1 after a Bar row, k after Beat_k) and o = order[c] (DEVICE
+ * int32 x n_order >= n_class[bar_attr]: -2 the neutral class, -1 a Bar class, k >= 0 Beat_k, -3 never allowed), class
+ * c is allowed when o == -1, or o >= 0 and o > b, or o == -2 and b >= 0.  The drawn class fixes the row's kind (o ==
+ * -2 NOTE, -1 BAR, >= 0 BEAT) and every other attribute is drawn under the mask row AND row `kind` of gram (DEVICE
+ * uint32, 3 x gram_words, rows NOTE / BAR / BEAT, bit layout of `masks`).  Keys, temperature, nucleus and the -inf
+ * treatment of removed classes are those of cwlt_sample_categorical_masked; with order all -1 and gram all ones the
+ * tokens and pairs are bitwise those of cwlt_sample_categorical_keyed / _masked / _logp.  logp (optional): the pairs of
+ * cwlt_sample_categorical_logp, lp_sampler the log q of the distribution each class was drawn from (bar-beat: given
+ * the position; the others: given the row's kind).
+ * Refused: null beat / order / gram / tokens, bar_attr outside [0, n_attr), n_order < n_class[bar_attr],
+ * gram_words * 32 < sum n_class, and what cwlt_sample_categorical_logp refuses (out_rows only with logp). */
+int cwlt_sample_categorical_grammar(const float* logits, const int* n_class, const float* temperature,
+                                    const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                    const int64_t* counter, const int64_t* key, const int64_t* step,
+                                    const int64_t* bar, const int64_t* sched, int64_t n_sched, const uint32_t* masks,
+                                    int64_t mask_rows, int mask_words, const int64_t* beat, const int* order,
+                                    int n_order, const uint32_t* gram, int gram_words, int bar_attr, int64_t* tokens,
+                                    float* logp, const int64_t* out_counter, int64_t out_rows, void* stream);
+/* cwlt_score_categorical under the row grammar: the kind of row n is that of its target's bar-beat class, beat[n] the
+ * position before the row.  An ill-formed target gets -inf in the sampler column of the offending attribute (bar-beat:
+ * a class the position rule removes; another attribute: a class outside the kind's gram row, every class when the
+ * bar-beat target is -3 or out of range) and a finite model column. */
+int cwlt_score_categorical_grammar(const float* logits, const int* n_class, const float* temperature,
+                                   const float* top_p, int n_attr, int64_t rows, int64_t ld, const int64_t* targets,
+                                   const int64_t* key, const int64_t* bar, const int64_t* sched, int64_t n_sched,
+                                   const uint32_t* masks, int64_t mask_rows, int mask_words, const int64_t* beat,
+                                   const int* order, int n_order, const uint32_t* gram, int gram_words, int bar_attr,
+                                   float* logp, void* stream);
+/* The grammar's position after each draw, one thread per row: when fresh[n] != 0 and song[n] >= 0 (the slot was just
+ * handed a song) beat[n] = beat0[song[n]] (DEVICE int64 x n_songs, the position each song's prompt leaves); otherwise
+ * beat[n] moves by o = order[tokens[n, bar_attr]]: -1 (Bar) and k >= 0 (Beat_k) are stored, anything else leaves it.
+ * fresh, song and beat0 are given together or all NULL (the lock-step loop).  rows <= 2^20. */
+int cwlt_grammar_track(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* order, int n_order,
+                       const int64_t* fresh, const int64_t* song, const int64_t* beat0, int64_t n_songs,
+                       int64_t* beat, void* stream);
+
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,
  * cwlt_stream_refill, cwlt_sample_categorical_keyed and cwlt_stream_advance.

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -131,6 +131,11 @@ _SIGNATURES = {
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr],
     "cwlt_score_categorical": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64] + [_ptr] * 4
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr],
+    "cwlt_sample_categorical_grammar": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64] + [_ptr] * 5
+    + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr],
+    "cwlt_score_categorical_grammar": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64] + [_ptr] * 4
+    + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr],
+    "cwlt_grammar_track": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr],
     "cwlt_count_bars": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr],
     "cwlt_stream_refill": [_ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr],
     "cwlt_stream_advance": [_ptr, _c_int, _c_i64, _c_int, _ptr, _c_int] + [_c_i64] * 4 + [_ptr] * 6 + [_c_i64, _ptr],

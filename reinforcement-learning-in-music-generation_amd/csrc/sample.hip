@@ -18,6 +18,12 @@
 // raw logits at c, log q(c)) with q the distribution the draw was made from (temperature, mask, nucleus kept set,
 // renormalised); the FORCED instantiations take c from a target array instead of drawing it and compute the same pair,
 // through the same body, so scoring the logits a draw came from at the class it drew gives the sampler's bits.
+//
+// Row grammar: the GRAMMAR instantiations tie the attributes of a row together.  The bar-beat class is
+// drawn under the position rule (GrammarArgs: beat, order) and decides the row's kind (NOTE / BAR / BEAT); every other
+// attribute is drawn under the kind's row of `gram`.  Each wave of another attribute first runs the draw body on the
+// bar-beat logits with bar-beat's own key and masks -- the very instructions the bar-beat wave runs, so all waves hold
+// the same class -- and then runs it again for its own attribute: no workgroup barrier, no hand-off through memory.
 #include "cwlt_common.h"
 
 #include <climits>
@@ -56,30 +62,38 @@ struct LogpArgs {
     const int64_t* targets;
 };
 
-// MASKED = false is the plain draw of the three unmasked entry points (M unused).  MASKED = true: disallowed classes
-// get -inf logits before the temperature, the max, the softmax and the nucleus, so the draw is over the renormalised
-// allowed distribution; with every bit set it is bitwise the plain draw.
-// LOGP: after the draw, write (lp_model, lp_sampler) of the drawn class (LogpArgs).  FORCED (implies LOGP): no draw, no
-// RNG, no token write; the class is the target's.  lp_sampler = (v_c - m) - log(sum of e over the kept classes), -inf
-// outside the mask or the nucleus kept set; lp_model = (x_c - mx) - log(sum exp(x - mx)) over the raw logits (its max
-// and sum are the sampler's own when inv_t == 1 and no mask row applies).
-template <bool MASKED, bool LOGP = false, bool FORCED = false>
-__global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
-    const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
-    const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
-    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step, MaskArgs M,
-    LogpArgs L) {
-    static_assert(LOGP || !FORCED, "FORCED writes log-probs");
-    __shared__ float e_s[CWLT_MAX_ATTR][256];
-    const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
-    if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
+// Row grammar of the GRAMMAR instantiations (unused otherwise; the last kernel argument, after LogpArgs, so every other
+// argument keeps its offset).  beat[n]: where row n's song stands in its bar: -1 after a Bar row, k after Beat_k.
+// order[c] for each class c of attribute bar_attr: -2 the neutral class (a note row), -1 a Bar class, k >= 0 Beat_k,
+// -3 never allowed.  c is allowed when order[c] == -1, or order[c] > beat[n] >= -1 with order[c] >= 0, or order[c] ==
+// -2 with beat[n] >= 0.  gram: 3 x words uint32 in the bit layout of MaskArgs::masks, row 0 what a NOTE row may carry
+// in each attribute, row 1 a BAR row, row 2 a BEAT row.
+struct GrammarArgs {
+    const int64_t* beat;
+    const int* order;
+    const uint32_t* gram;
+    int words;
+    int bar_attr;
+};
+
+constexpr int KIND_NONE = -1;                        // an ill-formed forced target: nothing is allowed
+constexpr int KIND_POSITION = 3;                     // the bar-beat attribute itself: the position rule, no gram row
+
+__device__ __forceinline__ int grammar_kind(int o) { return o == -2 ? 0 : o == -1 ? 1 : o >= 0 ? 2 : KIND_NONE; }
+
+// The draw of attribute a of row n by one wave (lane-blocked: lane l owns classes 4l .. 4l + 3), `ew` the wave's LDS
+// row -> the class.  write = false (GRAMMAR: another attribute's wave finding the row's bar-beat class) draws and
+// writes nothing.  kind (GRAMMAR): KIND_POSITION for the bar-beat attribute, else the gram row, KIND_NONE = no class.
+template <bool MASKED, bool LOGP, bool FORCED, bool GRAMMAR>
+__device__ __forceinline__ int draw_attr(const float* __restrict__ logits, long ld, const SampleArgs& A, int n_attr,
+                                         uint64_t seed, const int64_t* __restrict__ counter,
+                                         int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
+                                         int slot_keyed, const int64_t* __restrict__ row_key,
+                                         const int64_t* __restrict__ row_step, const MaskArgs& M, const LogpArgs& L,
+                                         const GrammarArgs& G, float* ew, int n, int lane, int a, long forced,
+                                         bool write, int kind) {
     const int nc = A.n[a];
     const float* x = logits + (long)n * ld + A.off[a];
-    long forced = 0;
-    if constexpr (FORCED) {
-        forced = L.targets[(long)n * n_attr + a];
-        if (forced < 0) return;                      // padding row: wave-uniform, nothing written
-    }
     // keyed by row: row n draws what the slot-keyed launch draws for row row_key[n] at counter row_step[n]
     const long step = FORCED ? 0 : row_step ? row_step[n] : counter ? *counter : 0;
     bool ok[4] = {true, true, true, true};
@@ -102,6 +116,34 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
             }
         }
     }
+    if constexpr (GRAMMAR) {
+        bool cut = false;                            // the grammar removes a class of this attribute
+        if (kind == KIND_POSITION) {
+            const long bt = G.beat[n];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = lane * 4 + j;
+                if (c < nc) {
+                    const int o = G.order[c];        // order holds >= nc entries (checked by the entry points)
+                    const bool g = o == -1 || (o >= 0 && o > bt) || (o == -2 && bt >= 0);
+                    cut = cut || !g;
+                    ok[j] = ok[j] && g;
+                }
+            }
+        } else {
+            const uint32_t* w = G.gram + (kind < 0 ? 0 : kind) * G.words;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int bit = A.off[a] + lane * 4 + j;             // < sum n_class <= 32 * words: inside the row
+                if (lane * 4 + j < nc) {
+                    const bool g = kind >= 0 && ((w[bit >> 5] >> (bit & 31)) & 1u) != 0;
+                    cut = cut || !g;
+                    ok[j] = ok[j] && g;
+                }
+            }
+        }
+        if constexpr (LOGP) row_masked = row_masked || __ballot(cut) != 0;   // permissive tables: the plain pair
+    }
     float v[4];
     float m = -INFINITY;
 #pragma unroll
@@ -123,7 +165,6 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
         // mass is <= p (the class that crosses p is kept); probabilities there are exp/(sum + 1e-5).  The mass
         // ahead of class i needs no sort: G_i = sum of e_j over classes ranked before i (larger e, ties: larger
         // index first, as argsort()[::-1] orders them).  One broadcast LDS read per class, four running sums per lane.
-        float* ew = e_s[a];
 #pragma unroll
         for (int j = 0; j < 4; ++j) ew[lane * 4 + j] = e[j];
         float tot = (e[0] + e[1]) + (e[2] + e[3]);
@@ -189,12 +230,12 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
             for (int d = 32; d >= 1; d >>= 1) last = max(last, __shfl_xor(last, d, 64));
             pick = last < 0 ? 0 : last;
         }
-        if (lane == 0) {
+        if (lane == 0 && write) {
             tokens[(long)n * n_attr + a] = pick;
             if (song && step < song_rows) song[((long)step * gridDim.x + n) * n_attr + a] = pick;
         }
     }
-    if constexpr (LOGP) {
+    if (LOGP && write) {
         // model log-prob: the raw logits' max and sum, or the sampler's own when they are the same numbers
         float mx = m, sx;
         if (A.inv_t[a] == 1.0f && !row_masked) {
@@ -226,26 +267,80 @@ __global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
             *reinterpret_cast<float2*>(L.logp + ((o * gridDim.x + n) * n_attr + a) * 2) = make_float2(lm, lq);
         }
     }
+    return pick;
+}
+
+// MASKED = false is the plain draw of the three unmasked entry points (M unused).  MASKED = true: disallowed classes
+// get -inf logits before the temperature, the max, the softmax and the nucleus, so the draw is over the renormalised
+// allowed distribution; with every bit set it is bitwise the plain draw.
+// LOGP: after the draw, write (lp_model, lp_sampler) of the drawn class (LogpArgs).  FORCED (implies LOGP): no draw, no
+// RNG, no token write; the class is the target's.  lp_sampler = (v_c - m) - log(sum of e over the kept classes), -inf
+// outside the mask or the nucleus kept set; lp_model = (x_c - mx) - log(sum exp(x - mx)) over the raw logits (its max
+// and sum are the sampler's own when inv_t == 1 and no mask row applies).
+// GRAMMAR: the row grammar (GrammarArgs) on top of the mask row, if any.  Drawing: every wave draws the bar-beat class
+// first (the bar-beat wave keeps it, the others only learn the row's kind from it), then its own attribute under the
+// kind's gram row.  FORCED: the kind is that of the target row's bar-beat class.
+template <bool MASKED, bool LOGP = false, bool FORCED = false, bool GRAMMAR = false>
+__global__ __launch_bounds__(64 * CWLT_MAX_ATTR) void sample_categorical_kernel(
+    const float* __restrict__ logits, long ld, SampleArgs A, int n_attr, uint64_t seed,
+    const int64_t* __restrict__ counter, int64_t* __restrict__ tokens, int64_t* __restrict__ song, long song_rows,
+    int slot_keyed, const int64_t* __restrict__ row_key, const int64_t* __restrict__ row_step, MaskArgs M,
+    LogpArgs L, GrammarArgs G) {
+    static_assert(LOGP || !FORCED, "FORCED writes log-probs");
+    __shared__ float e_s[CWLT_MAX_ATTR][256];
+    const int lane = threadIdx.x & 63, a = threadIdx.x >> 6, n = blockIdx.x;
+    if (a >= n_attr) return;                         // wave-uniform; no workgroup barriers in this kernel
+    long forced = 0;
+    if constexpr (FORCED) {
+        forced = L.targets[(long)n * n_attr + a];
+        if (forced < 0) return;                      // padding row: wave-uniform, nothing written
+    }
+    if constexpr (!GRAMMAR) {
+        draw_attr<MASKED, LOGP, FORCED, false>(logits, ld, A, n_attr, seed, counter, tokens, song, song_rows, slot_keyed,
+                                               row_key, row_step, M, L, G, e_s[a], n, lane, a, forced, true, KIND_NONE);
+    } else if constexpr (FORCED) {
+        int kind = KIND_POSITION;
+        if (a != G.bar_attr) {
+            const long tb = L.targets[(long)n * n_attr + G.bar_attr];
+            kind = tb >= 0 && tb < A.n[G.bar_attr] ? grammar_kind(G.order[tb]) : KIND_NONE;
+        }
+        draw_attr<MASKED, LOGP, true, true>(logits, ld, A, n_attr, seed, counter, tokens, song, song_rows, slot_keyed,
+                                            row_key, row_step, M, L, G, e_s[a], n, lane, a, forced, true, kind);
+    } else {
+        // every wave runs this call, on the same inputs: the same class in all of them
+        const bool own = a == G.bar_attr;
+        const int bb = draw_attr<MASKED, LOGP, false, true>(logits, ld, A, n_attr, seed, counter, tokens, song, song_rows,
+                                                            slot_keyed, row_key, row_step, M, L, G, e_s[a], n, lane,
+                                                            G.bar_attr, 0, own, KIND_POSITION);
+        if (own) return;                             // wave-uniform
+        __builtin_amdgcn_wave_barrier();             // the LDS row is reused: reads above stay before the writes below
+        draw_attr<MASKED, LOGP, false, true>(logits, ld, A, n_attr, seed, counter, tokens, song, song_rows, slot_keyed,
+                                             row_key, row_step, M, L, G, e_s[a], n, lane, a, 0, true,
+                                             grammar_kind(G.order[bb]));
+    }
 }
 
 }  // namespace cwlt
 
-template <bool MASKED, bool LOGP, bool FORCED>
+template <bool MASKED, bool LOGP, bool FORCED, bool GRAMMAR>
 static void launch_sample(int64_t rows, int n_attr, void* stream, const float* logits, int64_t ld,
                           const cwlt::SampleArgs& A, uint64_t seed, const int64_t* counter, int64_t* tokens,
                           int64_t* song, int64_t song_rows, int slot_keyed, const int64_t* row_key,
-                          const int64_t* row_step, const cwlt::MaskArgs& M, const cwlt::LogpArgs& L) {
-    hipLaunchKernelGGL((cwlt::sample_categorical_kernel<MASKED, LOGP, FORCED>), dim3((unsigned)rows), dim3(64 * n_attr),
-                       0, (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens, song,
-                       (long)song_rows, slot_keyed, row_key, row_step, M, L);
+                          const int64_t* row_step, const cwlt::MaskArgs& M, const cwlt::LogpArgs& L,
+                          const cwlt::GrammarArgs& G) {
+    hipLaunchKernelGGL((cwlt::sample_categorical_kernel<MASKED, LOGP, FORCED, GRAMMAR>), dim3((unsigned)rows),
+                       dim3(64 * n_attr), 0, (hipStream_t)stream, logits, (long)ld, A, n_attr, seed, counter, tokens,
+                       song, (long)song_rows, slot_keyed, row_key, row_step, M, L, G);
 }
 
-// lp: the log-prob output (LOGP instantiations); forced: score lp->targets instead of drawing (FORCED).
+// lp: the log-prob output (LOGP instantiations); forced: score lp->targets instead of drawing (FORCED); gr: the row
+// grammar (GRAMMAR), n_order its order entries.
 static int sample(const float* logits, const int* n_class, const float* temperature, const float* top_p, int n_attr,
                   int64_t rows, int64_t ld, uint64_t seed, const int64_t* counter, int64_t* tokens, int64_t* song,
                   int64_t song_rows, int slot_keyed, void* stream, const int64_t* row_key = nullptr,
                   const int64_t* row_step = nullptr, const cwlt::MaskArgs* mask = nullptr,
-                  const cwlt::LogpArgs* lp = nullptr, bool forced = false) {
+                  const cwlt::LogpArgs* lp = nullptr, bool forced = false, const cwlt::GrammarArgs* gr = nullptr,
+                  int n_order = 0) {
     using namespace cwlt;
     if (!logits || !n_class || (!tokens && !forced) || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0)
         return CWLT_ERR_ARG;
@@ -263,20 +358,34 @@ static int sample(const float* logits, const int* n_class, const float* temperat
     }
     if (ld < off) return CWLT_ERR_ARG;
     if (mask && (int64_t)mask->words * 32 < off) return CWLT_ERR_ARG;
+    if (gr) {
+        if (!gr->beat || !gr->order || !gr->gram || gr->bar_attr < 0 || gr->bar_attr >= n_attr) return CWLT_ERR_ARG;
+        if (n_order < n_class[gr->bar_attr] || (int64_t)gr->words * 32 < off) return CWLT_ERR_ARG;
+    }
     const MaskArgs M = mask ? *mask : MaskArgs{};
     const LogpArgs L = lp ? *lp : LogpArgs{};
+    const GrammarArgs G = gr ? *gr : GrammarArgs{};
+#define CWLT_SAMPLE_LAUNCH(MK, LP, FC, GR)                                                                            \
+    launch_sample<MK, LP, FC, GR>(rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows,        \
+                                  slot_keyed, row_key, row_step, M, L, G)
+#define CWLT_SAMPLE_FORM(LP, FC)                                                                                      \
+    do {                                                                                                              \
+        if (gr) {                                                                                                     \
+            if (mask) CWLT_SAMPLE_LAUNCH(true, LP, FC, true);                                                         \
+            else CWLT_SAMPLE_LAUNCH(false, LP, FC, true);                                                             \
+        } else {                                                                                                      \
+            if (mask) CWLT_SAMPLE_LAUNCH(true, LP, FC, false);                                                        \
+            else CWLT_SAMPLE_LAUNCH(false, LP, FC, false);                                                            \
+        }                                                                                                             \
+    } while (0)
     if (!lp)
-        (mask ? launch_sample<true, false, false> : launch_sample<false, false, false>)(
-            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
-            M, L);
+        CWLT_SAMPLE_FORM(false, false);
     else if (!forced)
-        (mask ? launch_sample<true, true, false> : launch_sample<false, true, false>)(
-            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
-            M, L);
+        CWLT_SAMPLE_FORM(true, false);
     else
-        (mask ? launch_sample<true, true, true> : launch_sample<false, true, true>)(
-            rows, n_attr, stream, logits, ld, A, seed, counter, tokens, song, song_rows, slot_keyed, row_key, row_step,
-            M, L);
+        CWLT_SAMPLE_FORM(true, true);
+#undef CWLT_SAMPLE_FORM
+#undef CWLT_SAMPLE_LAUNCH
     return (int)hipGetLastError();
 }
 
@@ -362,6 +471,56 @@ extern "C" int cwlt_score_categorical(const float* logits, const int* n_class, c
                   key, nullptr, masked ? &M : nullptr, &L, true);
 }
 
+// Grammar table arguments shared by the two grammar entries -> 0 ok, 1 refused (the rest is checked by sample()).
+static int grammar_args(const int64_t* beat, const int* order, const uint32_t* gram, int gram_words, int bar_attr,
+                        cwlt::GrammarArgs* G) {
+    if (!beat || !order || !gram || gram_words < 1) return 1;
+    *G = cwlt::GrammarArgs{beat, order, gram, gram_words, bar_attr};
+    return 0;
+}
+
+extern "C" int cwlt_sample_categorical_grammar(const float* logits, const int* n_class, const float* temperature,
+                                               const float* top_p, int n_attr, int64_t rows, int64_t ld, uint64_t seed,
+                                               const int64_t* counter, const int64_t* key, const int64_t* step,
+                                               const int64_t* bar, const int64_t* sched, int64_t n_sched,
+                                               const uint32_t* masks, int64_t mask_rows, int mask_words,
+                                               const int64_t* beat, const int* order, int n_order,
+                                               const uint32_t* gram, int gram_words, int bar_attr, int64_t* tokens,
+                                               float* logp, const int64_t* out_counter, int64_t out_rows,
+                                               void* stream) {
+    using namespace cwlt;
+    if (rows > (1L << 20)) return CWLT_ERR_ARG;
+    if (!key != !step || (!key && !counter)) return CWLT_ERR_ARG;    // keyed per row, or by slot and counter
+    if (logp && (out_rows < 1 || (out_counter == nullptr && out_rows != 1))) return CWLT_ERR_ARG;
+    MaskArgs M{};
+    bool masked = false;
+    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    GrammarArgs G{};
+    if (grammar_args(beat, order, gram, gram_words, bar_attr, &G)) return CWLT_ERR_ARG;
+    const LogpArgs L{logp, out_counter, (long)out_rows, nullptr};
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
+                  0, 1, stream, key, step, masked ? &M : nullptr, logp ? &L : nullptr, false, &G, n_order);
+}
+
+extern "C" int cwlt_score_categorical_grammar(const float* logits, const int* n_class, const float* temperature,
+                                              const float* top_p, int n_attr, int64_t rows, int64_t ld,
+                                              const int64_t* targets, const int64_t* key, const int64_t* bar,
+                                              const int64_t* sched, int64_t n_sched, const uint32_t* masks,
+                                              int64_t mask_rows, int mask_words, const int64_t* beat, const int* order,
+                                              int n_order, const uint32_t* gram, int gram_words, int bar_attr,
+                                              float* logp, void* stream) {
+    using namespace cwlt;
+    if (!logp || !targets || rows > (1L << 20)) return CWLT_ERR_ARG;
+    MaskArgs M{};
+    bool masked = false;
+    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    GrammarArgs G{};
+    if (grammar_args(beat, order, gram, gram_words, bar_attr, &G)) return CWLT_ERR_ARG;
+    const LogpArgs L{logp, nullptr, 1, targets};
+    return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, 0, nullptr, nullptr, nullptr, 0, 1, stream,
+                  key, nullptr, masked ? &M : nullptr, &L, true, &G, n_order);
+}
+
 namespace cwlt {
 
 // Bar count of the batch loop's constrained mode, after each draw: bar[n] += 1 when row n's bar-beat class is a Bar.
@@ -372,6 +531,26 @@ __global__ __launch_bounds__(256) void count_bars_kernel(const int64_t* __restri
     if (n >= rows) return;
     const int64_t tk = tokens[n * n_attr + bar_attr];
     if (tk >= 0 && tk < bar_classes && bar_mask[tk]) bar[n] += 1;
+}
+
+// Position in the bar of the row grammar, after each draw: a row flagged fresh whose slot holds a song starts from
+// that song's beat0; any other row moves by its drawn bar-beat class (Bar: -1, Beat_k: k, anything else: unchanged).
+__global__ __launch_bounds__(256) void grammar_track_kernel(const int64_t* __restrict__ tokens, long rows, int n_attr,
+                                                            int bar_attr, const int* __restrict__ order, int n_order,
+                                                            const int64_t* __restrict__ fresh,
+                                                            const int64_t* __restrict__ song,
+                                                            const int64_t* __restrict__ beat0, long n_songs,
+                                                            int64_t* __restrict__ beat) {
+    const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= rows) return;
+    if (fresh && fresh[n] != 0 && song[n] >= 0) {
+        if (song[n] < n_songs) beat[n] = beat0[song[n]];
+        return;
+    }
+    const int64_t tk = tokens[n * n_attr + bar_attr];
+    if (tk < 0 || tk >= n_order) return;
+    const int o = order[tk];
+    if (o == -1 || o >= 0) beat[n] = o;
 }
 
 }  // namespace cwlt
@@ -385,5 +564,19 @@ extern "C" int cwlt_count_bars(const int64_t* tokens, int64_t rows, int n_attr, 
         return CWLT_ERR_ARG;
     hipLaunchKernelGGL(count_bars_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        tokens, (long)rows, n_attr, bar_attr, bar_mask, bar_classes, bar);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cwlt_grammar_track(const int64_t* tokens, int64_t rows, int n_attr, int bar_attr, const int* order,
+                                  int n_order, const int64_t* fresh, const int64_t* song, const int64_t* beat0,
+                                  int64_t n_songs, int64_t* beat, void* stream) {
+    using namespace cwlt;
+    if (!tokens || !order || !beat) return CWLT_ERR_ARG;
+    if (rows < 1 || rows > (1L << 20) || n_attr < 1 || n_attr > CWLT_MAX_ATTR || bar_attr < 0 || bar_attr >= n_attr ||
+        n_order < 1)
+        return CWLT_ERR_ARG;
+    if ((fresh || song || beat0) && (!fresh || !song || !beat0 || n_songs < 1)) return CWLT_ERR_ARG;   // all or none
+    hipLaunchKernelGGL(grammar_track_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       tokens, (long)rows, n_attr, bar_attr, order, n_order, fresh, song, beat0, (long)n_songs, beat);
     return (int)hipGetLastError();
 }

@@ -276,6 +276,177 @@ def _device_constraints(table, dev):
             "masks": torch.as_tensor(np.ascontiguousarray(masks).view(np.int32)).to(dev)}
 
 
+class Grammar:
+    """The row grammar of CW songs, enforced inside the device sampler (cwlt_sample_categorical_grammar).
+    generate_batch / generate_stream / generate(batch_size=... | slots=...) / score_songs take it as `grammar=`.
+
+    A row is exactly one of three kinds, decided by its class in attribute `bar_attr`:
+      NOTE: bar_attr class 0; class 0 in every `metrical` attribute; any class but 0 in every `note` attribute;
+      BAR:  a bar_attr class named "Bar"; class 0 everywhere else;
+      BEAT: a bar_attr class Beat_<k>; any class but 0 (CONTI or a value) in every `metrical` attribute, class 0 in
+            every `note` attribute.
+    Position rule: each song carries `beat`: -1 after a Bar row, k after Beat_k, unchanged by note rows.  A Bar class
+    is always allowed, Beat_k when k > beat, class 0 (a note) when beat >= 0: beats ascend within a bar and no note
+    comes before a bar's first beat.  A prompt's rows are not constrained; they only move `beat`, from -1.
+    The bar-beat class is drawn first, under (the song's Constraint row, if any) AND (the position rule); every other
+    attribute under (constraint row) AND (the kind's row).  Masking, temperature, nucleus and keys are Constraint's.
+
+    The neutral class is class id 0 (as in Constraint); beat indices are parsed from the names Beat_<k>, or given as
+    beats={class id: index}.  Refused (ValueError): unknown attributes, an attribute in two roles, a bar_attr class that
+    is neither class 0, "Bar" nor a beat, no Bar class at all."""
+
+    NOTE, BAR, BEAT = 0, 1, 2
+
+    def __init__(self, word2event, bar_attr="bar-beat", metrical=("tempo", "chord"),
+                 note=("pitch", "duration", "velocity"), beats=None):
+        self.keys = list(word2event.keys())
+        self.n_class = [len(word2event[k]) for k in self.keys]
+        roles = [bar_attr] + list(metrical) + list(note)
+        for name in roles:
+            if name not in self.keys:
+                raise ValueError("unknown attribute %r (attributes: %s)" % (name, ", ".join(map(str, self.keys))))
+        if len(set(roles)) != len(roles):
+            raise ValueError("an attribute has two roles among bar_attr, metrical and note: %s" % (roles,))
+        self.bar_attr = self.keys.index(bar_attr)
+        self.metrical = [self.keys.index(k) for k in metrical]
+        self.note = [self.keys.index(k) for k in note]
+        beats = {} if beats is None else {int(c): int(k) for c, k in dict(beats).items()}
+        names = word2event[bar_attr]
+        n = self.n_class[self.bar_attr]
+        order = np.full(n, -3, dtype=np.int32)
+        order[0] = -2
+        for c in range(1, n):
+            name = names[c]
+            if c in beats:
+                if beats[c] < 0:
+                    raise ValueError("beats[%d] = %d: a beat index is >= 0" % (c, beats[c]))
+                order[c] = beats[c]
+            elif name == "Bar":
+                order[c] = -1
+            elif isinstance(name, str) and name.startswith("Beat_") and name[5:].isdigit():
+                order[c] = int(name[5:])
+            else:
+                raise ValueError("%s class %d (%r) is neither class 0, \"Bar\" nor Beat_<k>: pass beats={class id: "
+                                 "index}" % (bar_attr, c, name))
+        for c in beats:
+            if not 1 <= c < n:
+                raise ValueError("beats: class id %d outside 1..%d" % (c, n - 1))
+        if not (order == -1).any():
+            raise ValueError("%s has no class named \"Bar\"" % (bar_attr,))
+        self.order = order
+        self.bar_ids = [int(c) for c in np.nonzero(order == -1)[0]]
+
+    def kind(self, c):
+        """The kind of a row whose bar_attr class is c (NOTE / BAR / BEAT), None for a class outside the attribute."""
+        if not 0 <= int(c) < len(self.order):
+            return None
+        o = int(self.order[int(c)])
+        return self.NOTE if o == -2 else self.BAR if o == -1 else self.BEAT
+
+    def allowed(self, kind):
+        """Per attribute, the (n_class,) bool array of classes a row of `kind` may carry (bar_attr: the kind's own
+        classes; an attribute with no role: every class)."""
+        out = []
+        for a, n in enumerate(self.n_class):
+            ok = np.ones(n, dtype=bool)
+            if a == self.bar_attr:
+                ok = np.array([self.kind(c) == kind for c in range(n)])
+            elif (a in self.note and kind == self.NOTE) or (a in self.metrical and kind == self.BEAT):
+                ok[0] = False
+            elif a in self.note or a in self.metrical:
+                ok[1:] = False
+            out.append(ok)
+        return out
+
+    def position_allowed(self, beat):
+        """The (n_class[bar_attr],) bool array of bar_attr classes the position rule allows at `beat`."""
+        o, b = self.order.astype(np.int64), int(beat)
+        return (o == -1) | ((o >= 0) & (o > b)) | ((o == -2) & (b >= 0))
+
+    def tables(self):
+        """The device tables -> (order (n_class[bar_attr],) int32: -2 class 0, -1 Bar, k >= 0 Beat_k;
+        gram (3, ceil(sum n_class / 32)) uint32: rows NOTE, BAR, BEAT in the bit layout of Constraint.mask_rows)."""
+        W = -(-sum(self.n_class) // 32)
+        bits = np.zeros((3, W * 32), dtype=bool)
+        for kind in (self.NOTE, self.BAR, self.BEAT):
+            row = np.concatenate(self.allowed(kind))
+            bits[kind, :len(row)] = row
+        return self.order.copy(), np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(3, W)
+
+    def beat_states(self, song, beat=-1):
+        """The position before each row of `song` ((L, 6) rows) and after the last -> ((L,) int64, final), the first
+        row met at `beat` (-1: the start of a bar, what a song starts from)."""
+        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
+        c = song[:, self.bar_attr]
+        inside = (c >= 0) & (c < len(self.order))
+        o = np.where(inside, self.order.astype(np.int64)[np.where(inside, c, 0)], -3)
+        # after row t: the order of the last Bar / Beat row up to t, `beat` when there is none
+        last = np.maximum.accumulate(np.where(o >= -1, np.arange(len(song)), -1))
+        after = np.where(last >= 0, o[np.maximum(last, 0)], int(beat))
+        before = np.concatenate([[int(beat)], after[:-1]]).astype(np.int64)[:len(song)]
+        return before, int(after[-1]) if len(song) else int(beat)
+
+    def violations(self, song, n_prompt=0):
+        """Indices of the rows of `song` ((L, 6), its first n_prompt rows a prompt: tracked, not checked) that break
+        the kind table or the position rule."""
+        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
+        before, _ = self.beat_states(song)
+        c = song[:, self.bar_attr]
+        inside = (c >= 0) & (c < len(self.order))
+        o = np.where(inside, self.order.astype(np.int64)[np.where(inside, c, 0)], -3)
+        ok = (o == -1) | ((o >= 0) & (o > before)) | ((o == -2) & (before >= 0))
+        kind = np.where(o == -2, self.NOTE, np.where(o == -1, self.BAR, self.BEAT))
+        sets = [self.allowed(k) for k in (self.NOTE, self.BAR, self.BEAT)]
+        for a, n in enumerate(self.n_class):
+            if a == self.bar_attr:
+                continue
+            x = song[:, a]
+            table = np.stack([s[a] for s in sets])                     # (3, n_class[a])
+            ok &= (x >= 0) & (x < n) & table[kind, np.clip(x, 0, n - 1)]
+        return [int(t) for t in np.nonzero(~ok)[0] if t >= int(n_prompt)]
+
+
+def compile_grammar(grammar, constraints, n_songs, n_token, bar_cond):
+    """Grammar.tables() checked against the model's classes and the songs' constraints -> (order, gram).  Refused, so
+    that no reachable draw has an empty allowed set: a constraint row (any bar the device table holds) that leaves some
+    kind no class in some attribute, or allows no Bar class -- what the position rule always allows."""
+    if not isinstance(grammar, Grammar):
+        raise ValueError("grammar must be a Grammar, got %s" % type(grammar).__name__)
+    if list(grammar.n_class) != list(n_token):
+        raise ValueError("the grammar was built for classes %s, the model draws %s" % (grammar.n_class, list(n_token)))
+    if isinstance(constraints, Constraint):
+        constraints = [constraints]
+    seen = set()
+    kinds = [("note", grammar.allowed(Grammar.NOTE)), ("Bar", grammar.allowed(Grammar.BAR)),
+             ("beat", grammar.allowed(Grammar.BEAT))]
+    for c in constraints or []:
+        if not isinstance(c, Constraint) or id(c) in seen:
+            continue
+        seen.add(id(c))
+        if list(c.n_class) != list(n_token):
+            continue                                                   # compile_constraints refuses it
+        for i in range(len(c.mask_rows(bar_cond))):
+            ok = c.allowed(i + 1)
+            if not ok[grammar.bar_attr][grammar.bar_ids].any():
+                raise ValueError("grammar: the constraint allows no Bar class in bar %d, the one class the position "
+                                 "rule always allows" % (i + 1))
+            for name, sets in kinds:
+                for a, (x, y) in enumerate(zip(ok, sets)):
+                    if a != grammar.bar_attr and not (x & y).any():
+                        raise ValueError("grammar: in bar %d the constraint leaves a %s row no class of %r (class 0 "
+                                         "must stay allowed where the kind carries it: keep_neutral=True)"
+                                         % (i + 1, name, grammar.keys[a]))
+    return grammar.tables()
+
+
+def _device_grammar(grammar, tables, beat0s, dev):
+    """The grammar on the device: {"order", "gram" (int32 view), "beat0" (n_songs,) int64, "bar_attr"}."""
+    order, gram = tables
+    return {"order": torch.as_tensor(order).to(dev),
+            "gram": torch.as_tensor(np.ascontiguousarray(gram).view(np.int32)).to(dev),
+            "beat0": torch.as_tensor(np.asarray(beat0s, dtype=np.int64)).to(dev), "bar_attr": grammar.bar_attr}
+
+
 class _FusedPlan:
     """Host description of the model for `cwlt_decode_step` (include/cwlt.h: cwlt_decode_model): stacked
     QKV / head weights, device pointers of every parameter, the per-song state and workspace.  Holds references
@@ -597,12 +768,17 @@ class _DeviceLoop:
     then cwlt_count_bars advances the bar counts, both inside the captured token.
 
     logprobs=True: the draw is cwlt_sample_categorical_logp (the same tokens), which also writes each drawn class's
-    (model, sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects."""
+    (model, sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects.
+
+    grammar: the row grammar (_device_grammar): the draw is cwlt_sample_categorical_grammar (masked and with log-probs
+    as above when asked), then cwlt_count_bars if constrained, then cwlt_grammar_track moves each song's position."""
 
     def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None,
-                 mask=None, logprobs=False):
+                 mask=None, logprobs=False, grammar=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
         self.mask = mask
+        self.grammar = grammar
+        self.beat = None if grammar is None else grammar["beat0"].clone()       # one song per row, in song order
         self.A, self.N = len(sess.n_token), sess.n_songs
         self.ring = None if ring is None or int(ring) >= self.capacity else int(ring)
         rows = self.capacity if self.ring is None else self.ring
@@ -619,7 +795,19 @@ class _DeviceLoop:
     def _draw(self, logits):
         s = self.sess
         tok = s.tok.view(self.N, self.A)
-        if self.logp is not None:
+        if self.grammar is not None:
+            g, m = self.grammar, {} if self.mask is None else self.mask
+            ops.sample_categorical_grammar(logits, s.n_token, tok, self.seed, self.beat, g["order"], g["gram"],
+                                           g["bar_attr"], counter=self.count, bar=m.get("bar"), sched=m.get("sched"),
+                                           masks=m.get("masks"), logp=self.logp,
+                                           out_counter=None if self.logp is None else self.count,
+                                           temperature=self.temperature, top_p=self.top_p)
+            if self.mask is not None:
+                ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
+            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat)
+            if self.ring is None:
+                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
+        elif self.logp is not None:
             m = {} if self.mask is None else self.mask
             ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.logp, counter=self.count,
                                         bar=m.get("bar"), sched=m.get("sched"), masks=m.get("masks"),
@@ -717,11 +905,12 @@ class _StreamLoop:
     copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`)."""
 
     def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False):
+                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False, grammar=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
+        self._init_grammar(grammar)
         self.snap_state, self.snap_logits = snap_state, snap_logits.reshape(-1)
         self.n_layer = len(sess.memory)
         self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
@@ -753,6 +942,24 @@ class _StreamLoop:
         self._sample(logits, tok)
         ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
                            self.pos, self.bar, self.fresh, self.ctl, self.ring)
+        self._track(tok)
+
+    def _init_grammar(self, grammar):
+        """grammar (_device_grammar): slot s starts at beat0[s], the position of the song it starts with; a slot handed
+        a song later takes that song's beat0 in cwlt_grammar_track."""
+        self.grammar = grammar
+        self.beat = None
+        if grammar is not None:
+            self.beat = torch.full((self.S,), -1, dtype=torch.int64, device=self.sess.dev)
+            k = min(self.S, self.n_songs)
+            self.beat[:k] = grammar["beat0"][:k]
+
+    def _track(self, tok):
+        """After the advance: the grammar's position of every slot (its own launch, inside the captured token)."""
+        if self.grammar is not None:
+            g = self.grammar
+            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat, fresh=self.fresh, song=self.song,
+                              beat0=g["beat0"])
 
     def _init_logprobs(self, logprobs):
         dev = self.sess.dev
@@ -773,9 +980,16 @@ class _StreamLoop:
 
     def _sample(self, logits, tok):
         """Each slot's draw keyed by (song index, position in song); constrained (mask: _device_constraints) by the
-        song's mask row for the slot's bar count."""
+        song's mask row for the slot's bar count, and by the row grammar at the slot's position (grammar)."""
         s = self.sess
-        if self.lp_ring is not None:
+        if self.grammar is not None:
+            g = self.grammar
+            m = {} if self.mask is None else {"bar": self.bar, "sched": self.mask["sched"], "masks": self.mask["masks"]}
+            ops.sample_categorical_grammar(logits, s.n_token, tok, self.seed, self.beat, g["order"], g["gram"],
+                                           g["bar_attr"], key=self.song, step=self.pos, logp=self.lp_ring,
+                                           out_counter=None if self.lp_ring is None else self.ctl,
+                                           temperature=self.temperature, top_p=self.top_p, **m)
+        elif self.lp_ring is not None:
             m = {} if self.mask is None else {"bar": self.bar, "sched": self.mask["sched"], "masks": self.mask["masks"]}
             ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.lp_ring, key=self.song, step=self.pos,
                                         out_counter=self.ctl, temperature=self.temperature, top_p=self.top_p, **m)
@@ -844,11 +1058,12 @@ class _BankStreamLoop(_StreamLoop):
     cwlt_stream_advance_bank (a slot takes a song only below ctl[3], otherwise it waits)."""
 
     def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
-                 top_p=None, graph=None, prefill_rows=None, mask=None, logprobs=False):
+                 top_p=None, graph=None, prefill_rows=None, mask=None, logprobs=False, grammar=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
+        self._init_grammar(grammar)
         self.B, self.bank = int(B), int(bank)
         self.nb = self.bank // self.B
         self.n_blocks = -(-self.n_songs // self.B)
@@ -948,6 +1163,7 @@ class _BankStreamLoop(_StreamLoop):
         self._sample(logits, tok)
         ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
                                 self.song, self.pos, self.bar, self.cap, self.fresh, self.ctl, self.ring)
+        self._track(tok)
 
     def run(self, max_cap):
         """Run until the device's finished counter reaches n_songs -> rows (n, A + 2) of every song, time-ordered.
@@ -1023,12 +1239,13 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 
 def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_tokens, prompts, sampler, chunk, bank,
-                             prefill_rows, log, constraints=None, logprobs=False):
+                             prefill_rows, log, constraints=None, logprobs=False, grammar=None):
     start = time.perf_counter()
     n_token = list(model.n_token)
     heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
     table = None if constraints is None else \
         compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens)
+    gtables = None if grammar is None else compile_grammar(grammar, constraints, n_songs, n_token, bar_cond)
     sess = DecodeSession(model, n_songs=slots, kernel="gemm")
     sess.reset()
     seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
@@ -1040,7 +1257,9 @@ def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_to
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
     loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
                            temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows,
-                           mask=None if table is None else _device_constraints(table, sess.dev), logprobs=logprobs)
+                           mask=None if table is None else _device_constraints(table, sess.dev), logprobs=logprobs,
+                           grammar=None if grammar is None else
+                           _device_grammar(grammar, gtables, [grammar.beat_states(h)[1] for h in heads], sess.dev))
     rows = loop.run(max(caps))
     return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
                                       "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
@@ -1048,7 +1267,7 @@ def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_to
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                     return_logprobs=False):
+                     return_logprobs=False, grammar=None):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
@@ -1077,7 +1296,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompts is not None:
         heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
                                                                    max_tokens, prompts, sampler, chunk, bank,
-                                                                   prefill_rows, log, constraints, return_logprobs)
+                                                                   prefill_rows, log, constraints, return_logprobs,
+                                                                   grammar)
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
@@ -1095,6 +1315,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
         table = None if constraints is None else \
             compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, [bar0] * n_songs, max_tokens)
+        gtables = None if grammar is None else \
+            compile_grammar(grammar, constraints, n_songs, list(model.n_token), bar_cond)
         start = time.perf_counter()
         sess = DecodeSession(model, n_songs=slots, kernel="gemm")
         sess.reset()
@@ -1105,7 +1327,9 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
                            temperature=temperature, top_p=top_p, graph=sess.use_graph,
                            mask=None if table is None else _device_constraints(table, sess.dev),
-                           logprobs=return_logprobs)
+                           logprobs=return_logprobs,
+                           grammar=None if grammar is None else
+                           _device_grammar(grammar, gtables, [grammar.beat_states(head)[1]] * n_songs, sess.dev))
         rows = loop.run()
         heads = [head] * n_songs
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
@@ -1132,7 +1356,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                    return_logprobs=False):
+                    return_logprobs=False, grammar=None):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -1162,10 +1386,17 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     return_logprobs=True: -> (songs, logprobs), logprobs[k] the (L_k - P_k, 6, 2) f32 log-probs of song k's drawn rows
     (P_k its prompt's length), [..., 0] the model's and [..., 1] the sampler's (score_songs' layout), as
     the device sampler wrote them (cwlt_sample_categorical_logp): bitwise those of generate_batch(...,
-    return_logprobs=True).  The songs are the same as without the flag."""
+    return_logprobs=True).  The songs are the same as without the flag.
+
+    grammar: a Grammar (the row grammar): every drawn row is a note, a Bar or a Beat row and beats ascend
+    within a bar.  Each slot's draw is cwlt_sample_categorical_grammar at the slot's position in its bar, which
+    cwlt_grammar_track moves after the advance (a song's own prompt sets where it starts).  Combines with constraints
+    and return_logprobs; song k is still bitwise song k of generate_batch(..., grammar=grammar).  None: nothing
+    changes."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
-                            prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs)[0]
+                            prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs,
+                            grammar=grammar)[0]
 
 
 def _refuse_logprobs(return_logprobs, where):
@@ -1345,7 +1576,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
-                   log=None, prefill="blas", constraints=None, return_logprobs=False):
+                   log=None, prefill="blas", constraints=None, return_logprobs=False, grammar=None):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -1370,7 +1601,13 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     return_logprobs=True: -> (songs, logprobs), logprobs[i] the (L_i - P_i, 6, 2) f32 log-probs of song i's drawn rows
     (P_i its prompt's length; [..., 0] model, [..., 1] sampler, score_songs' layout), written by the
     device sampler itself (cwlt_sample_categorical_logp, into a float ring beside the token ring).  The songs are
-    bitwise those drawn without the flag."""
+    bitwise those drawn without the flag.
+
+    grammar: a Grammar (the row grammar): the draw is cwlt_sample_categorical_grammar -- bar-beat first,
+    under the position rule, then the other attributes under the row's kind -- and cwlt_grammar_track keeps each
+    song's position in its bar on the device, from where its prompt leaves it.  Combines with constraints (each mask
+    row is intersected with the grammar's) and return_logprobs (lp_sampler is log q of the distribution each class was
+    drawn from).  None: nothing changes."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if prefill not in ("blas", "gemm"):
@@ -1408,6 +1645,8 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     cap = max(caps)
     table = None if constraints is None else \
         compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, cnt_bar, max_tokens)
+    gtables = None if grammar is None else \
+        compile_grammar(grammar, constraints, n_songs, list(model.n_token), bar_cond)
     sess = DecodeSession(model, n_songs=n_songs, kernel="gemm")
     sess.reset()
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
@@ -1419,7 +1658,9 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         mask["bar_mask"] = torch.as_tensor(np.array([names[i] == "Bar" for i in range(sess.n_token[2])],
                                                     dtype=np.int32)).to(sess.dev)
     loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
-                       ring=chunk, mask=mask, logprobs=return_logprobs)
+                       ring=chunk, mask=mask, logprobs=return_logprobs,
+                       grammar=None if grammar is None else
+                       _device_grammar(grammar, gtables, [grammar.beat_states(p)[1] for p in heads], sess.dev))
     if prompts is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
                        .view(n_songs, 1, A).to(sess.dev))
@@ -1505,7 +1746,7 @@ def _score_inputs(songs, mask, n_token):
 
 
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
-                prefill_rows=None):
+                prefill_rows=None, grammar=None):
     """Log-likelihoods of given songs under the recurrent form, as generation samples them.
     -> list of (L_i - 1, 6, 2) float32 arrays; row t is about song[t + 1] given song[:t + 1] (pe[0] on every row, as
     DecodeSession.step and prefill compute it): [..., 0] the model log-prob log_softmax(logits_t[a])[song[t + 1, a]]
@@ -1525,6 +1766,9 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     (default PREFILL_ROWS; at most SCORE_BLOCK_SONGS songs), each block on a fresh scratch state: no session is
     touched.  The logits are scored by cwlt_score_categorical, the sampler's own kernel body, so the logits a draw came
     from, scored at the class it drew, give the sampler's pair bitwise.
+    grammar: a Grammar: row t + 1 is scored under the row grammar (cwlt_score_categorical_grammar), its kind that of
+    song[t + 1]'s own bar-beat class and its position Grammar.beat_states(song)[0][t + 1]; an ill-formed row gets -inf
+    in the sampler column of the offending attribute and a finite model column.
     Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
@@ -1553,6 +1797,11 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
         # max_tokens = the longest song: every song ends, so compile_constraints' "could never end" check is skipped
         table = compile_constraints(constraints, n, n_token, top + 1, [1] * n, max(len(x) for x in songs))
         dmask = None if table is None else _device_constraints(table, dev)
+    dgram = None
+    if grammar is not None:
+        top = max([int(b.max()) for b in bars if len(b)] + [1])
+        dgram = _device_grammar(grammar, compile_grammar(grammar, constraints, n, n_token, top + 1), [], dev)
+        beats = [grammar.beat_states(x)[0] for x in songs]
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
     enc = model.transformer_encoder
     H = enc.layers[0].attention.n_heads
@@ -1565,10 +1814,13 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
         toks = np.zeros((nb, Lb, A), dtype=np.int64)
         tgt = np.full((nb, Lb, A), -1, dtype=np.int64)          # the last row of a song and padding: not scored
         bar = np.ones((nb, Lb), dtype=np.int64)
+        beat = np.full((nb, Lb), -1, dtype=np.int64)
         for i, x in enumerate(blk):
             toks[i, :len(x)] = x
             tgt[i, :len(x) - 1] = x[1:]
             bar[i, :len(x) - 1] = bars[a0 + i]
+            if dgram is not None:
+                beat[i, :len(x) - 1] = beats[a0 + i][1:]
         memory = [[torch.zeros((nb, H, d, d), dtype=torch.float32, device=dev),
                    torch.zeros((nb, H, d), dtype=torch.float32, device=dev)] for _ in enc.layers]
         with torch.no_grad():
@@ -1578,8 +1830,16 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
             if dmask is not None:
                 m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
                      "bar": torch.as_tensor(bar.reshape(-1)).to(dev), "sched": dmask["sched"], "masks": dmask["masks"]}
-            lp = ops.score_categorical(lg.reshape(nb * Lb, -1), n_token, torch.as_tensor(tgt.reshape(-1, A)).to(dev),
-                                       temperature=temperature, top_p=top_p, **m)
+            if dgram is not None:
+                lp = ops.score_categorical_grammar(lg.reshape(nb * Lb, -1), n_token,
+                                                   torch.as_tensor(tgt.reshape(-1, A)).to(dev),
+                                                   torch.as_tensor(beat.reshape(-1)).to(dev), dgram["order"],
+                                                   dgram["gram"], dgram["bar_attr"], temperature=temperature,
+                                                   top_p=top_p, **m)
+            else:
+                lp = ops.score_categorical(lg.reshape(nb * Lb, -1), n_token,
+                                           torch.as_tensor(tgt.reshape(-1, A)).to(dev), temperature=temperature,
+                                           top_p=top_p, **m)
         lp = lp.view(nb, Lb, A, 2).cpu().numpy()
         out.extend(lp[i, :len(x) - 1].copy() for i, x in enumerate(blk))
     return out
@@ -1587,7 +1847,7 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False):
+             batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1601,12 +1861,16 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     constraints: one Constraint for every song or a list of n_songs Constraint / None entries (generate_batch,
     generate_stream), with slots or batch_size only: the one-song path samples on the host.
     logprobs=True (with slots or batch_size only): save each song's drawn-row log-probs (return_logprobs of
-    generate_stream / generate_batch) as get_<i>_logp.npy next to the song."""
+    generate_stream / generate_batch) as get_<i>_logp.npy next to the song.
+    grammar: a Grammar (generate_batch, generate_stream), with slots or batch_size only, as constraints."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
     if logprobs and batch_size is None and slots is None:
         raise ValueError("log-probs come from the device samplers of generate_batch / generate_stream: pass batch_size "
                          "or slots (or score the songs with score_songs)")
+    if grammar is not None and batch_size is None and slots is None:
+        raise ValueError("the row grammar runs in the device samplers of generate_batch / generate_stream: pass "
+                         "batch_size or slots (one song: generate_batch(n_songs=1, grammar=...))")
     if constraints is not None:
         if batch_size is None and slots is None:
             raise ValueError("constraints run in the device samplers of generate_batch / generate_stream: pass "
@@ -1635,7 +1899,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                 prompt=prompt, prompts=None if prompts is None else list(prompts),
-                                constraints=constraints, return_logprobs=logprobs)
+                                constraints=constraints, return_logprobs=logprobs, grammar=grammar)
         wall = time.time() - start
         if logprobs:
             songs = list(zip(*songs))
@@ -1655,7 +1919,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                                    prompts=prompt if prompts is None else list(prompts[first:first + group]),
                                    constraints=list(constraints[first:first + group])
                                    if isinstance(constraints, (list, tuple)) else constraints,
-                                   return_logprobs=logprobs)
+                                   return_logprobs=logprobs, grammar=grammar)
             wall = time.time() - start
             if logprobs:
                 songs = list(zip(*songs))

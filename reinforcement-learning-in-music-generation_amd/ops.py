@@ -1714,6 +1714,115 @@ def score_categorical(logits, n_class, targets, temperature=None, top_p=None, ke
     return out
 
 
+def _grammar_table(n_class, rows, beat, order, gram, bar_attr):
+    """Checks of the row grammar's device tables -> (beat, order, n_order, gram, words, bar_attr) ctypes arguments."""
+    if beat.dtype != torch.int64 or beat.numel() != rows or not beat.is_contiguous():
+        raise ValueError("beat must be a contiguous (rows,) int64 tensor")
+    if not 0 <= int(bar_attr) < len(n_class):
+        raise ValueError("bar_attr %d outside the %d attributes" % (bar_attr, len(n_class)))
+    if order.dtype != torch.int32 or order.dim() != 1 or not order.is_contiguous() or \
+            order.numel() < n_class[int(bar_attr)]:
+        raise ValueError("order must be a contiguous int32 tensor of >= %d entries" % n_class[int(bar_attr)])
+    if gram.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or gram.dim() != 2 or \
+            gram.shape[0] != 3 or not gram.is_contiguous():
+        raise ValueError("gram must be a contiguous (3, words) 32-bit tensor")
+    if gram.shape[1] * 32 < sum(n_class):
+        raise ValueError("gram: %d words per row hold fewer than the %d classes" % (gram.shape[1], sum(n_class)))
+    return (_lib.dev(beat, "beat"), _lib.dev(order, "order"), order.numel(), _lib.dev(gram, "gram"), gram.shape[1],
+            int(bar_attr))
+
+
+def sample_categorical_grammar(logits, n_class, tokens, seed, beat, order, gram, bar_attr=2, counter=None, key=None,
+                               step=None, bar=None, sched=None, masks=None, logp=None, out_counter=None,
+                               temperature=None, top_p=None):
+    """The draw under the row grammar (cwlt_sample_categorical_grammar): keyed as
+    sample_categorical_logp (slot and `counter`, or key / step), masked by bar / sched / masks when given, the bar-beat
+    class (attribute bar_attr) drawn first under the position rule -- beat (rows,) int64, order (>= n_class[bar_attr],)
+    int32 -- and every other attribute under the row of gram (3, words) its kind selects.  logp (optional): the (R, rows,
+    A, 2) f32 ring of sample_categorical_logp, row *out_counter % R."""
+    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
+        raise TypeError("sample_categorical_grammar takes f32 logits and int64 tokens")
+    rows, A = logits.shape[0], len(n_class)
+    if tokens.numel() != rows * A or not tokens.is_contiguous():
+        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
+    if (key is None) != (step is None) or (key is None and counter is None):
+        raise ValueError("sample_categorical_grammar is keyed by key and step, or by the slot and a counter")
+    for t in ([] if key is None else [key, step]):
+        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
+            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
+    if logp is not None:
+        if logp.dtype != torch.float32 or logp.dim() != 4 or tuple(logp.shape[1:]) != (rows, A, 2) or \
+                not logp.is_contiguous():
+            raise ValueError("logp must be a contiguous (R, %d, %d, 2) f32 ring" % (rows, A))
+        if out_counter is None and logp.shape[0] != 1:
+            raise ValueError("a logp ring of %d rows needs out_counter" % logp.shape[0])
+    table = _mask_table(n_class, rows, bar, sched, masks)
+    gtable = _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    _call("cwlt_sample_categorical_grammar", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
+          *gtable, _lib.dev(tokens, "tokens"), _lib.opt(logp), _lib.opt(out_counter),
+          1 if logp is None else logp.shape[0], _lib.stream_ptr())
+    return tokens
+
+
+def score_categorical_grammar(logits, n_class, targets, beat, order, gram, bar_attr=2, temperature=None, top_p=None,
+                              key=None, bar=None, sched=None, masks=None, out=None):
+    """score_categorical under the row grammar (cwlt_score_categorical_grammar): the kind of row n is that of its
+    target's bar-beat class, beat (rows,) int64 the position before each row -> (rows, A, 2) f32."""
+    if logits.dtype != torch.float32 or targets.dtype != torch.int64:
+        raise TypeError("score_categorical_grammar takes f32 logits and int64 targets")
+    rows, A = logits.shape[0], len(n_class)
+    if targets.numel() != rows * A or not targets.is_contiguous():
+        raise ValueError("targets must be a contiguous (rows, n_attr) int64 tensor")
+    if key is not None and bar is None:
+        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
+    _mask_table(n_class, rows, bar, sched, masks, key)
+    _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+    if out is None:
+        out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
+    if logits.stride(-1) != 1:
+        logits = logits.contiguous()
+    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
+    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
+    tv = targets.view(rows, A)
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        sl = lambda t: None if t is None else t[a:z]
+        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
+        gtable = _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
+        _call("cwlt_score_categorical_grammar", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A,
+              z - a, logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, *gtable,
+              _lib.dev(out[a:z], "logp"), _lib.stream_ptr())
+    return out
+
+
+def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):
+    """The row grammar's position after a draw (cwlt_grammar_track): beat[n] (rows,) int64 moves by the bar-beat class
+    of tokens (rows, A) int64 through order (int32: -1 Bar, k >= 0 Beat_k, else unchanged); with fresh / song (rows,)
+    int64 and beat0 (n_songs,) int64, a row flagged fresh with song >= 0 starts from beat0[song] instead."""
+    rows, A = beat.numel(), tokens.shape[-1]
+    if tokens.dtype != torch.int64 or beat.dtype != torch.int64 or not tokens.is_contiguous() or \
+            not beat.is_contiguous() or tokens.numel() != rows * A:
+        raise TypeError("grammar_track takes contiguous int64 tokens (rows, A) and beat (rows,)")
+    if order.dtype != torch.int32 or not order.is_contiguous():
+        raise TypeError("grammar_track takes a contiguous int32 order")
+    opt = [fresh, song, beat0]
+    if any(t is not None for t in opt):
+        if any(t is None or t.dtype != torch.int64 or not t.is_contiguous() for t in opt) or \
+                fresh.numel() != rows or song.numel() != rows:
+            raise ValueError("grammar_track: fresh and song (rows,) and beat0 (n_songs,) int64 go together")
+    _call("cwlt_grammar_track", _lib.dev(tokens, "tokens"), rows, A, int(bar_attr), _lib.dev(order, "order"),
+          order.numel(), _lib.opt(fresh), _lib.opt(song), _lib.opt(beat0), 0 if beat0 is None else beat0.numel(),
+          _lib.dev(beat, "beat"), _lib.stream_ptr())
+    return beat
+
+
 def count_bars(tokens, bar_attr, bar_mask, bar):
     """bar[n] += 1 where row n of tokens (rows, A) int64 has a Bar class in attribute bar_attr (bar_mask
     (n_class[bar_attr],) int32) -- cwlt_count_bars, the batch loop's bar count in constrained mode."""

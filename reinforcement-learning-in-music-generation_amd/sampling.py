@@ -100,3 +100,45 @@ def logprobs_f64(logits, target, temperature=1.0, top_p=None, allowed=None):
     if not keep[target]:
         return lm, -np.inf
     return lm, (v[target] - m) - np.log(e[keep].sum())
+
+
+def grammar_allowed_f64(bar_class, beat, order, gram, bar_attr, allowed=None):
+    """The allowed sets of one row under the row grammar -> list of (n,) bool arrays, one per attribute.
+    order: per class of attribute bar_attr, -2 class 0 (a note row), -1 a Bar class, k >= 0 Beat_k, -3 never allowed;
+    beat: the song's position before the row (-1 after a Bar row, k after Beat_k); gram[kind][a]: the (n,) bool classes
+    a row of kind 0 NOTE / 1 BAR / 2 BEAT may carry in attribute a; allowed: the row's constraint sets (None = all).
+    Attribute bar_attr gets the position rule (a Bar class always, Beat_k when k > beat, class 0 when beat >= 0); every
+    other attribute gets the gram row of the kind of `bar_class`, the row's bar_attr class (no class at all when
+    bar_class is outside the attribute or never allowed)."""
+    o = np.asarray(order, dtype=np.int64)
+    b = int(beat)
+    c = int(bar_class)
+    kind = None
+    if 0 <= c < len(o) and o[c] != -3:
+        kind = 0 if o[c] == -2 else 1 if o[c] == -1 else 2
+    out = []
+    for a in range(len(gram[0])):
+        if a == bar_attr:
+            ok = (o == -1) | ((o >= 0) & (o > b)) | ((o == -2) & (b >= 0))
+        elif kind is None:
+            ok = np.zeros(len(gram[0][a]), dtype=bool)
+        else:
+            ok = np.asarray(gram[kind][a], dtype=bool)
+        out.append(ok.copy() if allowed is None else ok & np.asarray(allowed[a], dtype=bool))
+    return out
+
+
+def grammar_logprobs_f64(logits, target, beat, order, gram, bar_attr, temperature=None, top_p=None, allowed=None):
+    """Float64 restatement of the grammar draw's log-probs for one row: logits (one (n,) vector per attribute), target
+    (one class per attribute) -> (A, 2) float64, [a] = logprobs_f64 of attribute a under the distribution the device
+    draws it from: bar_attr given the position `beat`, every other attribute given the kind of target[bar_attr]
+    (grammar_allowed_f64).  The model column is unchanged by the grammar; an ill-formed target has -inf in the sampler
+    column of the offending attribute."""
+    sets = grammar_allowed_f64(target[bar_attr], beat, order, gram, bar_attr, allowed)
+    A = len(sets)
+    out = np.zeros((A, 2))
+    for a in range(A):
+        t = 1.0 if temperature is None else temperature[a]
+        p = None if top_p is None else top_p[a]
+        out[a] = logprobs_f64(logits[a], target[a], t, p, sets[a])
+    return out
