@@ -753,6 +753,45 @@ class DecodeSession:
         return outs
 
 
+def _draw_token(logits, n_token, tok, seed, temperature, top_p, counter=None, key=None, step=None, mask=None, logp=None,
+                out_counter=None, grammar=None, beat=None, song=None):
+    """One token's draw for every row of logits into tok (rows, A), by the one rule of both loops: under a grammar
+    (_device_grammar, position `beat`) cwlt_sample_categorical_grammar, else with a log-prob ring `logp` (row
+    *out_counter) cwlt_sample_categorical_logp, else with a mask ({"bar", "sched", "masks"}) ..._masked, else the plain
+    draw.  Keyed per row by key / step (the stream: song index, position in song), or by the row's slot at `counter`
+    (the batch loop, whose plain draw also writes row *counter of `song`)."""
+    kw = dict(counter=counter, key=key, step=step, temperature=temperature, top_p=top_p)
+    m = {} if mask is None else {k: mask[k] for k in ("bar", "sched", "masks")}
+    if grammar is not None:
+        ops.sample_categorical_grammar(logits, n_token, tok, seed, beat, grammar["order"], grammar["gram"],
+                                       grammar["bar_attr"], logp=logp,
+                                       out_counter=None if logp is None else out_counter, **m, **kw)
+    elif logp is not None:
+        ops.sample_categorical_logp(logits, n_token, tok, seed, logp, out_counter=out_counter, **m, **kw)
+    elif mask is not None:
+        ops.sample_categorical_masked(logits, n_token, tok, seed, m["bar"], m["sched"], m["masks"], **kw)
+    elif key is not None:
+        ops.sample_categorical_keyed(logits, n_token, tok, seed, key, step, temperature=temperature, top_p=top_p)
+    else:
+        ops.sample_categorical(logits, n_token, tok, seed, counter=counter, song=song, temperature=temperature,
+                               top_p=top_p, slot_keys=True)
+
+
+def _enqueue_token(loop, name):
+    """Enqueue one more token of `loop` (its _one; call under torch.no_grad()): eager for the first two tokens and when
+    graphs are off; at the third, after a device synchronize, _one is captured as one hipGraph -- recorded, not
+    executed -- and replayed from then on.  A capture that cannot be replayed leaves the loop eager."""
+    if loop.use_graph and loop.enqueued >= 2 and loop._graph is None:
+        torch.cuda.synchronize(loop.sess.dev)
+        loop._graph = ops.capture_hip_graph(loop._one, torch.no_grad, name)[0]
+        loop.use_graph = loop._graph is not None
+    if loop.use_graph and loop.enqueued >= 2:
+        loop._graph.replay()
+    else:
+        loop._one()
+    loop.enqueued += 1
+
+
 class _DeviceLoop:
     """Generation loop that never returns to the host: per token the decode step, ONE sampling kernel
     (csrc/sample.hip) that writes the drawn ids of every song into the step's token buffer and into row `count` of
@@ -795,40 +834,18 @@ class _DeviceLoop:
     def _draw(self, logits):
         s = self.sess
         tok = s.tok.view(self.N, self.A)
+        # the plain draw writes the song row itself; every other one, and a ring, takes a copy of the token buffer
+        fused = self.ring is None and self.mask is None and self.logp is None and self.grammar is None
+        _draw_token(logits, s.n_token, tok, self.seed, self.temperature, self.top_p, counter=self.count, mask=self.mask,
+                    logp=self.logp, out_counter=self.count, grammar=self.grammar, beat=self.beat,
+                    song=self.song if fused else None)
+        if self.mask is not None:
+            ops.count_bars(tok, 2, self.mask["bar_mask"], self.mask["bar"])
         if self.grammar is not None:
-            g, m = self.grammar, {} if self.mask is None else self.mask
-            ops.sample_categorical_grammar(logits, s.n_token, tok, self.seed, self.beat, g["order"], g["gram"],
-                                           g["bar_attr"], counter=self.count, bar=m.get("bar"), sched=m.get("sched"),
-                                           masks=m.get("masks"), logp=self.logp,
-                                           out_counter=None if self.logp is None else self.count,
-                                           temperature=self.temperature, top_p=self.top_p)
-            if self.mask is not None:
-                ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
-            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat)
-            if self.ring is None:
-                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
-        elif self.logp is not None:
-            m = {} if self.mask is None else self.mask
-            ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.logp, counter=self.count,
-                                        bar=m.get("bar"), sched=m.get("sched"), masks=m.get("masks"),
-                                        out_counter=self.count, temperature=self.temperature, top_p=self.top_p)
-            if self.mask is not None:
-                ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
-            if self.ring is None:
-                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
-        elif self.mask is None:
-            ops.sample_categorical(logits, s.n_token, tok, self.seed, counter=self.count,
-                                   song=self.song if self.ring is None else None, temperature=self.temperature,
-                                   top_p=self.top_p, slot_keys=True)
-        else:
-            m = self.mask
-            ops.sample_categorical_masked(logits, s.n_token, tok, self.seed, m["bar"], m["sched"], m["masks"],
-                                          counter=self.count, temperature=self.temperature, top_p=self.top_p)
-            ops.count_bars(tok, 2, m["bar_mask"], m["bar"])
-            if self.ring is None:
-                self.song.index_copy_(0, self.count, tok.view(1, self.N, self.A))
+            ops.grammar_track(tok, self.grammar["bar_attr"], self.grammar["order"], self.beat)
+        if not fused:
+            self.song.index_copy_(0, self.count if self.ring is None else self.slot, tok.view(1, self.N, self.A))
         if self.ring is not None:
-            self.song.index_copy_(0, self.slot, tok.view(1, self.N, self.A))
             self.slot.add_(1).remainder_(self.ring)
         self.count.add_(1)
 
@@ -852,19 +869,7 @@ class _DeviceLoop:
         n = min(n, self.capacity - self.enqueued)
         with torch.no_grad():
             for _ in range(n):
-                if not self.use_graph or self.enqueued < 2:
-                    self._one()
-                else:
-                    if self._graph is None:
-                        torch.cuda.synchronize(self.sess.dev)
-                        self._graph = ops.capture_hip_graph(self._one, torch.no_grad, "decode loop")[0]   # recorded,
-                        if self._graph is None:                                                      # not executed
-                            self.use_graph = False
-                            self._one()
-                            self.enqueued += 1
-                            continue
-                    self._graph.replay()
-                self.enqueued += 1
+                _enqueue_token(self, "decode loop")
         return n
 
     def tokens(self, start, stop):
@@ -896,78 +901,81 @@ class _StreamLoop:
     sequence of launches (captured as one hipGraph after two eager tokens):
       the GEMM decode step on every slot;
       cwlt_stream_refill: slots flagged fresh get the snapshot's state and logits (the state every song starts from);
-      cwlt_sample_categorical_keyed: each slot's draw keyed by (song index, position in song);
+      the draw (_draw_token), each slot's keyed by (song index, position in song): cwlt_sample_categorical_keyed, or
+        the masked / log-prob / grammar entry when the stream has a mask (_device_constraints: the song's mask row for
+        the slot's bar count), log-probs or a grammar (_device_grammar: the row grammar at the slot's position);
       cwlt_stream_advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count
-        advanced, the song's end detected, finished slots handed the next song indices in slot order.
+        advanced, the song's end detected, finished slots handed the next song indices in slot order;
+      cwlt_grammar_track (under a grammar): every slot's position after the advance.
     The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host.
     logprobs=True: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
     log-probs into `lp_ring` (2 chunk, slots, A, 2) at the row ctl[0] selects -- the row of `ring` the advance writes --
-    copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`)."""
+    copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`).
+    waiting=True (the bank's loop): no slot holds a song or is fresh yet, `cap` is the slots' own (S,) caps with max_cap
+    the largest a song can have, and the device counters {tokens, assigned, finished} gain a fourth, `ready`."""
 
     def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False, grammar=None):
+                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False, grammar=None, waiting=False,
+                 max_cap=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
-        self.mask = mask
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
-        self._init_grammar(grammar)
-        self.snap_state, self.snap_logits = snap_state, snap_logits.reshape(-1)
+        self.snap_state, self.snap_logits = snap_state, snap_logits
         self.n_layer = len(sess.memory)
         self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
         self.z_floats = sess.memory[0][1][0].numel()             # one slot's Z (H x d)
         self.seed, self.temperature, self.top_p = seed, temperature, top_p
         self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
-        self.bar_cond, self.bar0, self.cap = int(bar_cond), int(bar0), int(cap)
+        self.bar_cond, self.bar0, self.cap = int(bar_cond), int(bar0), cap if waiting else int(cap)
+        self.max_cap = int(cap if max_cap is None else max_cap)    # the most tokens one song draws (run()'s step limit)
         slot = torch.arange(self.S, dtype=torch.int64, device=dev)
-        self.song = torch.where(slot < self.n_songs, slot, torch.full_like(slot, -1))
+        self.song = torch.where(slot < (0 if waiting else self.n_songs), slot, torch.full_like(slot, -1))
         self.pos = torch.zeros(self.S, dtype=torch.int64, device=dev)
         self.bar = torch.full((self.S,), self.bar0, dtype=torch.int64, device=dev)
-        self.fresh = torch.ones(self.S, dtype=torch.int64, device=dev)     # every slot starts from the snapshot
-        self.ctl = torch.tensor([0, min(self.S, self.n_songs), 0], dtype=torch.int64, device=dev)
+        self.fresh = torch.full((self.S,), 0 if waiting else 1, dtype=torch.int64, device=dev)   # 1: take the snapshot
+        ctl = [0, 0, 0, 0] if waiting else [0, min(self.S, self.n_songs), 0]
+        self.ctl = torch.tensor(ctl, dtype=torch.int64, device=dev)
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._init_logprobs(logprobs)
-        self._host_ctl = [torch.zeros(3, dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._events = [torch.cuda.Event(), torch.cuda.Event()]
-        self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
-        self._graph, self.enqueued = None, 0
-        self.wait_s = 0.0                                          # host time spent waiting on the device
-
-    def _one(self):
-        s = self.sess
-        tok = s.tok.view(self.S, self.A)
-        logits = s._device_step()
-        ops.stream_refill(s._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
-                          self.snap_logits, self.fresh)
-        self._sample(logits, tok)
-        ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
-                           self.pos, self.bar, self.fresh, self.ctl, self.ring)
-        self._track(tok)
-
-    def _init_grammar(self, grammar):
-        """grammar (_device_grammar): slot s starts at beat0[s], the position of the song it starts with; a slot handed
-        a song later takes that song's beat0 in cwlt_grammar_track."""
-        self.grammar = grammar
-        self.beat = None
+        self.mask = None if mask is None else dict(mask, bar=self.bar)
+        # grammar: slot s starts at beat0[s], the position of the song it starts with; a slot handed a song later takes
+        # that song's beat0 in cwlt_grammar_track
+        self.grammar, self.beat = grammar, None
         if grammar is not None:
-            self.beat = torch.full((self.S,), -1, dtype=torch.int64, device=self.sess.dev)
+            self.beat = torch.full((self.S,), -1, dtype=torch.int64, device=dev)
             k = min(self.S, self.n_songs)
             self.beat[:k] = grammar["beat0"][:k]
-
-    def _track(self, tok):
-        """After the advance: the grammar's position of every slot (its own launch, inside the captured token)."""
-        if self.grammar is not None:
-            g = self.grammar
-            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat, fresh=self.fresh, song=self.song,
-                              beat0=g["beat0"])
-
-    def _init_logprobs(self, logprobs):
-        dev = self.sess.dev
         self.lp_ring = torch.zeros((2 * self.chunk, self.S, self.A, 2), dtype=torch.float32, device=dev) \
             if logprobs else None
         self._host_lp = [torch.zeros((self.chunk, self.S, self.A, 2), dtype=torch.float32).pin_memory()
                          for _ in range(2)] if logprobs else None
         self.lp_parts = []
+        self._host_ctl = [torch.zeros(len(ctl), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._events = [torch.cuda.Event(), torch.cuda.Event()]
+        self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
+        self._graph, self.enqueued = None, 0
+        self.wait_s = 0.0                                          # host time spent waiting on the device
+
+    def _refill(self, logits):
+        ops.stream_refill(self.sess._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
+                          self.snap_logits, self.fresh)
+
+    def _advance(self, tok):
+        ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
+                           self.pos, self.bar, self.fresh, self.ctl, self.ring)
+
+    def _one(self):
+        s = self.sess
+        tok = s.tok.view(self.S, self.A)
+        logits = s._device_step()
+        self._refill(logits)
+        _draw_token(logits, s.n_token, tok, self.seed, self.temperature, self.top_p, key=self.song, step=self.pos,
+                    mask=self.mask, logp=self.lp_ring, out_counter=self.ctl, grammar=self.grammar, beat=self.beat)
+        self._advance(tok)
+        if self.grammar is not None:
+            g = self.grammar
+            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat, fresh=self.fresh, song=self.song,
+                              beat0=g["beat0"])
 
     def _read(self, h):
         """The rows of ring half h that belong to songs (waiting and idle slots write song < 0), and their log-probs
@@ -978,46 +986,11 @@ class _StreamLoop:
             self.lp_parts.append(self._host_lp[h].numpy().reshape(-1, self.A, 2)[keep])
         return rows[keep]
 
-    def _sample(self, logits, tok):
-        """Each slot's draw keyed by (song index, position in song); constrained (mask: _device_constraints) by the
-        song's mask row for the slot's bar count, and by the row grammar at the slot's position (grammar)."""
-        s = self.sess
-        if self.grammar is not None:
-            g = self.grammar
-            m = {} if self.mask is None else {"bar": self.bar, "sched": self.mask["sched"], "masks": self.mask["masks"]}
-            ops.sample_categorical_grammar(logits, s.n_token, tok, self.seed, self.beat, g["order"], g["gram"],
-                                           g["bar_attr"], key=self.song, step=self.pos, logp=self.lp_ring,
-                                           out_counter=None if self.lp_ring is None else self.ctl,
-                                           temperature=self.temperature, top_p=self.top_p, **m)
-        elif self.lp_ring is not None:
-            m = {} if self.mask is None else {"bar": self.bar, "sched": self.mask["sched"], "masks": self.mask["masks"]}
-            ops.sample_categorical_logp(logits, s.n_token, tok, self.seed, self.lp_ring, key=self.song, step=self.pos,
-                                        out_counter=self.ctl, temperature=self.temperature, top_p=self.top_p, **m)
-        elif self.mask is None:
-            ops.sample_categorical_keyed(logits, s.n_token, tok, self.seed, self.song, self.pos,
-                                         temperature=self.temperature, top_p=self.top_p)
-        else:
-            ops.sample_categorical_masked(logits, s.n_token, tok, self.seed, self.bar, self.mask["sched"],
-                                          self.mask["masks"], key=self.song, step=self.pos,
-                                          temperature=self.temperature, top_p=self.top_p)
-
     def _enqueue_chunk(self):
         """Enqueue `chunk` tokens and the copy of their ring half (and the counters) to pinned host memory."""
         with torch.no_grad():
             for _ in range(self.chunk):
-                if not self.use_graph or self.enqueued < 2:
-                    self._one()
-                else:
-                    if self._graph is None:
-                        torch.cuda.synchronize(self.sess.dev)
-                        self._graph = ops.capture_hip_graph(self._one, torch.no_grad, "stream step")[0]  # recorded,
-                        if self._graph is None:                                                     # not executed
-                            self.use_graph = False
-                            self._one()
-                            self.enqueued += 1
-                            continue
-                    self._graph.replay()
-                self.enqueued += 1
+                _enqueue_token(self, "stream step")
         k = self.enqueued // self.chunk - 1
         h = k % 2
         self._host[h].copy_(self.ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
@@ -1027,25 +1000,31 @@ class _StreamLoop:
         self._events[h].record()
         return h
 
+    def _wait(self, h):
+        t = time.perf_counter()
+        self._events[h].synchronize()
+        self.wait_s += time.perf_counter() - t
+
+    def _between_chunks(self, ctl, limit):
+        """Between two chunks of run(), with the counters of the chunk just read: the step limit."""
+        if self.enqueued > limit:
+            raise RuntimeError("stream did not finish %d songs in %d steps" % (self.n_songs, self.enqueued))
+
     def run(self):
         """Run until the device's finished counter reaches n_songs -> (rows (n, A + 2) of every song, time-ordered)."""
         parts = []
-        limit = -(-self.n_songs // self.S) * (self.cap + 1) + 2 * self.chunk     # every slot's songs, one by one
+        limit = -(-self.n_songs // self.S) * (self.max_cap + 1) + 2 * self.chunk     # every slot's songs, one by one
         h = self._enqueue_chunk()
         while True:
             nxt = self._enqueue_chunk()
-            t = time.perf_counter()
-            self._events[h].synchronize()
-            self.wait_s += time.perf_counter() - t
+            self._wait(h)
             parts.append(self._read(h))
-            if int(self._host_ctl[h][2]) >= self.n_songs:
+            ctl = self._host_ctl[h].numpy().copy()
+            if ctl[2] >= self.n_songs:
                 break
-            if self.enqueued > limit:
-                raise RuntimeError("stream did not finish %d songs in %d steps" % (self.n_songs, self.enqueued))
+            self._between_chunks(ctl, limit)
             h = nxt
-        t = time.perf_counter()
-        self._events[nxt].synchronize()                           # the one chunk enqueued past the end
-        self.wait_s += time.perf_counter() - t
+        self._wait(nxt)                                            # the one chunk enqueued past the end
         return np.concatenate(parts)
 
 
@@ -1059,20 +1038,16 @@ class _BankStreamLoop(_StreamLoop):
 
     def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
                  top_p=None, graph=None, prefill_rows=None, mask=None, logprobs=False, grammar=None):
-        self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
-        self.mask = mask
-        self.S, self.A = sess.n_songs, len(sess.n_token)
+        # no snapshot; until start() hands songs out the slots wait, count bars from 0 and carry caps of 1
         dev = sess.dev
-        self._init_grammar(grammar)
+        super().__init__(sess, None, None, n_songs, seed, bar_mask, bar_cond, 0,
+                         torch.ones(sess.n_songs, dtype=torch.int64, device=dev), chunk, temperature=temperature,
+                         top_p=top_p, graph=graph, mask=mask, logprobs=logprobs, grammar=grammar, waiting=True,
+                         max_cap=max(caps))
         self.B, self.bank = int(B), int(bank)
         self.nb = self.bank // self.B
         self.n_blocks = -(-self.n_songs // self.B)
-        self.n_layer = len(sess.memory)
         H, d = sess.memory[0][1].shape[1:]
-        self.s_floats, self.z_floats = H * d * d, H * d
-        self.seed, self.temperature, self.top_p = seed, temperature, top_p
-        self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
-        self.bar_cond = int(bar_cond)
         per = self.bank * (self.s_floats + self.z_floats)
         self.bank_state = torch.zeros(per * self.n_layer, dtype=torch.float32, device=dev)
         self.bank_mem = [[self.bank_state[i * per:i * per + self.bank * self.s_floats].view(self.bank, H, d, d),
@@ -1092,20 +1067,6 @@ class _BankStreamLoop(_StreamLoop):
         self.bar0_all = torch.as_tensor(np.asarray(bar0s, dtype=np.int64)).to(dev)
         self.cap_all = torch.as_tensor(np.asarray(caps, dtype=np.int64)).to(dev)
         self.prefill_rows = prefill_rows
-        self.song = torch.full((self.S,), -1, dtype=torch.int64, device=dev)
-        self.pos = torch.zeros(self.S, dtype=torch.int64, device=dev)
-        self.bar = torch.zeros(self.S, dtype=torch.int64, device=dev)
-        self.cap = torch.ones(self.S, dtype=torch.int64, device=dev)
-        self.fresh = torch.zeros(self.S, dtype=torch.int64, device=dev)
-        self.ctl = torch.zeros(4, dtype=torch.int64, device=dev)
-        self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
-        self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._init_logprobs(logprobs)
-        self._host_ctl = [torch.zeros(4, dtype=torch.int64).pin_memory() for _ in range(2)]
-        self._events = [torch.cuda.Event(), torch.cuda.Event()]
-        self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
-        self._graph, self.enqueued = None, 0
-        self.wait_s = 0.0
         self.next_block = 0                                        # blocks prefilled so far
         self.prefill_events = []                                   # (start, stop) CUDA events of every block
         self.gated_chunks = 0                                      # chunks that ended with every ready song assigned
@@ -1154,43 +1115,26 @@ class _BankStreamLoop(_StreamLoop):
         self.cap[:first] = self.cap_all[idx]
         self.ctl.copy_(torch.tensor([0, first, 0, ready], dtype=torch.int64))
 
-    def _one(self):
-        s = self.sess
-        tok = s.tok.view(self.S, self.A)
-        logits = s._device_step()
-        ops.stream_refill_bank(s._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
+    def _refill(self, logits):
+        ops.stream_refill_bank(self.sess._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
                                self.bank_logits, self.fresh, self.song)
-        self._sample(logits, tok)
+
+    def _advance(self, tok):
         ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
                                 self.song, self.pos, self.bar, self.cap, self.fresh, self.ctl, self.ring)
-        self._track(tok)
 
-    def run(self, max_cap):
-        """Run until the device's finished counter reaches n_songs -> rows (n, A + 2) of every song, time-ordered.
-        Between chunks the host prefills every block the reuse rule allows by the counters of the chunk it just read."""
-        parts = []
+    def _between_chunks(self, ctl, limit):
+        """A chunk that ended with every ready song assigned counts as gated (slots may have waited for a prefill: a
+        chunk more for the step limit); after the limit's check, prefill every block the reuse rule allows."""
+        if ctl[1] < self.n_songs and ctl[1] >= ctl[3]:
+            self.gated_chunks += 1
+        super()._between_chunks(ctl, limit + self.gated_chunks * self.chunk)
+        self._prefill_allowed(int(ctl[1]))
+
+    def run(self):
+        """_StreamLoop.run() after start(); between chunks the host prefills what the chunk just read allows."""
         self.start()
-        limit = -(-self.n_songs // self.S) * (int(max_cap) + 1) + 2 * self.chunk
-        h = self._enqueue_chunk()
-        while True:
-            nxt = self._enqueue_chunk()
-            t = time.perf_counter()
-            self._events[h].synchronize()
-            self.wait_s += time.perf_counter() - t
-            parts.append(self._read(h))
-            ctl = self._host_ctl[h].numpy().copy()
-            if ctl[2] >= self.n_songs:
-                break
-            if ctl[1] < self.n_songs and ctl[1] >= ctl[3]:
-                self.gated_chunks += 1                             # slots may have waited for a prefill: more steps
-            if self.enqueued > limit + self.gated_chunks * self.chunk:
-                raise RuntimeError("stream did not finish %d songs in %d steps" % (self.n_songs, self.enqueued))
-            self._prefill_allowed(int(ctl[1]))
-            h = nxt
-        t = time.perf_counter()
-        self._events[nxt].synchronize()
-        self.wait_s += time.perf_counter() - t
-        return np.concatenate(parts)
+        return super().run()
 
     def prefill_seconds(self):
         """GPU time of the block prefills (after run())."""
@@ -1212,8 +1156,10 @@ def _stream_snapshot(model, prompt, A):
 
 
 def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
-    """generate_batch's refusals for a list of per-song prompts -> (heads, bar0s, caps)."""
-    A = len(n_token)
+    """The refusals every generation entry makes for its prompts, a list of one array per song -> (heads (P_i, A) int64,
+    bar0s: each song's bar count before its first drawn row, caps: the rows it may draw, 16384 without max_tokens).
+    n_token: the model's classes, to refuse ids out of range as well (None: the prefill refuses them)."""
+    A = len(word2event)
     if len(prompts) != n_songs:
         raise ValueError("prompts: %d arrays for %d songs" % (len(prompts), n_songs))
     names = word2event["bar-beat"]
@@ -1222,8 +1168,8 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
         p = np.asarray(p, dtype=np.int64).reshape(-1, A)
         if len(p) == 0:
             raise ValueError("empty prompt (song %d)" % i)
-        bad = (p < 0) | (p >= np.asarray(n_token))
-        if bad.any():
+        bad = False if n_token is None else (p < 0) | (p >= np.asarray(n_token))
+        if np.any(bad):
             t, a = np.argwhere(bad)[0]
             raise ValueError("prompt %d, token %d: id %d out of range for attribute %d (%d classes)"
                              % (i, t, p[t, a], a, n_token[a]))
@@ -1260,7 +1206,7 @@ def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_to
                            mask=None if table is None else _device_constraints(table, sess.dev), logprobs=logprobs,
                            grammar=None if grammar is None else
                            _device_grammar(grammar, gtables, [grammar.beat_states(h)[1] for h in heads], sess.dev))
-    rows = loop.run(max(caps))
+    rows = loop.run()
     return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
                                       "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
 
@@ -1290,8 +1236,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         raise ValueError("generate_stream takes one shared (P, 6) prompt: ragged per-song prompts go in prompts=[...]")
     if prompt is not None and prompts is not None:
         raise ValueError("pass one shared prompt or per-song prompts, not both")
-    classes = list(word2event.keys())
-    A = len(classes)
+    A = len(word2event)
     extra = {}
     if prompts is not None:
         heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
@@ -1302,17 +1247,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
         bar_names = word2event["bar-beat"]
-        is_bar = lambda row: bar_names[int(row[2])] == "Bar"
-        head = INIT_CW[0].astype(np.int64)[None] if prompt is None else \
-            np.asarray(prompt, dtype=np.int64).reshape(-1, A)
-        if len(head) == 0:
-            raise ValueError("empty prompt")
-        bar0 = 1 + sum(is_bar(r) for r in head[1:])
-        if bar0 >= bar_cond:
-            raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (bar0, bar_cond))
-        if max_tokens is not None and max_tokens <= len(head):
-            raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(head)))
-        cap = 16384 if max_tokens is None else max_tokens - len(head)           # drawn tokens per song
+        (head,), (bar0,), (cap,) = _check_prompts([INIT_CW[0] if prompt is None else prompt], 1, word2event, None,
+                                                   bar_cond, max_tokens)
         table = None if constraints is None else \
             compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, [bar0] * n_songs, max_tokens)
         gtables = None if grammar is None else \
@@ -1446,6 +1382,68 @@ DQN_TEMPERATURE = (1.2, 1.0, 1.2, 1.0, 2.0, 5.0)
 DQN_TOP_P = (0.9, 0.99, None, 0.9, 0.9, None)
 
 
+def _one_song(model, word2event, head, cnt_bar, bar_cond, max_tokens, log, session, device_sampling, chunk, prefill):
+    """The body of inference_from_scratch / inference_from_prompt: `head`'s rows, then sampled rows until bar `bar_cond`
+    begins or max_tokens rows.  prefill=True: head is a prompt, prefilled in one pass, the first draw from its logits;
+    False: head's rows are fed through the step (on the device: its single row is the step's first input)."""
+    classes = list(word2event.keys())
+    sess = session or DecodeSession(model)
+    sess.reset()
+    is_bar = lambda row: word2event["bar-beat"][int(row[2])] == "Bar"
+
+    def show(cp, prefix=""):
+        if log is not None:
+            log(prefix + " | ".join("{:15s}".format(str(word2event[k][int(cp[i])])) for i, k in enumerate(classes)))
+
+    final_res = []
+    for row in head:
+        show(row)
+        final_res.append(row[None, ...])
+    if device_sampling:
+        if not prefill and len(head) != 1:
+            raise RuntimeError("device-side sampling starts from a single initial token")
+        cap = max_tokens - len(head) if max_tokens is not None else 16384
+        loop = _DeviceLoop(sess, cap, temperature=DQN_TEMPERATURE, top_p=DQN_TOP_P, carry_memory=True,
+                           graph=sess.use_graph)
+        if prefill:
+            loop.start(sess._prefill(head))
+        else:
+            sess.tok.copy_(torch.as_tensor(head[0], dtype=torch.int64).view(1, 1, -1).to(sess.dev))
+        done = 0
+        while done < cap:
+            stop = min(cap, done + chunk)
+            if prefill:
+                loop.run(stop - loop.enqueued)                    # start() drew the first token
+            else:
+                loop.run(chunk)                                   # clamped to the loop's capacity: ends at `stop` too
+            for next_arr in loop.tokens(done, stop)[:, 0]:
+                final_res.append(next_arr[None, ...])
+                show(next_arr, "bar: %d  ==" % cnt_bar)
+                if is_bar(next_arr):
+                    cnt_bar += 1
+                if cnt_bar == bar_cond:
+                    return np.concatenate(final_res)
+            done = stop
+        return np.concatenate(final_res)
+    if prefill:
+        logits = sess.prefill(head)
+    else:
+        for row in head:
+            logits = sess.step(row)
+    while True:
+        next_arr = sample_cw(sess.split(logits))
+        final_res.append(next_arr[None, ...])
+        show(next_arr, "bar: %d  ==" % cnt_bar)
+        logits = sess.step(next_arr)
+        if is_bar(next_arr):
+            cnt_bar += 1
+        if cnt_bar == bar_cond:
+            break
+        if max_tokens is not None and len(final_res) >= max_tokens:
+            break
+    return np.concatenate(final_res)
+
+
 def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=None, session=None,
                            device_sampling=False, chunk=128, return_logprobs=False):
     """testing-no-type-cp.py:126-179: start from the Bar token, sample until `bar_cond` bars have begun.
@@ -1457,54 +1455,7 @@ def inference_from_scratch(model, word2event, bar_cond, max_tokens=None, log=Non
     where the reference's loop would have stopped.  Same distribution, different random stream, ~1.2x faster (no host round trip per token).
     return_logprobs=True is refused (score_songs scores a song)."""
     _refuse_logprobs(return_logprobs, "inference_from_scratch")
-    classes = list(word2event.keys())
-    sess = session or DecodeSession(model)
-    sess.reset()
-
-    def show(cp, prefix=""):
-        if log is not None:
-            log(prefix + " | ".join("{:15s}".format(str(word2event[k][int(cp[i])])) for i, k in enumerate(classes)))
-
-    final_res = []
-    cnt_bar = 1
-    if device_sampling:
-        if len(INIT_CW) != 1:
-            raise RuntimeError("device-side sampling starts from a single initial token")
-        cap = max_tokens - 1 if max_tokens is not None else 16384
-        show(INIT_CW[0])
-        final_res.append(INIT_CW[0][None, ...])
-        sess.tok.copy_(torch.as_tensor(INIT_CW[0], dtype=torch.int64).view(1, 1, -1).to(sess.dev))
-        loop = _DeviceLoop(sess, cap, temperature=DQN_TEMPERATURE, top_p=DQN_TOP_P, carry_memory=True,
-                           graph=sess.use_graph)
-        done = 0
-        while done < cap:
-            n = loop.run(chunk)
-            for next_arr in loop.tokens(done, done + n)[:, 0]:
-                final_res.append(next_arr[None, ...])
-                show(next_arr, "bar: %d  ==" % cnt_bar)
-                if word2event["bar-beat"][int(next_arr[2])] == "Bar":
-                    cnt_bar += 1
-                if cnt_bar == bar_cond:
-                    return np.concatenate(final_res)
-            done += n
-        return np.concatenate(final_res)
-    logits = None
-    for row in INIT_CW:
-        show(row)
-        final_res.append(row[None, ...])
-        logits = sess.step(row)
-    while True:
-        next_arr = sample_cw(sess.split(logits))
-        final_res.append(next_arr[None, ...])
-        show(next_arr, "bar: %d  ==" % cnt_bar)
-        logits = sess.step(next_arr)
-        if word2event["bar-beat"][int(next_arr[2])] == "Bar":
-            cnt_bar += 1
-        if cnt_bar == bar_cond:
-            break
-        if max_tokens is not None and len(final_res) >= max_tokens:
-            break
-    return np.concatenate(final_res)
+    return _one_song(model, word2event, INIT_CW, 1, bar_cond, max_tokens, log, session, device_sampling, chunk, False)
 
 
 def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, log=None, session=None,
@@ -1521,58 +1472,8 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
     the loop's counter), with no host round trip between the prefill and the loop.
     return_logprobs=True is refused (score_songs scores a song)."""
     _refuse_logprobs(return_logprobs, "inference_from_prompt")
-    classes = list(word2event.keys())
-    prompt = np.asarray(prompt, dtype=np.int64).reshape(-1, len(classes))
-    if len(prompt) == 0:
-        raise ValueError("empty prompt")
-    cnt_bar = 1 + sum(word2event["bar-beat"][int(r[2])] == "Bar" for r in prompt[1:])
-    if cnt_bar >= bar_cond:
-        raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (cnt_bar, bar_cond))
-    if max_tokens is not None and max_tokens <= len(prompt):
-        raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(prompt)))
-    sess = session or DecodeSession(model)
-    sess.reset()
-
-    def show(cp, prefix=""):
-        if log is not None:
-            log(prefix + " | ".join("{:15s}".format(str(word2event[k][int(cp[i])])) for i, k in enumerate(classes)))
-
-    final_res = []
-    for row in prompt:
-        show(row)
-        final_res.append(row[None, ...])
-    if device_sampling:
-        cap = max_tokens - len(prompt) if max_tokens is not None else 16384
-        logits = sess._prefill(prompt)
-        loop = _DeviceLoop(sess, cap, temperature=DQN_TEMPERATURE, top_p=DQN_TOP_P, carry_memory=True,
-                           graph=sess.use_graph)
-        loop.start(logits)
-        done = 0
-        while done < cap:
-            stop = min(cap, done + chunk)
-            loop.run(stop - loop.enqueued)
-            for next_arr in loop.tokens(done, stop)[:, 0]:
-                final_res.append(next_arr[None, ...])
-                show(next_arr, "bar: %d  ==" % cnt_bar)
-                if word2event["bar-beat"][int(next_arr[2])] == "Bar":
-                    cnt_bar += 1
-                if cnt_bar == bar_cond:
-                    return np.concatenate(final_res)
-            done = stop
-        return np.concatenate(final_res)
-    logits = sess.prefill(prompt)
-    while True:
-        next_arr = sample_cw(sess.split(logits))
-        final_res.append(next_arr[None, ...])
-        show(next_arr, "bar: %d  ==" % cnt_bar)
-        logits = sess.step(next_arr)
-        if word2event["bar-beat"][int(next_arr[2])] == "Bar":
-            cnt_bar += 1
-        if cnt_bar == bar_cond:
-            break
-        if max_tokens is not None and len(final_res) >= max_tokens:
-            break
-    return np.concatenate(final_res)
+    (head,), (cnt_bar,), _ = _check_prompts([prompt], 1, word2event, None, bar_cond, max_tokens)
+    return _one_song(model, word2event, head, cnt_bar, bar_cond, max_tokens, log, session, device_sampling, chunk, True)
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
@@ -1620,28 +1521,15 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     n_songs, chunk = int(n_songs), int(chunk)
     if n_songs < 1 or chunk < 1:
         raise ValueError("n_songs and chunk must be >= 1")
-    classes = list(word2event.keys())
-    A = len(classes)
+    A = len(word2event)
     is_bar = lambda row: word2event["bar-beat"][int(row[2])] == "Bar"
     if prompts is None:
-        heads = [INIT_CW[0].astype(np.int64)[None]] * n_songs
+        heads = [INIT_CW[0]] * n_songs
     elif isinstance(prompts, (list, tuple)):
-        if len(prompts) != n_songs:
-            raise ValueError("prompts: %d arrays for %d songs" % (len(prompts), n_songs))
-        heads = [np.asarray(p, dtype=np.int64).reshape(-1, A) for p in prompts]
+        heads = prompts
     else:
-        heads = [np.asarray(prompts, dtype=np.int64).reshape(-1, A)] * n_songs
-    cnt_bar = []
-    for p in heads:
-        if len(p) == 0:
-            raise ValueError("empty prompt")
-        cnt = 1 + sum(is_bar(r) for r in p[1:])
-        if cnt >= bar_cond:
-            raise ValueError("the prompt already reaches bar %d of bar_cond=%d" % (cnt, bar_cond))
-        if max_tokens is not None and max_tokens <= len(p):
-            raise ValueError("max_tokens (%d) leaves no room after a %d-token prompt" % (max_tokens, len(p)))
-        cnt_bar.append(cnt)
-    caps = [16384 if max_tokens is None else max_tokens - len(p) for p in heads]     # drawn tokens per song
+        heads = [prompts] * n_songs
+    heads, cnt_bar, caps = _check_prompts(heads, n_songs, word2event, None, bar_cond, max_tokens)
     cap = max(caps)
     table = None if constraints is None else \
         compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, cnt_bar, max_tokens)
@@ -1895,20 +1783,23 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         else:
             np.save(os.path.join(path_gendir, "get_%d.npy" % sidx), res)
 
+    def record(first, songs, wall, how):
+        """Save a group's songs, each timed as its share of the group's wall time."""
+        if logprobs:
+            songs = list(zip(*songs))
+        for j, res in enumerate(songs):
+            save(first + j, res)
+            res = res[0] if logprobs else res
+            song_time_list.append(wall / len(songs))
+            words_len_list.append(len(res))
+            log("song %d: %d tokens in %.3f s (%s)" % (first + j, len(res), song_time_list[-1], how))
+
     if slots is not None:
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                 prompt=prompt, prompts=None if prompts is None else list(prompts),
                                 constraints=constraints, return_logprobs=logprobs, grammar=grammar)
-        wall = time.time() - start
-        if logprobs:
-            songs = list(zip(*songs))
-        for sidx, res in enumerate(songs):
-            save(sidx, res)
-            res = res[0] if logprobs else res
-            song_time_list.append(wall / n_songs)
-            words_len_list.append(len(res))
-            log("song %d: %d tokens in %.3f s (stream on %d slots)" % (sidx, len(res), song_time_list[-1], int(slots)))
+        record(0, songs, time.time() - start, "stream on %d slots" % int(slots))
     elif batch_size is not None:
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
@@ -1920,15 +1811,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                                    constraints=list(constraints[first:first + group])
                                    if isinstance(constraints, (list, tuple)) else constraints,
                                    return_logprobs=logprobs, grammar=grammar)
-            wall = time.time() - start
-            if logprobs:
-                songs = list(zip(*songs))
-            for j, res in enumerate(songs):
-                save(first + j, res)
-                res = res[0] if logprobs else res
-                song_time_list.append(wall / group)
-                words_len_list.append(len(res))
-                log("song %d: %d tokens in %.3f s (batch of %d)" % (first + j, len(res), song_time_list[-1], group))
+            record(first, songs, time.time() - start, "batch of %d" % group)
     else:
         sess = DecodeSession(model)
         for sidx in range(n_songs):

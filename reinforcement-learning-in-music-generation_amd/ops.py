@@ -1544,91 +1544,46 @@ def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
     return (out, xn) if want_normed else out
 
 
-def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, temperature=None, top_p=None,
-                       slot_keys=False):
-    """tokens[row, a] ~ Categorical(softmax(logits[row, segment a] / temperature[a])) on the device
-    (csrc/sample.hip; ppo_policy/inference.py:115-141).  logits (rows, >= sum n_class) f32; tokens (rows, A) int64
-    written in place; counter: device int64 scalar tensor that keys the draw (and indexes `song` (T, rows, A));
-    top_p[a] < 1 (or None = off) samples attribute a from its nucleus (dqn_policy/model.py:33-47).
-    slot_keys=True: the draw of row n does not depend on `rows` (cwlt_sample_categorical_slots; same draws at rows == 1)."""
-    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
-        raise TypeError("sample_categorical takes f32 logits and int64 tokens")
+def _sampler_head(fn, logits, n_class, ids, temperature, top_p, what="tokens"):
+    """The checks every sampler / scorer wrapper `fn` starts with -> (logits with a unit column stride, rows, A, the
+    temperature and top_p float arrays (None: off; a None top_p entry is 1)).  ids: the (rows, A) int64 `what`."""
+    if logits.dtype != torch.float32 or ids.dtype != torch.int64:
+        raise TypeError("%s takes f32 logits and int64 %s" % (fn, what))
     rows, A = logits.shape[0], len(n_class)
-    if tokens.numel() != rows * A or not tokens.is_contiguous():
-        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
+    if ids.numel() != rows * A or not ids.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous (rows, n_attr) int64 buffer" % (fn, what))
     if logits.stride(-1) != 1:
         logits = logits.contiguous()
     temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
     topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    _call("cwlt_sample_categorical_slots" if slot_keys else "cwlt_sample_categorical", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
-          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.dev(tokens, "tokens"), _lib.opt(song),
-          0 if song is None else song.shape[0], _lib.stream_ptr())
-    return tokens
+    return logits, rows, A, temp, topp
 
 
-
-# --------------------------------------------------------------------------------------------------
-# continuous batching (csrc/stream.hip, csrc/sample.hip): the per-token launches of generation.generate_stream
-# --------------------------------------------------------------------------------------------------
-def sample_categorical_keyed(logits, n_class, tokens, seed, key, step, temperature=None, top_p=None):
-    """sample_categorical with per-row keys: row n draws what slot_keys=True draws for row key[n] at counter step[n]
-    (cwlt_sample_categorical_keyed).  key, step: (rows,) int64 device tensors (song index < 2^20, position < 2^40)."""
-    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
-        raise TypeError("sample_categorical_keyed takes f32 logits and int64 tokens")
-    rows, A = logits.shape[0], len(n_class)
-    if tokens.numel() != rows * A or not tokens.is_contiguous():
-        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
-    for t in (key, step):
+def _row_keys(fn, rows, key, step, counter=None, counted=True):
+    """The row keying rule of the samplers: key and step together, (rows,) int64 each, or -- where `fn` takes a counter
+    (counted) -- the slot and that counter."""
+    if (key is None) != (step is None) or (key is None and (counter is None or not counted)):
+        raise ValueError("%s is keyed by key and step%s" % (fn, ", or by the slot and a counter" if counted else ""))
+    for t in ([] if key is None else [key, step]):
         if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
-            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    _call("cwlt_sample_categorical_keyed", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
-          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.dev(key, "key"), _lib.dev(step, "step"),
-          _lib.dev(tokens, "tokens"), _lib.stream_ptr())
-    return tokens
+            raise ValueError("%s: key and step must be contiguous (rows,) int64 tensors" % fn)
 
 
-def sample_categorical_masked(logits, n_class, tokens, seed, bar, sched, masks, counter=None, key=None, step=None,
-                              temperature=None, top_p=None):
-    """The constrained draw (cwlt_sample_categorical_masked): sample_categorical(slot_keys=True) at `counter` (song k =
-    row n) or sample_categorical_keyed with per-row key / step (song k = key[n]), with every class whose bit is clear
-    in the song's mask row treated as a -inf logit.  bar (rows,) int64: the song's bar count before this row; sched
-    (n_sched, 2) int64: per song index {first mask row, rows}, row used first + min(bar - 1, rows - 1); masks
-    (mask_rows, mask_words) int32 / uint32 bits, class c of attribute a at bit sum(n_class[:a]) + c.  Songs k < 0 or
-    >= n_sched and 0-row schedules draw unmasked.  All device tensors."""
-    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
-        raise TypeError("sample_categorical_masked takes f32 logits and int64 tokens")
-    rows, A = logits.shape[0], len(n_class)
-    if tokens.numel() != rows * A or not tokens.is_contiguous():
-        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
-    if (key is None) != (step is None) or (key is None and counter is None):
-        raise ValueError("sample_categorical_masked is keyed by key and step, or by the slot and a counter")
-    for t in [bar] + ([] if key is None else [key, step]):
-        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
-            raise ValueError("bar, key and step must be contiguous (rows,) int64 tensors")
-    if sched.dtype != torch.int64 or sched.dim() != 2 or sched.shape[1] != 2 or not sched.is_contiguous():
-        raise ValueError("sched must be a contiguous (n_songs, 2) int64 tensor")
-    if masks.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or masks.dim() != 2 or not masks.is_contiguous():
-        raise ValueError("masks must be a contiguous (rows, words) 32-bit tensor")
-    if masks.shape[1] * 32 < sum(n_class):
-        raise ValueError("masks: %d words per row hold fewer than the %d classes" % (masks.shape[1], sum(n_class)))
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    _call("cwlt_sample_categorical_masked", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
-          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step),
-          _lib.dev(bar, "bar"), _lib.dev(sched, "sched"), sched.shape[0], _lib.dev(masks, "masks"), masks.shape[0],
-          masks.shape[1], _lib.dev(tokens, "tokens"), _lib.stream_ptr())
-    return tokens
+def _logp_ring(logp, rows, A, out_counter):
+    """Checks of the optional (R, rows, A, 2) f32 log-prob ring -> R (1 without a ring)."""
+    if logp is None:
+        return 1
+    if logp.dtype != torch.float32 or logp.dim() != 4 or tuple(logp.shape[1:]) != (rows, A, 2) or \
+            not logp.is_contiguous():
+        raise ValueError("logp must be a contiguous (R, %d, %d, 2) f32 ring" % (rows, A))
+    if out_counter is None and logp.shape[0] != 1:
+        raise ValueError("a logp ring of %d rows needs out_counter" % logp.shape[0])
+    return logp.shape[0]
 
 
 def _mask_table(n_class, rows, bar, sched, masks, key=None):
-    """Checks of the optional constraint table shared by the log-prob entries -> (bar, sched, n_sched, masks, rows,
-    words) ctypes arguments (all NULL / 0 when unmasked)."""
+    """Checks of the optional constraint table -> (bar, sched, n_sched, masks, rows, words) ctypes arguments (all NULL /
+    0 when unmasked).  key: the scorers' song index per row, checked like bar."""
     if bar is None and sched is None and masks is None:
         return None, None, 0, None, 0, 0
     if bar is None or sched is None or masks is None:
@@ -1645,73 +1600,6 @@ def _mask_table(n_class, rows, bar, sched, masks, key=None):
         raise ValueError("masks: %d words per row hold fewer than the %d classes" % (masks.shape[1], sum(n_class)))
     return (_lib.dev(bar, "bar"), _lib.dev(sched, "sched"), sched.shape[0], _lib.dev(masks, "masks"), masks.shape[0],
             masks.shape[1])
-
-
-def sample_categorical_logp(logits, n_class, tokens, seed, logp, counter=None, key=None, step=None, bar=None,
-                            sched=None, masks=None, out_counter=None, temperature=None, top_p=None):
-    """The draw of sample_categorical(slot_keys=True) at `counter`, or of sample_categorical_keyed with key / step,
-    masked as sample_categorical_masked when bar / sched / masks are given -- the same tokens -- that also writes the
-    (model, sampler) log-probs of each drawn class (cwlt_sample_categorical_logp, DESIGN §4.6g).  logp: (R, rows, A, 2)
-    f32 device ring; the pair of row n, attribute a goes to logp[*out_counter % R, n, a] (out_counter: device int64,
-    e.g. the counter the loop advances after the draw; None needs R == 1)."""
-    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
-        raise TypeError("sample_categorical_logp takes f32 logits and int64 tokens")
-    rows, A = logits.shape[0], len(n_class)
-    if tokens.numel() != rows * A or not tokens.is_contiguous():
-        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
-    if (key is None) != (step is None) or (key is None and counter is None):
-        raise ValueError("sample_categorical_logp is keyed by key and step, or by the slot and a counter")
-    for t in ([] if key is None else [key, step]):
-        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
-            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
-    if logp.dtype != torch.float32 or logp.dim() != 4 or tuple(logp.shape[1:]) != (rows, A, 2) or \
-            not logp.is_contiguous():
-        raise ValueError("logp must be a contiguous (R, %d, %d, 2) f32 ring" % (rows, A))
-    if out_counter is None and logp.shape[0] != 1:
-        raise ValueError("a logp ring of %d rows needs out_counter" % logp.shape[0])
-    table = _mask_table(n_class, rows, bar, sched, masks)
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    _call("cwlt_sample_categorical_logp", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
-          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
-          _lib.dev(tokens, "tokens"), _lib.dev(logp, "logp"), _lib.opt(out_counter), logp.shape[0],
-          _lib.stream_ptr())
-    return tokens
-
-
-def score_categorical(logits, n_class, targets, temperature=None, top_p=None, key=None, bar=None, sched=None,
-                      masks=None, out=None):
-    """(model, sampler) log-probs of given classes (cwlt_score_categorical, DESIGN §4.6g): logits (rows, >= sum n_class)
-    f32, targets (rows, A) int64 (negative: padding, left unwritten) -> (rows, A, 2) f32.  Masked when bar / sched /
-    masks are given, song key[n] (None: n).  Bitwise the pairs sample_categorical_logp writes for the same logits,
-    settings and classes.  Rows go through in launches of at most 2^20."""
-    if logits.dtype != torch.float32 or targets.dtype != torch.int64:
-        raise TypeError("score_categorical takes f32 logits and int64 targets")
-    rows, A = logits.shape[0], len(n_class)
-    if targets.numel() != rows * A or not targets.is_contiguous():
-        raise ValueError("targets must be a contiguous (rows, n_attr) int64 tensor")
-    if key is not None and bar is None:
-        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
-    _mask_table(n_class, rows, bar, sched, masks, key)
-    if out is None:
-        out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    tv = targets.view(rows, A)
-    for a in range(0, rows, 1 << 20):
-        z = min(rows, a + (1 << 20))
-        sl = lambda t: None if t is None else t[a:z]
-        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
-        _call("cwlt_score_categorical", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
-              logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, _lib.dev(out[a:z], "logp"),
-              _lib.stream_ptr())
-    return out
 
 
 def _grammar_table(n_class, rows, beat, order, gram, bar_attr):
@@ -1732,6 +1620,74 @@ def _grammar_table(n_class, rows, beat, order, gram, bar_attr):
             int(bar_attr))
 
 
+def sample_categorical(logits, n_class, tokens, seed, counter=None, song=None, temperature=None, top_p=None,
+                       slot_keys=False):
+    """tokens[row, a] ~ Categorical(softmax(logits[row, segment a] / temperature[a])) on the device
+    (csrc/sample.hip; ppo_policy/inference.py:115-141).  logits (rows, >= sum n_class) f32; tokens (rows, A) int64
+    written in place; counter: device int64 scalar tensor that keys the draw (and indexes `song` (T, rows, A));
+    top_p[a] < 1 (or None = off) samples attribute a from its nucleus (dqn_policy/model.py:33-47).
+    slot_keys=True: the draw of row n does not depend on `rows` (cwlt_sample_categorical_slots; same draws at rows == 1)."""
+    logits, rows, A, temp, topp = _sampler_head("sample_categorical", logits, n_class, tokens, temperature, top_p)
+    _call("cwlt_sample_categorical_slots" if slot_keys else "cwlt_sample_categorical", _lib.dev(logits, "logits"),
+          _lib.int_array(n_class), temp, topp, A, rows, logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF,
+          _lib.opt(counter), _lib.dev(tokens, "tokens"), _lib.opt(song), 0 if song is None else song.shape[0],
+          _lib.stream_ptr())
+    return tokens
+
+
+# --------------------------------------------------------------------------------------------------
+# continuous batching (csrc/stream.hip, csrc/sample.hip): the per-token launches of generation.generate_stream
+# --------------------------------------------------------------------------------------------------
+def sample_categorical_keyed(logits, n_class, tokens, seed, key, step, temperature=None, top_p=None):
+    """sample_categorical with per-row keys: row n draws what slot_keys=True draws for row key[n] at counter step[n]
+    (cwlt_sample_categorical_keyed).  key, step: (rows,) int64 device tensors (song index < 2^20, position < 2^40)."""
+    fn = "sample_categorical_keyed"
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, tokens, temperature, top_p)
+    _row_keys(fn, rows, key, step, counted=False)
+    _call("cwlt_sample_categorical_keyed", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.dev(key, "key"), _lib.dev(step, "step"),
+          _lib.dev(tokens, "tokens"), _lib.stream_ptr())
+    return tokens
+
+
+def sample_categorical_masked(logits, n_class, tokens, seed, bar, sched, masks, counter=None, key=None, step=None,
+                              temperature=None, top_p=None):
+    """The constrained draw (cwlt_sample_categorical_masked): sample_categorical(slot_keys=True) at `counter` (song k =
+    row n) or sample_categorical_keyed with per-row key / step (song k = key[n]), with every class whose bit is clear
+    in the song's mask row treated as a -inf logit.  bar (rows,) int64: the song's bar count before this row; sched
+    (n_sched, 2) int64: per song index {first mask row, rows}, row used first + min(bar - 1, rows - 1); masks
+    (mask_rows, mask_words) int32 / uint32 bits, class c of attribute a at bit sum(n_class[:a]) + c.  Songs k < 0 or
+    >= n_sched and 0-row schedules draw unmasked.  All device tensors."""
+    fn = "sample_categorical_masked"
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, tokens, temperature, top_p)
+    _row_keys(fn, rows, key, step, counter)
+    if bar is None:
+        raise ValueError("%s needs the constraint table: bar, sched and masks" % fn)
+    table = _mask_table(n_class, rows, bar, sched, masks)
+    _call("cwlt_sample_categorical_masked", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
+          _lib.dev(tokens, "tokens"), _lib.stream_ptr())
+    return tokens
+
+
+def sample_categorical_logp(logits, n_class, tokens, seed, logp, counter=None, key=None, step=None, bar=None,
+                            sched=None, masks=None, out_counter=None, temperature=None, top_p=None):
+    """The draw of sample_categorical(slot_keys=True) at `counter`, or of sample_categorical_keyed with key / step,
+    masked as sample_categorical_masked when bar / sched / masks are given -- the same tokens -- that also writes the
+    (model, sampler) log-probs of each drawn class (cwlt_sample_categorical_logp, DESIGN §4.6g).  logp: (R, rows, A, 2)
+    f32 device ring; the pair of row n, attribute a goes to logp[*out_counter % R, n, a] (out_counter: device int64,
+    e.g. the counter the loop advances after the draw; None needs R == 1)."""
+    fn = "sample_categorical_logp"
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, tokens, temperature, top_p)
+    _row_keys(fn, rows, key, step, counter)
+    R = _logp_ring(logp, rows, A, out_counter)
+    table = _mask_table(n_class, rows, bar, sched, masks)
+    _call("cwlt_sample_categorical_logp", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
+          logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
+          _lib.dev(tokens, "tokens"), _lib.dev(logp, "logp"), _lib.opt(out_counter), R, _lib.stream_ptr())
+    return tokens
+
+
 def sample_categorical_grammar(logits, n_class, tokens, seed, beat, order, gram, bar_attr=2, counter=None, key=None,
                                step=None, bar=None, sched=None, masks=None, logp=None, out_counter=None,
                                temperature=None, top_p=None):
@@ -1740,66 +1696,59 @@ def sample_categorical_grammar(logits, n_class, tokens, seed, beat, order, gram,
     class (attribute bar_attr) drawn first under the position rule -- beat (rows,) int64, order (>= n_class[bar_attr],)
     int32 -- and every other attribute under the row of gram (3, words) its kind selects.  logp (optional): the (R, rows,
     A, 2) f32 ring of sample_categorical_logp, row *out_counter % R."""
-    if logits.dtype != torch.float32 or tokens.dtype != torch.int64:
-        raise TypeError("sample_categorical_grammar takes f32 logits and int64 tokens")
-    rows, A = logits.shape[0], len(n_class)
-    if tokens.numel() != rows * A or not tokens.is_contiguous():
-        raise ValueError("tokens must be a contiguous (rows, n_attr) buffer")
-    if (key is None) != (step is None) or (key is None and counter is None):
-        raise ValueError("sample_categorical_grammar is keyed by key and step, or by the slot and a counter")
-    for t in ([] if key is None else [key, step]):
-        if t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous():
-            raise ValueError("key and step must be contiguous (rows,) int64 tensors")
-    if logp is not None:
-        if logp.dtype != torch.float32 or logp.dim() != 4 or tuple(logp.shape[1:]) != (rows, A, 2) or \
-                not logp.is_contiguous():
-            raise ValueError("logp must be a contiguous (R, %d, %d, 2) f32 ring" % (rows, A))
-        if out_counter is None and logp.shape[0] != 1:
-            raise ValueError("a logp ring of %d rows needs out_counter" % logp.shape[0])
+    fn = "sample_categorical_grammar"
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, tokens, temperature, top_p)
+    _row_keys(fn, rows, key, step, counter)
+    R = _logp_ring(logp, rows, A, out_counter)
     table = _mask_table(n_class, rows, bar, sched, masks)
     gtable = _grammar_table(n_class, rows, beat, order, gram, bar_attr)
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
     _call("cwlt_sample_categorical_grammar", _lib.dev(logits, "logits"), _lib.int_array(n_class), temp, topp, A, rows,
           logits.stride(0), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.opt(counter), _lib.opt(key), _lib.opt(step), *table,
-          *gtable, _lib.dev(tokens, "tokens"), _lib.opt(logp), _lib.opt(out_counter),
-          1 if logp is None else logp.shape[0], _lib.stream_ptr())
+          *gtable, _lib.dev(tokens, "tokens"), _lib.opt(logp), _lib.opt(out_counter), R, _lib.stream_ptr())
     return tokens
+
+
+def _score(fn, logits, n_class, targets, temperature, top_p, key, bar, sched, masks, out, grammar=None):
+    """The scorers' body: the checks on all rows, then launches of at most 2^20 rows of cwlt_<fn>.  grammar: (beat, order,
+    gram, bar_attr) for the grammar entry, whose arguments follow the constraint table's."""
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, targets, temperature, top_p, "targets")
+    if key is not None and bar is None:
+        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
+    _mask_table(n_class, rows, bar, sched, masks, key)
+    if grammar is not None:
+        beat, order, gram, bar_attr = grammar
+        _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+    if out is None:
+        out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
+    tv = targets.view(rows, A)
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        sl = lambda t: None if t is None else t[a:z]
+        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
+        gtable = () if grammar is None else _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
+        _call("cwlt_" + fn, _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
+              logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, *gtable,
+              _lib.dev(out[a:z], "logp"), _lib.stream_ptr())
+    return out
+
+
+def score_categorical(logits, n_class, targets, temperature=None, top_p=None, key=None, bar=None, sched=None,
+                      masks=None, out=None):
+    """(model, sampler) log-probs of given classes (cwlt_score_categorical, DESIGN §4.6g): logits (rows, >= sum n_class)
+    f32, targets (rows, A) int64 (negative: padding, left unwritten) -> (rows, A, 2) f32.  Masked when bar / sched /
+    masks are given, song key[n] (None: n).  Bitwise the pairs sample_categorical_logp writes for the same logits,
+    settings and classes.  Rows go through in launches of at most 2^20."""
+    return _score("score_categorical", logits, n_class, targets, temperature, top_p, key, bar, sched, masks, out)
 
 
 def score_categorical_grammar(logits, n_class, targets, beat, order, gram, bar_attr=2, temperature=None, top_p=None,
                               key=None, bar=None, sched=None, masks=None, out=None):
     """score_categorical under the row grammar (cwlt_score_categorical_grammar): the kind of row n is that of its
     target's bar-beat class, beat (rows,) int64 the position before each row -> (rows, A, 2) f32."""
-    if logits.dtype != torch.float32 or targets.dtype != torch.int64:
-        raise TypeError("score_categorical_grammar takes f32 logits and int64 targets")
-    rows, A = logits.shape[0], len(n_class)
-    if targets.numel() != rows * A or not targets.is_contiguous():
-        raise ValueError("targets must be a contiguous (rows, n_attr) int64 tensor")
-    if key is not None and bar is None:
-        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
-    _mask_table(n_class, rows, bar, sched, masks, key)
-    _grammar_table(n_class, rows, beat, order, gram, bar_attr)
-    if out is None:
-        out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
-    if logits.stride(-1) != 1:
-        logits = logits.contiguous()
-    temp = None if temperature is None else (ctypes.c_float * A)(*[float(t) for t in temperature])
-    topp = None if top_p is None else (ctypes.c_float * A)(*[1.0 if p is None else float(p) for p in top_p])
-    tv = targets.view(rows, A)
-    for a in range(0, rows, 1 << 20):
-        z = min(rows, a + (1 << 20))
-        sl = lambda t: None if t is None else t[a:z]
-        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
-        gtable = _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
-        _call("cwlt_score_categorical_grammar", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A,
-              z - a, logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, *gtable,
-              _lib.dev(out[a:z], "logp"), _lib.stream_ptr())
-    return out
+    return _score("score_categorical_grammar", logits, n_class, targets, temperature, top_p, key, bar, sched, masks,
+                  out, (beat, order, gram, bar_attr))
 
 
 def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):
