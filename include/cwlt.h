@@ -266,6 +266,12 @@ int cwlt_cw_embed_proj_bwd(const int64_t* tokens, const int* nrows, int n_attr, 
  * of the largest softmax value; pmax (rows, n_attr) its probability; probs (rows, ldp) the softmax.
  * loss_part: cwlt_heads_blocks(rows) * n_attr f32. */
 int cwlt_heads_blocks(int64_t rows);
+/* Which of the two kernel families cwlt_heads_fwd / _ce_bwd / _logp_bwd run these arguments on (the launchers ask
+ * this very function): 1 = the tiled kernels (32 rows staged in LDS with 16-byte accesses), 0 = the wave-per-row
+ * kernels (n_attr == 8, ld not a multiple of 4 (f32) / 8 (bf16) elements, p0 or p1 not 16-byte aligned, or
+ * ld >= 480), negative = -(the CWLT_ERR_* the entry points return for them).  p0 = logits, p1 = dlogits
+ * (NULL: the forward, which has none). */
+int cwlt_heads_tiled(const int* n_class, int n_attr, int64_t ld, int dtype, const void* p0, const void* p1);
 int cwlt_heads_fwd(const void* logits, const int* n_class, int n_attr, const int64_t* target,
                    const float* mask, float* loss_part, float* loss_sum, int64_t* argmax,
                    float* pmax, float* probs, int64_t rows, int64_t ld, int64_t ldp,
@@ -306,6 +312,9 @@ int cwlt_heads_logp_bwd(const void* logits, const int* n_class, int n_attr, cons
                         const float* w, void* dlogits, int64_t rows, int64_t ld, int dtype, void* stream);
 
 /* ---- RL arithmetic (one launch each; the reference's indexing quirks reproduced) -----------------
+ * PRECONDITION (not checked on the device): every ids[r][t][f] given to cwlt_rollout_gather (modes 1, 2, which
+ * index probs with it) and every action[j][k][f] given to cwlt_dqn_td_fwd / _bwd lies in [0, n_class[f]).  A value
+ * outside its attribute reads (gather, TD forward) or writes (TD backward) outside the attribute's column segment.
  * cwlt_rollout_gather: greedy action rows (+ log-probs) from per-position argmax ids (R, T, A) int64 and
  *   softmax probs (R, T, ldp) f32.  mode 0 = DQN.choose_action (dqn_policy/IRL_dqn_train.py:256-264:
  *   positions [0, T-1, T-2, ...] because -0 == 0); mode 1 = PPO.choose_action (ppo_policy/ppo_train.py:

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -144,6 +144,7 @@ _SIGNATURES = {
     "cwlt_stream_advance_bank": [_ptr, _c_int, _c_i64, _c_int, _ptr, _c_int, _c_i64, _ptr, _ptr, _c_i64, _c_i64]
     + [_ptr] * 7 + [_c_i64, _ptr],
     "cwlt_heads_blocks": [_c_i64],
+    "cwlt_heads_tiled": [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr],
     "cwlt_heads_fwd": [_ptr, _ptr, _c_int] + [_ptr] * 7 + [_c_i64, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_heads_ce_bwd": [_ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_heads_logp_bwd": [_ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr],

@@ -396,6 +396,17 @@ static int fill_heads(HeadArgs& a, const int* n_class, int n_attr) {
     return CWLT_OK;
 }
 
+// The one family decision, shared by the three launchers and cwlt_heads_tiled: 1 = tiled kernels, 0 = wave-per-row
+// kernels, -CWLT_ERR_* = refused.  p0 = logits, p1 = dlogits (the forward passes logits twice).
+static int heads_family(HeadArgs& a, const int* n_class, int n_attr, int64_t ld, int dtype, const void* p0,
+                        const void* p1, TileOrder& ord, int& W1, size_t& lds) {
+    const int e = fill_heads(a, n_class, n_attr);
+    if (e) return -e;
+    if (!p0 || !p1 || ld < a.off[n_attr - 1] + a.n[n_attr - 1]) return -CWLT_ERR_ARG;
+    if (dtype != CWLT_F32 && dtype != CWLT_BF16) return -CWLT_ERR_DTYPE;
+    return tile_plan(a, ld, p0, p1, dtype == CWLT_BF16 ? 8 : 4, ord, W1, lds) ? 1 : 0;
+}
+
 }  // namespace cwlt
 
 extern "C" {
@@ -405,6 +416,15 @@ int cwlt_heads_blocks(int64_t rows) {
     if (b > 1024) b = 1024;
     if (b < 1) b = 1;
     return (int)b;
+}
+
+int cwlt_heads_tiled(const int* n_class, int n_attr, int64_t ld, int dtype, const void* p0, const void* p1) {
+    using namespace cwlt;
+    HeadArgs a;
+    TileOrder ord;
+    int W1 = 0;
+    size_t lds = 0;
+    return heads_family(a, n_class, n_attr, ld, dtype, p0, p1 ? p1 : p0, ord, W1, lds);
 }
 
 /* logits (rows, ld): attribute f in columns [sum_{g<f} n_class[g], +n_class[f]); n_class: HOST array.
@@ -417,10 +437,13 @@ int cwlt_heads_fwd(const void* logits, const int* n_class, int n_attr, const int
                    int64_t ld, int64_t ldp, int dtype, void* stream) {
     using namespace cwlt;
     HeadArgs a;
-    int e = fill_heads(a, n_class, n_attr);
-    if (e) return e;
+    TileOrder ord;
+    int W1 = 0;
+    size_t lds = 0;
+    const int fam = heads_family(a, n_class, n_attr, ld, dtype, logits, logits, ord, W1, lds);
+    if (fam < 0 && fam != -CWLT_ERR_DTYPE) return -fam;
     const int used = a.off[n_attr - 1] + a.n[n_attr - 1];
-    if (!logits || rows < 0 || ld < used) return CWLT_ERR_ARG;
+    if (rows < 0) return CWLT_ERR_ARG;
     if (loss_sum && (!loss_part || !target)) return CWLT_ERR_ARG;
     if (probs && ldp < used) return CWLT_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -428,11 +451,8 @@ int cwlt_heads_fwd(const void* logits, const int* n_class, int n_attr, const int
     int nb = cwlt_heads_blocks(rows);
     const int64_t* tg = loss_sum ? target : nullptr;
     float* lp = loss_sum ? loss_part : nullptr;
-    TileOrder ord;
-    int W1 = 0;
-    size_t lds = 0;
-    if ((dtype == CWLT_F32 || dtype == CWLT_BF16) &&
-        tile_plan(a, ld, logits, logits, dtype == CWLT_BF16 ? 8 : 4, ord, W1, lds)) {
+    int e;
+    if (fam == 1) {
         const int64_t ntile = (rows + HT_ROWS - 1) / HT_ROWS;
         if (ntile < nb) nb = (int)ntile;
         if (dtype == CWLT_F32)
@@ -441,14 +461,14 @@ int cwlt_heads_fwd(const void* logits, const int* n_class, int n_attr, const int
         else
             hipLaunchKernelGGL((heads_fwd_tile_kernel<bf16_t>), dim3(nb), dim3(256), lds, st, (const bf16_t*)logits, a,
                                ord, tg, mask, lp, argmax, pmax, probs, (long)rows, (long)ld, (long)ldp, W1, used);
-    } else if (dtype == CWLT_F32)
+    } else if (fam < 0)
+        return -fam;
+    else if (dtype == CWLT_F32)
         hipLaunchKernelGGL((heads_fwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)logits, a, tg, mask, lp,
                            argmax, pmax, probs, (long)rows, (long)ld, (long)ldp);
-    else if (dtype == CWLT_BF16)
+    else
         hipLaunchKernelGGL((heads_fwd_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)logits, a, tg, mask,
                            lp, argmax, pmax, probs, (long)rows, (long)ld, (long)ldp);
-    else
-        return CWLT_ERR_DTYPE;
     e = (int)hipGetLastError();
     if (e || !loss_sum) return e;
     return launch_colsum_finalize(loss_part, loss_sum, nb, (long)n_attr, n_attr, 1.0f, 0, st);
@@ -459,18 +479,18 @@ int cwlt_heads_ce_bwd(const void* logits, const int* n_class, int n_attr, const 
                       const float* coef, void* dlogits, int64_t rows, int64_t ld, int dtype, void* stream) {
     using namespace cwlt;
     HeadArgs a;
-    int e = fill_heads(a, n_class, n_attr);
-    if (e) return e;
-    const int used = a.off[n_attr - 1] + a.n[n_attr - 1];
-    if (!logits || !target || !coef || !dlogits || rows < 0 || ld < used) return CWLT_ERR_ARG;
-    if (rows == 0) return CWLT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int nb = cwlt_heads_blocks(rows);
     TileOrder ord;
     int W1 = 0;
     size_t lds = 0;
-    if ((dtype == CWLT_F32 || dtype == CWLT_BF16) &&
-        tile_plan(a, ld, logits, dlogits, dtype == CWLT_BF16 ? 8 : 4, ord, W1, lds)) {
+    const int fam = heads_family(a, n_class, n_attr, ld, dtype, logits, dlogits, ord, W1, lds);
+    if (fam < 0 && fam != -CWLT_ERR_DTYPE) return -fam;
+    const int used = a.off[n_attr - 1] + a.n[n_attr - 1];
+    if (!target || !coef || rows < 0) return CWLT_ERR_ARG;
+    if (rows == 0) return CWLT_OK;
+    if (fam < 0) return -fam;
+    hipStream_t st = (hipStream_t)stream;
+    int nb = cwlt_heads_blocks(rows);
+    if (fam == 1) {
         const int64_t ntile = (rows + HT_ROWS - 1) / HT_ROWS;
         if (ntile < nb) nb = (int)ntile;
         if (dtype == CWLT_F32)
@@ -486,11 +506,9 @@ int cwlt_heads_ce_bwd(const void* logits, const int* n_class, int n_attr, const 
     if (dtype == CWLT_F32)
         hipLaunchKernelGGL((heads_ce_bwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)logits, a, target,
                            mask, coef, (const float*)nullptr, (float*)dlogits, (long)rows, (long)ld, (int)ld);
-    else if (dtype == CWLT_BF16)
+    else
         hipLaunchKernelGGL((heads_ce_bwd_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)logits, a, target,
                            mask, coef, (const float*)nullptr, (bf16_t*)dlogits, (long)rows, (long)ld, (int)ld);
-    else
-        return CWLT_ERR_DTYPE;
     return (int)hipGetLastError();
 }
 
@@ -500,19 +518,19 @@ int cwlt_heads_logp_bwd(const void* logits, const int* n_class, int n_attr, cons
                         void* dlogits, int64_t rows, int64_t ld, int dtype, void* stream) {
     using namespace cwlt;
     HeadArgs a;
-    int e = fill_heads(a, n_class, n_attr);
-    if (e) return e;
-    const int used = a.off[n_attr - 1] + a.n[n_attr - 1];
-    if (!logits || !target || !g || !dlogits || rows < 0 || ld < used) return CWLT_ERR_ARG;
-    if (rows == 0) return CWLT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    int nb = cwlt_heads_blocks(rows);
-    // the kernel computes (softmax - onehot) * w; the caller passes w = -g
     TileOrder ord;
     int W1 = 0;
     size_t lds = 0;
-    if ((dtype == CWLT_F32 || dtype == CWLT_BF16) &&
-        tile_plan(a, ld, logits, dlogits, dtype == CWLT_BF16 ? 8 : 4, ord, W1, lds)) {
+    const int fam = heads_family(a, n_class, n_attr, ld, dtype, logits, dlogits, ord, W1, lds);
+    if (fam < 0 && fam != -CWLT_ERR_DTYPE) return -fam;
+    const int used = a.off[n_attr - 1] + a.n[n_attr - 1];
+    if (!target || !g || rows < 0) return CWLT_ERR_ARG;
+    if (rows == 0) return CWLT_OK;
+    if (fam < 0) return -fam;
+    hipStream_t st = (hipStream_t)stream;
+    int nb = cwlt_heads_blocks(rows);
+    // the kernel computes (softmax - onehot) * w; the caller passes w = -g
+    if (fam == 1) {
         const int64_t ntile = (rows + HT_ROWS - 1) / HT_ROWS;
         if (ntile < nb) nb = (int)ntile;
         if (dtype == CWLT_F32)
@@ -529,12 +547,10 @@ int cwlt_heads_logp_bwd(const void* logits, const int* n_class, int n_attr, cons
         hipLaunchKernelGGL((heads_ce_bwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)logits, a, target,
                            (const float*)nullptr, (const float*)nullptr, g, (float*)dlogits, (long)rows, (long)ld,
                            (int)ld);
-    else if (dtype == CWLT_BF16)
+    else
         hipLaunchKernelGGL((heads_ce_bwd_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)logits, a, target,
                            (const float*)nullptr, (const float*)nullptr, g, (bf16_t*)dlogits, (long)rows, (long)ld,
                            (int)ld);
-    else
-        return CWLT_ERR_DTYPE;
     return (int)hipGetLastError();
 }
 

@@ -1296,6 +1296,16 @@ def heads_forward(logits, n_class, target=None, mask=None, want_argmax=False, wa
     return res
 
 
+def heads_tiled(logits, n_class, dlogits=None):
+    """True when heads_forward / heads_ce / logp_argmax run `logits` (and the gradient buffer `dlogits` of a backward)
+    on the tiled kernels, False on the wave-per-row kernels: the launchers' own decision (cwlt_heads_tiled)."""
+    st = _lib.load().cwlt_heads_tiled(_lib.int_array(n_class), len(n_class), logits.stride(0),
+                                      _lib.dtype_code(logits.dtype), _lib.dev(logits, "logits"), _lib.opt(dlogits))
+    if st < 0:
+        _lib.check(-st, "cwlt_heads_tiled")
+    return st == 1
+
+
 class HeadsCEFn(torch.autograd.Function):
     """6 x compute_loss (dqn_policy/model.py:163-197): returns the (A) vector of masked-mean CE losses."""
 

@@ -81,6 +81,22 @@ def test_argument_validation_without_gpu(built):
     assert lib.cwlt_cw_embed_proj_fwd(buf16, buf16, nr, 6, buf16, null, buf16, 0, 4, 512, 0.0, 0, null, 1, null) == 0   # no rows
     assert lib.cwlt_cw_embed_proj_bwd(buf16, nr, 6, 512, buf16, buf16, buf16, 8, 256, 1, null) == 1001      # ldd < D
     assert lib.cwlt_cw_embed_proj_bwd(buf16, nr, 6, 512, buf16, buf16, null, 8, 512, 1, null) == 1001
+    # heads family query (the launchers' own decision): host arithmetic on the arguments, nothing is launched
+    a16, a4 = ctypes.c_void_p(4096), ctypes.c_void_p(4100)
+    assert lib.cwlt_heads_tiled(nr, 6, 384, 0, a16, null) == 1 and lib.cwlt_heads_tiled(nr, 6, 384, 1, a16, a16) == 1
+    assert lib.cwlt_heads_tiled(nr, 6, 339, 0, a16, null) == 0 and lib.cwlt_heads_tiled(nr, 6, 340, 0, a16, null) == 1
+    assert lib.cwlt_heads_tiled(nr, 6, 340, 1, a16, null) == 0 and lib.cwlt_heads_tiled(nr, 6, 344, 1, a16, null) == 1
+    assert lib.cwlt_heads_tiled(nr, 6, 384, 0, a4, null) == 0 and lib.cwlt_heads_tiled(nr, 6, 384, 0, a16, a4) == 0
+    assert lib.cwlt_heads_tiled(nr, 6, 476, 0, a16, null) == 1 and lib.cwlt_heads_tiled(nr, 6, 480, 0, a16, null) == 0
+    n8 = (ctypes.c_int * 8)(56, 135, 18, 87, 18, 25, 7, 64)
+    assert lib.cwlt_heads_tiled(n8, 7, 448, 0, a16, null) == 1 and lib.cwlt_heads_tiled(n8, 8, 448, 0, a16, null) == 0
+    assert lib.cwlt_heads_tiled(nr, 6, 338, 0, a16, null) == -1001 and lib.cwlt_heads_tiled(nr, 6, 384, 0, null, null) == -1001
+    assert lib.cwlt_heads_tiled(n8, 9, 448, 0, a16, null) == -1001 and lib.cwlt_heads_tiled(nr, 6, 384, 2, a16, null) == -1002
+    assert lib.cwlt_heads_tiled((ctypes.c_int * 1)(257), 1, 260, 0, a16, null) == -1001
+    # the entry points refuse the same arguments with the same codes, before any launch
+    assert lib.cwlt_heads_fwd(a16, nr, 6, null, null, null, null, null, null, null, 4, 338, 339, 0, null) == 1001
+    assert lib.cwlt_heads_ce_bwd(a16, nr, 6, a16, null, a16, a16, 4, 384, 2, null) == 1002
+    assert lib.cwlt_heads_logp_bwd(a16, nr, 6, a16, a16, null, 4, 384, 0, null) == 1001
     # generation step: an incomplete model description is refused before any launch
     m = built.DecodeModel()
     assert lib.cwlt_decode_workspace_floats(ctypes.byref(m)) == -1
