@@ -900,69 +900,68 @@ class _StreamLoop:
     that runs `n_songs` songs, each slot starting the next song as soon as its own one ends.  Per token, one fixed
     sequence of launches (captured as one hipGraph after two eager tokens):
       the GEMM decode step on every slot;
-      cwlt_stream_refill: slots flagged fresh get the snapshot's state and logits (the state every song starts from);
+      the refill: slots flagged fresh get the state and logits their new song starts from;
       the draw (_draw_token), each slot's keyed by (song index, position in song): cwlt_sample_categorical_keyed, or
         the masked / log-prob / grammar entry when the stream has a mask (_device_constraints: the song's mask row for
         the slot's bar count), log-probs or a grammar (_device_grammar: the row grammar at the slot's position);
-      cwlt_stream_advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count
-        advanced, the song's end detected, finished slots handed the next song indices in slot order;
+      the advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count advanced, the
+        song's end detected, finished slots handed the next song indices in slot order;
       cwlt_grammar_track (under a grammar): every slot's position after the advance.
     The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host.
     logprobs=True: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
     log-probs into `lp_ring` (2 chunk, slots, A, 2) at the row ctl[0] selects -- the row of `ring` the advance writes --
     copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`).
-    waiting=True (the bank's loop): no slot holds a song or is fresh yet, `cap` is the slots' own (S,) caps with max_cap
-    the largest a song can have, and the device counters {tokens, assigned, finished} gain a fourth, `ready`."""
 
-    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 temperature=None, top_p=None, graph=None, mask=None, logprobs=False, grammar=None, waiting=False,
-                 max_cap=None):
+    This class holds what both forms of the stream share.  A form supplies where songs start from: _refill and _advance
+    (its pair of csrc/stream.hip entries), n_ctl (the device counters {tokens, assigned, finished}, and what the form
+    adds), song_cap (the most tokens one song draws: run()'s step limit) and start() (its _hand_out)."""
+
+    n_ctl = 3
+
+    def __init__(self, sess, n_songs, seed, bar_mask, bar_cond, chunk, temperature=None, top_p=None, graph=None,
+                 mask=None, logprobs=False, grammar=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
-        self.snap_state, self.snap_logits = snap_state, snap_logits
         self.n_layer = len(sess.memory)
         self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
         self.z_floats = sess.memory[0][1][0].numel()             # one slot's Z (H x d)
         self.seed, self.temperature, self.top_p = seed, temperature, top_p
         self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
-        self.bar_cond, self.bar0, self.cap = int(bar_cond), int(bar0), cap if waiting else int(cap)
-        self.max_cap = int(cap if max_cap is None else max_cap)    # the most tokens one song draws (run()'s step limit)
-        slot = torch.arange(self.S, dtype=torch.int64, device=dev)
-        self.song = torch.where(slot < (0 if waiting else self.n_songs), slot, torch.full_like(slot, -1))
-        self.pos = torch.zeros(self.S, dtype=torch.int64, device=dev)
-        self.bar = torch.full((self.S,), self.bar0, dtype=torch.int64, device=dev)
-        self.fresh = torch.full((self.S,), 0 if waiting else 1, dtype=torch.int64, device=dev)   # 1: take the snapshot
-        ctl = [0, 0, 0, 0] if waiting else [0, min(self.S, self.n_songs), 0]
-        self.ctl = torch.tensor(ctl, dtype=torch.int64, device=dev)
+        self.bar_cond = int(bar_cond)
+        # the slots' song, position in it, bar count and fresh flag (1: refill me): set by start(), then the device's
+        self.song, self.pos, self.bar, self.fresh = (torch.zeros(self.S, dtype=torch.int64, device=dev)
+                                                     for _ in range(4))
+        self.ctl = torch.zeros(self.n_ctl, dtype=torch.int64, device=dev)
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
         self.mask = None if mask is None else dict(mask, bar=self.bar)
-        # grammar: slot s starts at beat0[s], the position of the song it starts with; a slot handed a song later takes
-        # that song's beat0 in cwlt_grammar_track
-        self.grammar, self.beat = grammar, None
-        if grammar is not None:
-            self.beat = torch.full((self.S,), -1, dtype=torch.int64, device=dev)
-            k = min(self.S, self.n_songs)
-            self.beat[:k] = grammar["beat0"][:k]
+        self.grammar = grammar
+        self.beat = None if grammar is None else torch.full((self.S,), -1, dtype=torch.int64, device=dev)
         self.lp_ring = torch.zeros((2 * self.chunk, self.S, self.A, 2), dtype=torch.float32, device=dev) \
             if logprobs else None
         self._host_lp = [torch.zeros((self.chunk, self.S, self.A, 2), dtype=torch.float32).pin_memory()
                          for _ in range(2)] if logprobs else None
         self.lp_parts = []
-        self._host_ctl = [torch.zeros(len(ctl), dtype=torch.int64).pin_memory() for _ in range(2)]
+        self._host_ctl = [torch.zeros(self.n_ctl, dtype=torch.int64).pin_memory() for _ in range(2)]
         self._events = [torch.cuda.Event(), torch.cuda.Event()]
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
         self._graph, self.enqueued = None, 0
         self.wait_s = 0.0                                          # host time spent waiting on the device
 
-    def _refill(self, logits):
-        ops.stream_refill(self.sess._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
-                          self.snap_logits, self.fresh)
-
-    def _advance(self, tok):
-        ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
-                           self.pos, self.bar, self.fresh, self.ctl, self.ring)
+    def _hand_out(self, first, wait, ctl):
+        """The hand-out before the first token: slots 0 .. first - 1 take songs 0 .. first - 1 and are fresh (under a
+        grammar every slot with a song for it starts at that song's beat0; a slot handed a song later takes that song's
+        in cwlt_grammar_track); a slot past them holds `wait` while there is a song for it, or idles (-1).  ctl: the
+        counters to start from."""
+        slot = torch.arange(self.S, dtype=torch.int64, device=self.sess.dev)
+        rest = torch.where(slot < self.n_songs, torch.full_like(slot, wait), torch.full_like(slot, -1))
+        self.song.copy_(torch.where(slot < first, slot, rest))
+        self.fresh.copy_((slot < first).to(torch.int64))
+        if self.grammar is not None:
+            k = min(self.S, self.n_songs)
+            self.beat[:k] = self.grammar["beat0"][:k]
+        self.ctl.copy_(torch.tensor(ctl, dtype=torch.int64))
 
     def _one(self):
         s = self.sess
@@ -1013,7 +1012,8 @@ class _StreamLoop:
     def run(self):
         """Run until the device's finished counter reaches n_songs -> (rows (n, A + 2) of every song, time-ordered)."""
         parts = []
-        limit = -(-self.n_songs // self.S) * (self.max_cap + 1) + 2 * self.chunk     # every slot's songs, one by one
+        limit = -(-self.n_songs // self.S) * (self.song_cap + 1) + 2 * self.chunk     # every slot's songs, one by one
+        self.start()
         h = self._enqueue_chunk()
         while True:
             nxt = self._enqueue_chunk()
@@ -1027,23 +1027,52 @@ class _StreamLoop:
         self._wait(nxt)                                            # the one chunk enqueued past the end
         return np.concatenate(parts)
 
+    def stats(self):
+        """After run(): what the form adds to generate_stream's stats."""
+        return {}
+
+
+class _SnapshotStreamLoop(_StreamLoop):
+    """The stream whose songs all start from one snapshot (snap_state, snap_logits: _stream_snapshot), with one bar0 and
+    one cap: cwlt_stream_refill and cwlt_stream_advance."""
+
+    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk, **kw):
+        super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
+        self.snap_state, self.snap_logits = snap_state, snap_logits
+        self.bar0, self.cap = int(bar0), int(cap)
+        self.song_cap = self.cap
+
+    def start(self):
+        """Slots 0, 1, ... take the first songs; slots past the last song idle."""
+        first = min(self.S, self.n_songs)
+        self._hand_out(first, -1, [0, first, 0])
+        self.bar.fill_(self.bar0)
+
+    def _refill(self, logits):
+        ops.stream_refill(self.sess._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
+                          self.snap_logits, self.fresh)
+
+    def _advance(self, tok):
+        ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
+                           self.pos, self.bar, self.fresh, self.ctl, self.ring)
+
 
 class _BankStreamLoop(_StreamLoop):
-    """_StreamLoop with a prompt of its own for every song.  Song k starts from entry k % bank of a device bank laid out
+    """The stream with a prompt of its own for every song.  Song k starts from entry k % bank of a device bank laid out
     like a `bank`-slot DecodeSession._state (per layer the S rows of all entries, then their Z rows), with its next-token
     logits, bar count and cap beside it.  Blocks of B consecutive songs are prefilled (CWTrunk._prefill_gemm, batch
     invariant) straight into their entries between chunks, on the stream's own stream, each followed by a device write
-    of ctl[3] = songs ready.  Per token: the GEMM decode step, cwlt_stream_refill_bank, the keyed sampler,
-    cwlt_stream_advance_bank (a slot takes a song only below ctl[3], otherwise it waits)."""
+    of ctl[3] = songs ready, the counter this form adds.  cwlt_stream_refill_bank and cwlt_stream_advance_bank: a slot
+    takes a song only below ctl[3], otherwise it waits (song -2), and keeps its song's cap in `cap`."""
 
-    def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, temperature=None,
-                 top_p=None, graph=None, prefill_rows=None, mask=None, logprobs=False, grammar=None):
-        # no snapshot; until start() hands songs out the slots wait, count bars from 0 and carry caps of 1
+    n_ctl = 4
+
+    def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, prefill_rows=None,
+                 **kw):
+        super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
         dev = sess.dev
-        super().__init__(sess, None, None, n_songs, seed, bar_mask, bar_cond, 0,
-                         torch.ones(sess.n_songs, dtype=torch.int64, device=dev), chunk, temperature=temperature,
-                         top_p=top_p, graph=graph, mask=mask, logprobs=logprobs, grammar=grammar, waiting=True,
-                         max_cap=max(caps))
+        self.cap = torch.ones(self.S, dtype=torch.int64, device=dev)
+        self.song_cap = int(max(caps))
         self.B, self.bank = int(B), int(bank)
         self.nb = self.bank // self.B
         self.n_blocks = -(-self.n_songs // self.B)
@@ -1101,19 +1130,14 @@ class _BankStreamLoop(_StreamLoop):
             self._prefill_block()
 
     def start(self):
-        """Before the first token: prefill the first nb blocks and hand the ready songs to slots 0, 1, ... in order
-        (slots past them wait while songs remain, or idle)."""
+        """Prefill the first nb blocks and hand the ready songs to slots 0, 1, ... in order; slots past them wait while
+        songs remain, or idle."""
         self._prefill_allowed(0)
         ready = min(self.n_songs, self.next_block * self.B)
         first = min(self.S, ready)
-        slot = torch.arange(self.S, dtype=torch.int64, device=self.sess.dev)
-        wait = torch.where(slot < self.n_songs, torch.full_like(slot, -2), torch.full_like(slot, -1))
-        self.song.copy_(torch.where(slot < first, slot, wait))
-        idx = slot[:first]
-        self.fresh.copy_((slot < first).to(torch.int64))
-        self.bar[:first] = self.bar0_all[idx]
-        self.cap[:first] = self.cap_all[idx]
-        self.ctl.copy_(torch.tensor([0, first, 0, ready], dtype=torch.int64))
+        self._hand_out(first, -2, [0, first, 0, ready])
+        self.bar[:first] = self.bar0_all[:first]
+        self.cap[:first] = self.cap_all[:first]
 
     def _refill(self, logits):
         ops.stream_refill_bank(self.sess._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
@@ -1131,14 +1155,11 @@ class _BankStreamLoop(_StreamLoop):
         super()._between_chunks(ctl, limit + self.gated_chunks * self.chunk)
         self._prefill_allowed(int(ctl[1]))
 
-    def run(self):
-        """_StreamLoop.run() after start(); between chunks the host prefills what the chunk just read allows."""
-        self.start()
-        return super().run()
-
-    def prefill_seconds(self):
-        """GPU time of the block prefills (after run())."""
-        return sum(a.elapsed_time(b) for a, b in self.prefill_events) / 1e3
+    def stats(self):
+        """After run(): the block size, bank entries, GPU seconds of the block prefills, blocks, gated chunks."""
+        return {"block": self.B, "bank": self.bank,
+                "prefill_seconds": sum(a.elapsed_time(b) for a, b in self.prefill_events) / 1e3,
+                "prefill_blocks": self.next_block, "gated_chunks": self.gated_chunks}
 
 
 def _stream_snapshot(model, prompt, A):
@@ -1184,33 +1205,6 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
     return heads, bar0s, caps
 
 
-def _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond, max_tokens, prompts, sampler, chunk, bank,
-                             prefill_rows, log, constraints=None, logprobs=False, grammar=None):
-    start = time.perf_counter()
-    n_token = list(model.n_token)
-    heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
-    table = None if constraints is None else \
-        compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens)
-    gtables = None if grammar is None else compile_grammar(grammar, constraints, n_songs, n_token, bar_cond)
-    sess = DecodeSession(model, n_songs=slots, kernel="gemm")
-    sess.reset()
-    seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
-    per_entry = 4 * (sess._state.numel() // slots + sess.width + 2)
-    B, bank = stream_bank_plan([len(h) for h in heads], slots, prefill_rows, bank, per_entry,
-                               torch.cuda.mem_get_info(sess.dev)[0])
-    names = word2event["bar-beat"]
-    bar_mask = [int(names[i] == "Bar") for i in range(sess.n_token[2])]
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-    loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
-                           temperature=temperature, top_p=top_p, graph=sess.use_graph, prefill_rows=prefill_rows,
-                           mask=None if table is None else _device_constraints(table, sess.dev), logprobs=logprobs,
-                           grammar=None if grammar is None else
-                           _device_grammar(grammar, gtables, [grammar.beat_states(h)[1] for h in heads], sess.dev))
-    rows = loop.run()
-    return heads, rows, loop, start, {"block": B, "bank": bank, "prefill_seconds": loop.prefill_seconds(),
-                                      "prefill_blocks": loop.next_block, "gated_chunks": loop.gated_chunks}
-
-
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
                      return_logprobs=False, grammar=None):
@@ -1237,37 +1231,42 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompt is not None and prompts is not None:
         raise ValueError("pass one shared prompt or per-song prompts, not both")
     A = len(word2event)
-    extra = {}
+    start = time.perf_counter()
+    n_token = list(model.n_token)
     if prompts is not None:
-        heads, rows, loop, start, extra = _generate_stream_prompts(model, word2event, n_songs, slots, bar_cond,
-                                                                   max_tokens, prompts, sampler, chunk, bank,
-                                                                   prefill_rows, log, constraints, return_logprobs,
-                                                                   grammar)
+        heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
-        bar_names = word2event["bar-beat"]
-        (head,), (bar0,), (cap,) = _check_prompts([INIT_CW[0] if prompt is None else prompt], 1, word2event, None,
-                                                   bar_cond, max_tokens)
-        table = None if constraints is None else \
-            compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, [bar0] * n_songs, max_tokens)
-        gtables = None if grammar is None else \
-            compile_grammar(grammar, constraints, n_songs, list(model.n_token), bar_cond)
-        start = time.perf_counter()
-        sess = DecodeSession(model, n_songs=slots, kernel="gemm")
-        sess.reset()
-        seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
-        snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else head, A)
-        bar_mask = [int(bar_names[i] == "Bar") for i in range(sess.n_token[2])]   # every class named "Bar", not one id
-        temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-        loop = _StreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                           temperature=temperature, top_p=top_p, graph=sess.use_graph,
-                           mask=None if table is None else _device_constraints(table, sess.dev),
-                           logprobs=return_logprobs,
-                           grammar=None if grammar is None else
-                           _device_grammar(grammar, gtables, [grammar.beat_states(head)[1]] * n_songs, sess.dev))
-        rows = loop.run()
-        heads = [head] * n_songs
+        heads, bar0s, caps = ([v[0]] * n_songs for v in _check_prompts(
+            [INIT_CW[0] if prompt is None else prompt], 1, word2event, None, bar_cond, max_tokens))
+    table = None if constraints is None else \
+        compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens)
+    gtables = None if grammar is None else compile_grammar(grammar, constraints, n_songs, n_token, bar_cond)
+    if prompts is None:
+        start = time.perf_counter()                           # the shared form's clock starts after the host's compiles
+    sess = DecodeSession(model, n_songs=slots, kernel="gemm")
+    sess.reset()
+    seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
+    names = word2event["bar-beat"]
+    bar_mask = [int(names[i] == "Bar") for i in range(sess.n_token[2])]       # every class named "Bar", not one id
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    beat0s = None if grammar is None else [grammar.beat_states(h)[1] for h in heads] if prompts is not None else \
+        [grammar.beat_states(heads[0])[1]] * n_songs
+    kw = dict(temperature=temperature, top_p=top_p, graph=sess.use_graph,
+              mask=None if table is None else _device_constraints(table, sess.dev), logprobs=return_logprobs,
+              grammar=None if grammar is None else _device_grammar(grammar, gtables, beat0s, sess.dev))
+    if prompts is not None:
+        per_entry = 4 * (sess._state.numel() // slots + sess.width + 2)
+        B, bank = stream_bank_plan([len(h) for h in heads], slots, prefill_rows, bank, per_entry,
+                                   torch.cuda.mem_get_info(sess.dev)[0])
+        loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
+                               prefill_rows=prefill_rows, **kw)
+    else:
+        snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else heads[0], A)
+        loop = _SnapshotStreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0s[0], caps[0],
+                                   chunk, **kw)
+    rows = loop.run()
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
     order = np.argsort(rows[:, 0], kind="stable")
     rows = rows[order]
@@ -1282,7 +1281,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     stats = {"steps": loop.enqueued, "tokens": int(sum(len(x) for x in songs)), "drawn": int(len(rows)),
              "slot_steps": loop.enqueued * slots, "seconds": seconds, "wait_seconds": loop.wait_s,
              "graph": loop._graph is not None}
-    stats.update(extra)
+    stats.update(loop.stats())
     if log is not None:
         log("stream of %d songs on %d slots: %d tokens, %d steps" % (n_songs, slots, stats["tokens"], loop.enqueued))
     if return_logprobs:            # filtered by the same mask as the rows, in the same order: the same sort applies

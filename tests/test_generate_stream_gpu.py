@@ -160,12 +160,15 @@ def test_stream_advance_kernel(cuda, slots):
     mask[[1, 9]] = 1
     n_songs = slots + slots // 2 + 1
     song = np.where(np.arange(slots) % 6 == 3, -1, np.arange(slots)).astype(np.int64)
+    song[3] = -2                                            # a stray -2 is no candidate here: it stays, song-less
     pos = rng.integers(0, cap, slots).astype(np.int64)
     bar = rng.integers(bar0, bar_cond, slots).astype(np.int64)
     ctl = np.array([5, slots, 1], dtype=np.int64)
     ring = np.full((R, slots, A + 2), 7, dtype=np.int64)
     d = {k: torch.as_tensor(v).to(cuda) for k, v in dict(song=song, pos=pos, bar=bar, ctl=ctl, ring=ring).items()}
     d["fresh"] = torch.full((slots,), 5, dtype=torch.int64, device=cuda)
+    ctl4 = torch.cat([d["ctl"], torch.zeros(1, dtype=torch.int64, device=cuda)])
+    d["ctl"] = ctl4[:3]                                     # were ctl[3] = 0 read as songs ready, no slot took a song
     dmask = torch.as_tensor(mask).to(cuda)
     first = None
     for step in range(12):
@@ -190,32 +193,49 @@ def test_stream_advance_kernel(cuda, slots):
             assert first[ended].tolist() == [slots + i if slots + i < n_songs else -1 for i in range(len(ended))]
     assert ctl[1] == n_songs                                # the pool ran out of songs: more idle slots
     assert (song == -1).sum() > (np.arange(slots) % 6 == 3).sum()
+    assert ctl4.cpu().tolist() == ctl.tolist() + [0]        # three counters: the element after them is not written
+    assert song[3] == -2 and (ring[:, 3, 0] == -2).all() and (ring[:, 3, -1] == 0).all()
     assert ring[:, :, -1].sum() > 0
+
+
+def _slot_views(t, n, L, s_f, z_f):
+    """Per layer the (n, s_f) S rows and (n, z_f) Z rows of a flat DecodeSession._state of n slots (views)."""
+    per = s_f + z_f
+    return [(t[i * n * per:i * n * per + n * s_f].view(n, s_f), t[i * n * per + n * s_f:(i + 1) * n * per].view(n, z_f))
+            for i in range(L)]
+
+
+# 7 slots: one wave.  300 slots, 544 float4 per slot: three blocks, fresh flags in every wave of the first 256-slot chunk
+# (both edges of waves 0 / 1 and 2 / 3) and in the second chunk
+REFILL_CASES = [(7, 3, 32, 8, [1, 3, 4]), (300, 2, 1024, 64, [0, 63, 64, 191, 255, 256, 299])]
+
+
+def _refill_mismatch(state, want, logits, want_lg, slots, L, s_f, z_f):
+    """The slots whose state in any layer, or logits row, is not exactly the expected one."""
+    bad = (logits != want_lg).any(1)
+    for (S, Z), (wS, wZ) in zip(_slot_views(state, slots, L, s_f, z_f), _slot_views(want, slots, L, s_f, z_f)):
+        bad |= (S != wS).any(1) | (Z != wZ).any(1)
+    return torch.nonzero(bad).flatten().tolist()
 
 
 def test_stream_refill_kernel(cuda):
     g = torch.Generator(device=cuda).manual_seed(3)
-    slots, L, s_f, z_f, W = 7, 3, 32, 8, 19
-    state = torch.randn(L * slots * (s_f + z_f), device=cuda, generator=g)
-    snap = torch.randn(L * (s_f + z_f), device=cuda, generator=g)
-    logits = torch.randn(slots, W + 5, device=cuda, generator=g)
-    snap_logits = torch.randn(W, device=cuda, generator=g)
-    fresh = torch.tensor([0, 1, 0, 1, 1, 0, 0], dtype=torch.int64, device=cuda)
-    st0, lg0 = state.clone(), logits.clone()
-    ops.stream_refill(state, snap, L, s_f, z_f, logits, snap_logits, fresh)
-    view = lambda t: [(t[i * slots * (s_f + z_f):i * slots * (s_f + z_f) + slots * s_f].view(slots, s_f),
-                       t[i * slots * (s_f + z_f) + slots * s_f:(i + 1) * slots * (s_f + z_f)].view(slots, z_f))
-                      for i in range(L)]
-    for i, ((S, Z), (S0, Z0)) in enumerate(zip(view(state), view(st0))):
-        sn = snap[i * (s_f + z_f):(i + 1) * (s_f + z_f)]
-        for s in range(slots):
-            if fresh[s]:
-                assert torch.equal(S[s], sn[:s_f]) and torch.equal(Z[s], sn[s_f:]), (i, s)
-            else:
-                assert torch.equal(S[s], S0[s]) and torch.equal(Z[s], Z0[s]), (i, s)
-    for s in range(slots):
-        want = torch.cat([snap_logits, lg0[s, W:]]) if fresh[s] else lg0[s]
-        assert torch.equal(logits[s], want), s
+    W = 19
+    for slots, L, s_f, z_f, idx in REFILL_CASES:
+        state = torch.randn(L * slots * (s_f + z_f), device=cuda, generator=g)
+        snap = torch.randn(L * (s_f + z_f), device=cuda, generator=g)
+        logits = torch.randn(slots, W + 5, device=cuda, generator=g)       # a row wider than n_logits
+        snap_logits = torch.randn(W, device=cuda, generator=g)
+        fresh = torch.zeros(slots, dtype=torch.int64, device=cuda)
+        fresh[idx] = 1
+        # every slot: the snapshot where fresh, untouched elsewhere, the columns past n_logits included
+        want, want_lg = state.clone(), logits.clone()
+        for (S, Z), (sS, sZ) in zip(_slot_views(want, slots, L, s_f, z_f), _slot_views(snap, 1, L, s_f, z_f)):
+            S[idx], Z[idx] = sS[0], sZ[0]
+        want_lg[idx, :W] = snap_logits
+        assert _refill_mismatch(state, want, logits, want_lg, slots, L, s_f, z_f) == idx      # the check can fail
+        ops.stream_refill(state, snap, L, s_f, z_f, logits, snap_logits, fresh)
+        assert _refill_mismatch(state, want, logits, want_lg, slots, L, s_f, z_f) == [], slots
 
 
 @pytest.mark.parametrize("sampler", ["dqn", "categorical"])

@@ -12,6 +12,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from fill import fill_params  # noqa: E402
+from test_generate_stream_gpu import _refill_mismatch, _slot_views  # noqa: E402
 
 import rlmg_amd  # noqa: E402,F401
 from rlmg_amd import generation, ops  # noqa: E402
@@ -138,30 +139,35 @@ def test_invariant_prefill(cuda):
         assert float(np.abs(out - lg.cpu().numpy()).max()) < 1e-5 and _scaled_err(st, sess._state) < 1e-5, k
 
 
+# (slots, layers, s_floats, z_floats, {fresh slot: its song}); songs >= 5 wrap the bank, fresh slots with -1 / -2 stay.
+# 9 slots: one wave.  300 slots, 544 float4 per slot: three blocks, fresh flags in every wave of the first 256-slot
+# chunk (both edges of waves 0 / 1 and 2 / 3) and in the second chunk
+REFILL_BANK_CASES = [(9, 3, 32, 8, {1: 7, 3: 11, 4: 4, 6: -1, 7: -2, 8: 5}),
+                     (300, 2, 1024, 64, {0: 3, 63: -1, 64: 7, 191: 11, 255: -2, 256: 4, 299: 10})]
+
+
 def test_refill_bank_kernel(cuda):
     g = torch.Generator(device=cuda).manual_seed(3)
-    slots, bank, L, s_f, z_f, W = 9, 5, 3, 32, 8, 19
-    per = s_f + z_f
-    state = torch.randn(L * slots * per, device=cuda, generator=g)
-    bstate = torch.randn(L * bank * per, device=cuda, generator=g)
-    logits = torch.randn(slots, W + 5, device=cuda, generator=g)
-    blogits = torch.randn(bank, W, device=cuda, generator=g)
-    fresh = torch.tensor([0, 1, 0, 1, 1, 0, 1, 1, 1], dtype=torch.int64, device=cuda)
-    song = torch.tensor([3, 7, 2, 11, 4, -1, -1, -2, 5], dtype=torch.int64, device=cuda)   # 7, 11, 5 wrap the bank
-    st0, lg0 = state.clone(), logits.clone()
-    ops.stream_refill_bank(state, bstate, L, s_f, z_f, logits, blogits, fresh, song)
-    view = lambda t, n: [(t[i * n * per:i * n * per + n * s_f].view(n, s_f),
-                          t[i * n * per + n * s_f:(i + 1) * n * per].view(n, z_f)) for i in range(L)]
-    for (S, Z), (S0, Z0), (BS, BZ) in zip(view(state, slots), view(st0, slots), view(bstate, bank)):
-        for s in range(slots):
-            if fresh[s] and song[s] >= 0:
-                e = int(song[s]) % bank
-                assert torch.equal(S[s], BS[e]) and torch.equal(Z[s], BZ[e]), s
-            else:
-                assert torch.equal(S[s], S0[s]) and torch.equal(Z[s], Z0[s]), s
-    for s in range(slots):
-        want = torch.cat([blogits[int(song[s]) % bank], lg0[s, W:]]) if fresh[s] and song[s] >= 0 else lg0[s]
-        assert torch.equal(logits[s], want), s
+    bank, W = 5, 19
+    for slots, L, s_f, z_f, songs in REFILL_BANK_CASES:
+        state = torch.randn(L * slots * (s_f + z_f), device=cuda, generator=g)
+        bstate = torch.randn(L * bank * (s_f + z_f), device=cuda, generator=g)
+        logits = torch.randn(slots, W + 5, device=cuda, generator=g)       # a row wider than n_logits
+        blogits = torch.randn(bank, W, device=cuda, generator=g)
+        fresh = torch.zeros(slots, dtype=torch.int64, device=cuda)
+        fresh[list(songs)] = 1
+        song = torch.arange(slots, dtype=torch.int64, device=cuda) % 13 - 2    # not fresh: any song, negative too
+        song[list(songs)] = torch.tensor(list(songs.values()), device=cuda)
+        idx = [s for s, k in songs.items() if k >= 0]
+        e = [songs[s] % bank for s in idx]
+        # every slot: its song's entry where fresh with a song, untouched elsewhere, the columns past n_logits included
+        want, want_lg = state.clone(), logits.clone()
+        for (S, Z), (bS, bZ) in zip(_slot_views(want, slots, L, s_f, z_f), _slot_views(bstate, bank, L, s_f, z_f)):
+            S[idx], Z[idx] = bS[e], bZ[e]
+        want_lg[idx, :W] = blogits[e]
+        assert _refill_mismatch(state, want, logits, want_lg, slots, L, s_f, z_f) == idx      # the check can fail
+        ops.stream_refill_bank(state, bstate, L, s_f, z_f, logits, blogits, fresh, song)
+        assert _refill_mismatch(state, want, logits, want_lg, slots, L, s_f, z_f) == [], slots
 
 
 def _advance_bank_model(tokens, mask, bar_cond, bank_bar0, bank_cap, n_songs, song, pos, bar, cap, ctl, ring):

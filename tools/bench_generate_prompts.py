@@ -11,7 +11,8 @@ Writes JSON lines to --out (default profiles/generate_prompts_bench.jsonl) and p
     FLOPs of the valid rows);
   * kind "bank_kernels": per-token device time of refill + advance against refill_bank + advance_bank at S slots;
   * kind "check": how many songs of generate_batch(prompts, prefill="gemm") differ from the stream's (must be 0).
---only-stream S: run generate_stream(prompts=..., slots=S) alone once after a warm-up (for a rocprofv3 kernel trace)."""
+--only-stream S: run generate_stream(prompts=..., slots=S) alone once after a warm-up (for a rocprofv3 kernel trace).
+--only-bank-kernels: the "step" and "bank_kernels" records alone (an A/B of csrc/stream.hip between two trees)."""
 import argparse
 import json
 import os
@@ -127,6 +128,7 @@ def main():
     ap.add_argument("--max-tokens", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--only-stream", type=int, default=0)
+    ap.add_argument("--only-bank-kernels", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_prompts_bench.jsonl"))
     a = ap.parse_args()
     from rlmg_amd.dqn_policy import model
@@ -153,6 +155,29 @@ def main():
         print(json.dumps(d), flush=True)
         lines.append(d)
 
+    enc = net.transformer_encoder
+
+    def step_and_bank_kernels(S):
+        rate = _replay_rate(net, S, a.steps)
+        step_s = S / rate
+        emit({"kind": "step", "slots": S, "steps": a.steps, "tokens_per_s": rate, "step_ms": step_s * 1e3})
+        old, new = _bank_kernels(S, len(enc.layers), enc.layers[0].attention.n_heads, sum(N_CLASS), 200, net.in_linear.weight.device)
+        emit({"kind": "bank_kernels", "slots": S, "refill_advance_us": old * 1e6, "bank_pair_us": new * 1e6,
+              "step_us": step_s * 1e6, "delta_over_step": (new - old) / step_s})
+        torch.cuda.empty_cache()
+        return rate
+
+    def write():
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            for d in lines:
+                f.write(json.dumps(d) + "\n")
+
+    if a.only_bank_kernels:
+        for S in a.slots:
+            step_and_bank_kernels(S)
+        return write()
+
     # one block of prompts through each prefill kernel
     block = prompts[:a.block]
     P = max(len(p) for p in block)
@@ -169,16 +194,9 @@ def main():
     del sess
     torch.cuda.empty_cache()
 
-    enc = net.transformer_encoder
     streams = {}
     for S in a.slots:
-        rate = _replay_rate(net, S, a.steps)
-        step_s = S / rate
-        emit({"kind": "step", "slots": S, "steps": a.steps, "tokens_per_s": rate, "step_ms": step_s * 1e3})
-        old, new = _bank_kernels(S, len(enc.layers), enc.layers[0].attention.n_heads, sum(N_CLASS), 200, net.in_linear.weight.device)
-        emit({"kind": "bank_kernels", "slots": S, "refill_advance_us": old * 1e6, "bank_pair_us": new * 1e6,
-              "step_us": step_s * 1e6, "delta_over_step": (new - old) / step_s})
-        torch.cuda.empty_cache()
+        rate = step_and_bank_kernels(S)
         torch.manual_seed(SEED)
         songs, st = generation._generate_stream(net, w2e, a.songs, slots=S, bar_cond=a.bar_cond,
                                                 max_tokens=a.max_tokens, prompts=prompts)
@@ -228,10 +246,7 @@ def main():
         differ = sum(not (x.shape == y.shape and (x == y).all()) for x, y in zip(songs, ref))
         emit({"kind": "check", "slots": S, "songs": a.songs, "batch_seconds": wall,
               "songs_differing_from_generate_batch_gemm": int(differ)})
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(d) + "\n")
+    write()
 
 
 if __name__ == "__main__":
