@@ -570,6 +570,27 @@ int cwlt_grammar_track(const int64_t* tokens, int64_t rows, int n_attr, int bar_
                        const int64_t* fresh, const int64_t* song, const int64_t* beat0, int64_t n_songs,
                        int64_t* beat, void* stream);
 
+/* Policy entropy and KL against a reference model (csrc/policy_stats.hip).  For row n of logits (rows x
+ * ld f32) and attribute a: p = softmax of the raw logits, q the distribution cwlt_score_categorical(_grammar) scores
+ * row n under -- tempered logits, the mask row of song key[n] (NULL: n) at bar count bar[n], the row grammar, the
+ * nucleus kept set, renormalised, the kept set bitwise the sampler's.  Writes f32 nats to out[(n * n_attr + a) * 2]:
+ * {H(p), H(q)}; with ref_logits (rows x ref_ld f32, a second model's logits for the same rows) to out[(n * n_attr + a)
+ * * 4]: {H(p), H(q), KL(p || p'), KL(q || q')}, p' and q' the same constructions on ref_logits under the same mask,
+ * grammar and settings.  KL(q || q') is +inf when a class of q's kept set is outside q''s (a nucleus only).
+ * bar_class (DEVICE int64 x rows, nullable): the row's own bar-beat class; negative: a padding row, left unwritten.
+ * Under a grammar it fixes the row's kind as the bar-beat target does in cwlt_score_categorical_grammar (attribute
+ * bar_attr itself follows the position rule at beat[n]); without one only its sign is read.  A row whose allowed set
+ * is empty (an ill-formed row under a grammar) gets NaN in the q columns and finite p columns.
+ * bar / sched / masks: all of the constraint table or none of it; beat / order / gram: all of the grammar or none.
+ * Refused: what cwlt_score_categorical_grammar refuses of these arguments, ref_ld < sum n_class with ref_logits, a
+ * grammar without bar_class, rows > 2^20. */
+int cwlt_policy_stats(const float* logits, const int* n_class, const float* temperature, const float* top_p,
+                      int n_attr, int64_t rows, int64_t ld, const float* ref_logits, int64_t ref_ld,
+                      const int64_t* bar_class, const int64_t* key, const int64_t* bar, const int64_t* sched,
+                      int64_t n_sched, const uint32_t* masks, int64_t mask_rows, int mask_words, const int64_t* beat,
+                      const int* order, int n_order, const uint32_t* gram, int gram_words, int bar_attr, float* out,
+                      void* stream);
+
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,
  * cwlt_stream_refill, cwlt_sample_categorical_keyed and cwlt_stream_advance.

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -134,6 +134,8 @@ _SIGNATURES = {
     "cwlt_sample_categorical_grammar": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _c_u64] + [_ptr] * 5
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr],
     "cwlt_score_categorical_grammar": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64] + [_ptr] * 4
+    + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr],
+    "cwlt_policy_stats": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _c_i64] + [_ptr] * 4
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr],
     "cwlt_grammar_track": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr],
     "cwlt_count_bars": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr],

@@ -1632,6 +1632,95 @@ def _score_inputs(songs, mask, n_token):
     return out
 
 
+def _check_scoring_model(model, what="scoring"):
+    if not getattr(model, "_recurrent", False):
+        raise RuntimeError("%s needs a model built with is_training=False (recurrent encoder)" % what)
+    if model.training:
+        raise RuntimeError("%s runs in eval() mode (agent_pretrain.py:657)" % what)
+    if model.compute_dtype != torch.float32:
+        raise RuntimeError("%s computes in f32: this model runs %s activations" % (what, model.compute_dtype))
+
+
+def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, prefill_rows, grammar, reference=None):
+    """What score_songs and policy_stats share: their checks, the constraint and grammar tables, then the songs in
+    blocks of whole songs under prefill_rows token rows (at most SCORE_BLOCK_SONGS songs), each prefilled on a fresh
+    scratch state with the heads on every row -- by `model`, and by `reference` (a second model over the same tokens)
+    when given.  Yields per block (songs of the block, Lb, [logits (nb * Lb, n_logits) per model], targets (nb * Lb, A)
+    int64 on the device: row t of a song holds song[t + 1], -1 on its last row and on padding, {"temperature", "top_p"},
+    the constraint table keywords of ops.score_categorical ({} without constraints), (beat, order, gram, bar_attr) of
+    the grammar or None)."""
+    if sampler not in ("dqn", "categorical"):
+        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
+    if kernel not in ("blas", "gemm"):
+        raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
+    _check_scoring_model(model)
+    n_token = list(model.n_token)
+    dev = next(model.parameters()).device
+    models = [model]
+    if reference is not None:
+        _check_scoring_model(reference, "the reference model: scoring")
+        if list(reference.n_token) != n_token:
+            raise ValueError("the reference model has classes %s, the model %s" % (list(reference.n_token), n_token))
+        if next(reference.parameters()).device != dev:
+            raise ValueError("the reference model must sit on the model's device (%s)" % (dev,))
+        models.append(reference)
+    A = len(n_token)
+    songs = _score_inputs(songs, mask, n_token)
+    n = len(songs)
+    if n == 0:
+        return
+    rows_budget = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
+    if rows_budget < 1:
+        raise ValueError("prefill_rows must be >= 1, got %d" % rows_budget)
+    bars = [song_bar_counts(x, word2event) for x in songs]
+    dmask = None
+    if constraints is not None:
+        top = max([int(b.max()) for b in bars if len(b)] + [1])
+        # max_tokens = the longest song: every song ends, so compile_constraints' "could never end" check is skipped
+        table = compile_constraints(constraints, n, n_token, top + 1, [1] * n, max(len(x) for x in songs))
+        dmask = None if table is None else _device_constraints(table, dev)
+    dgram = None
+    if grammar is not None:
+        top = max([int(b.max()) for b in bars if len(b)] + [1])
+        dgram = _device_grammar(grammar, compile_grammar(grammar, constraints, n, n_token, top + 1), [], dev)
+        beats = [grammar.beat_states(x)[0] for x in songs]
+    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
+    for a0 in range(0, n, per):
+        blk = songs[a0:a0 + per]
+        nb, Lb = len(blk), max(len(x) for x in blk)
+        toks = np.zeros((nb, Lb, A), dtype=np.int64)
+        tgt = np.full((nb, Lb, A), -1, dtype=np.int64)          # the last row of a song and padding: not scored
+        bar = np.ones((nb, Lb), dtype=np.int64)
+        beat = np.full((nb, Lb), -1, dtype=np.int64)
+        for i, x in enumerate(blk):
+            toks[i, :len(x)] = x
+            tgt[i, :len(x) - 1] = x[1:]
+            bar[i, :len(x) - 1] = bars[a0 + i]
+            if dgram is not None:
+                beat[i, :len(x) - 1] = beats[a0 + i][1:]
+        lgs = []
+        with torch.no_grad():
+            for net in models:
+                enc = net.transformer_encoder
+                H = enc.layers[0].attention.n_heads
+                d = net.d_model // H
+                memory = [[torch.zeros((nb, H, d, d), dtype=torch.float32, device=dev),
+                           torch.zeros((nb, H, d), dtype=torch.float32, device=dev)] for _ in enc.layers]
+                lg = net.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
+                                        logits="all")
+                lgs.append(lg.reshape(nb * Lb, -1))
+        m = {}
+        if dmask is not None:
+            m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
+                 "bar": torch.as_tensor(bar.reshape(-1)).to(dev), "sched": dmask["sched"], "masks": dmask["masks"]}
+        gram = None
+        if dgram is not None:
+            gram = (torch.as_tensor(beat.reshape(-1)).to(dev), dgram["order"], dgram["gram"], dgram["bar_attr"])
+        yield (blk, Lb, lgs, torch.as_tensor(tgt.reshape(-1, A)).to(dev), {"temperature": temperature, "top_p": top_p},
+               m, gram)
+
+
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
                 prefill_rows=None, grammar=None):
     """Log-likelihoods of given songs under the recurrent form, as generation samples them.
@@ -1657,78 +1746,44 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     song[t + 1]'s own bar-beat class and its position Grammar.beat_states(song)[0][t + 1]; an ill-formed row gets -inf
     in the sampler column of the offending attribute and a finite model column.
     Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range."""
-    if sampler not in ("dqn", "categorical"):
-        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
-    if kernel not in ("blas", "gemm"):
-        raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
-    if not getattr(model, "_recurrent", False):
-        raise RuntimeError("scoring needs a model built with is_training=False (recurrent encoder)")
-    if model.training:
-        raise RuntimeError("scoring runs in eval() mode (agent_pretrain.py:657)")
-    if model.compute_dtype != torch.float32:
-        raise RuntimeError("scoring computes in f32: this model runs %s activations" % model.compute_dtype)
-    n_token = list(model.n_token)
-    A = len(n_token)
-    songs = _score_inputs(songs, mask, n_token)
-    n = len(songs)
-    if n == 0:
-        return []
-    rows_budget = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
-    if rows_budget < 1:
-        raise ValueError("prefill_rows must be >= 1, got %d" % rows_budget)
-    dev = next(model.parameters()).device
-    bars = [song_bar_counts(x, word2event) for x in songs]
-    dmask = None
-    if constraints is not None:
-        top = max([int(b.max()) for b in bars if len(b)] + [1])
-        # max_tokens = the longest song: every song ends, so compile_constraints' "could never end" check is skipped
-        table = compile_constraints(constraints, n, n_token, top + 1, [1] * n, max(len(x) for x in songs))
-        dmask = None if table is None else _device_constraints(table, dev)
-    dgram = None
-    if grammar is not None:
-        top = max([int(b.max()) for b in bars if len(b)] + [1])
-        dgram = _device_grammar(grammar, compile_grammar(grammar, constraints, n, n_token, top + 1), [], dev)
-        beats = [grammar.beat_states(x)[0] for x in songs]
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-    enc = model.transformer_encoder
-    H = enc.layers[0].attention.n_heads
-    d = model.d_model // H
-    per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
     out = []
-    for a0 in range(0, n, per):
-        blk = songs[a0:a0 + per]
-        nb, Lb = len(blk), max(len(x) for x in blk)
-        toks = np.zeros((nb, Lb, A), dtype=np.int64)
-        tgt = np.full((nb, Lb, A), -1, dtype=np.int64)          # the last row of a song and padding: not scored
-        bar = np.ones((nb, Lb), dtype=np.int64)
-        beat = np.full((nb, Lb), -1, dtype=np.int64)
-        for i, x in enumerate(blk):
-            toks[i, :len(x)] = x
-            tgt[i, :len(x) - 1] = x[1:]
-            bar[i, :len(x) - 1] = bars[a0 + i]
-            if dgram is not None:
-                beat[i, :len(x) - 1] = beats[a0 + i][1:]
-        memory = [[torch.zeros((nb, H, d, d), dtype=torch.float32, device=dev),
-                   torch.zeros((nb, H, d), dtype=torch.float32, device=dev)] for _ in enc.layers]
-        with torch.no_grad():
-            lg = model.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
-                                      logits="all")
-            m = {}
-            if dmask is not None:
-                m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
-                     "bar": torch.as_tensor(bar.reshape(-1)).to(dev), "sched": dmask["sched"], "masks": dmask["masks"]}
-            if dgram is not None:
-                lp = ops.score_categorical_grammar(lg.reshape(nb * Lb, -1), n_token,
-                                                   torch.as_tensor(tgt.reshape(-1, A)).to(dev),
-                                                   torch.as_tensor(beat.reshape(-1)).to(dev), dgram["order"],
-                                                   dgram["gram"], dgram["bar_attr"], temperature=temperature,
-                                                   top_p=top_p, **m)
-            else:
-                lp = ops.score_categorical(lg.reshape(nb * Lb, -1), n_token,
-                                           torch.as_tensor(tgt.reshape(-1, A)).to(dev), temperature=temperature,
-                                           top_p=top_p, **m)
-        lp = lp.view(nb, Lb, A, 2).cpu().numpy()
+    for blk, Lb, (lg,), tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
+                                                               mask, prefill_rows, grammar):
+        if gram is not None:
+            lp = ops.score_categorical_grammar(lg, list(model.n_token), tgt, *gram, **settings, **m)
+        else:
+            lp = ops.score_categorical(lg, list(model.n_token), tgt, **settings, **m)
+        lp = lp.view(len(blk), Lb, -1, 2).cpu().numpy()
         out.extend(lp[i, :len(x) - 1].copy() for i, x in enumerate(blk))
+    return out
+
+
+def policy_stats(model, word2event, songs, reference=None, sampler="categorical", constraints=None, kernel="gemm",
+                 mask=None, prefill_rows=None, grammar=None):
+    """Entropy of the policy along given songs, and its KL against a reference model.
+    -> list of (L_i - 1, 6, 2) float32 arrays, (L_i - 1, 6, 4) with `reference`; rows as in score_songs: row t is about
+    the distribution of song[t + 1] given song[:t + 1].  In nats: [..., 0] H(p), p the model's softmax (temperature 1,
+    no mask, no nucleus); [..., 1] H(q), q what the device sampler draws row t + 1 from (the sampler's temperature and
+    nucleus, the song's constraint row, the row grammar with the kind of song[t + 1]'s own bar-beat class -- the q
+    score_songs scores under); with `reference` [..., 2] KL(p || p') and [..., 3] KL(q || q'), p' and q' the same
+    constructions on the reference model's logits for the same rows.  KL(q || q') is +inf where q keeps a class that
+    q' does not (a nucleus only).  An ill-formed row still has its distributions -- the grammar removes classes, and
+    compile_grammar refuses constraints that would leave a kind no class -- so no entry is NaN (the kernel's answer to an
+    empty allowed set).
+    songs, sampler, constraints, kernel, mask, prefill_rows, grammar: as in score_songs, on the same blocks of whole
+    songs, bar counts and grammar positions; with kernel="gemm" a song's result is bitwise the same whatever the other
+    songs, their order and prefill_rows.  reference: a second model over the same vocabulary (any width or depth):
+    recurrent, in eval(), f32, on the model's device; its prefill runs on the same blocks and one cwlt_policy_stats call
+    per block takes both logits tensors.
+    Refused: what score_songs refuses, and a reference that fails the conditions above."""
+    out = []
+    for blk, Lb, lgs, tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
+                                                             mask, prefill_rows, grammar, reference):
+        bar_attr = 0 if gram is None else gram[3]               # without a grammar only the sign is read
+        st = ops.policy_stats(lgs[0], list(model.n_token), None if reference is None else lgs[1],
+                              bar_class=tgt[:, bar_attr].contiguous(), grammar=gram, **settings, **m)
+        st = st.view(len(blk), Lb, *st.shape[1:]).cpu().numpy()
+        out.extend(st[i, :len(x) - 1].copy() for i, x in enumerate(blk))
     return out
 
 

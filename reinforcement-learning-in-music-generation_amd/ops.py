@@ -1556,11 +1556,12 @@ def decode_gemm(w, bias, x, ln=None, ln2=None, eps=1e-5, res=None, act=None, wan
 
 def _sampler_head(fn, logits, n_class, ids, temperature, top_p, what="tokens"):
     """The checks every sampler / scorer wrapper `fn` starts with -> (logits with a unit column stride, rows, A, the
-    temperature and top_p float arrays (None: off; a None top_p entry is 1)).  ids: the (rows, A) int64 `what`."""
-    if logits.dtype != torch.float32 or ids.dtype != torch.int64:
+    temperature and top_p float arrays (None: off; a None top_p entry is 1)).  ids: the (rows, A) int64 `what` (None: an
+    entry without one)."""
+    if logits.dtype != torch.float32 or (ids is not None and ids.dtype != torch.int64):
         raise TypeError("%s takes f32 logits and int64 %s" % (fn, what))
     rows, A = logits.shape[0], len(n_class)
-    if ids.numel() != rows * A or not ids.is_contiguous():
+    if ids is not None and (ids.numel() != rows * A or not ids.is_contiguous()):
         raise ValueError("%s: %s must be a contiguous (rows, n_attr) int64 buffer" % (fn, what))
     if logits.stride(-1) != 1:
         logits = logits.contiguous()
@@ -1759,6 +1760,57 @@ def score_categorical_grammar(logits, n_class, targets, beat, order, gram, bar_a
     target's bar-beat class, beat (rows,) int64 the position before each row -> (rows, A, 2) f32."""
     return _score("score_categorical_grammar", logits, n_class, targets, temperature, top_p, key, bar, sched, masks,
                   out, (beat, order, gram, bar_attr))
+
+
+def policy_stats(logits, n_class, ref_logits=None, temperature=None, top_p=None, key=None, bar=None, sched=None,
+                 masks=None, bar_class=None, grammar=None, out=None):
+    """Entropy of the model's and of the sampler's distribution per row and attribute, and with ref_logits (a second
+    model's logits for the same rows, its own row stride) their KL against the reference's (cwlt_policy_stats, DESIGN
+    §4.6i): logits (rows, >= sum n_class) f32 -> (rows, A, 2) f32 {H(p), H(q)} or (rows, A, 4) {H(p), H(q), KL(p || p'),
+    KL(q || q')} in nats.  p = softmax(logits); q what score_categorical(_grammar) scores the row under: temperature,
+    top_p, the constraint table (key / bar / sched / masks) and grammar = (beat, order, gram, bar_attr).  bar_class
+    (rows,) int64: the row's own bar-beat class -- negative: padding, left unwritten; it fixes the row's kind under a
+    grammar, which needs it.  KL(q || q') is +inf where q's kept set is not inside q''s; a row with no allowed class has
+    NaN in the q columns.  Rows go through in launches of at most 2^20."""
+    fn = "policy_stats"
+    rows, A = logits.shape[0], len(n_class)
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, None, temperature, top_p)
+    if logits.dim() != 2 or logits.shape[1] < sum(n_class):
+        raise ValueError("%s: logits must be (rows, >= %d)" % (fn, sum(n_class)))
+    if bar_class is None:
+        if grammar is not None:
+            raise ValueError("%s: a grammar needs bar_class, the row's own bar-beat class" % fn)
+    elif bar_class.dtype != torch.int64 or bar_class.numel() != rows or not bar_class.is_contiguous():
+        raise ValueError("%s: bar_class must be a contiguous (rows,) int64 tensor" % fn)
+    C = 2
+    if ref_logits is not None:
+        if ref_logits.dtype != torch.float32 or ref_logits.dim() != 2 or ref_logits.shape[0] != rows or \
+                ref_logits.shape[1] < sum(n_class) or ref_logits.device != logits.device:
+            raise ValueError("%s: ref_logits must be (%d, >= %d) f32 on the logits' device" % (fn, rows, sum(n_class)))
+        if ref_logits.stride(-1) != 1:
+            ref_logits = ref_logits.contiguous()
+        C = 4
+    if key is not None and bar is None:
+        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
+    _mask_table(n_class, rows, bar, sched, masks, key)
+    if grammar is not None:
+        beat, order, gram, bar_attr = grammar
+        _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+    if out is None:
+        out = torch.empty((rows, A, C), dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, C) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous (%d, %d, %d) f32 tensor" % (rows, A, C))
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        sl = lambda t: None if t is None else t[a:z]
+        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
+        gtable = (None, None, 0, None, 0, 0) if grammar is None else \
+            _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
+        _call("cwlt_policy_stats", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
+              logits.stride(0), _lib.opt(sl(ref_logits)), 0 if ref_logits is None else ref_logits.stride(0),
+              _lib.opt(sl(bar_class)), _lib.opt(sl(key)), *table, *gtable, _lib.dev(out[a:z], "out"),
+              _lib.stream_ptr())
+    return out
 
 
 def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):

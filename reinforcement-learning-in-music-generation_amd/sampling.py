@@ -89,6 +89,16 @@ def logprobs_f64(logits, target, temperature=1.0, top_p=None, allowed=None):
     if not ok[target]:
         return lm, -np.inf
     v = x / float(temperature)
+    m, e, keep = _kept_set_f64(v, ok, top_p)
+    if not keep[target]:
+        return lm, -np.inf
+    return lm, (v[target] - m) - np.log(e[keep].sum())
+
+
+def _kept_set_f64(v, ok, top_p):
+    """The support of the sampler's q over tempered logits v with allowed classes ok (at least one) -> (m, e, keep): the
+    allowed max, exp(v - m) on the allowed classes (0 elsewhere), the kept set of logprobs_f64's nucleus rule."""
+    n = len(v)
     m = v[ok].max()
     e = np.where(ok, np.exp(np.where(ok, v, m) - m), 0.0)
     keep = ok.copy()
@@ -97,9 +107,47 @@ def logprobs_f64(logits, target, temperature=1.0, top_p=None, allowed=None):
         ahead = np.empty(n)
         ahead[order] = np.concatenate([[0.0], np.cumsum(e[order])[:-1]])
         keep &= ahead / e.sum() / (1.0 + 1e-5) <= top_p
-    if not keep[target]:
-        return lm, -np.inf
-    return lm, (v[target] - m) - np.log(e[keep].sum())
+    return m, e, keep
+
+
+def all_logprobs_f64(logits, temperature=1.0, top_p=None, allowed=None):
+    """logprobs_f64 for every class at once: logits (n,) -> (model log-probs (n,), sampler log-probs (n,), -inf outside
+    the kept set; None when `allowed` leaves no class)."""
+    x = np.asarray(logits, dtype=np.float64)
+    lm = (x - x.max()) - np.log(np.exp(x - x.max()).sum())
+    ok = np.ones(len(x), dtype=bool) if allowed is None else np.asarray(allowed, dtype=bool)
+    if not ok.any():
+        return lm, None
+    v = x / float(temperature)
+    m, e, keep = _kept_set_f64(v, ok, top_p)
+    return lm, np.where(keep, (v - m) - np.log(e[keep].sum()), -np.inf)
+
+
+def policy_stats_f64(logits, ref_logits=None, temperature=1.0, top_p=None, allowed=None):
+    """Float64 restatement of cwlt_policy_stats for one attribute: logits (n,) -> [H(p), H(q)], with
+    ref_logits (n,) also [.., KL(p || p'), KL(q || q')], in nats.  p = softmax(logits), p' = softmax(ref_logits); q and q'
+    the sampler's distributions of logprobs_f64 on each (temperature, `allowed`, the nucleus kept set, renormalised).
+    Sums run term by term over the kept set, on log-probabilities formed from the logits.  KL(q || q') is +inf when q's
+    kept set is not inside q''s; with no allowed class the q entries are NaN."""
+    def dists(z):
+        return all_logprobs_f64(z, temperature, top_p, allowed)
+
+    def entropy(l):
+        k = np.isfinite(l)
+        return float(-(np.exp(l[k]) * l[k]).sum())
+
+    def kl(l, r):
+        k = np.isfinite(l)
+        if np.isinf(r[k]).any():
+            return np.inf
+        return float((np.exp(l[k]) * (l[k] - r[k])).sum())
+
+    lp, lq = dists(logits)
+    out = [entropy(lp), np.nan if lq is None else entropy(lq)]
+    if ref_logits is not None:
+        rp, rq = dists(ref_logits)
+        out += [kl(lp, rp), np.nan if lq is None else kl(lq, rq)]
+    return np.array(out, dtype=np.float64)
 
 
 def grammar_allowed_f64(bar_class, beat, order, gram, bar_attr, allowed=None):
