@@ -1,4 +1,4 @@
-"""The bf16 GEMM family (csrc/gemm_bf16.hip, gemm_nt.hip, gemm_ln.hip, gemm_small.hip, wgrad.hip, wgrad2.hip) in f64 (TEST
+"""The bf16 GEMM family (csrc/gemm_bf16.hip, gemm_nt.hip, gemm_ln.hip, gemm_small.hip, wgrad.hip) in f64 (TEST
 INFRASTRUCTURE; see oracle/__init__.py): the references, input makers, measures and error bounds of
 tests/test_gemm_f64_gpu.py, pinned by tests/test_oracle_gemm_f64_cpu.py.  Plain torch, any device, none of the project's
 kernels.  Every comparison is PER ELEMENT (per row for the LayerNorm epilogue): a tolerance set by the largest element of a
@@ -38,7 +38,6 @@ hardware is not documented to do worse, and doing better only leaves slack):
         (red0 + red1) + (red2 + red3) through LDS: two tree levels)                              (K / 128) / 6 + 5 + 2, + 1 each
     gemm_nt_mul_kernel, gemm_ln_kernel (BK = 32, two 32x32x16 per step and accumulator)         (K / 16) / 6 + 4
     wgrad_kernel / wgrad_group_kernel (a slice of mslice rows in steps of 32 = two 32x32x16)    (mslice / 16) / 6 + 4
-    wgrad2_kernel (slices rounded up to 64 rows, 16x16x32)                                       (ms2 / 32) / 6 + 5
         wgrad_reduce_kernel: the S partials added serially: + S / 6; accumulate: + 1
         S = cwlt_wgrad_splits(M, N1, N2) and mslice as cwlt_wgrad_bf16 cuts them (restated below: wgrad_splits, wgrad_slices)
     The weight gradients are f32: no bf16 term, |got - ref| <= 4 u sqrt(n) (|A|^T |B| [+ |out0|]).
@@ -102,7 +101,6 @@ LN_M, LN_K, LN_N = (1, 127, 128, 129, 300), (64, 128, 192, 2048), 512
 SMALL_K, SMALL_M, SMALL_N = (32, 96, 128, 256, 384, 512, 768, 1024, 1536), (1, 31, 32, 33, 255, 256, 257), (8, 24, 40, 64, 72)
 SMALL_GELU_K = (128, 256, 512, 1024)
 WG_M, WG_WIDTHS = (1, 31, 33, 255, 257, 2561, 4097), ((8, 8), (256, 256), (264, 8), (248, 520), (512, 256))
-WG2_M, WG2_WIDTHS = (257, 2561, 4097), ((256, 256), (512, 256))
 
 
 def big_cases():
@@ -239,19 +237,16 @@ def wgrad_splits(M, N1, N2):
     return min(s, max(M // 256, 1))
 
 
-def wgrad_slices(M, N1, N2, v2=False):
-    """(S, rows per slice) as cwlt_wgrad_bf16 cuts the token rows; v2: whether the CWLT_WGRAD_V2=1 form takes the launch."""
+def wgrad_slices(M, N1, N2):
+    """(S, rows per slice) as cwlt_wgrad_bf16 cuts the token rows."""
     S = wgrad_splits(M, N1, N2)
     ms = -(-M // S)
-    ms = -(-ms // 32) * 32
-    if v2 and N1 % 256 == 0 and N2 % 256 == 0 and -(-ms // 64) * 64 >= 256:
-        return S, -(-ms // 64) * 64, True
-    return S, ms, False
+    return S, -(-ms // 32) * 32
 
 
-def n_wgrad(M, N1, N2, acc=False, v2=False):
-    S, ms, is_v2 = wgrad_slices(M, N1, N2, v2)
-    return (ms / 32 / 6 + 5 if is_v2 else ms / 16 / 6 + 4) + S / 6 + bool(acc)
+def n_wgrad(M, N1, N2, acc=False):
+    S, ms = wgrad_slices(M, N1, N2)
+    return ms / 16 / 6 + 4 + S / 6 + bool(acc)
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -39,6 +39,7 @@
 // Bound: MFMA for K >= 1024 (2 M N K flop), HBM for K = 512 (M (K + N) 2 bytes [+ M N 2 with accumulate]).
 #include "cwlt_common.h"
 #include "cwlt_gelu.h"
+#include "cwlt_lds_dma.h"
 #include <stdlib.h>
 
 namespace cwlt {
@@ -51,22 +52,8 @@ constexpr int RING = NSLOT * HALF;              // 128 KiB
 constexpr int EXTRA = 32768;                    // bias strip (N <= 8192 floats) / stamps of a trace build
 constexpr int MAXN_BIAS = EXTRA / 4;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-// one 1 KiB piece (8 rows of a slot) issued from inline asm so that the waits can be counted by hand (through the
-// builtin hipcc drains every piece in flight before the next LDS read); M0 carries the LDS address
-#define GB_DMA1(v0, rs, la, so)                                                                        \
-    {                                                                                                  \
-        unsigned keep;                                                                                 \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"                          \
-                     "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t"                                    \
-                     "s_mov_b32 m0, %0"                                                                \
-                     : "=&s"(keep)                                                                     \
-                     : "v"(v0), "s"(rs), "s"(la), "s"(so)                                              \
-                     : "memory", "scc");                                                               \
-    }
-// the two pieces of a half-tile (rows r0 .. r0 + 7 and r0 + 8 .. r0 + 15 of the slot) back to back
+// the two pieces of a half-tile (rows r0 .. r0 + 7 and r0 + 8 .. r0 + 15 of the slot, 1 KiB each) back to back under one
+// M0 save / restore, waits counted by hand (see cwlt_lds_dma.h)
 #define GB_DMA2(v0, v1, rs, la, so)                                                                    \
     {                                                                                                  \
         unsigned keep;                                                                                 \
@@ -89,10 +76,6 @@ typedef __attribute__((address_space(3))) void lds_void;
 //      EPI_MUL:  c = bf16(a w^T) * g (g READ), part (row tiles, N) = column sums of c -- the FFN backward
 //                (cwlt_gemm_nt_mul).  Same arithmetic, rounding points and dropout stream as gemm_nt.hip's 128 x 256 kernel.
 // TRACE: s_memtime stamps of one tile's segments (diagnostic build).
-// ABL (timing experiments only, results are wrong): 1 = no DMA pieces inside the main loop, 2 = no fragment reads inside
-// it, 4 = no barriers inside it, 8 = no counted waits inside it.
-// EP: the next tile's first four half-tiles are requested from inside this tile's LAST K-tile (one per phase) instead of
-// after the main loop.
 enum { EPI_GELU = 4, EPI_MUL = 8 };
 struct FfnArgs {               // EPI_GELU / EPI_MUL only
     bf16_t* G;                 // gd: written (GELU) / read (MUL), dense (M, N) like C
@@ -103,7 +86,7 @@ struct FfnArgs {               // EPI_GELU / EPI_MUL only
     const uint64_t* seed_base;
 };
 
-template <int EPI, bool TRACE, int ABL = 0, bool EP = true>
+template <int EPI, bool TRACE>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                             const float* __restrict__ bias, bf16_t* C, long M, int N,
                                                             int K, long lda, long ldw, long ldc, int nblk,
@@ -179,15 +162,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
         if (lane == 0) lds_trace[w * 1024 + (tq & 1023)] = now_;                           \
         ++tq;                                                                              \
     }
-#define GB_READ_A_(dst, mh, k)                                                             \
+#define GB_READ_A(dst, mh, k)                                                              \
     _Pragma("unroll") for (int mb_ = 0; mb_ < 4; ++mb_)                                    \
         dst[mb_][k] = GB_FRAG(bufo + ((mh) ? 3 : 0) * HALF + a_off[k] + mb_ * 2048);
-#define GB_READ_A(dst, mh, k) if (!(ABL & 2)) { GB_READ_A_(dst, mh, k) }
-#define GB_READ_W_(dst, nh)                                                                \
+#define GB_READ_W(dst, nh)                                                                 \
     _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_)                                       \
         _Pragma("unroll") for (int b_ = 0; b_ < 2; ++b_)                                   \
             dst[b_][k_] = GB_FRAG(bufo + (1 + (nh)) * HALF + w_off[k_] + b_ * 512);
-#define GB_READ_W(dst, nh) if (!(ABL & 2)) { GB_READ_W_(dst, nh) }
 #define GB_MFMA4(WF, mh, nh, b_, k_)                                                       \
     _Pragma("unroll") for (int mb_ = 0; mb_ < 4; ++mb_)                                    \
         acc[2 * (nh) + (b_)][4 * (mh) + mb_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(    \
@@ -200,12 +181,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
 #define GB_PHASE(WF, mh, nh, issue, j, tp, pr, vm, vm0)                                    \
     __builtin_amdgcn_sched_barrier(0);                                                     \
     if (issue) {              /* compile-time true / false, or one wave-uniform branch (the last K-tile) */ \
-        if (!(ABL & 1)) GB_ISSUE(j, tp, pr)                                                \
-        if (!(ABL & 8) && (vm) < 32) GB_WAIT(vm);                                          \
+        GB_ISSUE(j, tp, pr)                                                                \
+        if ((vm) < 32) GB_WAIT(vm);                                                        \
     } else {                                                                               \
-        if (!(ABL & 8) && (vm0) < 32) GB_WAIT(vm0);                                        \
+        if ((vm0) < 32) GB_WAIT(vm0);                                                      \
     }                                                                                      \
-    if (!(ABL & 4)) __builtin_amdgcn_s_barrier();                                          \
+    __builtin_amdgcn_s_barrier();                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                     \
     GB_STAMP()                                                                             \
     __builtin_amdgcn_s_setprio(1);                                                         \
@@ -215,7 +196,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
     GB_MFMA4(WF, mh, nh, 1, 1)                                                             \
     __builtin_amdgcn_s_setprio(0);                                                         \
     __builtin_amdgcn_sched_barrier(0);                                                     \
-    if (!(ABL & 4)) __builtin_amdgcn_s_barrier();                                          \
+    __builtin_amdgcn_s_barrier();                                                          \
     __builtin_amdgcn_sched_barrier(0);                                                     \
     GB_STAMP()
 
@@ -333,14 +314,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         GB_STAMP()
-        if (ABL & 2) {                                      // timing experiment: the fragments are read once per tile
-            GB_READ_A_(AF, 0, 0) GB_READ_A_(AF, 0, 1) GB_READ_W_(WF0, 0) GB_READ_W_(WF1, 1)
-        }
         if (wm) __builtin_amdgcn_s_barrier();               // waves 4-7 run one barrier behind waves 0-3
         __builtin_amdgcn_sched_barrier(0);
 
         // phase P of G = 4 nK issues half-tile P - 1 + D while that is < G; the waits of the last phases shrink with
-        // what is left in flight.  The last K-tile then requests the next tile's half-tiles 0..3 (EP), one per phase:
+        // what is left in flight.  The last K-tile then requests the next tile's half-tiles 0..3, one per phase:
         // the buffer they go to was last read a K-tile ago, and what is still in flight of THIS tile stays counted.
         int t = 0;
         if (nK == 2) {
@@ -351,15 +329,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
             GB_KTILE(t, D, par, true, true, true, false, S, S, S, NONE, NONE, NONE, NONE, 4)
         }
         {
-            const bool early = EP && has_next;
-            if (early) {
+            if (has_next) {
                 GB_TILE(nxt, m0n, n0n)
                 GB_DESC(m0n, n0n)                           // this tile's last piece went out a phase ago
             }
             // ONE body for both cases (two copies of a K-tile behind an if / else made the register allocator spill the
             // accumulators at the join): with a successor its four phases issue that tile's half-tiles 0..3 and wait
             // for what is left of this one (4, 4, -, -); without, they wait (2, 0, 0, 0)
-            GB_KTILE(0, 0, parn, early, early, early, early, 4, 4, NONE, NONE, 2, 0, 0, 0)
+            GB_KTILE(0, 0, parn, has_next, has_next, has_next, has_next, 4, 4, NONE, NONE, 2, 0, 0, 0)
         }
         if (!wm) __builtin_amdgcn_s_barrier();              // every wave has passed the same number of barriers
         __builtin_amdgcn_sched_barrier(0);
@@ -399,15 +376,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
         // ---- the next tile of this workgroup: what is left of its first D half-tiles goes out now, before the stores
         // (every LDS read of this tile is done; its K-tile 1 goes where this tile's last K-tile was)
         if (has_next) {
-            if (EP) {
 #pragma unroll
-                for (int g = 4; g < D; ++g) GB_ISSUE(g & 3, g >> 2, parn)
-            } else {
-                GB_TILE(nxt, m0n, n0n)
-                GB_DESC(m0n, n0n)
-#pragma unroll
-                for (int g = 0; g < D; ++g) GB_ISSUE(g & 3, g >> 2, parn)
-            }
+            for (int g = 4; g < D; ++g) GB_ISSUE(g & 3, g >> 2, parn)
         }
         __builtin_amdgcn_sched_barrier(0);
         GB_STAMP()
@@ -457,8 +427,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
                     // both outputs are streamed past the caches: at the sizes this kernel runs at (>= 32 768 rows: 128 MiB
                     // per output) neither survives in L2 / MALL until its reader, and with the default policy the 128 KiB of
                     // g per tile pushed the A strips and W slices out of L2 between their uses (counter traffic of the
-                    // kernel 6.71 GB per launch against 4.83 algorithmic; variant bit 17 = default policy, for the A/B)
-                    __builtin_amdgcn_raw_buffer_store_b128(r, crs, (int)(c_voff[q] + mb * c_step), 0, (ABL & 16) ? 0 : 2);
+                    // kernel 6.71 GB per launch against 4.83 algorithmic)
+                    __builtin_amdgcn_raw_buffer_store_b128(r, crs, (int)(c_voff[q] + mb * c_step), 0, 2);
                     __builtin_amdgcn_raw_buffer_store_b128(dq, grs, (int)(c_voff[q] + mb * c_step), 0, 2);
                 }
         } else {
@@ -552,8 +522,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(const bf16_t* __restr
 #undef GB_MFMA4
 #undef GB_READ_W
 #undef GB_READ_A
-#undef GB_READ_W_
-#undef GB_READ_A_
 #undef GB_ISSUE
 #undef GB_TILE
 #undef GB_DESC
@@ -599,38 +567,18 @@ static int launch_gemm_big(int epi, const void* a, const void* w, const float* b
     const long ntc = (N + gb::TN - 1) / gb::TN;
     const long ngroup = (grid / 8 + ntc - 1) / ntc > 0 ? (grid / 8 + ntc - 1) / ntc : 1;     // row tiles an XCD holds at a time
     const int stagger = (int)(stag8 * ((K / gb::BK) * 3500L + 14000L) / (8 * ngroup * 64));
-    const int abl = (var >> 4) & 15;
     typedef void (*kfn_t)(const bf16_t*, const bf16_t*, const float*, bf16_t*, long, int, int, long, long, long, int,
                           uint32_t*, int, gb::FfnArgs);
     kfn_t kfn = nullptr;
     uint32_t* tr = (epi == 0) ? g_trace : nullptr;
-    const bool late = var & 1;
     switch (epi) {
-        case 0:
-            kfn = tr ? (late ? gb::gemm_bf16_kernel<0, true, 0, false> : gb::gemm_bf16_kernel<0, true, 0, true>)
-                     : (late ? gb::gemm_bf16_kernel<0, false, 0, false> : gb::gemm_bf16_kernel<0, false, 0, true>);
-            break;
-        case 1: kfn = late ? gb::gemm_bf16_kernel<1, false, 0, false> : gb::gemm_bf16_kernel<1, false, 0, true>; break;
-        case 2: kfn = late ? gb::gemm_bf16_kernel<2, false, 0, false> : gb::gemm_bf16_kernel<2, false, 0, true>; break;
-        case 3: kfn = late ? gb::gemm_bf16_kernel<3, false, 0, false> : gb::gemm_bf16_kernel<3, false, 0, true>; break;
-        case gb::EPI_GELU:
-            kfn = (var & (1 << 17)) ? gb::gemm_bf16_kernel<gb::EPI_GELU, false, 16, true>
-                                    : gb::gemm_bf16_kernel<gb::EPI_GELU, false, 0, true>;
-            break;
-        case gb::EPI_MUL: kfn = gb::gemm_bf16_kernel<gb::EPI_MUL, false, 0, true>; break;
+        case 0: kfn = tr ? gb::gemm_bf16_kernel<0, true> : gb::gemm_bf16_kernel<0, false>; break;
+        case 1: kfn = gb::gemm_bf16_kernel<1, false>; break;
+        case 2: kfn = gb::gemm_bf16_kernel<2, false>; break;
+        case 3: kfn = gb::gemm_bf16_kernel<3, false>; break;
+        case gb::EPI_GELU: kfn = gb::gemm_bf16_kernel<gb::EPI_GELU, false>; break;
+        case gb::EPI_MUL: kfn = gb::gemm_bf16_kernel<gb::EPI_MUL, false>; break;
         default: return CWLT_ERR_ARG;
-    }
-    if (epi == 0 && !tr && abl) {
-        switch (abl) {
-            case 1: kfn = gb::gemm_bf16_kernel<0, false, 1>; break;
-            case 2: kfn = gb::gemm_bf16_kernel<0, false, 2>; break;
-            case 3: kfn = gb::gemm_bf16_kernel<0, false, 3>; break;
-            case 4: kfn = gb::gemm_bf16_kernel<0, false, 4>; break;
-            case 5: kfn = gb::gemm_bf16_kernel<0, false, 5>; break;
-            case 6: kfn = gb::gemm_bf16_kernel<0, false, 6>; break;
-            case 7: kfn = gb::gemm_bf16_kernel<0, false, 7>; break;
-            default: kfn = gb::gemm_bf16_kernel<0, false, 8>; break;
-        }
     }
     hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(512), 0, stream, (const bf16_t*)a, (const bf16_t*)w, bias,
                        (bf16_t*)c, (long)M, N, K, (long)lda, (long)ldw, (long)ldc, (int)nblk, tr, stagger, ffn);
@@ -654,14 +602,13 @@ long gemm_ffn_big_tiles(long M) { return (M + gb::TM - 1) / gb::TM; }
 
 extern "C" {
 
-/* Tuning switch for A/B measurements (tools/bench_gemm.py); variant < 0 restores the default.  Bit 0: the next tile's
- * first operands are requested after the main loop instead of from inside its last K-tile.  Bits 1-3: start stagger of
- * the workgroups, in eighths of a tile period (default: 4 for K <= 1024, else 0).  Bits 4-7 (bias-free,
- * non-accumulating launches only): timing experiments with WRONG results -- 1 no DMA pieces, 2 no fragment reads, 4 no
- * barriers, 8 no counted waits inside the main loop.  Bits 8-15: at most that many x 8 workgroups (0: one per CU).
+/* Tuning numbers for A/B measurements (tools/bench_gemm.py); variant < 0 restores the defaults.  Bits 1-3: start stagger
+ * of the workgroups, in eighths of a tile period (default: 4 for K <= 1024, else 0).  Bits 8-15: at most that many x 8
+ * workgroups (0: one per CU).  A variant >= 0 with any other bit set is CWLT_ERR_ARG and changes nothing.
  * trace != NULL (8192 uint32 of device memory): the next bias-free, non-accumulating launches run the diagnostic build,
  * which leaves the s_memtime stamps of workgroup 0's second tile there (8 waves x 1024). */
 int cwlt_gemm_bf16_tune(int variant, void* trace) {
+    if (variant >= 0 && (variant & ~0xff0e)) return CWLT_ERR_ARG;
     g_variant = variant;
     g_trace = (uint32_t*)trace;
     return CWLT_OK;

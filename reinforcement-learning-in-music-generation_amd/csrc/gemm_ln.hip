@@ -16,6 +16,7 @@
 // row statistics in f32 by DPP reductions, two 1 KiB coalesced stores per row.
 // Bound: HBM.  Algorithmic bytes per launch R x (K + 3 N) x 2 (a, x read; s, y written); the weight (N x K) stays in L2.
 #include "cwlt_common.h"
+#include "cwlt_lds_dma.h"
 #include <stdlib.h>
 
 namespace cwlt {
@@ -27,9 +28,7 @@ constexpr int STG = (TMR + TNC) * BK * 2;       // 40 KiB per stage; the W rows 
 constexpr int LDE = TNC + 8;                    // epilogue tile row stride (bf16): 1040 B
 constexpr int LDS_BYTES = TMR * LDE * 2 > NSTAGE * STG ? TMR * LDE * 2 : NSTAGE * STG;      // 133 120 B
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 __global__ __launch_bounds__(1024) void gemm_ln_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, const float* __restrict__ bias,
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(1024) void gemm_ln_kernel(
     const uint32_t w_16 = (uint32_t)(16 * ldw * 2);
     const uint32_t lds_a = (uint32_t)(uintptr_t)(lds_void*)lds + (w & 7) * 1024;
     const uint32_t lds_w = (uint32_t)(uintptr_t)(lds_void*)lds + TMR * 64 + w * 2048;
-    // issued from inline asm so that the waits can be counted by hand (see wgrad.hip); M0 carries the LDS address
+    // a wave's two w-pieces under one M0 save / restore, waits counted by hand (see cwlt_lds_dma.h)
 #define GL_DMA_W(stage, step)                                                                                     \
     {                                                                                                             \
         unsigned keep;                                                                                            \
@@ -80,18 +79,7 @@ __global__ __launch_bounds__(1024) void gemm_ln_kernel(
                      : "v"(w_voff), "s"(lw), "s"(wrs), "s"(sk_), "s"(sk2)                                         \
                      : "memory", "scc");                                                                          \
     }
-#define GL_DMA_A(stage, step)                                                                                     \
-    {                                                                                                             \
-        unsigned keep;                                                                                            \
-        const uint32_t la = lds_a + (uint32_t)(stage) * STG;                                                      \
-        const uint32_t sk_ = (uint32_t)(step) * (BK * 2);                                                         \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 4\n\t"                                     \
-                     "buffer_load_dwordx4 %1, %3, %4 offen lds\n\t"                                               \
-                     "s_mov_b32 m0, %0"                                                                           \
-                     : "=&s"(keep)                                                                                \
-                     : "v"(a_voff), "s"(la), "s"(ars), "s"(sk_)                                                   \
-                     : "memory", "scc");                                                                          \
-    }
+#define GL_DMA_A(stage, step) lds_dma_piece(a_voff, ars, lds_a + (uint32_t)(stage) * STG, (uint32_t)(step) * (BK * 2))
 #define GL_DMA(stage, step)        \
     {                              \
         if (w < 8) GL_DMA_A(stage, step); \

@@ -20,6 +20,7 @@
 // dealt so that the column tiles of one row tile run on ONE XCD.
 #include "cwlt_common.h"
 #include "cwlt_gelu.h"
+#include "cwlt_lds_dma.h"
 #include <stdlib.h>
 
 namespace cwlt {
@@ -30,9 +31,7 @@ constexpr int NSTAGE = 3;                       // LDS ring: 3 x (128 dy rows + 
 constexpr int STG = (TMR + TNC) * BK * 2;       // bytes of one stage (24 KiB); the W rows start at TMR * 64
 constexpr int LDE = 264;                        // epilogue tile row stride (bf16): 528 B
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 // Epilogue modes of the kernel:
 //   EPI_MUL   c = bf16(a w^T) * g (g read),  part: (row tiles, N) f32 column sums of c (NULL: not wanted)   [FFN backward]
@@ -43,12 +42,12 @@ typedef __attribute__((address_space(3))) void lds_void;
 //             reaching HBM                                                                                  [FFN forward]
 enum { EPI_MUL = 0, EPI_GELU = 1 };
 
-template <int EPI, bool NT_STREAMS, bool ILV = true>
+template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ W, bf16_t* G, bf16_t* __restrict__ Cout,
     float* __restrict__ part, long M, int N, int K, long lda, long ldw, long ldg, long ldc,
     const float* __restrict__ bias, uint32_t thresh, float keep_scale, uint64_t seed,
-    const uint64_t* __restrict__ seed_base, int spread) {
+    const uint64_t* __restrict__ seed_base) {
     // operand ring: NSTAGE x [dy rows | W rows], 64-byte rows (32 k values), unpadded; the epilogue tile
     // [128][264] bf16 = 67 584 B reuses it
     __shared__ __attribute__((aligned(16))) char lds[NSTAGE * STG];
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
     // chip alternates between a phase in which nobody touches HBM (main loops) and one in which everybody stores
     // (epilogues).  A start offset of 0..7 x ~4 us for the first two workgroups of every CU spreads the epilogues over
     // the tile time; later workgroups inherit the spread from the ones they replace.
-    if (spread && blockIdx.x < 2 * 256 && gridDim.x > 2 * 256)
+    if (blockIdx.x < 2 * 256 && gridDim.x > 2 * 256)
         for (int i = (blockIdx.x >> 3) & 7; i > 0; --i) __builtin_amdgcn_s_sleep(127);
     const long mrows = min((long)TMR, M - m0);
 
@@ -97,7 +96,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
     const uint32_t w_voff = ((uint32_t)drow * (uint32_t)ldw + dchunk * 8) * 2;
     const uint32_t w_half = (uint32_t)(128 * ldw * 2);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void*)lds + w * 1024;      // this wave's dy piece inside a stage
-    // issued from inline asm so that the waits can be counted by hand (see wgrad.hip); M0 carries the LDS address
+    // the step's three pieces under one M0 save / restore, waits counted by hand (see cwlt_lds_dma.h)
 #define GN_DMA(stage, step)                                                                                       \
     {                                                                                                             \
         unsigned keep;                                                                                            \
@@ -120,44 +119,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
     // that cannot issue its piece cannot issue the MFMAs behind it either
 #define GN_DMA1(stage, step, which)                                                                               \
     {                                                                                                             \
-        unsigned keep;                                                                                            \
         const uint32_t la = lds0 + (uint32_t)(stage) * STG + ((which) == 0 ? 0u : (which) == 1 ? 0x2000u : 0x4000u); \
         const uint32_t sk_ = (uint32_t)(step) * (BK * 2) + ((which) == 2 ? w_half : 0u);                         \
         if ((which) == 0)                                                                                         \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"                              \
-                         "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"                         \
-                         : "=&s"(keep)                                                                            \
-                         : "v"(a_voff), "s"(ars), "s"(la), "s"(sk_)                                               \
-                         : "memory", "scc");                                                                      \
+            lds_dma_piece(a_voff, ars, la, sk_);                                                                  \
         else                                                                                                      \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"                              \
-                         "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"                         \
-                         : "=&s"(keep)                                                                            \
-                         : "v"(w_voff), "s"(wrs), "s"(la), "s"(sk_)                                               \
-                         : "memory", "scc");                                                                      \
+            lds_dma_piece(w_voff, wrs, la, sk_);                                                                  \
     }
     // fragment byte offsets of this lane inside a row block: row l31, chunk (2 ks + hf) at position ^ ((l31 >> 2) & 3)
     const int swz = (l31 >> 2) & 3;
     const int of0 = l31 * 64 + ((hf ^ swz) << 4), of1 = l31 * 64 + (((2 + hf) ^ swz) << 4);
     const int oa = (64 * wm) * 64, ow = TMR * 64 + (64 * wn) * 64;      // wave tile bases; + 32 rows = + 2048 bytes
 #define GN_FRAG(p) __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(p))
-#define GN_COMPUTE(stage)                                                                     \
-    {                                                                                         \
-        const char* sb = lds + (stage) * STG;                                                 \
-        const bf16x8 w00 = GN_FRAG(sb + ow + of0), w01 = GN_FRAG(sb + ow + 2048 + of0);       \
-        const bf16x8 x00 = GN_FRAG(sb + oa + of0), x01 = GN_FRAG(sb + oa + 2048 + of0);       \
-        const bf16x8 w10 = GN_FRAG(sb + ow + of1), w11 = GN_FRAG(sb + ow + 2048 + of1);       \
-        const bf16x8 x10 = GN_FRAG(sb + oa + of1), x11 = GN_FRAG(sb + oa + 2048 + of1);       \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w00, x00, acc[0][0], 0, 0, 0);    \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w01, x00, acc[0][1], 0, 0, 0);    \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w00, x01, acc[1][0], 0, 0, 0);    \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w01, x01, acc[1][1], 0, 0, 0);    \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w10, x10, acc[0][0], 0, 0, 0);    \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w11, x10, acc[0][1], 0, 0, 0);    \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w10, x11, acc[1][0], 0, 0, 0);    \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w11, x11, acc[1][1], 0, 0, 0);    \
-    }
-
     // a step with the next-but-one step's three pieces issued between its MFMA groups (more = false: no pieces)
 #define GN_COMPUTE_DMA(stage, nstage, nstepi, more)                                           \
     {                                                                                         \
@@ -214,19 +187,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         const int st = s % NSTAGE;
-        if (ILV) {
-            GN_COMPUTE_DMA(st, (s + 2) % NSTAGE, s + 2, s + 2 < nstep);
-        } else {
-            if (s + 2 < nstep) GN_DMA((s + 2) % NSTAGE, s + 2);
-            GN_COMPUTE(st);
-        }
+        GN_COMPUTE_DMA(st, (s + 2) % NSTAGE, s + 2, s + 2 < nstep);
     }
     __syncthreads();                                  // every wave is done with the ring: the epilogue tile reuses it
 #undef GN_DMA
 #undef GN_DMA1
 #undef GN_COMPUTE_DMA
 #undef GN_FRAG
-#undef GN_COMPUTE
 
     // epilogue.  This thread's 8 chunks of the tile: rows (tid >> 5) + 16 i, columns 8 (tid & 31) .. + 7.
     const int erow = tid >> 5, ecol = (tid & 31) * 8;
@@ -238,9 +205,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             // once-read stream: non-temporal (aux = 2) so that it does not evict the operand strips the co-resident
-            // workgroup's main loop re-reads from L2 (CWLT_GEMM_NT=0 builds use the default policy for A/B comparison)
+            // workgroup's main loop re-reads from L2
             const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(
-                gr, (int)(((uint32_t)(erow + 16 * i) * (uint32_t)ldg + ecol) * 2), 0, NT_STREAMS ? 2 : 0);
+                gr, (int)(((uint32_t)(erow + 16 * i) * (uint32_t)ldg + ecol) * 2), 0, 2);
             gv[i] = make_uint4(v[0], v[1], v[2], v[3]);
         }
     }
@@ -372,11 +339,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
                 }
                 // g is the next GEMM's operand: default policy; gd waits for the backward: streamed past the caches
                 *reinterpret_cast<u32x4_t*>(pc) = r;
-                u32x4_t* dst = reinterpret_cast<u32x4_t*>(pg);
-                if (NT_STREAMS)
-                    __builtin_nontemporal_store(q, dst);
-                else
-                    *dst = q;
+                __builtin_nontemporal_store(q, reinterpret_cast<u32x4_t*>(pg));
             }
         }
         return;
@@ -410,11 +373,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
             r[1] = f32x2_to_bf16x2(t[2], t[3]);
             r[2] = f32x2_to_bf16x2(t[4], t[5]);
             r[3] = f32x2_to_bf16x2(t[6], t[7]);
-            u32x4_t* dst = reinterpret_cast<u32x4_t*>(pc);
-            if (NT_STREAMS)
-                __builtin_nontemporal_store(r, dst);
-            else
-                *dst = r;
+            __builtin_nontemporal_store(r, reinterpret_cast<u32x4_t*>(pc));
         }
     }
     if (part) {
@@ -437,10 +396,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_mul_kernel(
 }  // namespace gn
 }  // namespace cwlt
 
-static int interleave_dma() {   // CWLT_GEMM_NT_ILV=0: all of a step's pieces issued behind the barrier (A/B switch)
-    static const int v = [] { const char* e = getenv("CWLT_GEMM_NT_ILV"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
-}
 // CWLT_FFN_BIG=0: always the 128 x 256 two-workgroups-per-CU kernel below (A/B switch).  Default: from 32 768 rows on the
 // FFN forms run on gemm_bf16.hip's 256 x 256 persistent kernel (one workgroup per CU needs many row tiles to fill the chip).
 // (CWLT_FFN_BIG=f / b: only the forward / only the backward form.)
@@ -451,10 +406,6 @@ static bool ffn_big(int64_t M, int N, int K, bool fwd = true) {
     }();
     static const long min_rows = [] { const char* e = getenv("CWLT_FFN_BIG_MIN_ROWS"); return e ? atol(e) : 32768L; }();
     return (v & (fwd ? 1 : 2)) && M >= min_rows && K >= 128 && N <= 8192;
-}
-static int spread_starts() {   // CWLT_GEMM_NT_SPREAD=0: all workgroups start at once (A/B switch)
-    static const int v = [] { const char* e = getenv("CWLT_GEMM_NT_SPREAD"); return (e && e[0] == '0') ? 0 : 1; }();
-    return v;
 }
 
 extern "C" {
@@ -489,13 +440,9 @@ int cwlt_gemm_nt_mul(const void* a, const void* w, const void* g, void* c, float
     const long mtiles = (M + gn::TMR - 1) / gn::TMR;
     const long mt8 = (mtiles + 7) / 8 * 8;            // row tiles are dealt to the 8 XCDs: pad to a multiple of 8
     const long nblk = mt8 * (N / gn::TNC);
-    static const bool nts = [] { const char* e = getenv("CWLT_GEMM_NT"); return !(e && e[0] == '0'); }();   // A/B switch
-    auto kfn = !interleave_dma() ? gn::gemm_nt_mul_kernel<gn::EPI_MUL, true, false>
-               : nts             ? gn::gemm_nt_mul_kernel<gn::EPI_MUL, true, true>
-                                 : gn::gemm_nt_mul_kernel<gn::EPI_MUL, false, true>;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)nblk), dim3(512), 0, st, (const bf16_t*)a, (const bf16_t*)w,
+    hipLaunchKernelGGL(gn::gemm_nt_mul_kernel<gn::EPI_MUL>, dim3((unsigned)nblk), dim3(512), 0, st, (const bf16_t*)a, (const bf16_t*)w,
                        const_cast<bf16_t*>((const bf16_t*)g), (bf16_t*)c, part, (long)M, N, K, (long)lda, (long)ldw,
-                       (long)ldg, (long)ldc, (const float*)nullptr, 0u, 1.0f, (uint64_t)0, (const uint64_t*)nullptr, spread_starts());
+                       (long)ldg, (long)ldc, (const float*)nullptr, 0u, 1.0f, (uint64_t)0, (const uint64_t*)nullptr);
     int e = (int)hipGetLastError();
     if (e || !colsum) return e;
     return launch_colsum_finalize(part, colsum, (int)mtiles, (long)N, N, 1.0f, 0, st);
@@ -524,13 +471,9 @@ int cwlt_gemm_nt_bias_gelu_dropout(const void* a, const void* w, const float* bi
     const long mtiles = (M + gn::TMR - 1) / gn::TMR;
     const long mt8 = (mtiles + 7) / 8 * 8;
     const long nblk = mt8 * (N / gn::TNC);
-    static const bool nts = [] { const char* e = getenv("CWLT_GEMM_NT"); return !(e && e[0] == '0'); }();
-    auto kfn = !interleave_dma() ? gn::gemm_nt_mul_kernel<gn::EPI_GELU, true, false>
-               : nts             ? gn::gemm_nt_mul_kernel<gn::EPI_GELU, true, true>
-                                 : gn::gemm_nt_mul_kernel<gn::EPI_GELU, false, true>;
-    hipLaunchKernelGGL(kfn, dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)w,
+    hipLaunchKernelGGL(gn::gemm_nt_mul_kernel<gn::EPI_GELU>, dim3((unsigned)nblk), dim3(512), 0, (hipStream_t)stream, (const bf16_t*)a, (const bf16_t*)w,
                        (bf16_t*)gd, (bf16_t*)g, (float*)nullptr, (long)M, N, K, (long)lda, (long)ldw, (long)N, (long)N,
-                       bias, drop_thresh(p), drop_scale(p), seed, seed_base, spread_starts());
+                       bias, drop_thresh(p), drop_scale(p), seed, seed_base);
     return (int)hipGetLastError();
 }
 

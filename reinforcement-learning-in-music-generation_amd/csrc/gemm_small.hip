@@ -22,11 +22,11 @@
 
 #include "cwlt_common.h"
 #include "cwlt_gelu.h"
+#include "cwlt_lds_dma.h"
 
 namespace cwlt {
 namespace gs {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int TM = 64, TN = 64, PD = 8;
 
 template <bool BIAS, bool ACCUM>

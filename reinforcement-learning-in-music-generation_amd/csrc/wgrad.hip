@@ -14,6 +14,7 @@
 //     an f32 partial tile and a fixed-order reduce kernel sums them straight into the f32 gradient
 //     buffer (deterministic, no atomics, no bf16 rounding of the gradient).
 #include "cwlt_common.h"
+#include "cwlt_lds_dma.h"
 #include <stdlib.h>
 
 namespace cwlt {
@@ -24,10 +25,8 @@ constexpr int NSTAGE = 4;                 // LDS ring: 4 x (32 x 256 A rows + 32
 constexpr int ROW = 256;                  // LDS row = 256 bf16 = 512 B, unpadded (LDS-DMA writes 1 KiB = two whole rows)
 constexpr int OPB = BK * ROW * 2;         // bytes of one operand stage (16 KiB)
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ constexpr int acc_row(int r, int hf) { return (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
@@ -54,7 +53,7 @@ __device__ __forceinline__ bf16x8 tfrag_at(const char* base) {
 
 // The kernel proper, as a function of the workgroup's index `id` among the ntile * S workgroups of ONE product: the plain
 // kernel passes blockIdx.x, the grouped kernel (several products in one launch) the index inside the product it belongs to.
-template <bool EDGE, bool ILV>
+template <bool EDGE>
 __device__ __forceinline__ void wgrad_body(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                            float* __restrict__ part, long M, int N1, int N2, long lda, long ldb,
                                            long mslice, const int id, const int S) {
@@ -110,10 +109,8 @@ __device__ __forceinline__ void wgrad_body(const bf16_t* __restrict__ A, const b
     const uint32_t a_voff = ((uint32_t)drow * (uint32_t)lda + dchunk * 8) * 2;
     const uint32_t b_voff = ((uint32_t)drow * (uint32_t)ldb + dchunk * 8) * 2;
     const uint32_t a_step = (uint32_t)(BK * lda * 2), b_step = (uint32_t)(BK * ldb * 2);   // bytes per 32-row step
-    // The two pieces are issued from inline asm: through the builtin, hipcc (ROCm 7.2) cannot tell which LDS bytes a
-    // DMA writes and drains ALL of them (s_waitcnt vmcnt(0)) before the first fragment read of every step, which
-    // serialises the ring.  Here the waits are counted by hand (vmcnt(4) below).  M0 carries the LDS address and
-    // is compiler-reserved: saved and restored inside the statement; s_nop: SGPR write -> M0 / VMEM-read hazards.
+    // The step's two pieces under one M0 save / restore, from inline asm so that the waits can be counted by hand
+    // (vmcnt(4) below; see cwlt_lds_dma.h).
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void*)lds + w * 1024;      // this wave's piece inside a stage
 #define WG_DMA(stage, step)                                                                                       \
     {                                                                                                             \
@@ -129,47 +126,20 @@ __device__ __forceinline__ void wgrad_body(const bf16_t* __restrict__ A, const b
                      : "v"(a_voff), "s"(ars), "s"(la), "s"(sa), "v"(b_voff), "s"(brs), "s"(sb_)                   \
                      : "memory", "scc");                                                                          \
     }
-    // one piece at a time (which = 0: A, 1: B), for issue between the step's MFMAs (see gemm_nt.hip, GN_COMPUTE_DMA)
+    // one piece at a time (which = 0: A, 1: B), for issue between the step's MFMAs
 #define WG_DMA1(stage, step, which)                                                                               \
     {                                                                                                             \
-        unsigned keep;                                                                                            \
         const uint32_t la = lds0 + (uint32_t)(stage) * (2 * OPB) + ((which) ? 0x4000u : 0u);                      \
         if (which)                                                                                                \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"                              \
-                         "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"                         \
-                         : "=&s"(keep)                                                                            \
-                         : "v"(b_voff), "s"(brs), "s"(la), "s"((uint32_t)(step) * b_step)                         \
-                         : "memory", "scc");                                                                      \
+            lds_dma_piece(b_voff, brs, la, (uint32_t)(step) * b_step);                                            \
         else                                                                                                      \
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\t"                              \
-                         "buffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"                         \
-                         : "=&s"(keep)                                                                            \
-                         : "v"(a_voff), "s"(ars), "s"(la), "s"((uint32_t)(step) * a_step)                         \
-                         : "memory", "scc");                                                                      \
+            lds_dma_piece(a_voff, ars, la, (uint32_t)(step) * a_step);                                            \
     }
     // fragment read offsets of this lane inside a stage (k0 = 0; the second k-step adds 16 rows)
     const int oa0 = tfrag_off(64 * wn1, lane), oa1 = tfrag_off(64 * wn1 + 32, lane);
     const int ob0 = OPB + tfrag_off(64 * wn2, lane), ob1 = OPB + tfrag_off(64 * wn2 + 32, lane);
     // all 16 fragment reads of the step are issued first (both k-steps, distinct registers), so the second k-step's
     // LDS latency hides behind the first one's MFMAs instead of being waited for after them
-#define WG_COMPUTE(stage)                                                                  \
-    {                                                                                      \
-        const char* sb = lds + (stage) * (2 * OPB);                                        \
-        constexpr int ko = 16 * ROW * 2;                                                   \
-        const bf16x8 a0 = tfrag_at(sb + oa0), b0 = tfrag_at(sb + ob0);                     \
-        const bf16x8 a1 = tfrag_at(sb + oa1), b1 = tfrag_at(sb + ob1);                     \
-        const bf16x8 c0_ = tfrag_at(sb + oa0 + ko), d0_ = tfrag_at(sb + ob0 + ko);         \
-        const bf16x8 c1_ = tfrag_at(sb + oa1 + ko), d1_ = tfrag_at(sb + ob1 + ko);         \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);   \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);   \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);   \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);   \
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0_, d0_, acc[0][0], 0, 0, 0); \
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0_, d1_, acc[0][1], 0, 0, 0); \
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1_, d0_, acc[1][0], 0, 0, 0); \
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1_, d1_, acc[1][1], 0, 0, 0); \
-    }
-
 #define WG_COMPUTE_DMA(stage, nstage, nstepi)                                              \
     {                                                                                      \
         const char* sb = lds + (stage) * (2 * OPB);                                        \
@@ -216,18 +186,12 @@ __device__ __forceinline__ void wgrad_body(const bf16_t* __restrict__ A, const b
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (ILV) {
-            WG_COMPUTE_DMA(s & 3, (s + 3) & 3, s + 3);
-        } else {
-            WG_DMA((s + 3) & 3, s + 3);
-            WG_COMPUTE(s & 3);
-        }
+        WG_COMPUTE_DMA(s & 3, (s + 3) & 3, s + 3);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // pieces still in flight target LDS: drain before exit
 #undef WG_DMA
 #undef WG_DMA1
 #undef WG_COMPUTE_DMA
-#undef WG_COMPUTE
     const int r0 = t1 * TM + 64 * wn1, c0 = t2 * TN + 64 * wn2 + l31;
     float* pb = part + ((long)slice * N1 + r0) * N2 + c0;
     if (!EDGE || (r0 + 64 <= N1 && t2 * TN + 64 * wn2 + 64 <= N2)) {          // interior wave tile: unguarded stores
@@ -249,13 +213,13 @@ __device__ __forceinline__ void wgrad_body(const bf16_t* __restrict__ A, const b
     }
 }
 
-template <bool EDGE, bool ILV = true>
+template <bool EDGE>
 __global__ __launch_bounds__(1024) void wgrad_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B,
                                                       float* __restrict__ part, long M, int N1, int N2, long lda,
                                                       long ldb, long mslice) {
     const int ntile = ((N1 + TM - 1) / TM) * ((N2 + TN - 1) / TN);
-    wgrad_body<EDGE, ILV>(A, B, part, M, N1, N2, lda, ldb, mslice, (int)blockIdx.x,
-                          (int)(gridDim.x / ntile));       // the launcher's grid is exactly ntile * S workgroups
+    wgrad_body<EDGE>(A, B, part, M, N1, N2, lda, ldb, mslice, (int)blockIdx.x,
+                     (int)(gridDim.x / ntile));       // the launcher's grid is exactly ntile * S workgroups
 }
 
 // Up to four products over the SAME token rows in one launch (the four weight gradients of an encoder layer at few token
@@ -272,14 +236,13 @@ struct WgGroup {
     long rstart[5];             // float4 ranges of the reduce launch
     int count;
 };
-template <bool ILV>
 __global__ __launch_bounds__(1024) void wgrad_group_kernel(const WgGroup g, long M) {
     int p = 0;
 #pragma unroll
     for (int i = 1; i < 4; ++i)
         if (i < g.count && (int)blockIdx.x >= g.start[i]) p = i;
-    wgrad_body<false, ILV>(g.a[p], g.b[p], g.part[p], M, g.n1[p], g.n2[p], g.lda[p], g.ldb[p], g.mslice[p],
-                           (int)blockIdx.x - g.start[p], g.S[p]);
+    wgrad_body<false>(g.a[p], g.b[p], g.part[p], M, g.n1[p], g.n2[p], g.lda[p], g.ldb[p], g.mslice[p],
+                      (int)blockIdx.x - g.start[p], g.S[p]);
 }
 // the reduce of every product of a group: thread t of the launch owns float4 t - rstart[p] of product p
 __global__ __launch_bounds__(256) void wgrad_reduce_group_kernel(const WgGroup g, int accumulate) {
@@ -355,22 +318,6 @@ int cwlt_wgrad_bf16(const void* a, const void* b, float* part, float* out, int64
     long mslice = (M + S - 1) / S;
     mslice = (mslice + wg::BK - 1) / wg::BK * wg::BK;                   // whole 32-row steps
     hipStream_t st = (hipStream_t)stream;
-    // CWLT_WGRAD_V2=1 (both widths multiples of 256, slices of at least 4 K-tiles): the 8-wave form on gemm_bf16.hip's main
-    // loop (wgrad2.hip).  Measured equal to this file's 16-wave kernel -- 945-958 / 918-924 / 284-287 / 807-811 us against
-    // 970-985 / 919-922 / 288-292 / 803-806 on the four layer shapes at R = 524 288 (profiles/r04_wgrad2.txt): both run at
-    // the 1.15-1.2 PFLOP/s the chip holds under this load (1.68 GHz), so it stays a switch.
-    static const bool v2 = [] { const char* e = getenv("CWLT_WGRAD_V2"); return e && e[0] == '1'; }();
-    if (v2 && !(N1 & 255) && !(N2 & 255)) {
-        const long ms2 = (mslice + 63) / 64 * 64;
-        if (ms2 >= 256 && (int64_t)ms2 * (lda > ldb ? lda : ldb) * 2 < (1ll << 31)) {
-            int e = launch_wgrad2(a, b, part, (long)M, N1, N2, (long)lda, (long)ldb, ms2, S, st);
-            if (e) return e;
-            const long n = (long)N1 * N2;
-            hipLaunchKernelGGL(wg::wgrad_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, part, out,
-                               S, n, accumulate);
-            return (int)hipGetLastError();
-        }
-    }
     const bool edge = (N1 & 255) || (N2 & 255);
     constexpr int lds_bytes = wg::NSTAGE * 2 * wg::OPB;                 // 128 KiB: above the 64 KiB default limit
     // the opt-in is per device: remember which devices have it (a process may launch on several)
@@ -378,21 +325,15 @@ int cwlt_wgrad_bf16(const void* a, const void* b, float* part, float* out, int64
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     if (dev >= 64 || !((lds_set >> dev) & 1ull)) {
-        // all four instantiations (ILV defaults to true: <true> is <true, true>) -- CWLT_WGRAD_ILV=0 launches the other two
-        const void* kfns[4] = {(const void*)wg::wgrad_kernel<true, true>, (const void*)wg::wgrad_kernel<false, true>,
-                               (const void*)wg::wgrad_kernel<true, false>, (const void*)wg::wgrad_kernel<false, false>};
-        int e = 0;
-        for (int i = 0; i < 4 && !e; ++i)
-            e = (int)hipFuncSetAttribute(kfns[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        int e = (int)hipFuncSetAttribute((const void*)wg::wgrad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         lds_bytes);
+        if (!e)
+            e = (int)hipFuncSetAttribute((const void*)wg::wgrad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         lds_bytes);
         if (e) return e;
         if (dev < 64) lds_set |= 1ull << dev;
     }
-    // the step's two pieces issued between its MFMAs instead of both behind the barrier (gemm_nt.hip, GN_COMPUTE_DMA):
-    // 1 009 / 956 / 291 / 847 -> 981 / 952 / 284 / 822 us on the four layer shapes, same box; CWLT_WGRAD_ILV=0: block issue
-    static const bool ilv = [] { const char* e = getenv("CWLT_WGRAD_ILV"); return !(e && e[0] == '0'); }();
-    auto kfn = ilv ? (edge ? wg::wgrad_kernel<true, true> : wg::wgrad_kernel<false, true>)
-                   : (edge ? wg::wgrad_kernel<true, false> : wg::wgrad_kernel<false, false>);
-    hipLaunchKernelGGL(kfn,
+    hipLaunchKernelGGL(edge ? wg::wgrad_kernel<true> : wg::wgrad_kernel<false>,
                        dim3(((N1 + 255) / 256) * ((N2 + 255) / 256) * S), dim3(1024), lds_bytes, st, (const bf16_t*)a,
                        (const bf16_t*)b, part, (long)M, N1, N2, (long)lda, (long)ldb, mslice);
     int e = (int)hipGetLastError();
@@ -447,18 +388,13 @@ int cwlt_wgrad_bf16_group(const void* const* a, const void* const* b, float* con
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
     if (dev >= 64 || !((lds_set >> dev) & 1ull)) {
-        int e = (int)hipFuncSetAttribute((const void*)wg::wgrad_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        int e = (int)hipFuncSetAttribute((const void*)wg::wgrad_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                          lds_bytes);
-        if (!e)
-            e = (int)hipFuncSetAttribute((const void*)wg::wgrad_group_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
         if (e) return e;
         if (dev < 64) lds_set |= 1ull << dev;
     }
-    static const bool ilv = [] { const char* e = getenv("CWLT_WGRAD_ILV"); return !(e && e[0] == '0'); }();
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ilv ? wg::wgrad_group_kernel<true> : wg::wgrad_group_kernel<false>, dim3((unsigned)g.start[count]),
-                       dim3(1024), lds_bytes, st, g, (long)M);
+    hipLaunchKernelGGL(wg::wgrad_group_kernel, dim3((unsigned)g.start[count]), dim3(1024), lds_bytes, st, g, (long)M);
     int e = (int)hipGetLastError();
     if (e) return e;
     hipLaunchKernelGGL(wg::wgrad_reduce_group_kernel, dim3((unsigned)(g.rstart[count] / 256)), dim3(256), 0, st, g, accumulate);

@@ -102,6 +102,11 @@ def test_argument_validation_without_gpu(built):
     assert lib.cwlt_decode_workspace_floats(ctypes.byref(m)) == -1
     assert lib.cwlt_decode_step(ctypes.byref(m), buf, buf, null, buf, 1, null) == 1001
     assert lib.cwlt_decode_gemv(buf, null, buf, null, null, null, null, 1e-5, null, buf, null, 8, 6, 0, 1, 6, 8, 8, 6, null) == 1001
+    # GEMM tuning numbers (host state only): stagger (bits 1-3) and grid cap (bits 8-15) are taken, any other bit is refused
+    assert lib.cwlt_gemm_bf16_tune(1, None) == 1001 and lib.cwlt_gemm_bf16_tune(1 << 4, None) == 1001
+    assert lib.cwlt_gemm_bf16_tune(1 << 17, None) == 1001
+    assert lib.cwlt_gemm_bf16_tune(1 << 8, None) == 0 and lib.cwlt_gemm_bf16_tune(2 << 1, None) == 0
+    assert lib.cwlt_gemm_bf16_tune(-1, None) == 0
 
 
 def test_product_has_no_cpu_fallback(built):

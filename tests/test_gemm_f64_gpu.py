@@ -1,7 +1,7 @@
 """GPU: the bf16 GEMM family -- cwlt_gemm_bf16 (256 x 256 persistent tiles), the FFN epilogues cwlt_gemm_nt_mul /
 cwlt_gemm_nt_bias_gelu_dropout on the 128 x 256 and on the 256 x 256 kernel, the LayerNorm epilogue
 (cwlt_gemm_nt_bias_dropout_add_layernorm), cwlt_gemm_bf16_small / _small_gelu and the weight gradients cwlt_wgrad_bf16 /
-_group / wgrad2 -- PER ELEMENT against the f64 result of the same bf16 operands, under the bounds derived in
+_group -- PER ELEMENT against the f64 result of the same bf16 operands, under the bounds derived in
 oracle/gemm_f64.py (pinned by tests/test_oracle_gemm_f64_cpu.py), at the smallest shapes that reach each tile edge and each
 dispatch branch of the launchers.  The instantiations behind switches that are read once per process run in child
 processes, one per set of switches.  Every figure is the worst |error| / bound of its case (<= 1 passes); run with -s for
@@ -119,7 +119,7 @@ def test_gemm_bf16_accumulates_into_a_column_block(cuda, bias):
     assert torch.all(big_c[:, :N] == 3.0) and torch.all(big_c[:, 2 * N:] == 3.0)
 
 
-@pytest.mark.parametrize("variant", [1 << 8, (1 << 8) | 1])
+@pytest.mark.parametrize("variant", [1 << 8])
 @pytest.mark.parametrize("K", [128, 192])
 def test_gemm_bf16_several_tiles_per_workgroup(cuda, variant, K):
     """8 workgroups: 9 row tiles padded to 16, three column tiles with the last one partial, six tiles per workgroup with
@@ -307,7 +307,7 @@ def test_layernorm_epilogue_per_row(cuda, K):
 # ----------------------------------------------------------------------------------------------------------------------
 # weight gradients
 # ----------------------------------------------------------------------------------------------------------------------
-def run_wgrad(dev, M, N1, N2, strided, v2=False):
+def run_wgrad(dev, M, N1, N2, strided):
     a, b = o.make_wgrad(M, N1, N2, M + N1 + N2, strided)
     if strided:
         wa = torch.empty(M, N1 + 24, dtype=torch.bfloat16, device=dev).copy_(a._base)
@@ -318,12 +318,12 @@ def run_wgrad(dev, M, N1, N2, strided, v2=False):
     got = ops.wgrad(ad, bd)
     assert torch.equal(got, ops.wgrad(ad, bd))                         # fixed summation order
     ref, S = o.wgrad_reference(a, b)
-    res = {"plain": o.worst(o.f32_ratios(got, ref, S, o.n_wgrad(M, N1, N2, False, v2)))}
+    res = {"plain": o.worst(o.f32_ratios(got, ref, S, o.n_wgrad(M, N1, N2, False)))}
     out0 = torch.randn(N1, N2, generator=torch.Generator().manual_seed(M))
     acc = out0.to(dev)
     ops.wgrad(ad, bd, out=acc, accumulate=True)
     ref, S = o.wgrad_reference(a, b, out0)
-    res["acc"] = o.worst(o.f32_ratios(acc, ref, S, o.n_wgrad(M, N1, N2, True, v2)))
+    res["acc"] = o.worst(o.f32_ratios(acc, ref, S, o.n_wgrad(M, N1, N2, True)))
     return res
 
 
@@ -366,37 +366,17 @@ def test_wgrad_group_with_an_empty_slice(cuda, M):
 # ----------------------------------------------------------------------------------------------------------------------
 def child_ffn_big(dev):
     """CWLT_FFN_BIG_MIN_ROWS=1: the FFN forms on the 256 x 256 persistent kernel (ragged last row tile, column-sum partials
-    of that tile), then several tiles per workgroup (the sums' LDS strip reused between a workgroup's tiles), and the GELU
-    form's second instantiation (variant bit 17)."""
+    of that tile), then several tiles per workgroup (the sums' LDS strip reused between a workgroup's tiles)."""
     run_ffn_cases(dev, o.FFN_BIG_M, o.FFN_BIG_K, True, "gemm_bf16 256x256 ffn")
     _lib.load().cwlt_gemm_bf16_tune(1 << 8, None)
     try:
         run_ffn_cases(dev, (2049,), o.FFN_BIG_K, True, "gemm_bf16 256x256 ffn, 8 workgroups")
-        _lib.load().cwlt_gemm_bf16_tune(1 << 17, None)          # the GELU form's instantiation with the default store policy
-        note("gemm_bf16 256x256 ffn gelu, variant bit 17  257 x 256 x 192", run_gelu(dev, 257, 256, 192, 0.1, big=True))
     finally:
         _lib.load().cwlt_gemm_bf16_tune(-1, None)
 
 
-def child_block_issue(dev):
-    """CWLT_GEMM_NT_ILV=0 CWLT_WGRAD_ILV=0 CWLT_GEMM_SMALL_SPLITK=0: gemm_nt_mul_kernel<.., true, false>, wgrad_kernel<.., false>,
-    wgrad_group_kernel<false>, whole-K gemm_small at K % 128 == 0."""
-    run_ffn_cases(dev, (129, 1025), o.NT_K, False, "gemm_nt block issue")
-    for M in (33, 2561, 4097):
-        res = {}
-        for N1, N2 in o.WG_WIDTHS:
-            merge(res, run_wgrad(dev, M, N1, N2, M == 2561))
-        note("wgrad block issue M = %4d" % M, res)
-    g = torch.Generator().manual_seed(1)
-    pairs = [(torch.randn(2561, n1, generator=g).bfloat16(), torch.randn(2561, n2, generator=g).bfloat16())
-             for n1, n2 in ((256, 256), (512, 256))]
-    dp = [(a.to(dev), b.to(dev)) for a, b in pairs]
-    res = {}
-    for (a, b), y, x in zip(pairs, ops.wgrad_group(dp), [ops.wgrad(a, b) for a, b in dp]):
-        assert torch.equal(x, y)
-        ref, S = o.wgrad_reference(a, b)
-        merge(res, {"group": o.worst(o.f32_ratios(y, ref, S, o.n_wgrad(2561, a.shape[1], b.shape[1])))})
-    note("wgrad_group block issue M = 2561", res)
+def child_whole_k_small(dev):
+    """CWLT_GEMM_SMALL_SPLITK=0: whole-K gemm_small at K % 128 == 0."""
     for K in (128, 256, 512, 1536):
         res = {}
         for M, N in ((1, 8), (33, 72), (257, 40)):
@@ -405,22 +385,9 @@ def child_block_issue(dev):
         note("gemm_small whole K = %4d" % K, res)
 
 
-def child_default_policy_wgrad2(dev):
-    """CWLT_GEMM_NT=0 CWLT_GEMM_NT_SPREAD=0 CWLT_WGRAD_V2=1: gemm_nt_mul_kernel<.., false, true>, wgrad2 (both widths
-    multiples of 256, slices of at least 256 rows) with empty slices, plain and accumulate, dense and column slices."""
-    run_ffn_cases(dev, (129, 1025), o.NT_K, False, "gemm_nt default cache policy")
-    for M in o.WG2_M:
-        for strided in (False, True):
-            res = {}
-            for N1, N2 in o.WG2_WIDTHS:
-                merge(res, run_wgrad(dev, M, N1, N2, strided, v2=True))
-            note("wgrad2 M = %4d%s" % (M, ", column slices" if strided else ""), res)
-
-
 CHILDREN = {
     "child_ffn_big": {"CWLT_FFN_BIG_MIN_ROWS": "1"},
-    "child_block_issue": {"CWLT_GEMM_NT_ILV": "0", "CWLT_WGRAD_ILV": "0", "CWLT_GEMM_SMALL_SPLITK": "0"},
-    "child_default_policy_wgrad2": {"CWLT_GEMM_NT": "0", "CWLT_GEMM_NT_SPREAD": "0", "CWLT_WGRAD_V2": "1"},
+    "child_whole_k_small": {"CWLT_GEMM_SMALL_SPLITK": "0"},
 }
 
 

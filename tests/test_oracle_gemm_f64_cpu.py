@@ -65,8 +65,6 @@ def test_makers_and_slice_arithmetic():
     assert o.wgrad_slices(2561, 256, 256)[:2] == (10, 288) and o.wgrad_slices(4097, 256, 256)[:2] == (16, 288)
     assert 9 * 288 >= 2561 and 15 * 288 >= 4097                  # slice 9 / slice 15 start past the last row
     assert o.wgrad_slices(31, 8, 8)[:2] == (1, 32)
-    assert o.wgrad_slices(4097, 512, 256, v2=True) == (16, 320, True) and o.wgrad_slices(257, 256, 256, v2=True) == (1, 320, True)
-    assert o.wgrad_slices(2561, 264, 8, v2=True)[2] is False
     assert o.drop_scale(0.0) == 1.0 and o.drop_scale(0.1) == float(torch.tensor(65536.0 / (65536 - 6554), dtype=torch.float32))
     assert abs(o.drop_scale(0.1) * 0.9 - 1) < 2.0 ** -17 and o.drop_scale(0.5) == 2.0
     assert [o.small_splitk(M, 128) for M in (16384, 16385)] == [True, False] and not o.small_splitk(1, 96)
@@ -174,16 +172,15 @@ def test_wgrad_emulation_inside_the_bound_and_its_mutants_outside(M):
     for N1, N2 in o.WG_WIDTHS:
         a, b = o.make_wgrad(M, N1, N2, M + N1 + N2, strided=(N1 == 264))
         out0 = torch.randn(N1, N2, generator=torch.Generator().manual_seed(M))
-        for v2 in (False, True):
-            sl = o.wgrad_slices(M, N1, N2, v2)[:2]
-            for acc in (False, True):
-                ref, S = o.wgrad_reference(a, b, out0 if acc else None)
-                n = o.n_wgrad(M, N1, N2, acc, v2)
-                r = o.worst(o.f32_ratios(o.emulate_wgrad(a, b, sl, out0 if acc else None), ref, S, n))
-                res["inside"] = max(res.get("inside", 0), r)
-                for mut in ("drop_step", "slice_twice"):
-                    r = o.worst(o.f32_ratios(o.emulate_wgrad(a, b, sl, out0 if acc else None, mutate=mut), ref, S, n))
-                    res[mut] = min(res.get(mut, float("inf")), r)
+        sl = o.wgrad_slices(M, N1, N2)[:2]
+        for acc in (False, True):
+            ref, S = o.wgrad_reference(a, b, out0 if acc else None)
+            n = o.n_wgrad(M, N1, N2, acc)
+            r = o.worst(o.f32_ratios(o.emulate_wgrad(a, b, sl, out0 if acc else None), ref, S, n))
+            res["inside"] = max(res.get("inside", 0), r)
+            for mut in ("drop_step", "slice_twice"):
+                r = o.worst(o.f32_ratios(o.emulate_wgrad(a, b, sl, out0 if acc else None, mutate=mut), ref, S, n))
+                res[mut] = min(res.get(mut, float("inf")), r)
     say("weight gradients, M = %d" % M, **res)
     assert res["inside"] <= 1 and res["drop_step"] > 1 and res["slice_twice"] > 1
 

@@ -1,9 +1,9 @@
 """Per-shape table of the projection GEMMs: cwlt_gemm_bf16 (csrc/gemm_bf16.hip) against hipBLASLt (torch.mm / addmm /
 addmm_) on the same box, same random operands, interleaved rounds in one process (GPU box only).
 
-usage: python tools/bench_gemm.py [M] [--variants 0,1] [--rounds 5]
-       python tools/bench_gemm.py [M] --trace N K [--variants 0,1]     in-kernel s_memtime stamps of one tile (diagnostic build)
-       python tools/bench_gemm.py [M] --ablate N K                     main-loop ablations, start staggers, small grids
+usage: python tools/bench_gemm.py [M] [--variants 0,8] [--rounds 5]
+       python tools/bench_gemm.py [M] --trace N K [--variants 0,8]     in-kernel s_memtime stamps of one tile (diagnostic build)
+       python tools/bench_gemm.py [M] --ablate N K                     start staggers, small grids
 Prints, per shape of the encoder layer at M token rows: correctness against an f64 product of the same bf16 operands,
 then median / min microseconds and TFLOP/s of both.
 """
@@ -61,7 +61,7 @@ def trace(M, N, K, variants):
     nK = K // 64
     for v in variants:
         buf = torch.zeros(8 * 1024, dtype=torch.int32, device=dev)
-        lib.cwlt_gemm_bf16_tune(v, _lib.dev(buf))
+        assert lib.cwlt_gemm_bf16_tune(v, _lib.dev(buf)) == 0, "variant %d: only bits 1-3 and 8-15" % v
         for _ in range(3):
             ops.gemm_bf16(a, w)
         torch.cuda.synchronize()
@@ -83,32 +83,21 @@ def trace(M, N, K, variants):
 
 
 def ablate(M, N, K, rounds):
-    """Where the tile time goes (results of the ablated kernels are wrong by construction): main loop with parts switched
-    off, grids smaller than the chip (is the tile boundary bandwidth- or latency-bound?), start staggers."""
+    """Where the tile time goes: start staggers, and grids smaller than the chip (is the tile boundary bandwidth- or
+    latency-bound?)."""
     lib = _lib.load()
     dev = torch.device("cuda:0")
     a = torch.randn(M, K, device=dev).bfloat16()
     w = (torch.randn(N, K, device=dev) * 0.05).bfloat16()
     c = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
-    names = {0: "everything", 1: "no DMA in the loop", 2: "no fragment reads", 3: "no DMA, no reads (MFMA + barriers)",
-             4: "no barriers", 5: "no DMA, no barriers", 6: "no reads, no barriers", 7: "MFMA only"}
 
     def run(v):
         def f():
-            lib.cwlt_gemm_bf16_tune(v, None)
+            assert lib.cwlt_gemm_bf16_tune(v, None) == 0, "variant %d: only bits 1-3 and 8-15" % v
             ops.gemm_bf16(a, w, out=c)
         return f
     fl = 2.0 * M * N * K
-    print("N=%d K=%d M=%d: main-loop ablations (us, median of %d rounds)" % (N, K, M, rounds))
-    ts = time_rounds([run(ab << 4) for ab in range(8)], rounds)
-    for ab in range(8):
-        t = sorted(ts[ab])[len(ts[ab]) // 2]
-        print("  %-36s %8.1f us (%5.0f TF-equivalent)" % (names[ab], t * 1e3, fl / t / 1e9))
-    ts = time_rounds([run(0), run(8 << 4), run(1)], rounds)
-    for nm, t_ in zip(("everything (again)", "no counted waits in the loop",
-                       "next tile's operands requested after the main loop"), ts):
-        t = sorted(t_)[len(t_) // 2]
-        print("  %-36s %8.1f us (%5.0f TF-equivalent)" % (nm, t * 1e3, fl / t / 1e9))
+    print("N=%d K=%d M=%d (us, median of %d rounds)" % (N, K, M, rounds))
     print("start stagger (eighths of a tile period over 16 groups of workgroups):")
     ts = time_rounds([run(sg << 1) for sg in range(8)], rounds)
     for sg in range(8):
@@ -142,7 +131,7 @@ def main():
     lib = _lib.load()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    print("M = %d rows; variant bit 0: next tile's operands requested after the main loop (default: from inside the last K-tile); bits 1-3: start stagger in eighths of a tile (variant -1 = the shipped default)" % M)
+    print("M = %d rows; variant bits 1-3: start stagger in eighths of a tile, bits 8-15: grid cap in eights of workgroups (variant -1 = the shipped default)" % M)
     for name, N, K, has_bias, acc, form in SHAPES:
         a = torch.randn(M, K, device=dev).bfloat16()
         w = (torch.randn(N, K, device=dev) * 0.05).bfloat16()
@@ -157,7 +146,7 @@ def main():
         if acc:
             ref = ref + c0[sl].double()
         for v in variants:
-            lib.cwlt_gemm_bf16_tune(v, None)
+            assert lib.cwlt_gemm_bf16_tune(v, None) == 0, "variant %d: only bits 1-3 and 8-15" % v
             out = c0.clone() if acc else None
             out = ops.gemm_bf16(a, w, bias, out=out, accumulate=acc)
             err = (out[sl].double() - ref).abs().max().item() / ref.abs().max().item()
@@ -185,7 +174,7 @@ def main():
         nlib = len(fns)
         for v in variants:
             def run(v=v):
-                lib.cwlt_gemm_bf16_tune(v, None)
+                assert lib.cwlt_gemm_bf16_tune(v, None) == 0, "variant %d: only bits 1-3 and 8-15" % v
                 ops.gemm_bf16(a, w, bias, out=cacc2 if acc else cw, accumulate=acc)
             fns.append(run)
         ts = time_rounds(fns, rounds)

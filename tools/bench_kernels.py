@@ -103,10 +103,10 @@ def bench_ffn1():
     h = torch.mm(x, w1.t())
     t1 = timeit(lambda: ops.gelu_fwd(h, b, 0.1, 77, gd_inplace=True))
     t2 = timeit(lambda: ops.ffn1_gelu_dropout(x, w1, b, 0.1, 77))
-    var = os.environ.get("CWLT_GEMM_VARIANT")              # cwlt_gemm_bf16_tune bits (131072: g stored with the default policy)
+    var = os.environ.get("CWLT_GEMM_VARIANT")              # cwlt_gemm_bf16_tune number (bits 1-3 start stagger, bits 8-15 grid cap)
     if var:
         from rlmg_amd import _lib
-        _lib.load().cwlt_gemm_bf16_tune(int(var), None)
+        assert _lib.load().cwlt_gemm_bf16_tune(int(var), None) == 0, "CWLT_GEMM_VARIANT: only bits 1-3 and 8-15"
         t3 = [timeit(lambda: ops.ffn1_gelu_dropout(x, w1, b, 0.1, 77)) for _ in range(3)]
         _lib.load().cwlt_gemm_bf16_tune(-1, None)
         t4 = [timeit(lambda: ops.ffn1_gelu_dropout(x, w1, b, 0.1, 77)) for _ in range(3)]

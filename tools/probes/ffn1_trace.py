@@ -1,6 +1,6 @@
 """GPU box: per-workgroup timeline of the one-kernel FFN forward (needs a libcwlt built with the trace hook of
 tools/probes/ffn1_trace.patch; CWLT_GEMM_TRACE=1).  Prints how many workgroups are in their epilogue at once, how long
-epilogues and main loops take, and how both depend on the start spread (CWLT_GEMM_NT_SPREAD)."""
+epilogues and main loops take, and how both depend on the start spread (a switch of the kernel when this was measured; unconditional now)."""
 import ctypes
 import os
 import sys
