@@ -24,32 +24,11 @@
 // attribute is drawn under the kind's row of `gram`.  Each wave of another attribute first runs the draw body on the
 // bar-beat logits with bar-beat's own key and masks -- the very instructions the bar-beat wave runs, so all waves hold
 // the same class -- and then runs it again for its own attribute: no workgroup barrier, no hand-off through memory.
-#include "cwlt_common.h"
+#include "cwlt_sampler_support.h"
 
 #include <climits>
 
-#define CWLT_MAX_ATTR 8
-
 namespace cwlt {
-
-struct SampleArgs {
-    int n[CWLT_MAX_ATTR];
-    int off[CWLT_MAX_ATTR];
-    float inv_t[CWLT_MAX_ATTR];                      // 1 / temperature per attribute
-    float top_p[CWLT_MAX_ATTR];                      // nucleus mass per attribute; >= 1: plain categorical
-};
-
-// Allowed-class table of the masked draw (cwlt_sample_categorical_masked): the song of row n is k (row_key[n], or n
-// when slot-keyed by the counter); its mask row is sched[2k] + min(bar[n] - 1, sched[2k + 1] - 1), `words` uint32 per
-// row, class c of attribute a allowed when bit off[a] + c is set.  k < 0 (idle / waiting slots), k >= n_sched, a
-// schedule of length 0 and a row outside [0, rows) all draw unmasked.
-struct MaskArgs {
-    const int64_t* bar;
-    const int64_t* sched;
-    const uint32_t* masks;
-    long n_sched, rows;
-    int words;
-};
 
 // Log-prob output of the LOGP / FORCED instantiations (unused otherwise; it is the last kernel argument, so the
 // other arguments keep their offsets).  The pair of row n, attribute a goes to logp[((o * rows + n) * n_attr + a) * 2]
@@ -61,25 +40,6 @@ struct LogpArgs {
     long out_rows;
     const int64_t* targets;
 };
-
-// Row grammar of the GRAMMAR instantiations (unused otherwise; the last kernel argument, after LogpArgs, so every other
-// argument keeps its offset).  beat[n]: where row n's song stands in its bar: -1 after a Bar row, k after Beat_k.
-// order[c] for each class c of attribute bar_attr: -2 the neutral class (a note row), -1 a Bar class, k >= 0 Beat_k,
-// -3 never allowed.  c is allowed when order[c] == -1, or order[c] > beat[n] >= -1 with order[c] >= 0, or order[c] ==
-// -2 with beat[n] >= 0.  gram: 3 x words uint32 in the bit layout of MaskArgs::masks, row 0 what a NOTE row may carry
-// in each attribute, row 1 a BAR row, row 2 a BEAT row.
-struct GrammarArgs {
-    const int64_t* beat;
-    const int* order;
-    const uint32_t* gram;
-    int words;
-    int bar_attr;
-};
-
-constexpr int KIND_NONE = -1;                        // an ill-formed forced target: nothing is allowed
-constexpr int KIND_POSITION = 3;                     // the bar-beat attribute itself: the position rule, no gram row
-
-__device__ __forceinline__ int grammar_kind(int o) { return o == -2 ? 0 : o == -1 ? 1 : o >= 0 ? 2 : KIND_NONE; }
 
 // The draw of attribute a of row n by one wave (lane-blocked: lane l owns classes 4l .. 4l + 3), `ew` the wave's LDS
 // row -> the class.  write = false (GRAMMAR: another attribute's wave finding the row's bar-beat class) draws and
@@ -96,99 +56,15 @@ __device__ __forceinline__ int draw_attr(const float* __restrict__ logits, long 
     const float* x = logits + (long)n * ld + A.off[a];
     // keyed by row: row n draws what the slot-keyed launch draws for row row_key[n] at counter row_step[n]
     const long step = FORCED ? 0 : row_step ? row_step[n] : counter ? *counter : 0;
-    bool ok[4] = {true, true, true, true};
-    bool row_masked = false;
-    if constexpr (MASKED) {
-        const long k = row_key ? row_key[n] : (long)n;
-        if (k >= 0 && k < M.n_sched) {
-            const long first = M.sched[2 * k], len = M.sched[2 * k + 1];
-            long b = M.bar[n] - 1;
-            b = b < 0 ? 0 : b < len - 1 ? b : len - 1;
-            const long r = first + b;
-            if (len > 0 && r >= 0 && r < M.rows) {
-                row_masked = true;
-                const uint32_t* w = M.masks + r * M.words;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int bit = A.off[a] + lane * 4 + j;         // < sum n_class <= 32 * words: inside the row
-                    ok[j] = lane * 4 + j < nc ? ((w[bit >> 5] >> (bit & 31)) & 1u) != 0 : false;
-                }
-            }
-        }
-    }
-    if constexpr (GRAMMAR) {
-        bool cut = false;                            // the grammar removes a class of this attribute
-        if (kind == KIND_POSITION) {
-            const long bt = G.beat[n];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = lane * 4 + j;
-                if (c < nc) {
-                    const int o = G.order[c];        // order holds >= nc entries (checked by the entry points)
-                    const bool g = o == -1 || (o >= 0 && o > bt) || (o == -2 && bt >= 0);
-                    cut = cut || !g;
-                    ok[j] = ok[j] && g;
-                }
-            }
-        } else {
-            const uint32_t* w = G.gram + (kind < 0 ? 0 : kind) * G.words;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int bit = A.off[a] + lane * 4 + j;             // < sum n_class <= 32 * words: inside the row
-                if (lane * 4 + j < nc) {
-                    const bool g = kind >= 0 && ((w[bit >> 5] >> (bit & 31)) & 1u) != 0;
-                    cut = cut || !g;
-                    ok[j] = ok[j] && g;
-                }
-            }
-        }
-        if constexpr (LOGP) row_masked = row_masked || __ballot(cut) != 0;   // permissive tables: the plain pair
-    }
-    float v[4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = lane * 4 + j;
-        v[j] = c < nc && ok[j] ? x[c] * A.inv_t[a] : -INFINITY;
-        m = fmaxf(m, v[j]);
-    }
-    m = wave_max(m);
-    float e[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) e[j] = lane * 4 + j < nc && ok[j] ? expf(v[j] - m) : 0.f;
-    bool keep[4];                                    // the support of q: allowed, and inside the nucleus
-#pragma unroll
-    for (int j = 0; j < 4; ++j) keep[j] = lane * 4 + j < nc && ok[j];
-    float tot_all = 0.f;                             // sum of e before the nucleus cut (nucleus rows only)
-    if (A.top_p[a] < 1.0f) {
-        // nucleus (dqn_policy/model.py:33-47): in descending-probability order keep every class whose PRECEDING
-        // mass is <= p (the class that crosses p is kept); probabilities there are exp/(sum + 1e-5).  The mass
-        // ahead of class i needs no sort: G_i = sum of e_j over classes ranked before i (larger e, ties: larger
-        // index first, as argsort()[::-1] orders them).  One broadcast LDS read per class, four running sums per lane.
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ew[lane * 4 + j] = e[j];
-        float tot = (e[0] + e[1]) + (e[2] + e[3]);
-        tot = wave_sum(tot);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        float ahead[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < nc; ++c) {
-            const float ec = ew[c];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int i = lane * 4 + j;
-                ahead[j] += (ec > e[j] || (ec == e[j] && c > i)) ? ec : 0.f;
-            }
-        }
-        const float limit = A.top_p[a] * (tot * (1.0f + 1e-5f));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e[j] = ahead[j] <= limit ? e[j] : 0.f;
-        if constexpr (LOGP) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) keep[j] = keep[j] && ahead[j] <= limit;
-            tot_all = tot;
-        }
-    }
+    const AllowedClasses al = allowed_classes<MASKED, GRAMMAR>(A, M, G, row_key, n, lane, a, kind);
+    const bool(&ok)[4] = al.ok;
+    bool row_masked = al.row_masked;
+    if constexpr (GRAMMAR && LOGP) row_masked = row_masked || __ballot(al.cut) != 0;   // permissive tables: the plain pair
+    const SamplerSupport sup = sampler_support<LOGP>(x, A, a, nc, lane, ok[0], ok[1], ok[2], ok[3], ew);
+    const float v[4] = {sup.v[0], sup.v[1], sup.v[2], sup.v[3]};
+    float e[4] = {sup.e[0], sup.e[1], sup.e[2], sup.e[3]};
+    const bool(&keep)[4] = sup.keep;                 // the support of q
+    const float m = sup.m, tot_all = sup.tot_all;    // tot_all: the sum of e before the nucleus cut (nucleus rows only)
     float run = 0.f, cum[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -342,26 +218,12 @@ static int sample(const float* logits, const int* n_class, const float* temperat
                   const cwlt::LogpArgs* lp = nullptr, bool forced = false, const cwlt::GrammarArgs* gr = nullptr,
                   int n_order = 0) {
     using namespace cwlt;
-    if (!logits || !n_class || (!tokens && !forced) || n_attr <= 0 || n_attr > CWLT_MAX_ATTR || rows <= 0)
-        return CWLT_ERR_ARG;
+    if (!logits || (!tokens && !forced) || rows <= 0) return CWLT_ERR_ARG;
     SampleArgs A;
-    int off = 0;
-    for (int a = 0; a < n_attr; ++a) {
-        if (n_class[a] <= 0 || n_class[a] > 256) return CWLT_ERR_ARG;
-        if (temperature && !(temperature[a] > 0.f)) return CWLT_ERR_ARG;
-        A.n[a] = n_class[a];
-        A.off[a] = off;
-        A.inv_t[a] = temperature ? 1.0f / temperature[a] : 1.0f;
-        A.top_p[a] = top_p ? top_p[a] : 1.0f;
-        if (!(A.top_p[a] > 0.f)) return CWLT_ERR_ARG;
-        off += n_class[a];
-    }
-    if (ld < off) return CWLT_ERR_ARG;
-    if (mask && (int64_t)mask->words * 32 < off) return CWLT_ERR_ARG;
-    if (gr) {
-        if (!gr->beat || !gr->order || !gr->gram || gr->bar_attr < 0 || gr->bar_attr >= n_attr) return CWLT_ERR_ARG;
-        if (n_order < n_class[gr->bar_attr] || (int64_t)gr->words * 32 < off) return CWLT_ERR_ARG;
-    }
+    int width = 0;
+    if (sample_args(n_class, temperature, top_p, n_attr, ld, &A, &width)) return CWLT_ERR_ARG;
+    if (mask && table_words(mask->words, width)) return CWLT_ERR_ARG;
+    if (gr && grammar_args(*gr, n_order, n_class, n_attr, width)) return CWLT_ERR_ARG;
     const MaskArgs M = mask ? *mask : MaskArgs{};
     const LogpArgs L = lp ? *lp : LogpArgs{};
     const GrammarArgs G = gr ? *gr : GrammarArgs{};
@@ -420,22 +282,13 @@ extern "C" int cwlt_sample_categorical_masked(const float* logits, const int* n_
                                               const uint32_t* masks, int64_t mask_rows, int mask_words,
                                               int64_t* tokens, void* stream) {
     using namespace cwlt;
-    if (!bar || !sched || !masks || rows > (1L << 20)) return CWLT_ERR_ARG;
+    if (rows > (1L << 20)) return CWLT_ERR_ARG;
     if (!key != !step || (!key && !counter)) return CWLT_ERR_ARG;    // keyed per row, or by slot and counter
-    if (n_sched < 1 || mask_rows < 1 || mask_words < 1) return CWLT_ERR_ARG;
-    const MaskArgs M{bar, sched, masks, (long)n_sched, (long)mask_rows, mask_words};
+    MaskArgs M{};
+    bool masked = false;                             // this entry needs the table
+    if (mask_args(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked) || !masked) return CWLT_ERR_ARG;
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
                   0, 1, stream, key, step, &M);
-}
-
-// Mask table arguments shared by the log-prob entries: all three pointers, or none (unmasked).  -> 0 ok, 1 refused.
-static int logp_mask(const int64_t* bar, const int64_t* sched, int64_t n_sched, const uint32_t* masks,
-                     int64_t mask_rows, int mask_words, cwlt::MaskArgs* M, bool* masked) {
-    *masked = bar || sched || masks;
-    if (!*masked) return 0;
-    if (!bar || !sched || !masks || n_sched < 1 || mask_rows < 1 || mask_words < 1) return 1;
-    *M = cwlt::MaskArgs{bar, sched, masks, (long)n_sched, (long)mask_rows, mask_words};
-    return 0;
 }
 
 extern "C" int cwlt_sample_categorical_logp(const float* logits, const int* n_class, const float* temperature,
@@ -450,7 +303,7 @@ extern "C" int cwlt_sample_categorical_logp(const float* logits, const int* n_cl
     if (!key != !step || (!key && !counter)) return CWLT_ERR_ARG;    // keyed per row, or by slot and counter
     MaskArgs M{};
     bool masked = false;
-    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    if (mask_args(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
     const LogpArgs L{logp, out_counter, (long)out_rows, nullptr};
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
                   0, 1, stream, key, step, masked ? &M : nullptr, &L);
@@ -465,18 +318,10 @@ extern "C" int cwlt_score_categorical(const float* logits, const int* n_class, c
     if (!logp || !targets || rows > (1L << 20)) return CWLT_ERR_ARG;
     MaskArgs M{};
     bool masked = false;
-    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    if (mask_args(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
     const LogpArgs L{logp, nullptr, 1, targets};
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, 0, nullptr, nullptr, nullptr, 0, 1, stream,
                   key, nullptr, masked ? &M : nullptr, &L, true);
-}
-
-// Grammar table arguments shared by the two grammar entries -> 0 ok, 1 refused (the rest is checked by sample()).
-static int grammar_args(const int64_t* beat, const int* order, const uint32_t* gram, int gram_words, int bar_attr,
-                        cwlt::GrammarArgs* G) {
-    if (!beat || !order || !gram || gram_words < 1) return 1;
-    *G = cwlt::GrammarArgs{beat, order, gram, gram_words, bar_attr};
-    return 0;
 }
 
 extern "C" int cwlt_sample_categorical_grammar(const float* logits, const int* n_class, const float* temperature,
@@ -494,9 +339,8 @@ extern "C" int cwlt_sample_categorical_grammar(const float* logits, const int* n
     if (logp && (out_rows < 1 || (out_counter == nullptr && out_rows != 1))) return CWLT_ERR_ARG;
     MaskArgs M{};
     bool masked = false;
-    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
-    GrammarArgs G{};
-    if (grammar_args(beat, order, gram, gram_words, bar_attr, &G)) return CWLT_ERR_ARG;
+    if (mask_args(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    const GrammarArgs G{beat, order, gram, gram_words, bar_attr};   // checked by sample()
     const LogpArgs L{logp, out_counter, (long)out_rows, nullptr};
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, seed, key ? nullptr : counter, tokens, nullptr,
                   0, 1, stream, key, step, masked ? &M : nullptr, logp ? &L : nullptr, false, &G, n_order);
@@ -513,9 +357,8 @@ extern "C" int cwlt_score_categorical_grammar(const float* logits, const int* n_
     if (!logp || !targets || rows > (1L << 20)) return CWLT_ERR_ARG;
     MaskArgs M{};
     bool masked = false;
-    if (logp_mask(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
-    GrammarArgs G{};
-    if (grammar_args(beat, order, gram, gram_words, bar_attr, &G)) return CWLT_ERR_ARG;
+    if (mask_args(bar, sched, n_sched, masks, mask_rows, mask_words, &M, &masked)) return CWLT_ERR_ARG;
+    const GrammarArgs G{beat, order, gram, gram_words, bar_attr};   // checked by sample()
     const LogpArgs L{logp, nullptr, 1, targets};
     return sample(logits, n_class, temperature, top_p, n_attr, rows, ld, 0, nullptr, nullptr, nullptr, 0, 1, stream,
                   key, nullptr, masked ? &M : nullptr, &L, true, &G, n_order);

@@ -1719,28 +1719,45 @@ def sample_categorical_grammar(logits, n_class, tokens, seed, beat, order, gram,
     return tokens
 
 
-def _score(fn, logits, n_class, targets, temperature, top_p, key, bar, sched, masks, out, grammar=None):
-    """The scorers' body: the checks on all rows, then launches of at most 2^20 rows of cwlt_<fn>.  grammar: (beat, order,
-    gram, bar_attr) for the grammar entry, whose arguments follow the constraint table's."""
-    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, targets, temperature, top_p, "targets")
+def _rows(t, a, z):
+    """Rows a .. z of a per-row tensor; None stays None."""
+    return None if t is None else t[a:z]
+
+
+def _table_slices(n_class, rows, key, bar, sched, masks, grammar, no_grammar=()):
+    """The body the scorers and policy_stats share: the checks of the constraint table and of grammar = (beat, order,
+    gram, bar_attr) (None: none) on all rows, then -- a generator -- per launch of at most 2^20 rows (a, z, key, table,
+    gtable): the rows a .. z, their slice of key (None without keys) and the two tables' ctypes arguments for them;
+    gtable is no_grammar without a grammar."""
     if key is not None and bar is None:
         raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
     _mask_table(n_class, rows, bar, sched, masks, key)
     if grammar is not None:
         beat, order, gram, bar_attr = grammar
         _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+
+    def slices():
+        for a in range(0, rows, 1 << 20):
+            z = min(rows, a + (1 << 20))
+            k = _rows(key, a, z)
+            yield (a, z, k, _mask_table(n_class, z - a, _rows(bar, a, z), sched, masks, k), no_grammar if grammar is None
+                   else _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr))
+    return slices()
+
+
+def _score(fn, logits, n_class, targets, temperature, top_p, key, bar, sched, masks, out, grammar=None):
+    """The scorers' body: the checks on all rows, then launches of at most 2^20 rows of cwlt_<fn>.  grammar: (beat, order,
+    gram, bar_attr) for the grammar entry, whose arguments follow the constraint table's."""
+    logits, rows, A, temp, topp = _sampler_head(fn, logits, n_class, targets, temperature, top_p, "targets")
+    slices = _table_slices(n_class, rows, key, bar, sched, masks, grammar)
     if out is None:
         out = torch.empty((rows, A, 2), dtype=torch.float32, device=logits.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, 2) or not out.is_contiguous():
         raise ValueError("out must be a contiguous (%d, %d, 2) f32 tensor" % (rows, A))
     tv = targets.view(rows, A)
-    for a in range(0, rows, 1 << 20):
-        z = min(rows, a + (1 << 20))
-        sl = lambda t: None if t is None else t[a:z]
-        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
-        gtable = () if grammar is None else _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
+    for a, z, k, table, gtable in slices:
         _call("cwlt_" + fn, _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
-              logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(sl(key)), *table, *gtable,
+              logits.stride(0), _lib.dev(tv[a:z], "targets"), _lib.opt(k), *table, *gtable,
               _lib.dev(out[a:z], "logp"), _lib.stream_ptr())
     return out
 
@@ -1790,25 +1807,15 @@ def policy_stats(logits, n_class, ref_logits=None, temperature=None, top_p=None,
         if ref_logits.stride(-1) != 1:
             ref_logits = ref_logits.contiguous()
         C = 4
-    if key is not None and bar is None:
-        raise ValueError("key selects a song's constraint row: it needs bar, sched and masks")
-    _mask_table(n_class, rows, bar, sched, masks, key)
-    if grammar is not None:
-        beat, order, gram, bar_attr = grammar
-        _grammar_table(n_class, rows, beat, order, gram, bar_attr)
+    slices = _table_slices(n_class, rows, key, bar, sched, masks, grammar, (None, None, 0, None, 0, 0))
     if out is None:
         out = torch.empty((rows, A, C), dtype=torch.float32, device=logits.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (rows, A, C) or not out.is_contiguous():
         raise ValueError("out must be a contiguous (%d, %d, %d) f32 tensor" % (rows, A, C))
-    for a in range(0, rows, 1 << 20):
-        z = min(rows, a + (1 << 20))
-        sl = lambda t: None if t is None else t[a:z]
-        table = _mask_table(n_class, z - a, sl(bar), sched, masks, sl(key))
-        gtable = (None, None, 0, None, 0, 0) if grammar is None else \
-            _grammar_table(n_class, z - a, beat[a:z], order, gram, bar_attr)
+    for a, z, k, table, gtable in slices:
         _call("cwlt_policy_stats", _lib.dev(logits[a:z], "logits"), _lib.int_array(n_class), temp, topp, A, z - a,
-              logits.stride(0), _lib.opt(sl(ref_logits)), 0 if ref_logits is None else ref_logits.stride(0),
-              _lib.opt(sl(bar_class)), _lib.opt(sl(key)), *table, *gtable, _lib.dev(out[a:z], "out"),
+              logits.stride(0), _lib.opt(_rows(ref_logits, a, z)), 0 if ref_logits is None else ref_logits.stride(0),
+              _lib.opt(_rows(bar_class, a, z)), _lib.opt(k), *table, *gtable, _lib.dev(out[a:z], "out"),
               _lib.stream_ptr())
     return out
 

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 instruction streams of the bf16 GEMM family between two csrc trees, kernel by kernel.
+"""Compare the gfx950 instruction streams of two csrc trees, kernel by kernel, for the files given on the command line.
 
-    python tools/isa_compare.py <parent csrc> <new csrc> [file.hip ...]
+    python tools/isa_compare.py <parent csrc> <new csrc> file.hip [file.hip ...]
 
-Each file is compiled in both trees with build.py's flags plus `--cuda-device-only -S`.  Per kernel the instruction lines
-are compared as text after dropping comments and the function number in `.LBB<n>_` labels.  Kernels are matched by
-demangled name; the template arguments that selected a retired variant are dropped from the parent's names (RETIRED), so
-a parent kernel that matches nothing on the new side is one of the retired instantiations.  For kernels that differ, the
-compiler's resource-usage remarks of both sides are printed.  No GPU needed.
+Any file of csrc can be given (headers are picked up from each tree); without files, the bf16 GEMM family the tool was
+first written for.  Each file is compiled in both trees with build.py's flags plus `--cuda-device-only -S`.  Per kernel
+the instruction lines are compared as text after dropping comments and the function number in `.LBB<n>_` labels.
+Kernels are matched by demangled name; the template arguments that selected a retired GEMM variant are dropped from the
+parent's names (RETIRED), so a parent kernel that matches nothing on the new side is one of the retired instantiations.
+For kernels that differ, the compiler's resource-usage remarks of both sides are printed.  Read the instruction counts
+too: a helper that can fall off its end without a return compiles silently into kernels of one instruction.  No GPU
+needed.
 """
 import difflib, importlib.util, os, re, subprocess, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# compared when no file is named on the command line; any file of csrc can be named there
 FILES = ["gemm_bf16.hip", "gemm_nt.hip", "gemm_ln.hip", "gemm_small.hip", "wgrad.hip"]
 RETIRED = [(r"(gemm_bf16_kernel<\d+, \w+), 0, true>", r"\1>"), (r"(wgrad_kernel<\w+), true>", r"\1>"),
            (r"wgrad_group_kernel<true>", "wgrad_group_kernel"), (r"(gemm_nt_mul_kernel<\d+), true, true>", r"\1>")]
