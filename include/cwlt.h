@@ -589,6 +589,23 @@ int cwlt_policy_stats(const float* logits, const int* n_class, const float* temp
                       const int* order, int n_order, const uint32_t* gram, int gram_words, int bar_attr, float* out,
                       void* stream);
 
+/* Blend of a policy with a reference model at sampling time (csrc/blend.hip).  For row n of logits (rows
+ * x ld f32) and ref_logits (rows x ref_ld f32, a second model's logits for the same rows) and attribute a with columns
+ * [off_a, off_a + n_class[a]): out[n, c] = w logits[n, c] + (1 - w) ref_logits[n, c] (out rows x ld_out f32), so that
+ * softmax(out) is softmax(logits)^w softmax(ref_logits)^(1 - w) renormalised.  w = alpha[k * n_attr + a] (DEVICE f32,
+ * n_alpha x n_attr): k = 0 when n_alpha == 1, else key[n] (DEVICE int64 x rows; NULL: n); a row with k outside [0,
+ * n_alpha) -- an idle (-1) or waiting (-2) stream slot -- is copied from logits.  1 - w is formed once in f32, then two
+ * products and a sum (an fma or not), with no special case: w = 1 returns logits and w = 0 ref_logits exactly for
+ * finite inputs (a -0 may come back +0).  Columns at or past sum n_class are neither read nor written.  out may be
+ * logits itself (ld_out == ld): each element is read, then written, by one thread; otherwise out overlaps neither
+ * input.  16-byte accesses when the three bases are 16-byte aligned and the three strides multiples of 4, scalar ones
+ * otherwise.  n_class is a HOST array.
+ * Refused: a NULL logits, ref_logits, alpha, out or n_class, n_attr outside 1 .. 8, a class count outside 1 .. 256, a
+ * stride below sum n_class, n_alpha < 1, rows < 1 or > 2^20, out == ref_logits. */
+int cwlt_blend_logits(const float* logits, int64_t ld, const float* ref_logits, int64_t ref_ld, const int* n_class,
+                      int n_attr, const float* alpha, int64_t n_alpha, const int64_t* key, float* out, int64_t ld_out,
+                      int64_t rows, void* stream);
+
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,
  * cwlt_stream_refill, cwlt_sample_categorical_keyed and cwlt_stream_advance.

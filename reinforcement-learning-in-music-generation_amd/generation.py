@@ -447,6 +447,61 @@ def _device_grammar(grammar, tables, beat0s, dev):
             "beat0": torch.as_tensor(np.asarray(beat0s, dtype=np.int64)).to(dev), "bar_attr": grammar.bar_attr}
 
 
+def compile_alpha(alpha, n_songs, n_attr):
+    """The blend weights of generation with a reference model -> the device table's host form, float32
+    (1, n_attr) (every song) or (n_songs, n_attr).  alpha: a scalar; (n_songs,) one value per song; (1, n_attr) one per
+    attribute; (n_songs, n_attr).  A one-dimensional alpha is always per song.  Entries are finite floats of any sign
+    or size: 1 is the model, 0 the reference, above 1 extrapolates.  Refused (ValueError): any other shape, a
+    non-finite or non-numeric entry."""
+    n_songs, A = int(n_songs), int(n_attr)
+    try:
+        a = None if alpha is None else np.asarray(alpha, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None:
+        raise ValueError("alpha must be a number or an array of numbers, got %s" % type(alpha).__name__)
+    if a.ndim == 0:
+        a = np.full((1, A), float(a))
+    elif a.ndim == 1 and a.shape[0] == n_songs:
+        a = np.repeat(a[:, None], A, axis=1)
+    elif a.ndim != 2 or a.shape[1] != A or a.shape[0] not in (1, n_songs):
+        raise ValueError("alpha must be a scalar, (n_songs,) = (%d,), (1, %d) or (%d, %d), got shape %s"
+                         % (n_songs, A, n_songs, A, a.shape))
+    with np.errstate(over="ignore"):
+        out = a.astype(np.float32)
+    if not np.isfinite(out).all():
+        raise ValueError("alpha entries must be finite (in float32)")
+    return np.ascontiguousarray(out)
+
+
+def _check_blend(model, reference, alpha, where):
+    """The refusals of reference= / alpha= of a generation entry or score_songs -> True when `where` blends.  The two go
+    together, and the reference meets _song_blocks' conditions."""
+    if reference is None and alpha is None:
+        return False
+    if reference is None:
+        raise ValueError("%s: alpha blends the model with a reference model: pass reference= as well" % where)
+    if alpha is None:
+        raise ValueError("%s: reference= needs alpha= (1: the model, 0: the reference; the reference's own songs or "
+                         "scores come from calling %s on it)" % (where, where))
+    _check_scoring_model(reference, "the reference model: generation")
+    if list(reference.n_token) != list(model.n_token):
+        raise ValueError("the reference model has classes %s, the model %s" % (list(reference.n_token),
+                                                                              list(model.n_token)))
+    if next(reference.parameters()).device != next(model.parameters()).device:
+        raise ValueError("the reference model must sit on the model's device (%s)" % (next(model.parameters()).device,))
+    return True
+
+
+def _reference_session(sess, reference):
+    """The second decode state of a blended loop: a GEMM-step session of `reference` with sess's rows, stepping on the
+    token buffer sess's sampler writes.  Takes no seed."""
+    ref = DecodeSession(reference, n_songs=sess.n_songs, kernel="gemm")
+    ref.tok = sess.tok
+    ref.reset()
+    return ref
+
+
 class _FusedPlan:
     """Host description of the model for `cwlt_decode_step` (include/cwlt.h: cwlt_decode_model): stacked
     QKV / head weights, device pointers of every parameter, the per-song state and workspace.  Holds references
@@ -810,11 +865,16 @@ class _DeviceLoop:
     (model, sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects.
 
     grammar: the row grammar (_device_grammar): the draw is cwlt_sample_categorical_grammar (masked and with log-probs
-    as above when asked), then cwlt_count_bars if constrained, then cwlt_grammar_track moves each song's position."""
+    as above when asked), then cwlt_count_bars if constrained, then cwlt_grammar_track moves each song's position.
+
+    ref, alpha: the blend with a reference model: `ref` (_reference_session) steps on the same token
+    buffer right after the model, cwlt_blend_logits (alpha: the (1 | n_songs, A) f32 device table, row n song n) turns
+    the model's logits into the blend's in place, and the draw goes on as above.  None: the launches are today's."""
 
     def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None,
-                 mask=None, logprobs=False, grammar=None):
+                 mask=None, logprobs=False, grammar=None, ref=None, alpha=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
+        self.ref, self.alpha = ref, alpha
         self.mask = mask
         self.grammar = grammar
         self.beat = None if grammar is None else grammar["beat0"].clone()       # one song per row, in song order
@@ -849,19 +909,29 @@ class _DeviceLoop:
             self.slot.add_(1).remainder_(self.ring)
         self.count.add_(1)
 
+    def _blend(self, logits, ref_logits):
+        """The blended logits, written over the model's (ref_logits None: the model's own, untouched)."""
+        if ref_logits is None:
+            return logits
+        return ops.blend_logits(logits, ref_logits, self.sess.n_token, self.alpha, out=logits)
+
     def _one(self):
         s = self.sess
         if not self.carry:
             s._state.zero_()
-        self._draw(s._device_step())
+            if self.ref is not None:
+                self.ref._state.zero_()
+        logits = s._device_step()
+        self._draw(self._blend(logits, None if self.ref is None else self.ref._device_step()))
 
-    def start(self, logits):
-        """Draw the first token from logits the session already holds on the device (a prefill's), as `_one` draws
-        every later one: into the step's token buffer and row 0 of the song, keyed by the counter."""
+    def start(self, logits, ref_logits=None):
+        """Draw the first token from logits the session already holds on the device (a prefill's; ref_logits: the
+        reference session's, blended in first), as `_one` draws every later one: into the step's token buffer and row 0
+        of the song, keyed by the counter."""
         if self.enqueued:
             raise RuntimeError("start() draws the loop's first token")
         with torch.no_grad():
-            self._draw(logits)
+            self._draw(self._blend(logits, ref_logits))
         self.enqueued = 1
 
     def run(self, n):
@@ -968,6 +1038,7 @@ class _StreamLoop:
         tok = s.tok.view(self.S, self.A)
         logits = s._device_step()
         self._refill(logits)
+        logits = self._blend(logits)
         _draw_token(logits, s.n_token, tok, self.seed, self.temperature, self.top_p, key=self.song, step=self.pos,
                     mask=self.mask, logp=self.lp_ring, out_counter=self.ctl, grammar=self.grammar, beat=self.beat)
         self._advance(tok)
@@ -975,6 +1046,10 @@ class _StreamLoop:
             g = self.grammar
             ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat, fresh=self.fresh, song=self.song,
                               beat0=g["beat0"])
+
+    def _blend(self, logits):
+        """Between the refill and the draw: the logits the draw reads (a form that blends overrides it)."""
+        return logits
 
     def _read(self, h):
         """The rows of ring half h that belong to songs (waiting and idle slots write song < 0), and their log-probs
@@ -1034,13 +1109,31 @@ class _StreamLoop:
 
 class _SnapshotStreamLoop(_StreamLoop):
     """The stream whose songs all start from one snapshot (snap_state, snap_logits: _stream_snapshot), with one bar0 and
-    one cap: cwlt_stream_refill and cwlt_stream_advance."""
+    one cap: cwlt_stream_refill and cwlt_stream_advance.
 
-    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk, **kw):
+    blend = (ref, ref_snap_state, ref_snap_logits, alpha): the blend with a reference model.  `ref`
+    (_reference_session) is a second pool of the same slots on the same token buffer, with the reference's own snapshot:
+    per token it steps and is refilled right after the model's pool, by the same fresh flags, then cwlt_blend_logits
+    (alpha: the (1 | n_songs, A) f32 device table, keyed by the slots' song indices -- an idle slot's row is copied)
+    turns the model's logits into the blend's in place, and the draw, advance and grammar track go on as without it:
+    still one stream and one linear captured graph per token."""
+
+    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk, blend=None,
+                 **kw):
         super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
         self.snap_state, self.snap_logits = snap_state, snap_logits
         self.bar0, self.cap = int(bar0), int(cap)
         self.song_cap = self.cap
+        self.blend = blend
+
+    def _blend(self, logits):
+        if self.blend is None:
+            return logits
+        ref, snap_state, snap_logits, alpha = self.blend
+        ref_logits = ref._device_step()
+        ops.stream_refill(ref._state, snap_state, len(ref.memory), ref.memory[0][0][0].numel(),
+                          ref.memory[0][1][0].numel(), ref_logits, snap_logits, self.fresh)
+        return ops.blend_logits(logits, ref_logits, self.sess.n_token, alpha, key=self.song, out=logits)
 
     def start(self):
         """Slots 0, 1, ... take the first songs; slots past the last song idle."""
@@ -1207,7 +1300,7 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                     return_logprobs=False, grammar=None):
+                     return_logprobs=False, grammar=None, reference=None, alpha=None):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
@@ -1231,6 +1324,12 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompt is not None and prompts is not None:
         raise ValueError("pass one shared prompt or per-song prompts, not both")
     A = len(word2event)
+    blended = _check_blend(model, reference, alpha, "generate_stream")
+    if blended and prompts is not None:
+        raise ValueError("generate_stream blends songs that start from one snapshot: per-song prompts would need a "
+                         "second bank and a second prefill schedule -- generate_batch(prompts=[...], reference=..., "
+                         "alpha=...) is the supported form")
+    atable = compile_alpha(alpha, n_songs, A) if blended else None
     start = time.perf_counter()
     n_token = list(model.n_token)
     if prompts is not None:
@@ -1264,8 +1363,13 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
                                prefill_rows=prefill_rows, **kw)
     else:
         snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else heads[0], A)
+        blend = None
+        if blended:                                           # after the seed: the second pool takes none
+            blend = (_reference_session(sess, reference),
+                     *_stream_snapshot(reference, None if prompt is None else heads[0], A),
+                     torch.as_tensor(atable).to(sess.dev))
         loop = _SnapshotStreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0s[0], caps[0],
-                                   chunk, **kw)
+                                   chunk, blend=blend, **kw)
     rows = loop.run()
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
     order = np.argsort(rows[:, 0], kind="stable")
@@ -1291,7 +1395,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                    return_logprobs=False, grammar=None):
+                    return_logprobs=False, grammar=None, reference=None, alpha=None):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -1327,11 +1431,20 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     within a bar.  Each slot's draw is cwlt_sample_categorical_grammar at the slot's position in its bar, which
     cwlt_grammar_track moves after the advance (a song's own prompt sets where it starts).  Combines with constraints
     and return_logprobs; song k is still bitwise song k of generate_batch(..., grammar=grammar).  None: nothing
+    changes.
+
+    reference, alpha: draw from the blend of the model with a reference model, softmax(alpha x + (1 - alpha) r) per
+    attribute (alpha's forms: compile_alpha, one row per song or one for all).  A second pool of `slots`
+    decode slots runs the reference on the same tokens and cwlt_blend_logits, keyed by each slot's song, writes the
+    blended logits the sampler reads; song k is bitwise song k of generate_batch(..., reference=, alpha=).  The log-prob
+    pair is then (log pi_alpha, log q) on the blended logits.  With the shared-snapshot forms only (no prompt, or one
+    shared prompt): per-song prompts are refused -- generate_batch(prompts=[...], reference=, alpha=) takes them.  The
+    reference: same classes, recurrent, eval(), f32, on the model's device, any width or depth.  None: nothing
     changes."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
                             prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs,
-                            grammar=grammar)[0]
+                            grammar=grammar, reference=reference, alpha=alpha)[0]
 
 
 def _refuse_logprobs(return_logprobs, where):
@@ -1476,7 +1589,8 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
-                   log=None, prefill="blas", constraints=None, return_logprobs=False, grammar=None):
+                   log=None, prefill="blas", constraints=None, return_logprobs=False, grammar=None, reference=None,
+                   alpha=None):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -1507,7 +1621,18 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     under the position rule, then the other attributes under the row's kind -- and cwlt_grammar_track keeps each
     song's position in its bar on the device, from where its prompt leaves it.  Combines with constraints (each mask
     row is intersected with the grammar's) and return_logprobs (lp_sampler is log q of the distribution each class was
-    drawn from).  None: nothing changes."""
+    drawn from).  None: nothing changes.
+
+    reference, alpha: draw from the blend of the model with a reference model: with x the model's logits
+    of one attribute and r the reference's, softmax(alpha x + (1 - alpha) r), i.e. pi^alpha pi_ref^(1 - alpha)
+    renormalised -- alpha = 1 is the model, 0 the reference, above 1 extrapolates.  alpha: a scalar, (n_songs,), (1, 6)
+    or (n_songs, 6) (compile_alpha).  A second session steps the reference on the same token buffer (and prefills the
+    same prompts with the same `prefill` kernel), cwlt_blend_logits writes the blended logits and the samplers,
+    constraints and grammar work on them as on a model's own; the seed is taken once, as without a reference, so
+    alpha = 1 gives bitwise the model's songs and alpha = 0 the reference's.  Under a blend the log-prob pair is
+    [..., 0] = log pi_alpha (the blended logits, temperature 1, no mask) and [..., 1] = log q of the sampler's
+    distribution built on them; each model's own log-probs come from score_songs without a blend.  The reference: same
+    classes, recurrent, eval(), f32, on the model's device, any width or depth.  One without the other is refused."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if prefill not in ("blas", "gemm"):
@@ -1534,8 +1659,11 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, cnt_bar, max_tokens)
     gtables = None if grammar is None else \
         compile_grammar(grammar, constraints, n_songs, list(model.n_token), bar_cond)
+    blended = _check_blend(model, reference, alpha, "generate_batch")
+    atable = compile_alpha(alpha, n_songs, A) if blended else None
     sess = DecodeSession(model, n_songs=n_songs, kernel="gemm")
     sess.reset()
+    ref = _reference_session(sess, reference) if blended else None
     temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
     mask = None
     if table is not None:
@@ -1547,7 +1675,8 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
                        ring=chunk, mask=mask, logprobs=return_logprobs,
                        grammar=None if grammar is None else
-                       _device_grammar(grammar, gtables, [grammar.beat_states(p)[1] for p in heads], sess.dev))
+                       _device_grammar(grammar, gtables, [grammar.beat_states(p)[1] for p in heads], sess.dev),
+                       ref=ref, alpha=torch.as_tensor(atable).to(sess.dev) if blended else None)
     if prompts is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
                        .view(n_songs, 1, A).to(sess.dev))
@@ -1557,7 +1686,8 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
         for i, p in enumerate(heads):
             toks[i, :len(p)] = p
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
-        loop.start(sess._prefill(toks, lengths, kernel=prefill))
+        loop.start(sess._prefill(toks, lengths, kernel=prefill),
+                   ref._prefill(toks, lengths, kernel=prefill) if blended else None)
     drawn = [[] for _ in range(n_songs)]
     lp_drawn = [[] for _ in range(n_songs)] if return_logprobs else None
     live = set(range(n_songs))
@@ -1641,14 +1771,16 @@ def _check_scoring_model(model, what="scoring"):
         raise RuntimeError("%s computes in f32: this model runs %s activations" % (what, model.compute_dtype))
 
 
-def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, prefill_rows, grammar, reference=None):
+def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, prefill_rows, grammar, reference=None,
+                 alpha=None):
     """What score_songs and policy_stats share: their checks, the constraint and grammar tables, then the songs in
     blocks of whole songs under prefill_rows token rows (at most SCORE_BLOCK_SONGS songs), each prefilled on a fresh
     scratch state with the heads on every row -- by `model`, and by `reference` (a second model over the same tokens)
     when given.  Yields per block (songs of the block, Lb, [logits (nb * Lb, n_logits) per model], targets (nb * Lb, A)
     int64 on the device: row t of a song holds song[t + 1], -1 on its last row and on padding, {"temperature", "top_p"},
     the constraint table keywords of ops.score_categorical ({} without constraints), (beat, order, gram, bar_attr) of
-    the grammar or None)."""
+    the grammar or None).  alpha (with reference; compile_alpha's forms, one row per song): the model's logits are
+    replaced by the blend's, alpha x + (1 - alpha) r row by row (cwlt_blend_logits, keyed by the row's song index)."""
     if sampler not in ("dqn", "categorical"):
         raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
     if kernel not in ("blas", "gemm"):
@@ -1667,8 +1799,11 @@ def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, p
     A = len(n_token)
     songs = _score_inputs(songs, mask, n_token)
     n = len(songs)
+    if alpha is not None and reference is None:
+        raise ValueError("alpha blends the model with a reference model: pass reference= as well")
     if n == 0:
         return
+    dalpha = None if alpha is None else torch.as_tensor(compile_alpha(alpha, n, A)).to(dev)
     rows_budget = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
     if rows_budget < 1:
         raise ValueError("prefill_rows must be >= 1, got %d" % rows_budget)
@@ -1710,6 +1845,9 @@ def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, p
                 lg = net.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
                                         logits="all")
                 lgs.append(lg.reshape(nb * Lb, -1))
+            if dalpha is not None:
+                lgs[0] = ops.blend_logits(lgs[0], lgs[1], n_token, dalpha, out=lgs[0],
+                                          key=torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb))
         m = {}
         if dmask is not None:
             m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
@@ -1722,7 +1860,7 @@ def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, p
 
 
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
-                prefill_rows=None, grammar=None):
+                prefill_rows=None, grammar=None, reference=None, alpha=None):
     """Log-likelihoods of given songs under the recurrent form, as generation samples them.
     -> list of (L_i - 1, 6, 2) float32 arrays; row t is about song[t + 1] given song[:t + 1] (pe[0] on every row, as
     DecodeSession.step and prefill compute it): [..., 0] the model log-prob log_softmax(logits_t[a])[song[t + 1, a]]
@@ -1745,10 +1883,19 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     grammar: a Grammar: row t + 1 is scored under the row grammar (cwlt_score_categorical_grammar), its kind that of
     song[t + 1]'s own bar-beat class and its position Grammar.beat_states(song)[0][t + 1]; an ill-formed row gets -inf
     in the sampler column of the offending attribute and a finite model column.
-    Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range."""
+    reference, alpha: score the songs under the blend of the model with a reference model (alpha's
+    forms: compile_alpha, one row per song): both models prefill the same blocks, cwlt_blend_logits replaces the
+    model's logits by alpha x + (1 - alpha) r, and [..., 0] is log pi_alpha (the blended logits, temperature 1, no
+    mask), [..., 1] log q of the sampler's distribution built on them -- what generate_batch / generate_stream(
+    reference=, alpha=, return_logprobs=True) return.  Each model's own log-probs come from a call without a blend.
+    Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range; reference
+    without alpha or the reverse, and a reference policy_stats would refuse."""
+    if (reference is None) != (alpha is None):
+        _check_blend(model, reference, alpha, "score_songs")
     out = []
-    for blk, Lb, (lg,), tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
-                                                               mask, prefill_rows, grammar):
+    for blk, Lb, lgs, tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
+                                                             mask, prefill_rows, grammar, reference, alpha):
+        lg = lgs[0]
         if gram is not None:
             lp = ops.score_categorical_grammar(lg, list(model.n_token), tgt, *gram, **settings, **m)
         else:
@@ -1759,7 +1906,7 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
 
 
 def policy_stats(model, word2event, songs, reference=None, sampler="categorical", constraints=None, kernel="gemm",
-                 mask=None, prefill_rows=None, grammar=None):
+                 mask=None, prefill_rows=None, grammar=None, alpha=None):
     """Entropy of the policy along given songs, and its KL against a reference model.
     -> list of (L_i - 1, 6, 2) float32 arrays, (L_i - 1, 6, 4) with `reference`; rows as in score_songs: row t is about
     the distribution of song[t + 1] given song[:t + 1].  In nats: [..., 0] H(p), p the model's softmax (temperature 1,
@@ -1775,10 +1922,14 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
     songs, their order and prefill_rows.  reference: a second model over the same vocabulary (any width or depth):
     recurrent, in eval(), f32, on the model's device; its prefill runs on the same blocks and one cwlt_policy_stats call
     per block takes both logits tensors.
-    Refused: what score_songs refuses, and a reference that fails the conditions above."""
+    alpha (with reference; compile_alpha's forms, one row per song): the stats of the BLENDED policy pi_alpha against
+    the reference: cwlt_blend_logits replaces the model's logits by alpha x + (1 - alpha) r before the
+    one cwlt_policy_stats call, so [..., 2] is KL(pi_alpha || pi_ref), the x-axis of the reward / KL frontier, and 0 at
+    alpha = 0.  alpha = 1 gives the stats without it; a reference without alpha keeps that meaning.
+    Refused: what score_songs refuses, a reference that fails the conditions above, alpha without a reference."""
     out = []
     for blk, Lb, lgs, tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
-                                                             mask, prefill_rows, grammar, reference):
+                                                             mask, prefill_rows, grammar, reference, alpha):
         bar_attr = 0 if gram is None else gram[3]               # without a grammar only the sign is read
         st = ops.policy_stats(lgs[0], list(model.n_token), None if reference is None else lgs[1],
                               bar_class=tgt[:, bar_attr].contiguous(), grammar=gram, **settings, **m)
@@ -1789,7 +1940,8 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
 
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
-             batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None):
+             batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None,
+             reference=None, alpha=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1804,9 +1956,18 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     generate_stream), with slots or batch_size only: the one-song path samples on the host.
     logprobs=True (with slots or batch_size only): save each song's drawn-row log-probs (return_logprobs of
     generate_stream / generate_batch) as get_<i>_logp.npy next to the song.
-    grammar: a Grammar (generate_batch, generate_stream), with slots or batch_size only, as constraints."""
+    grammar: a Grammar (generate_batch, generate_stream), with slots or batch_size only, as constraints.
+    reference, alpha: blend the model with a reference model at sampling time (generate_batch, generate_stream; DESIGN
+    §4.6j), with slots or batch_size only; a per-song alpha is cut per batch_size group like prompts."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if (reference is not None or alpha is not None) and batch_size is None and slots is None:
+        raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
+                         "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
+    atable = None
+    if reference is not None or alpha is not None:
+        _check_blend(model, reference, alpha, "generate")
+        atable = compile_alpha(alpha, n_songs, len(word2event))
     if logprobs and batch_size is None and slots is None:
         raise ValueError("log-probs come from the device samplers of generate_batch / generate_stream: pass batch_size "
                          "or slots (or score the songs with score_songs)")
@@ -1852,7 +2013,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         start = time.time()
         songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                 prompt=prompt, prompts=None if prompts is None else list(prompts),
-                                constraints=constraints, return_logprobs=logprobs, grammar=grammar)
+                                constraints=constraints, return_logprobs=logprobs, grammar=grammar,
+                                reference=reference, alpha=atable)
         record(0, songs, time.time() - start, "stream on %d slots" % int(slots))
     elif batch_size is not None:
         if int(batch_size) < 1:
@@ -1864,7 +2026,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                                    prompts=prompt if prompts is None else list(prompts[first:first + group]),
                                    constraints=list(constraints[first:first + group])
                                    if isinstance(constraints, (list, tuple)) else constraints,
-                                   return_logprobs=logprobs, grammar=grammar)
+                                   return_logprobs=logprobs, grammar=grammar, reference=reference,
+                                   alpha=atable if atable is None or len(atable) == 1 else atable[first:first + group])
             record(first, songs, time.time() - start, "batch of %d" % group)
     else:
         sess = DecodeSession(model)

@@ -1820,6 +1820,40 @@ def policy_stats(logits, n_class, ref_logits=None, temperature=None, top_p=None,
     return out
 
 
+def blend_logits(logits, ref_logits, n_class, alpha, key=None, out=None):
+    """out = alpha logits + (1 - alpha) ref_logits, attribute by attribute (cwlt_blend_logits): the logits
+    of pi^alpha pi_ref^(1 - alpha).  logits, ref_logits (rows, >= sum n_class) f32 with unit column strides and row
+    strides of their own; alpha (n_alpha, A) f32 on the device: row 0 when n_alpha == 1, else row key[n] ((rows,) int64;
+    None: n), a row whose key is outside [0, n_alpha) copied from logits.  out: None (a new (rows, sum n_class) tensor),
+    `logits` itself (in place), or a tensor that overlaps neither input; columns past sum n_class are left alone.
+    alpha = 1 returns logits and alpha = 0 ref_logits exactly.  Rows go through in launches of at most 2^20."""
+    fn, W, A = "blend_logits", sum(n_class), len(n_class)
+    for t, name in ((logits, "logits"), (ref_logits, "ref_logits")) + (() if out is None else ((out, "out"),)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < W or t.stride(1) != 1 or \
+                t.shape[0] != logits.shape[0] or t.device != logits.device:
+            raise ValueError("%s: %s must be (%d, >= %d) f32 with a unit column stride on the logits' device"
+                             % (fn, name, logits.shape[0], W))
+    rows = logits.shape[0]
+    if alpha.dtype != torch.float32 or alpha.dim() != 2 or alpha.shape[1] != A or alpha.shape[0] < 1 or \
+            not alpha.is_contiguous():
+        raise ValueError("%s: alpha must be a contiguous (n_alpha, %d) f32 tensor" % (fn, A))
+    if key is not None and (key.dtype != torch.int64 or key.numel() != rows or not key.is_contiguous()):
+        raise ValueError("%s: key must be a contiguous (rows,) int64 tensor" % fn)
+    if key is None and alpha.shape[0] not in (1, rows):
+        raise ValueError("%s: without a key alpha has one row or one per row (%d), got %d" % (fn, rows, alpha.shape[0]))
+    if out is None:
+        out = torch.empty((rows, W), dtype=torch.float32, device=logits.device)
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        # without a key the alpha row of row n is n: a later launch starts at its own rows of the table
+        al = alpha if key is not None or alpha.shape[0] == 1 else alpha[a:z]
+        _call("cwlt_blend_logits", _lib.dev(logits[a:z], "logits"), logits.stride(0),
+              _lib.dev(ref_logits[a:z], "ref_logits"), ref_logits.stride(0), _lib.int_array(n_class), A,
+              _lib.dev(al, "alpha"), al.shape[0], _lib.opt(_rows(key, a, z)), _lib.dev(out[a:z], "out"), out.stride(0),
+              z - a, _lib.stream_ptr())
+    return out
+
+
 def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):
     """The row grammar's position after a draw (cwlt_grammar_track): beat[n] (rows,) int64 moves by the bar-beat class
     of tokens (rows, A) int64 through order (int32: -1 Bar, k >= 0 Beat_k, else unchanged); with fresh / song (rows,)

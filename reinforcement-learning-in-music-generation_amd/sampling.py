@@ -150,6 +150,25 @@ def policy_stats_f64(logits, ref_logits=None, temperature=1.0, top_p=None, allow
     return np.array(out, dtype=np.float64)
 
 
+def blend_logits_f64(logits, ref_logits, n_class, alpha):
+    """Float64 restatement of cwlt_blend_logits: logits, ref_logits (rows, >= sum n_class) -> (rows, sum
+    n_class) float64, attribute a's columns alpha[n, a] x + (1 - alpha[n, a]) r, the logits of pi^alpha pi_ref^(1 -
+    alpha).  alpha: (1, A) (every row) or (rows, A), ALREADY rounded to f32 -- the alpha the kernel sees; 1 - alpha is
+    then formed exactly here and rounded once in the kernel."""
+    x = np.asarray(logits, dtype=np.float64)
+    r = np.asarray(ref_logits, dtype=np.float64)
+    al = np.asarray(alpha)
+    if al.dtype != np.float32:
+        raise TypeError("blend_logits_f64 takes alpha already rounded to float32, got %s" % al.dtype)
+    A, W = len(n_class), int(sum(n_class))
+    if x.ndim != 2 or r.ndim != 2 or len(r) != len(x) or x.shape[1] < W or r.shape[1] < W:
+        raise ValueError("logits and ref_logits must be (rows, >= %d)" % W)
+    if al.ndim != 2 or al.shape[1] != A or al.shape[0] not in (1, len(x)):
+        raise ValueError("alpha must be (1, %d) or (%d, %d)" % (A, len(x), A))
+    w = np.repeat(al.astype(np.float64), [int(n) for n in n_class], axis=1)         # (1 | rows, W): alpha per column
+    return w * x[:, :W] + (1.0 - w) * r[:, :W]
+
+
 def grammar_allowed_f64(bar_class, beat, order, gram, bar_attr, allowed=None):
     """The allowed sets of one row under the row grammar -> list of (n,) bool arrays, one per attribute.
     order: per class of attribute bar_attr, -2 class 0 (a note row), -1 a Bar class, k >= 0 Beat_k, -3 never allowed;
