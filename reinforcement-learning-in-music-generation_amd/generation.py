@@ -24,6 +24,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .draw_plan import (DQN_TEMPERATURE, DQN_TOP_P, Constraint, DeviceDraw, DrawPlan, Grammar,  # noqa: F401
+                        check_entry, compile_alpha, compile_constraints, compile_grammar)
 from .sampling import sample_cw
 
 INIT_CW = np.array([[0, 0, 1, 0, 0, 0]])          # "Bar" token, testing-no-type-cp.py:135-137
@@ -97,409 +99,6 @@ def bank_may_prefill(j, B, bank, assigned):
     the device's assigned counter, as copied back one chunk behind)."""
     nb = bank // B
     return j < nb or int(assigned) >= (j - nb + 1) * B
-
-
-class Constraint:
-    """What a song may contain, attribute by attribute, enforced inside the device sampler
-    (cwlt_sample_categorical_masked).  generate_batch / generate_stream / generate(batch_size=... | slots=...) take it
-    as `constraints=`.
-
-    allow: {attribute name (a key of word2event, e.g. "pitch"): events}, a static allowed set for every bar.
-    per_bar: {attribute name: [events, events, ...]}, a schedule whose entry i applies to bar i + 1.
-    Events are event names (values of word2event[attribute]) or class ids; a single name or id is one event.
-    Bars follow the generation bar rule: the count starts at 1 and counts the Bar tokens of the prompt's rows after the
-    first; a drawn row is constrained by the entry for the count BEFORE that row, and the count goes up after a row
-    whose bar-beat class is a Bar class -- so the Bar token that opens bar c + 1 is still drawn under bar c's entry.
-    Past the end of a schedule its last entry holds; cycle=True repeats the schedule instead.
-    keep_neutral=True: in every attribute the constraint restricts, class 0 and every class named "CONTI" stay allowed
-    (note rows carry 0 in tempo / chord / bar-beat, metrical rows 0 in pitch / duration / velocity and often CONTI in
-    tempo / chord), so a pitch range or a chord set does not force every row to be a note or a beat.
-    The draw: disallowed classes are -inf logits before the temperature, the max, the softmax and the nucleus (top_p is
-    taken over the renormalised allowed distribution).  Draw keys are unchanged, so a constraint that allows every
-    class gives bitwise the unconstrained songs.  Prompt rows are never constrained.
-    Refused (ValueError): unknown attribute or event names, ids out of range, an empty allowed set, an attribute in both
-    allow and per_bar."""
-
-    def __init__(self, word2event, allow=None, per_bar=None, cycle=False, keep_neutral=True):
-        self.keys = list(word2event.keys())
-        self.n_class = [len(word2event[k]) for k in self.keys]
-        self.cycle, self.keep_neutral = bool(cycle), bool(keep_neutral)
-        allow = {} if allow is None else dict(allow)
-        per_bar = {} if per_bar is None else dict(per_bar)
-        both = sorted(set(allow) & set(per_bar))
-        if both:
-            raise ValueError("attribute %r is in both allow and per_bar" % both[0])
-        self.static = {self._attr(name): self._allowed(word2event, name, ev) for name, ev in allow.items()}
-        self.schedule = {}
-        for name, entries in per_bar.items():
-            a = self._attr(name)
-            if isinstance(entries, (str, bytes)) or not hasattr(entries, "__len__") or len(entries) == 0:
-                raise ValueError("per_bar[%r] must be a non-empty list with one collection of events per bar" % (name,))
-            self.schedule[a] = [self._allowed(word2event, name, ev, i) for i, ev in enumerate(entries)]
-        self.bar_attr = self.keys.index("bar-beat") if "bar-beat" in self.keys else None
-        self.bar_ids = [] if self.bar_attr is None else \
-            [i for i, e in word2event["bar-beat"].items() if e == "Bar"]
-
-    def _attr(self, name):
-        if name not in self.keys:
-            raise ValueError("unknown attribute %r (attributes: %s)" % (name, ", ".join(map(str, self.keys))))
-        return self.keys.index(name)
-
-    def _allowed(self, word2event, name, events, bar=None):
-        where = "%r" % (name,) if bar is None else "%r, bar %d" % (name, bar + 1)
-        names = word2event[name]
-        n = len(names)
-        if isinstance(events, (str, bytes, int, np.integer)):
-            events = [events]
-        keep = np.zeros(n, dtype=bool)
-        count = 0
-        for ev in events:
-            count += 1
-            if isinstance(ev, (int, np.integer)) and not isinstance(ev, bool):
-                if not 0 <= int(ev) < n:
-                    raise ValueError("%s: class id %d out of range (%d classes)" % (where, int(ev), n))
-                keep[int(ev)] = True
-                continue
-            ids = [i for i, e in names.items() if e == ev]
-            if not ids:
-                raise ValueError("%s: unknown event %r" % (where, ev))
-            keep[ids] = True
-        if count == 0:
-            raise ValueError("%s: the allowed set is empty" % where)
-        if self.keep_neutral:
-            keep[0] = True
-            keep[[i for i, e in names.items() if e == "CONTI"]] = True
-        return keep
-
-    def allowed(self, bar):
-        """Per attribute, the (n_class,) bool array of classes allowed in bar `bar` (the count before the row)."""
-        out = []
-        i = max(int(bar) - 1, 0)
-        for a, n in enumerate(self.n_class):
-            if a in self.static:
-                out.append(self.static[a])
-            elif a in self.schedule:
-                sch = self.schedule[a]
-                out.append(sch[i % len(sch)] if self.cycle else sch[min(i, len(sch) - 1)])
-            else:
-                out.append(np.ones(n, dtype=bool))
-        return out
-
-    def mask_rows(self, bar_cond):
-        """The device table of this constraint for songs that end at bar `bar_cond` -> (R, ceil(sum n_class / 32))
-        uint32: row i is bar i + 1, class c of attribute a is bit sum(n_class[:a]) + c.  Without a schedule R = 1;
-        cycle=True expands the schedule to bar_cond - 1 rows (no kept row is drawn at a count >= bar_cond); otherwise R
-        is the longest schedule, cut at bar_cond - 1.  The device clamps to the last row."""
-        last = max(1, int(bar_cond) - 1)
-        if not self.schedule:
-            R = 1
-        elif self.cycle:
-            R = last
-        else:
-            R = min(max(len(v) for v in self.schedule.values()), last)
-        W = -(-sum(self.n_class) // 32)
-        bits = np.zeros((R, W * 32), dtype=bool)
-        for i in range(R):
-            row = np.concatenate(self.allowed(i + 1))
-            bits[i, :len(row)] = row
-        return np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(R, W)
-
-    def can_end(self, bar0, bar_cond):
-        """False when some bar in [bar0, bar_cond) allows no Bar class: a song there could never reach bar_cond."""
-        if self.bar_attr is None or (self.bar_attr not in self.static and self.bar_attr not in self.schedule):
-            return True
-        for b in range(int(bar0), int(bar_cond)):
-            if not self.allowed(b)[self.bar_attr][self.bar_ids].any():
-                return False
-        return True
-
-    def violations(self, song, bar0=1):
-        """Indices of the rows of `song` ((L, 6) drawn rows, e.g. generated[len(prompt):]) that break the constraint,
-        the first row drawn at bar count bar0 (1 from scratch; a prompt's own count after a prompt)."""
-        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
-        bad, b = [], int(bar0)
-        bar_ids = set(self.bar_ids)
-        for t, row in enumerate(song):
-            ok = self.allowed(b)
-            if any(not (0 <= int(c) < n and ok[a][int(c)]) for a, (c, n) in enumerate(zip(row, self.n_class))):
-                bad.append(t)
-            if self.bar_attr is not None and int(row[self.bar_attr]) in bar_ids:
-                b += 1
-        return bad
-
-
-def compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens):
-    """The device table of `constraints` (one Constraint for every song, or a list of n_songs entries, None =
-    unconstrained) -> None when no song is constrained, else (sched (n_songs, 2) int64 {first row, rows}, masks (R, W)
-    uint32).  One Constraint object's rows are shared by all songs that use it; an unconstrained song has 0 rows.
-    bar0s: each song's bar count before its first drawn row.  Without max_tokens a song whose bar-beat restriction
-    allows no Bar class in some bar it can reach would never end: refused."""
-    if isinstance(constraints, Constraint):
-        constraints = [constraints] * n_songs
-    elif isinstance(constraints, (list, tuple)):
-        if len(constraints) != n_songs:
-            raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
-    else:
-        raise ValueError("constraints must be a Constraint or a list of n_songs Constraint / None entries, got %s"
-                         % type(constraints).__name__)
-    if all(c is None for c in constraints):
-        return None
-    sched = np.zeros((n_songs, 2), dtype=np.int64)
-    parts, rows, ends, total = [], {}, {}, 0
-    for k, c in enumerate(constraints):
-        if c is None:
-            continue
-        if not isinstance(c, Constraint):
-            raise ValueError("constraints[%d] is a %s, not a Constraint or None" % (k, type(c).__name__))
-        if list(c.n_class) != list(n_token):
-            raise ValueError("constraints[%d] was built for classes %s, the model draws %s" % (k, c.n_class,
-                                                                                            list(n_token)))
-        if id(c) not in rows:
-            parts.append(c.mask_rows(bar_cond))
-            rows[id(c)] = (total, len(parts[-1]))
-            total += len(parts[-1])
-        sched[k] = rows[id(c)]
-        if max_tokens is None:
-            key = (id(c), int(bar0s[k]))
-            if key not in ends:
-                ends[key] = c.can_end(bar0s[k], bar_cond)
-            if not ends[key]:
-                raise ValueError("constraints[%d] allows no Bar in some bar before bar_cond=%d: the song could never "
-                                 "end (pass max_tokens, or allow a Bar class in every bar)" % (k, bar_cond))
-    return sched, np.concatenate(parts)
-
-
-def _device_constraints(table, dev):
-    """compile_constraints' table on the device: {"sched", "masks"} (int32 view of the mask words)."""
-    sched, masks = table
-    return {"sched": torch.as_tensor(sched).to(dev),
-            "masks": torch.as_tensor(np.ascontiguousarray(masks).view(np.int32)).to(dev)}
-
-
-class Grammar:
-    """The row grammar of CW songs, enforced inside the device sampler (cwlt_sample_categorical_grammar).
-    generate_batch / generate_stream / generate(batch_size=... | slots=...) / score_songs take it as `grammar=`.
-
-    A row is exactly one of three kinds, decided by its class in attribute `bar_attr`:
-      NOTE: bar_attr class 0; class 0 in every `metrical` attribute; any class but 0 in every `note` attribute;
-      BAR:  a bar_attr class named "Bar"; class 0 everywhere else;
-      BEAT: a bar_attr class Beat_<k>; any class but 0 (CONTI or a value) in every `metrical` attribute, class 0 in
-            every `note` attribute.
-    Position rule: each song carries `beat`: -1 after a Bar row, k after Beat_k, unchanged by note rows.  A Bar class
-    is always allowed, Beat_k when k > beat, class 0 (a note) when beat >= 0: beats ascend within a bar and no note
-    comes before a bar's first beat.  A prompt's rows are not constrained; they only move `beat`, from -1.
-    The bar-beat class is drawn first, under (the song's Constraint row, if any) AND (the position rule); every other
-    attribute under (constraint row) AND (the kind's row).  Masking, temperature, nucleus and keys are Constraint's.
-
-    The neutral class is class id 0 (as in Constraint); beat indices are parsed from the names Beat_<k>, or given as
-    beats={class id: index}.  Refused (ValueError): unknown attributes, an attribute in two roles, a bar_attr class that
-    is neither class 0, "Bar" nor a beat, no Bar class at all."""
-
-    NOTE, BAR, BEAT = 0, 1, 2
-
-    def __init__(self, word2event, bar_attr="bar-beat", metrical=("tempo", "chord"),
-                 note=("pitch", "duration", "velocity"), beats=None):
-        self.keys = list(word2event.keys())
-        self.n_class = [len(word2event[k]) for k in self.keys]
-        roles = [bar_attr] + list(metrical) + list(note)
-        for name in roles:
-            if name not in self.keys:
-                raise ValueError("unknown attribute %r (attributes: %s)" % (name, ", ".join(map(str, self.keys))))
-        if len(set(roles)) != len(roles):
-            raise ValueError("an attribute has two roles among bar_attr, metrical and note: %s" % (roles,))
-        self.bar_attr = self.keys.index(bar_attr)
-        self.metrical = [self.keys.index(k) for k in metrical]
-        self.note = [self.keys.index(k) for k in note]
-        beats = {} if beats is None else {int(c): int(k) for c, k in dict(beats).items()}
-        names = word2event[bar_attr]
-        n = self.n_class[self.bar_attr]
-        order = np.full(n, -3, dtype=np.int32)
-        order[0] = -2
-        for c in range(1, n):
-            name = names[c]
-            if c in beats:
-                if beats[c] < 0:
-                    raise ValueError("beats[%d] = %d: a beat index is >= 0" % (c, beats[c]))
-                order[c] = beats[c]
-            elif name == "Bar":
-                order[c] = -1
-            elif isinstance(name, str) and name.startswith("Beat_") and name[5:].isdigit():
-                order[c] = int(name[5:])
-            else:
-                raise ValueError("%s class %d (%r) is neither class 0, \"Bar\" nor Beat_<k>: pass beats={class id: "
-                                 "index}" % (bar_attr, c, name))
-        for c in beats:
-            if not 1 <= c < n:
-                raise ValueError("beats: class id %d outside 1..%d" % (c, n - 1))
-        if not (order == -1).any():
-            raise ValueError("%s has no class named \"Bar\"" % (bar_attr,))
-        self.order = order
-        self.bar_ids = [int(c) for c in np.nonzero(order == -1)[0]]
-
-    def kind(self, c):
-        """The kind of a row whose bar_attr class is c (NOTE / BAR / BEAT), None for a class outside the attribute."""
-        if not 0 <= int(c) < len(self.order):
-            return None
-        o = int(self.order[int(c)])
-        return self.NOTE if o == -2 else self.BAR if o == -1 else self.BEAT
-
-    def allowed(self, kind):
-        """Per attribute, the (n_class,) bool array of classes a row of `kind` may carry (bar_attr: the kind's own
-        classes; an attribute with no role: every class)."""
-        out = []
-        for a, n in enumerate(self.n_class):
-            ok = np.ones(n, dtype=bool)
-            if a == self.bar_attr:
-                ok = np.array([self.kind(c) == kind for c in range(n)])
-            elif (a in self.note and kind == self.NOTE) or (a in self.metrical and kind == self.BEAT):
-                ok[0] = False
-            elif a in self.note or a in self.metrical:
-                ok[1:] = False
-            out.append(ok)
-        return out
-
-    def position_allowed(self, beat):
-        """The (n_class[bar_attr],) bool array of bar_attr classes the position rule allows at `beat`."""
-        o, b = self.order.astype(np.int64), int(beat)
-        return (o == -1) | ((o >= 0) & (o > b)) | ((o == -2) & (b >= 0))
-
-    def tables(self):
-        """The device tables -> (order (n_class[bar_attr],) int32: -2 class 0, -1 Bar, k >= 0 Beat_k;
-        gram (3, ceil(sum n_class / 32)) uint32: rows NOTE, BAR, BEAT in the bit layout of Constraint.mask_rows)."""
-        W = -(-sum(self.n_class) // 32)
-        bits = np.zeros((3, W * 32), dtype=bool)
-        for kind in (self.NOTE, self.BAR, self.BEAT):
-            row = np.concatenate(self.allowed(kind))
-            bits[kind, :len(row)] = row
-        return self.order.copy(), np.packbits(bits, axis=1, bitorder="little").view("<u4").reshape(3, W)
-
-    def beat_states(self, song, beat=-1):
-        """The position before each row of `song` ((L, 6) rows) and after the last -> ((L,) int64, final), the first
-        row met at `beat` (-1: the start of a bar, what a song starts from)."""
-        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
-        c = song[:, self.bar_attr]
-        inside = (c >= 0) & (c < len(self.order))
-        o = np.where(inside, self.order.astype(np.int64)[np.where(inside, c, 0)], -3)
-        # after row t: the order of the last Bar / Beat row up to t, `beat` when there is none
-        last = np.maximum.accumulate(np.where(o >= -1, np.arange(len(song)), -1))
-        after = np.where(last >= 0, o[np.maximum(last, 0)], int(beat))
-        before = np.concatenate([[int(beat)], after[:-1]]).astype(np.int64)[:len(song)]
-        return before, int(after[-1]) if len(song) else int(beat)
-
-    def violations(self, song, n_prompt=0):
-        """Indices of the rows of `song` ((L, 6), its first n_prompt rows a prompt: tracked, not checked) that break
-        the kind table or the position rule."""
-        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
-        before, _ = self.beat_states(song)
-        c = song[:, self.bar_attr]
-        inside = (c >= 0) & (c < len(self.order))
-        o = np.where(inside, self.order.astype(np.int64)[np.where(inside, c, 0)], -3)
-        ok = (o == -1) | ((o >= 0) & (o > before)) | ((o == -2) & (before >= 0))
-        kind = np.where(o == -2, self.NOTE, np.where(o == -1, self.BAR, self.BEAT))
-        sets = [self.allowed(k) for k in (self.NOTE, self.BAR, self.BEAT)]
-        for a, n in enumerate(self.n_class):
-            if a == self.bar_attr:
-                continue
-            x = song[:, a]
-            table = np.stack([s[a] for s in sets])                     # (3, n_class[a])
-            ok &= (x >= 0) & (x < n) & table[kind, np.clip(x, 0, n - 1)]
-        return [int(t) for t in np.nonzero(~ok)[0] if t >= int(n_prompt)]
-
-
-def compile_grammar(grammar, constraints, n_songs, n_token, bar_cond):
-    """Grammar.tables() checked against the model's classes and the songs' constraints -> (order, gram).  Refused, so
-    that no reachable draw has an empty allowed set: a constraint row (any bar the device table holds) that leaves some
-    kind no class in some attribute, or allows no Bar class -- what the position rule always allows."""
-    if not isinstance(grammar, Grammar):
-        raise ValueError("grammar must be a Grammar, got %s" % type(grammar).__name__)
-    if list(grammar.n_class) != list(n_token):
-        raise ValueError("the grammar was built for classes %s, the model draws %s" % (grammar.n_class, list(n_token)))
-    if isinstance(constraints, Constraint):
-        constraints = [constraints]
-    seen = set()
-    kinds = [("note", grammar.allowed(Grammar.NOTE)), ("Bar", grammar.allowed(Grammar.BAR)),
-             ("beat", grammar.allowed(Grammar.BEAT))]
-    for c in constraints or []:
-        if not isinstance(c, Constraint) or id(c) in seen:
-            continue
-        seen.add(id(c))
-        if list(c.n_class) != list(n_token):
-            continue                                                   # compile_constraints refuses it
-        for i in range(len(c.mask_rows(bar_cond))):
-            ok = c.allowed(i + 1)
-            if not ok[grammar.bar_attr][grammar.bar_ids].any():
-                raise ValueError("grammar: the constraint allows no Bar class in bar %d, the one class the position "
-                                 "rule always allows" % (i + 1))
-            for name, sets in kinds:
-                for a, (x, y) in enumerate(zip(ok, sets)):
-                    if a != grammar.bar_attr and not (x & y).any():
-                        raise ValueError("grammar: in bar %d the constraint leaves a %s row no class of %r (class 0 "
-                                         "must stay allowed where the kind carries it: keep_neutral=True)"
-                                         % (i + 1, name, grammar.keys[a]))
-    return grammar.tables()
-
-
-def _device_grammar(grammar, tables, beat0s, dev):
-    """The grammar on the device: {"order", "gram" (int32 view), "beat0" (n_songs,) int64, "bar_attr"}."""
-    order, gram = tables
-    return {"order": torch.as_tensor(order).to(dev),
-            "gram": torch.as_tensor(np.ascontiguousarray(gram).view(np.int32)).to(dev),
-            "beat0": torch.as_tensor(np.asarray(beat0s, dtype=np.int64)).to(dev), "bar_attr": grammar.bar_attr}
-
-
-def compile_alpha(alpha, n_songs, n_attr):
-    """The blend weights of generation with a reference model -> the device table's host form, float32
-    (1, n_attr) (every song) or (n_songs, n_attr).  alpha: a scalar; (n_songs,) one value per song; (1, n_attr) one per
-    attribute; (n_songs, n_attr).  A one-dimensional alpha is always per song.  Entries are finite floats of any sign
-    or size: 1 is the model, 0 the reference, above 1 extrapolates.  Refused (ValueError): any other shape, a
-    non-finite or non-numeric entry."""
-    n_songs, A = int(n_songs), int(n_attr)
-    try:
-        a = None if alpha is None else np.asarray(alpha, dtype=np.float64)
-    except (TypeError, ValueError):
-        a = None
-    if a is None:
-        raise ValueError("alpha must be a number or an array of numbers, got %s" % type(alpha).__name__)
-    if a.ndim == 0:
-        a = np.full((1, A), float(a))
-    elif a.ndim == 1 and a.shape[0] == n_songs:
-        a = np.repeat(a[:, None], A, axis=1)
-    elif a.ndim != 2 or a.shape[1] != A or a.shape[0] not in (1, n_songs):
-        raise ValueError("alpha must be a scalar, (n_songs,) = (%d,), (1, %d) or (%d, %d), got shape %s"
-                         % (n_songs, A, n_songs, A, a.shape))
-    with np.errstate(over="ignore"):
-        out = a.astype(np.float32)
-    if not np.isfinite(out).all():
-        raise ValueError("alpha entries must be finite (in float32)")
-    return np.ascontiguousarray(out)
-
-
-def _check_blend(model, reference, alpha, where):
-    """The refusals of reference= / alpha= of a generation entry or score_songs -> True when `where` blends.  The two go
-    together, and the reference meets _song_blocks' conditions."""
-    if reference is None and alpha is None:
-        return False
-    if reference is None:
-        raise ValueError("%s: alpha blends the model with a reference model: pass reference= as well" % where)
-    if alpha is None:
-        raise ValueError("%s: reference= needs alpha= (1: the model, 0: the reference; the reference's own songs or "
-                         "scores come from calling %s on it)" % (where, where))
-    _check_scoring_model(reference, "the reference model: generation")
-    if list(reference.n_token) != list(model.n_token):
-        raise ValueError("the reference model has classes %s, the model %s" % (list(reference.n_token),
-                                                                              list(model.n_token)))
-    if next(reference.parameters()).device != next(model.parameters()).device:
-        raise ValueError("the reference model must sit on the model's device (%s)" % (next(model.parameters()).device,))
-    return True
-
-
-def _reference_session(sess, reference):
-    """The second decode state of a blended loop: a GEMM-step session of `reference` with sess's rows, stepping on the
-    token buffer sess's sampler writes.  Takes no seed."""
-    ref = DecodeSession(reference, n_songs=sess.n_songs, kernel="gemm")
-    ref.tok = sess.tok
-    ref.reset()
-    return ref
 
 
 class _FusedPlan:
@@ -800,6 +399,16 @@ class DecodeSession:
         res = self._host_logits.numpy()
         return res[0] if self.n_songs == 1 else res
 
+    def shadow(self, model):
+        """The second decode state of a blended loop: a GEMM-step session of `model` (the blend's reference; None: none)
+        with this session's rows, stepping on the token buffer this session's sampler writes.  Takes no seed."""
+        if model is None:
+            return None
+        ref = DecodeSession(model, n_songs=self.n_songs, kernel="gemm")
+        ref.tok = self.tok
+        ref.reset()
+        return ref
+
     def split(self, logits):
         outs, o = [], 0
         for n in self.n_token:
@@ -808,28 +417,26 @@ class DecodeSession:
         return outs
 
 
-def _draw_token(logits, n_token, tok, seed, temperature, top_p, counter=None, key=None, step=None, mask=None, logp=None,
-                out_counter=None, grammar=None, beat=None, song=None):
-    """One token's draw for every row of logits into tok (rows, A), by the one rule of both loops: under a grammar
-    (_device_grammar, position `beat`) cwlt_sample_categorical_grammar, else with a log-prob ring `logp` (row
-    *out_counter) cwlt_sample_categorical_logp, else with a mask ({"bar", "sched", "masks"}) ..._masked, else the plain
-    draw.  Keyed per row by key / step (the stream: song index, position in song), or by the row's slot at `counter`
-    (the batch loop, whose plain draw also writes row *counter of `song`)."""
-    kw = dict(counter=counter, key=key, step=step, temperature=temperature, top_p=top_p)
-    m = {} if mask is None else {k: mask[k] for k in ("bar", "sched", "masks")}
-    if grammar is not None:
-        ops.sample_categorical_grammar(logits, n_token, tok, seed, beat, grammar["order"], grammar["gram"],
-                                       grammar["bar_attr"], logp=logp,
-                                       out_counter=None if logp is None else out_counter, **m, **kw)
+def _draw_token(plan, logits, n_token, tok, seed, counter=None, key=None, step=None, bar=None, beat=None, logp=None,
+                out_counter=None, song=None):
+    """One token's draw for every row of logits into tok (rows, A), by the one rule of both loops, from `plan`
+    (DeviceDraw): under a grammar (at positions `beat`) cwlt_sample_categorical_grammar, else with a log-prob ring `logp`
+    (row *out_counter) ..._logp, else with a constraint table (at bar counts `bar`) ..._masked, else the plain draw.
+    Keyed per row by key / step (the stream: song index, position in song), or by the row's slot at `counter` (the
+    batch loop, whose plain draw also writes row *counter of `song`)."""
+    kw = dict(counter=counter, key=key, step=step, **plan.keywords(bar))
+    if plan.order is not None:
+        ops.sample_categorical_grammar(logits, n_token, tok, seed, *plan.grammar(beat), logp=logp,
+                                       out_counter=None if logp is None else out_counter, **kw)
     elif logp is not None:
-        ops.sample_categorical_logp(logits, n_token, tok, seed, logp, out_counter=out_counter, **m, **kw)
-    elif mask is not None:
-        ops.sample_categorical_masked(logits, n_token, tok, seed, m["bar"], m["sched"], m["masks"], **kw)
+        ops.sample_categorical_logp(logits, n_token, tok, seed, logp, out_counter=out_counter, **kw)
+    elif plan.sched is not None:
+        ops.sample_categorical_masked(logits, n_token, tok, seed, **kw)
     elif key is not None:
-        ops.sample_categorical_keyed(logits, n_token, tok, seed, key, step, temperature=temperature, top_p=top_p)
+        ops.sample_categorical_keyed(logits, n_token, tok, seed, key, step, **plan.keywords())
     else:
-        ops.sample_categorical(logits, n_token, tok, seed, counter=counter, song=song, temperature=temperature,
-                               top_p=top_p, slot_keys=True)
+        ops.sample_categorical(logits, n_token, tok, seed, counter=counter, song=song, slot_keys=True,
+                               **plan.keywords())
 
 
 def _enqueue_token(loop, name):
@@ -857,36 +464,31 @@ class _DeviceLoop:
     do not need capacity x n_songs rows; read each R-row stretch before the next R tokens overwrite it.  The draws are
     the same either way (they are keyed by the counter).
 
-    mask: constrained mode, {"sched", "masks"} (_device_constraints) and "bar" ((n_songs,) int64 device bar counts
-    before the next row), "bar_mask" ((n_class[2],) int32 Bar classes): the draw is cwlt_sample_categorical_masked,
-    then cwlt_count_bars advances the bar counts, both inside the captured token.
+    plan (DeviceDraw; None: the plain draw at temperature 1) says what the draw is (_draw_token); the loop keeps what
+    moves.  With a constraint table `bar`, (n_songs,) int64 bar counts before the next row, from plan.bar0s:
+    cwlt_count_bars advances them after the draw.  plan.logprobs: the draw also writes each drawn class's (model,
+    sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects.  With a grammar
+    `beat`, each song's position, from plan.beat0: cwlt_grammar_track moves it after cwlt_count_bars.  plan.ref,
+    plan.alpha (the blend): `ref` (DecodeSession.shadow) steps on the same token buffer right after the
+    model and cwlt_blend_logits (alpha's row n is song n) turns the model's logits into the blend's in place."""
 
-    logprobs=True: the draw is cwlt_sample_categorical_logp (the same tokens), which also writes each drawn class's
-    (model, sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects.
-
-    grammar: the row grammar (_device_grammar): the draw is cwlt_sample_categorical_grammar (masked and with log-probs
-    as above when asked), then cwlt_count_bars if constrained, then cwlt_grammar_track moves each song's position.
-
-    ref, alpha: the blend with a reference model: `ref` (_reference_session) steps on the same token
-    buffer right after the model, cwlt_blend_logits (alpha: the (1 | n_songs, A) f32 device table, row n song n) turns
-    the model's logits into the blend's in place, and the draw goes on as above.  None: the launches are today's."""
-
-    def __init__(self, sess, capacity, temperature=None, top_p=None, carry_memory=True, graph=None, ring=None,
-                 mask=None, logprobs=False, grammar=None, ref=None, alpha=None):
+    def __init__(self, sess, capacity, plan=None, carry_memory=True, graph=None, ring=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
-        self.ref, self.alpha = ref, alpha
-        self.mask = mask
-        self.grammar = grammar
-        self.beat = None if grammar is None else grammar["beat0"].clone()       # one song per row, in song order
+        self.plan = plan = DeviceDraw() if plan is None else plan
+        self.ref, self.bar, self.bar_mask = plan.ref, None, None
+        if plan.sched is not None:
+            self.bar = torch.as_tensor(np.asarray(plan.bar0s, dtype=np.int64)).to(sess.dev)
+            self.bar_mask = torch.as_tensor(plan.bar_mask).to(sess.dev)
+        self.beat = None if plan.order is None else plan.beat0.clone()          # one song per row, in song order
         self.A, self.N = len(sess.n_token), sess.n_songs
         self.ring = None if ring is None or int(ring) >= self.capacity else int(ring)
         rows = self.capacity if self.ring is None else self.ring
         self.song = torch.zeros((rows, self.N, self.A), dtype=torch.int64, device=sess.dev)
-        self.logp = torch.zeros((rows, self.N, self.A, 2), dtype=torch.float32, device=sess.dev) if logprobs else None
+        self.logp = torch.zeros((rows, self.N, self.A, 2), dtype=torch.float32, device=sess.dev) \
+            if plan.logprobs else None
         self.count = torch.zeros(1, dtype=torch.int64, device=sess.dev)
         if self.ring is not None:
             self.slot = torch.zeros(1, dtype=torch.int64, device=sess.dev)       # count % ring
-        self.temperature, self.top_p = temperature, top_p
         self.seed = ops.next_seed()                       # keyed from torch.manual_seed, like the dropout seeds
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
         self._graph, self.enqueued = None, 0
@@ -895,14 +497,13 @@ class _DeviceLoop:
         s = self.sess
         tok = s.tok.view(self.N, self.A)
         # the plain draw writes the song row itself; every other one, and a ring, takes a copy of the token buffer
-        fused = self.ring is None and self.mask is None and self.logp is None and self.grammar is None
-        _draw_token(logits, s.n_token, tok, self.seed, self.temperature, self.top_p, counter=self.count, mask=self.mask,
-                    logp=self.logp, out_counter=self.count, grammar=self.grammar, beat=self.beat,
-                    song=self.song if fused else None)
-        if self.mask is not None:
-            ops.count_bars(tok, 2, self.mask["bar_mask"], self.mask["bar"])
-        if self.grammar is not None:
-            ops.grammar_track(tok, self.grammar["bar_attr"], self.grammar["order"], self.beat)
+        fused = self.ring is None and self.bar is None and self.logp is None and self.beat is None
+        _draw_token(self.plan, logits, s.n_token, tok, self.seed, counter=self.count, bar=self.bar, beat=self.beat,
+                    logp=self.logp, out_counter=self.count, song=self.song if fused else None)
+        if self.bar is not None:
+            ops.count_bars(tok, 2, self.bar_mask, self.bar)
+        if self.beat is not None:
+            ops.grammar_track(tok, self.plan.bar_attr, self.plan.order, self.beat)
         if not fused:
             self.song.index_copy_(0, self.count if self.ring is None else self.slot, tok.view(1, self.N, self.A))
         if self.ring is not None:
@@ -913,7 +514,7 @@ class _DeviceLoop:
         """The blended logits, written over the model's (ref_logits None: the model's own, untouched)."""
         if ref_logits is None:
             return logits
-        return ops.blend_logits(logits, ref_logits, self.sess.n_token, self.alpha, out=logits)
+        return ops.blend_logits(logits, ref_logits, self.sess.n_token, self.plan.alpha, out=logits)
 
     def _one(self):
         s = self.sess
@@ -972,13 +573,13 @@ class _StreamLoop:
       the GEMM decode step on every slot;
       the refill: slots flagged fresh get the state and logits their new song starts from;
       the draw (_draw_token), each slot's keyed by (song index, position in song): cwlt_sample_categorical_keyed, or
-        the masked / log-prob / grammar entry when the stream has a mask (_device_constraints: the song's mask row for
-        the slot's bar count), log-probs or a grammar (_device_grammar: the row grammar at the slot's position);
+        the masked / log-prob / grammar entry when `plan` (DeviceDraw) has a constraint table (the song's mask row for
+        the slot's bar count), log-probs or a grammar (the row grammar at the slot's position);
       the advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count advanced, the
         song's end detected, finished slots handed the next song indices in slot order;
       cwlt_grammar_track (under a grammar): every slot's position after the advance.
     The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host.
-    logprobs=True: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
+    plan.logprobs: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
     log-probs into `lp_ring` (2 chunk, slots, A, 2) at the row ctl[0] selects -- the row of `ring` the advance writes --
     copied out behind the same event and filtered by the same song >= 0 mask as the token rows (`lp_parts`).
 
@@ -988,15 +589,15 @@ class _StreamLoop:
 
     n_ctl = 3
 
-    def __init__(self, sess, n_songs, seed, bar_mask, bar_cond, chunk, temperature=None, top_p=None, graph=None,
-                 mask=None, logprobs=False, grammar=None):
+    def __init__(self, sess, n_songs, seed, bar_mask, bar_cond, chunk, plan=None, graph=None):
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
         self.n_layer = len(sess.memory)
         self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
         self.z_floats = sess.memory[0][1][0].numel()             # one slot's Z (H x d)
-        self.seed, self.temperature, self.top_p = seed, temperature, top_p
+        self.seed = seed
+        self.plan = plan = DeviceDraw() if plan is None else plan
         self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
         self.bar_cond = int(bar_cond)
         # the slots' song, position in it, bar count and fresh flag (1: refill me): set by start(), then the device's
@@ -1005,13 +606,11 @@ class _StreamLoop:
         self.ctl = torch.zeros(self.n_ctl, dtype=torch.int64, device=dev)
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
-        self.mask = None if mask is None else dict(mask, bar=self.bar)
-        self.grammar = grammar
-        self.beat = None if grammar is None else torch.full((self.S,), -1, dtype=torch.int64, device=dev)
+        self.beat = None if plan.order is None else torch.full((self.S,), -1, dtype=torch.int64, device=dev)
         self.lp_ring = torch.zeros((2 * self.chunk, self.S, self.A, 2), dtype=torch.float32, device=dev) \
-            if logprobs else None
+            if plan.logprobs else None
         self._host_lp = [torch.zeros((self.chunk, self.S, self.A, 2), dtype=torch.float32).pin_memory()
-                         for _ in range(2)] if logprobs else None
+                         for _ in range(2)] if plan.logprobs else None
         self.lp_parts = []
         self._host_ctl = [torch.zeros(self.n_ctl, dtype=torch.int64).pin_memory() for _ in range(2)]
         self._events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1028,9 +627,9 @@ class _StreamLoop:
         rest = torch.where(slot < self.n_songs, torch.full_like(slot, wait), torch.full_like(slot, -1))
         self.song.copy_(torch.where(slot < first, slot, rest))
         self.fresh.copy_((slot < first).to(torch.int64))
-        if self.grammar is not None:
+        if self.beat is not None:
             k = min(self.S, self.n_songs)
-            self.beat[:k] = self.grammar["beat0"][:k]
+            self.beat[:k] = self.plan.beat0[:k]
         self.ctl.copy_(torch.tensor(ctl, dtype=torch.int64))
 
     def _one(self):
@@ -1038,18 +637,12 @@ class _StreamLoop:
         tok = s.tok.view(self.S, self.A)
         logits = s._device_step()
         self._refill(logits)
-        logits = self._blend(logits)
-        _draw_token(logits, s.n_token, tok, self.seed, self.temperature, self.top_p, key=self.song, step=self.pos,
-                    mask=self.mask, logp=self.lp_ring, out_counter=self.ctl, grammar=self.grammar, beat=self.beat)
+        _draw_token(self.plan, logits, s.n_token, tok, self.seed, key=self.song, step=self.pos, bar=self.bar,
+                    beat=self.beat, logp=self.lp_ring, out_counter=self.ctl)
         self._advance(tok)
-        if self.grammar is not None:
-            g = self.grammar
-            ops.grammar_track(tok, g["bar_attr"], g["order"], self.beat, fresh=self.fresh, song=self.song,
-                              beat0=g["beat0"])
-
-    def _blend(self, logits):
-        """Between the refill and the draw: the logits the draw reads (a form that blends overrides it)."""
-        return logits
+        if self.beat is not None:
+            ops.grammar_track(tok, self.plan.bar_attr, self.plan.order, self.beat, fresh=self.fresh, song=self.song,
+                              beat0=self.plan.beat0)
 
     def _read(self, h):
         """The rows of ring half h that belong to songs (waiting and idle slots write song < 0), and their log-probs
@@ -1111,29 +704,20 @@ class _SnapshotStreamLoop(_StreamLoop):
     """The stream whose songs all start from one snapshot (snap_state, snap_logits: _stream_snapshot), with one bar0 and
     one cap: cwlt_stream_refill and cwlt_stream_advance.
 
-    blend = (ref, ref_snap_state, ref_snap_logits, alpha): the blend with a reference model.  `ref`
-    (_reference_session) is a second pool of the same slots on the same token buffer, with the reference's own snapshot:
-    per token it steps and is refilled right after the model's pool, by the same fresh flags, then cwlt_blend_logits
-    (alpha: the (1 | n_songs, A) f32 device table, keyed by the slots' song indices -- an idle slot's row is copied)
+    plan.ref, plan.alpha with ref_snap = (state, logits): the blend with a reference model.  `ref`
+    (DecodeSession.shadow) is a second pool of the same slots on the same token buffer, with its own snapshot: per token
+    it steps and is refilled right after the model's pool, by the same fresh flags, then cwlt_blend_logits (alpha: the
+    (1 | n_songs, A) f32 device table, keyed by the slots' song indices -- an idle slot's row is copied)
     turns the model's logits into the blend's in place, and the draw, advance and grammar track go on as without it:
     still one stream and one linear captured graph per token."""
 
-    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk, blend=None,
-                 **kw):
+    def __init__(self, sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0, cap, chunk,
+                 ref_snap=None, **kw):
         super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
         self.snap_state, self.snap_logits = snap_state, snap_logits
         self.bar0, self.cap = int(bar0), int(cap)
         self.song_cap = self.cap
-        self.blend = blend
-
-    def _blend(self, logits):
-        if self.blend is None:
-            return logits
-        ref, snap_state, snap_logits, alpha = self.blend
-        ref_logits = ref._device_step()
-        ops.stream_refill(ref._state, snap_state, len(ref.memory), ref.memory[0][0][0].numel(),
-                          ref.memory[0][1][0].numel(), ref_logits, snap_logits, self.fresh)
-        return ops.blend_logits(logits, ref_logits, self.sess.n_token, alpha, key=self.song, out=logits)
+        self.ref_snap = ref_snap
 
     def start(self):
         """Slots 0, 1, ... take the first songs; slots past the last song idle."""
@@ -1144,6 +728,12 @@ class _SnapshotStreamLoop(_StreamLoop):
     def _refill(self, logits):
         ops.stream_refill(self.sess._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
                           self.snap_logits, self.fresh)
+        ref = self.plan.ref
+        if ref is not None:                                     # the reference's pool, then the blend over `logits`
+            ref_logits = ref._device_step()
+            ops.stream_refill(ref._state, self.ref_snap[0], len(ref.memory), ref.memory[0][0][0].numel(),
+                              ref.memory[0][1][0].numel(), ref_logits, self.ref_snap[1], self.fresh)
+            ops.blend_logits(logits, ref_logits, self.sess.n_token, self.plan.alpha, key=self.song, out=logits)
 
     def _advance(self, tok):
         ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
@@ -1300,18 +890,12 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                     return_logprobs=False, grammar=None, reference=None, alpha=None):
+                     return_logprobs=False, grammar=None, reference=None, alpha=None, where="generate_stream"):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
-    return_logprobs=True: -> ((songs, logprobs), stats)."""
-    if sampler not in ("dqn", "categorical"):
-        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
-    if model.training:
-        raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
-    if model.compute_dtype != torch.float32:
-        raise RuntimeError("the GEMM decode step computes in f32: this model runs %s activations (generate one song at "
-                           "a time with fused=False instead)" % model.compute_dtype)
+    return_logprobs=True: -> ((songs, logprobs), stats).  where: the entry the refusals name."""
+    check_entry(model, "generation", sampler)
     n_songs, slots, chunk = int(n_songs), int(slots), int(chunk)
     if n_songs < 1 or chunk < 1:
         raise ValueError("n_songs and chunk must be >= 1")
@@ -1324,24 +908,20 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     if prompt is not None and prompts is not None:
         raise ValueError("pass one shared prompt or per-song prompts, not both")
     A = len(word2event)
-    blended = _check_blend(model, reference, alpha, "generate_stream")
-    if blended and prompts is not None:
-        raise ValueError("generate_stream blends songs that start from one snapshot: per-song prompts would need a "
-                         "second bank and a second prefill schedule -- generate_batch(prompts=[...], reference=..., "
-                         "alpha=...) is the supported form")
-    atable = compile_alpha(alpha, n_songs, A) if blended else None
     start = time.perf_counter()
-    n_token = list(model.n_token)
     if prompts is not None:
-        heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens)
+        heads, bar0s, caps = _check_prompts(prompts, n_songs, word2event, list(model.n_token), bar_cond, max_tokens)
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
         heads, bar0s, caps = ([v[0]] * n_songs for v in _check_prompts(
             [INIT_CW[0] if prompt is None else prompt], 1, word2event, None, bar_cond, max_tokens))
-    table = None if constraints is None else \
-        compile_constraints(constraints, n_songs, n_token, bar_cond, bar0s, max_tokens)
-    gtables = None if grammar is None else compile_grammar(grammar, constraints, n_songs, n_token, bar_cond)
+    plan = DrawPlan(model, word2event, n_songs, where, sampler, constraints, grammar, reference, alpha, return_logprobs,
+                    bar_cond, bar0s, max_tokens, heads)
+    if plan.reference is not None and prompts is not None:
+        raise ValueError("generate_stream blends songs that start from one snapshot: per-song prompts would need a "
+                         "second bank and a second prefill schedule -- generate_batch(prompts=[...], reference=..., "
+                         "alpha=...) is the supported form")
     if prompts is None:
         start = time.perf_counter()                           # the shared form's clock starts after the host's compiles
     sess = DecodeSession(model, n_songs=slots, kernel="gemm")
@@ -1349,12 +929,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     seed = ops.next_seed()                                    # where generate_batch's _DeviceLoop takes it
     names = word2event["bar-beat"]
     bar_mask = [int(names[i] == "Bar") for i in range(sess.n_token[2])]       # every class named "Bar", not one id
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-    beat0s = None if grammar is None else [grammar.beat_states(h)[1] for h in heads] if prompts is not None else \
-        [grammar.beat_states(heads[0])[1]] * n_songs
-    kw = dict(temperature=temperature, top_p=top_p, graph=sess.use_graph,
-              mask=None if table is None else _device_constraints(table, sess.dev), logprobs=return_logprobs,
-              grammar=None if grammar is None else _device_grammar(grammar, gtables, beat0s, sess.dev))
+    # the reference's pool is made after the seed: it takes none
+    kw = dict(plan=DeviceDraw(plan, sess.dev, sess.shadow(plan.reference)), graph=sess.use_graph)
     if prompts is not None:
         per_entry = 4 * (sess._state.numel() // slots + sess.width + 2)
         B, bank = stream_bank_plan([len(h) for h in heads], slots, prefill_rows, bank, per_entry,
@@ -1362,14 +938,11 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
                                prefill_rows=prefill_rows, **kw)
     else:
-        snap_state, snap_logits = _stream_snapshot(model, None if prompt is None else heads[0], A)
-        blend = None
-        if blended:                                           # after the seed: the second pool takes none
-            blend = (_reference_session(sess, reference),
-                     *_stream_snapshot(reference, None if prompt is None else heads[0], A),
-                     torch.as_tensor(atable).to(sess.dev))
+        head = None if prompt is None else heads[0]
+        snap_state, snap_logits = _stream_snapshot(model, head, A)
+        ref_snap = None if plan.reference is None else _stream_snapshot(plan.reference, head, A)
         loop = _SnapshotStreamLoop(sess, snap_state, snap_logits, n_songs, seed, bar_mask, bar_cond, bar0s[0], caps[0],
-                                   chunk, blend=blend, **kw)
+                                   chunk, ref_snap=ref_snap, **kw)
     rows = loop.run()
     # rows are time-ordered and each song lives in one slot: a stable sort by song index keeps every song's order
     order = np.argsort(rows[:, 0], kind="stable")
@@ -1417,30 +990,13 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     entries, capped by the songs and a quarter of free device memory (one entry at d_model 512 / 12 layers / 8 heads
     is 12 x 8 x 64 x 65 x 4 B = 1.6 MB).  `bank` (a multiple of B) overrides the bank size.
 
-    constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained).
-    The host compiles them into one device table before the first token (compile_constraints) and each slot's draw
-    is masked by its song's row for the slot's bar count (cwlt_sample_categorical_masked); song k is still bitwise
-    song k of generate_batch(..., constraints=constraints).
-
-    return_logprobs=True: -> (songs, logprobs), logprobs[k] the (L_k - P_k, 6, 2) f32 log-probs of song k's drawn rows
-    (P_k its prompt's length), [..., 0] the model's and [..., 1] the sampler's (score_songs' layout), as
-    the device sampler wrote them (cwlt_sample_categorical_logp): bitwise those of generate_batch(...,
-    return_logprobs=True).  The songs are the same as without the flag.
-
-    grammar: a Grammar (the row grammar): every drawn row is a note, a Bar or a Beat row and beats ascend
-    within a bar.  Each slot's draw is cwlt_sample_categorical_grammar at the slot's position in its bar, which
-    cwlt_grammar_track moves after the advance (a song's own prompt sets where it starts).  Combines with constraints
-    and return_logprobs; song k is still bitwise song k of generate_batch(..., grammar=grammar).  None: nothing
-    changes.
-
-    reference, alpha: draw from the blend of the model with a reference model, softmax(alpha x + (1 - alpha) r) per
-    attribute (alpha's forms: compile_alpha, one row per song or one for all).  A second pool of `slots`
-    decode slots runs the reference on the same tokens and cwlt_blend_logits, keyed by each slot's song, writes the
-    blended logits the sampler reads; song k is bitwise song k of generate_batch(..., reference=, alpha=).  The log-prob
-    pair is then (log pi_alpha, log q) on the blended logits.  With the shared-snapshot forms only (no prompt, or one
-    shared prompt): per-song prompts are refused -- generate_batch(prompts=[...], reference=, alpha=) takes them.  The
-    reference: same classes, recurrent, eval(), f32, on the model's device, any width or depth.  None: nothing
-    changes."""
+    constraints, return_logprobs, grammar, reference / alpha: as in generate_batch, from the same plan (DrawPlan), and
+    song k -- its (L_k - P_k, 6, 2) log-probs too -- is bitwise song k of generate_batch with the same options.  Each
+    slot's draw is masked by its song's row for the slot's bar count and, under a grammar, made at the slot's position
+    in its bar, which cwlt_grammar_track moves after the advance (a song's own prompt sets where it starts).  Under a
+    blend a second pool of `slots` decode slots runs the reference on the same tokens and cwlt_blend_logits, keyed by
+    each slot's song, writes the blended logits the sampler reads: with the shared-snapshot forms only (no prompt, or
+    one shared prompt) -- per-song prompts are refused, generate_batch(prompts=[...], reference=, alpha=) takes them."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
                             prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs,
@@ -1489,11 +1045,6 @@ def categorical_rollout(model, token_count, init=None, carry_memory=False, graph
     return loop.tokens(0, token_count)[:, 0]
 
 
-# per-attribute sampler settings of forward_output_sampling (dqn_policy/model.py:281-286), attribute order
-DQN_TEMPERATURE = (1.2, 1.0, 1.2, 1.0, 2.0, 5.0)
-DQN_TOP_P = (0.9, 0.99, None, 0.9, 0.9, None)
-
-
 def _one_song(model, word2event, head, cnt_bar, bar_cond, max_tokens, log, session, device_sampling, chunk, prefill):
     """The body of inference_from_scratch / inference_from_prompt: `head`'s rows, then sampled rows until bar `bar_cond`
     begins or max_tokens rows.  prefill=True: head is a prompt, prefilled in one pass, the first draw from its logits;
@@ -1515,7 +1066,7 @@ def _one_song(model, word2event, head, cnt_bar, bar_cond, max_tokens, log, sessi
         if not prefill and len(head) != 1:
             raise RuntimeError("device-side sampling starts from a single initial token")
         cap = max_tokens - len(head) if max_tokens is not None else 16384
-        loop = _DeviceLoop(sess, cap, temperature=DQN_TEMPERATURE, top_p=DQN_TOP_P, carry_memory=True,
+        loop = _DeviceLoop(sess, cap, DeviceDraw(DrawPlan(model, word2event, 1, "inference", "dqn"), sess.dev),
                            graph=sess.use_graph)
         if prefill:
             loop.start(sess._prefill(head))
@@ -1607,77 +1158,58 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     (default) or "gemm" (batch invariant: song i's start depends on prompts[i] alone -- generate_stream(prompts=...)
     gives the same songs).
 
-    constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained),
-    compiled into one device table before the first token.  The loop then keeps each song's bar count on the device
-    (from its prompt's count; cwlt_count_bars after every draw) and masks each draw by the song's row for that count
-    (cwlt_sample_categorical_masked).  None: the unconstrained sampler, unchanged.
-
+    constraints: one Constraint for every song, or a list of n_songs Constraint / None entries (None: unconstrained).
+    The loop keeps each song's bar count on the device (from its prompt's count; cwlt_count_bars after every draw) and
+    masks each draw by the song's row for that count (cwlt_sample_categorical_masked).
     return_logprobs=True: -> (songs, logprobs), logprobs[i] the (L_i - P_i, 6, 2) f32 log-probs of song i's drawn rows
     (P_i its prompt's length; [..., 0] model, [..., 1] sampler, score_songs' layout), written by the
     device sampler itself (cwlt_sample_categorical_logp, into a float ring beside the token ring).  The songs are
     bitwise those drawn without the flag.
-
-    grammar: a Grammar (the row grammar): the draw is cwlt_sample_categorical_grammar -- bar-beat first,
-    under the position rule, then the other attributes under the row's kind -- and cwlt_grammar_track keeps each
-    song's position in its bar on the device, from where its prompt leaves it.  Combines with constraints (each mask
-    row is intersected with the grammar's) and return_logprobs (lp_sampler is log q of the distribution each class was
-    drawn from).  None: nothing changes.
-
+    grammar: a Grammar (the row grammar): the draw is cwlt_sample_categorical_grammar and
+    cwlt_grammar_track keeps each song's position in its bar on the device, from where its prompt leaves it.  Combines
+    with constraints (each mask row is intersected with the grammar's) and return_logprobs (lp_sampler is log q of the
+    distribution each class was drawn from).
     reference, alpha: draw from the blend of the model with a reference model: with x the model's logits
     of one attribute and r the reference's, softmax(alpha x + (1 - alpha) r), i.e. pi^alpha pi_ref^(1 - alpha)
-    renormalised -- alpha = 1 is the model, 0 the reference, above 1 extrapolates.  alpha: a scalar, (n_songs,), (1, 6)
-    or (n_songs, 6) (compile_alpha).  A second session steps the reference on the same token buffer (and prefills the
-    same prompts with the same `prefill` kernel), cwlt_blend_logits writes the blended logits and the samplers,
-    constraints and grammar work on them as on a model's own; the seed is taken once, as without a reference, so
-    alpha = 1 gives bitwise the model's songs and alpha = 0 the reference's.  Under a blend the log-prob pair is
+    renormalised (alpha's forms: compile_alpha).  A second session steps the reference on the same token buffer (and
+    prefills the same prompts with the same `prefill` kernel), cwlt_blend_logits writes the blended logits and the
+    samplers, constraints and grammar work on them as on a model's own; the seed is taken once, as without a reference,
+    so alpha = 1 gives bitwise the model's songs and alpha = 0 the reference's.  Under a blend the log-prob pair is
     [..., 0] = log pi_alpha (the blended logits, temperature 1, no mask) and [..., 1] = log q of the sampler's
     distribution built on them; each model's own log-probs come from score_songs without a blend.  The reference: same
-    classes, recurrent, eval(), f32, on the model's device, any width or depth.  One without the other is refused."""
-    if sampler not in ("dqn", "categorical"):
-        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
-    if prefill not in ("blas", "gemm"):
-        raise ValueError("prefill must be 'blas' or 'gemm', got %r" % (prefill,))
-    if model.training:
-        raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
-    if model.compute_dtype != torch.float32:
-        raise RuntimeError("the GEMM decode step computes in f32: this model runs %s activations (generate one song at "
-                           "a time with fused=False instead)" % model.compute_dtype)
-    n_songs, chunk = int(n_songs), int(chunk)
-    if n_songs < 1 or chunk < 1:
+    classes, recurrent, eval(), f32, on the model's device, any width or depth.  One without the other is refused.
+    All of these are compiled once, before the first token, into one plan (DrawPlan); None: nothing changes."""
+    heads, caps, plan = _batch_setup("generate_batch", model, word2event, n_songs, bar_cond, max_tokens, prompts,
+                                     sampler, chunk, prefill, constraints=constraints, logprobs=return_logprobs,
+                                     grammar=grammar, reference=reference, alpha=alpha)
+    return _run_batch(model, word2event, heads, caps, plan, bar_cond, int(chunk), log,
+                      None if prompts is None else prefill)
+
+
+def _batch_setup(where, model, word2event, n_songs, bar_cond, max_tokens, prompts, sampler, chunk, prefill, **draw):
+    """generate_batch's refusals, in the one order of the entries (names, model, counts, prompts, then the plan's) ->
+    (heads: every song's prompt rows, INIT_CW from scratch; caps: the rows each may draw; the DrawPlan)."""
+    check_entry(model, "generation", sampler, prefill=prefill)
+    n_songs = int(n_songs)
+    if n_songs < 1 or int(chunk) < 1:
         raise ValueError("n_songs and chunk must be >= 1")
-    A = len(word2event)
+    heads = prompts if isinstance(prompts, (list, tuple)) else [INIT_CW[0] if prompts is None else prompts] * n_songs
+    heads, bar0s, caps = _check_prompts(heads, n_songs, word2event, None, bar_cond, max_tokens)
+    return heads, caps, DrawPlan(model, word2event, n_songs, where, sampler, bar_cond=bar_cond, bar0s=bar0s,
+                                 max_tokens=max_tokens, heads=heads, **draw)
+
+
+def _run_batch(model, word2event, heads, caps, plan, bar_cond, chunk, log, prefill):
+    """generate_batch after its refusals: the songs of `plan` (one per entry of heads and caps), prefilled with kernel
+    `prefill` (None: from scratch, heads are INIT_CW) -> songs, or (songs, logprobs) under plan.logprobs."""
+    n_songs, return_logprobs, A = plan.n_songs, plan.logprobs, len(word2event)
     is_bar = lambda row: word2event["bar-beat"][int(row[2])] == "Bar"
-    if prompts is None:
-        heads = [INIT_CW[0]] * n_songs
-    elif isinstance(prompts, (list, tuple)):
-        heads = prompts
-    else:
-        heads = [prompts] * n_songs
-    heads, cnt_bar, caps = _check_prompts(heads, n_songs, word2event, None, bar_cond, max_tokens)
-    cap = max(caps)
-    table = None if constraints is None else \
-        compile_constraints(constraints, n_songs, list(model.n_token), bar_cond, cnt_bar, max_tokens)
-    gtables = None if grammar is None else \
-        compile_grammar(grammar, constraints, n_songs, list(model.n_token), bar_cond)
-    blended = _check_blend(model, reference, alpha, "generate_batch")
-    atable = compile_alpha(alpha, n_songs, A) if blended else None
+    cnt_bar, cap = list(plan.bar0s), max(caps)
     sess = DecodeSession(model, n_songs=n_songs, kernel="gemm")
     sess.reset()
-    ref = _reference_session(sess, reference) if blended else None
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
-    mask = None
-    if table is not None:
-        mask = _device_constraints(table, sess.dev)
-        mask["bar"] = torch.as_tensor(np.asarray(cnt_bar, dtype=np.int64)).to(sess.dev)
-        names = word2event["bar-beat"]
-        mask["bar_mask"] = torch.as_tensor(np.array([names[i] == "Bar" for i in range(sess.n_token[2])],
-                                                    dtype=np.int32)).to(sess.dev)
-    loop = _DeviceLoop(sess, cap, temperature=temperature, top_p=top_p, carry_memory=True, graph=sess.use_graph,
-                       ring=chunk, mask=mask, logprobs=return_logprobs,
-                       grammar=None if grammar is None else
-                       _device_grammar(grammar, gtables, [grammar.beat_states(p)[1] for p in heads], sess.dev),
-                       ref=ref, alpha=torch.as_tensor(atable).to(sess.dev) if blended else None)
-    if prompts is None:
+    ref = sess.shadow(plan.reference)                                 # before the loop: it takes the seed, this none
+    loop = _DeviceLoop(sess, cap, DeviceDraw(plan, sess.dev, ref), graph=sess.use_graph, ring=chunk)
+    if prefill is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (n_songs, 1)), dtype=torch.int64)
                        .view(n_songs, 1, A).to(sess.dev))
     else:
@@ -1687,7 +1219,7 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
             toks[i, :len(p)] = p
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
         loop.start(sess._prefill(toks, lengths, kernel=prefill),
-                   ref._prefill(toks, lengths, kernel=prefill) if blended else None)
+                   None if ref is None else ref._prefill(toks, lengths, kernel=prefill))
     drawn = [[] for _ in range(n_songs)]
     lp_drawn = [[] for _ in range(n_songs)] if return_logprobs else None
     live = set(range(n_songs))
@@ -1762,64 +1294,37 @@ def _score_inputs(songs, mask, n_token):
     return out
 
 
-def _check_scoring_model(model, what="scoring"):
-    if not getattr(model, "_recurrent", False):
-        raise RuntimeError("%s needs a model built with is_training=False (recurrent encoder)" % what)
-    if model.training:
-        raise RuntimeError("%s runs in eval() mode (agent_pretrain.py:657)" % what)
-    if model.compute_dtype != torch.float32:
-        raise RuntimeError("%s computes in f32: this model runs %s activations" % (what, model.compute_dtype))
+def _score_setup(where, model, word2event, songs, mask, sampler, kernel, **draw):
+    """The refusals score_songs and policy_stats share, in the entries' one order (names, model, songs, the plan's) ->
+    (_score_inputs' songs, their song_bar_counts, the DrawPlan: for the songs' largest bar count, and songs that end)."""
+    check_entry(model, "scoring", sampler, kernel=kernel)
+    songs = _score_inputs(songs, mask, list(model.n_token))
+    bars = [song_bar_counts(x, word2event) for x in songs]
+    top = max([int(b.max()) for b in bars if len(b)] + [1])
+    return songs, bars, DrawPlan(model, word2event, len(songs), where, sampler, bar_cond=top + 1,
+                                 max_tokens=max([len(x) for x in songs] + [1]), what="scoring", **draw)
 
 
-def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, prefill_rows, grammar, reference=None,
-                 alpha=None):
-    """What score_songs and policy_stats share: their checks, the constraint and grammar tables, then the songs in
-    blocks of whole songs under prefill_rows token rows (at most SCORE_BLOCK_SONGS songs), each prefilled on a fresh
-    scratch state with the heads on every row -- by `model`, and by `reference` (a second model over the same tokens)
-    when given.  Yields per block (songs of the block, Lb, [logits (nb * Lb, n_logits) per model], targets (nb * Lb, A)
-    int64 on the device: row t of a song holds song[t + 1], -1 on its last row and on padding, {"temperature", "top_p"},
-    the constraint table keywords of ops.score_categorical ({} without constraints), (beat, order, gram, bar_attr) of
-    the grammar or None).  alpha (with reference; compile_alpha's forms, one row per song): the model's logits are
-    replaced by the blend's, alpha x + (1 - alpha) r row by row (cwlt_blend_logits, keyed by the row's song index)."""
-    if sampler not in ("dqn", "categorical"):
-        raise ValueError("sampler must be 'dqn' or 'categorical', got %r" % (sampler,))
-    if kernel not in ("blas", "gemm"):
-        raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
-    _check_scoring_model(model)
-    n_token = list(model.n_token)
-    dev = next(model.parameters()).device
-    models = [model]
-    if reference is not None:
-        _check_scoring_model(reference, "the reference model: scoring")
-        if list(reference.n_token) != n_token:
-            raise ValueError("the reference model has classes %s, the model %s" % (list(reference.n_token), n_token))
-        if next(reference.parameters()).device != dev:
-            raise ValueError("the reference model must sit on the model's device (%s)" % (dev,))
-        models.append(reference)
-    A = len(n_token)
-    songs = _score_inputs(songs, mask, n_token)
-    n = len(songs)
-    if alpha is not None and reference is None:
-        raise ValueError("alpha blends the model with a reference model: pass reference= as well")
+def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
+    """What score_songs and policy_stats share after _score_setup: the songs in blocks of whole songs under prefill_rows
+    token rows (at most SCORE_BLOCK_SONGS songs), each prefilled on a fresh scratch state with the heads on every row --
+    by `model`, and by plan.reference (a second model over the same tokens) when there is one.  Yields per block (songs
+    of the block, Lb, [logits (nb * Lb, n_logits) per model], targets (nb * Lb, A) int64 on the device: row t of a song
+    holds song[t + 1], -1 on its last row and on padding, the plan on the device (DeviceDraw), and what each row adds
+    to it: its song index `key` (under constraints or a blend), bar count `bar` (under constraints) and position `beat`
+    (under a grammar), else None).  Under plan.alpha the model's logits are replaced by the blend's, alpha x +
+    (1 - alpha) r row by row (cwlt_blend_logits, keyed by `key`)."""
+    n_token, dev = plan.n_token, next(model.parameters()).device
+    models = [model] if plan.reference is None else [model, plan.reference]
+    A, n = len(n_token), len(songs)
     if n == 0:
         return
-    dalpha = None if alpha is None else torch.as_tensor(compile_alpha(alpha, n, A)).to(dev)
     rows_budget = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
     if rows_budget < 1:
         raise ValueError("prefill_rows must be >= 1, got %d" % rows_budget)
-    bars = [song_bar_counts(x, word2event) for x in songs]
-    dmask = None
-    if constraints is not None:
-        top = max([int(b.max()) for b in bars if len(b)] + [1])
-        # max_tokens = the longest song: every song ends, so compile_constraints' "could never end" check is skipped
-        table = compile_constraints(constraints, n, n_token, top + 1, [1] * n, max(len(x) for x in songs))
-        dmask = None if table is None else _device_constraints(table, dev)
-    dgram = None
-    if grammar is not None:
-        top = max([int(b.max()) for b in bars if len(b)] + [1])
-        dgram = _device_grammar(grammar, compile_grammar(grammar, constraints, n, n_token, top + 1), [], dev)
-        beats = [grammar.beat_states(x)[0] for x in songs]
-    temperature, top_p = (DQN_TEMPERATURE, DQN_TOP_P) if sampler == "dqn" else (None, None)
+    draw = DeviceDraw(plan, dev)
+    if draw.order is not None:
+        beats = [plan.grammar.beat_states(x)[0] for x in songs]
     per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
     for a0 in range(0, n, per):
         blk = songs[a0:a0 + per]
@@ -1832,9 +1337,11 @@ def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, p
             toks[i, :len(x)] = x
             tgt[i, :len(x) - 1] = x[1:]
             bar[i, :len(x) - 1] = bars[a0 + i]
-            if dgram is not None:
+            if draw.order is not None:
                 beat[i, :len(x) - 1] = beats[a0 + i][1:]
-        lgs = []
+        lgs, key = [], None
+        if draw.sched is not None or draw.alpha is not None:
+            key = torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb)
         with torch.no_grad():
             for net in models:
                 enc = net.transformer_encoder
@@ -1845,18 +1352,11 @@ def _song_blocks(model, word2event, songs, sampler, constraints, kernel, mask, p
                 lg = net.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
                                         logits="all")
                 lgs.append(lg.reshape(nb * Lb, -1))
-            if dalpha is not None:
-                lgs[0] = ops.blend_logits(lgs[0], lgs[1], n_token, dalpha, out=lgs[0],
-                                          key=torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb))
-        m = {}
-        if dmask is not None:
-            m = {"key": torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb),
-                 "bar": torch.as_tensor(bar.reshape(-1)).to(dev), "sched": dmask["sched"], "masks": dmask["masks"]}
-        gram = None
-        if dgram is not None:
-            gram = (torch.as_tensor(beat.reshape(-1)).to(dev), dgram["order"], dgram["gram"], dgram["bar_attr"])
-        yield (blk, Lb, lgs, torch.as_tensor(tgt.reshape(-1, A)).to(dev), {"temperature": temperature, "top_p": top_p},
-               m, gram)
+            if draw.alpha is not None:
+                lgs[0] = ops.blend_logits(lgs[0], lgs[1], n_token, draw.alpha, out=lgs[0], key=key)
+        dbar = None if draw.sched is None else torch.as_tensor(bar.reshape(-1)).to(dev)
+        dbeat = None if draw.order is None else torch.as_tensor(beat.reshape(-1)).to(dev)
+        yield blk, Lb, lgs, torch.as_tensor(tgt.reshape(-1, A)).to(dev), draw, key, dbar, dbeat
 
 
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
@@ -1890,16 +1390,15 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     reference=, alpha=, return_logprobs=True) return.  Each model's own log-probs come from a call without a blend.
     Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range; reference
     without alpha or the reverse, and a reference policy_stats would refuse."""
-    if (reference is None) != (alpha is None):
-        _check_blend(model, reference, alpha, "score_songs")
+    songs, bars, plan = _score_setup("score_songs", model, word2event, songs, mask, sampler, kernel,
+                                     constraints=constraints, grammar=grammar, reference=reference, alpha=alpha)
     out = []
-    for blk, Lb, lgs, tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
-                                                             mask, prefill_rows, grammar, reference, alpha):
-        lg = lgs[0]
-        if gram is not None:
-            lp = ops.score_categorical_grammar(lg, list(model.n_token), tgt, *gram, **settings, **m)
+    for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
+        kw = d.keywords(bar, key=key)
+        if d.order is not None:
+            lp = ops.score_categorical_grammar(lgs[0], plan.n_token, tgt, *d.grammar(beat), **kw)
         else:
-            lp = ops.score_categorical(lg, list(model.n_token), tgt, **settings, **m)
+            lp = ops.score_categorical(lgs[0], plan.n_token, tgt, **kw)
         lp = lp.view(len(blk), Lb, -1, 2).cpu().numpy()
         out.extend(lp[i, :len(x) - 1].copy() for i, x in enumerate(blk))
     return out
@@ -1927,12 +1426,14 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
     one cwlt_policy_stats call, so [..., 2] is KL(pi_alpha || pi_ref), the x-axis of the reward / KL frontier, and 0 at
     alpha = 0.  alpha = 1 gives the stats without it; a reference without alpha keeps that meaning.
     Refused: what score_songs refuses, a reference that fails the conditions above, alpha without a reference."""
+    songs, bars, plan = _score_setup("policy_stats", model, word2event, songs, mask, sampler, kernel,
+                                     constraints=constraints, grammar=grammar, reference=reference, alpha=alpha,
+                                     lone_reference=True)
     out = []
-    for blk, Lb, lgs, tgt, settings, m, gram in _song_blocks(model, word2event, songs, sampler, constraints, kernel,
-                                                             mask, prefill_rows, grammar, reference, alpha):
-        bar_attr = 0 if gram is None else gram[3]               # without a grammar only the sign is read
-        st = ops.policy_stats(lgs[0], list(model.n_token), None if reference is None else lgs[1],
-                              bar_class=tgt[:, bar_attr].contiguous(), grammar=gram, **settings, **m)
+    for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
+        st = ops.policy_stats(lgs[0], plan.n_token, None if reference is None else lgs[1], grammar=d.grammar(beat),
+                              bar_class=tgt[:, d.bar_attr or 0].contiguous(),     # no grammar: only the sign is read
+                              **d.keywords(bar, key=key))
         st = st.view(len(blk), Lb, *st.shape[1:]).cpu().numpy()
         out.extend(st[i, :len(x) - 1].copy() for i, x in enumerate(blk))
     return out
@@ -1952,34 +1453,25 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     the stream's wall time divided by n_songs.  Not together with batch_size.
     prompts: a list of n_songs (P_i, 6) arrays, song i continues prompts[i] (not together with prompt): on the stream
     with slots, each batch_size group with its own slice of the list, or one song at a time.
-    constraints: one Constraint for every song or a list of n_songs Constraint / None entries (generate_batch,
-    generate_stream), with slots or batch_size only: the one-song path samples on the host.
-    logprobs=True (with slots or batch_size only): save each song's drawn-row log-probs (return_logprobs of
-    generate_stream / generate_batch) as get_<i>_logp.npy next to the song.
-    grammar: a Grammar (generate_batch, generate_stream), with slots or batch_size only, as constraints.
-    reference, alpha: blend the model with a reference model at sampling time (generate_batch, generate_stream; DESIGN
-    §4.6j), with slots or batch_size only; a per-song alpha is cut per batch_size group like prompts."""
+    constraints, grammar, reference / alpha (generate_batch, generate_stream) and logprobs=True (their return_logprobs:
+    each song's drawn-row log-probs are saved as get_<i>_logp.npy next to the song): with slots or batch_size only, the
+    one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs)."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
         raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
                          "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
-    atable = None
-    if reference is not None or alpha is not None:
-        _check_blend(model, reference, alpha, "generate")
-        atable = compile_alpha(alpha, n_songs, len(word2event))
     if logprobs and batch_size is None and slots is None:
         raise ValueError("log-probs come from the device samplers of generate_batch / generate_stream: pass batch_size "
                          "or slots (or score the songs with score_songs)")
     if grammar is not None and batch_size is None and slots is None:
         raise ValueError("the row grammar runs in the device samplers of generate_batch / generate_stream: pass "
                          "batch_size or slots (one song: generate_batch(n_songs=1, grammar=...))")
-    if constraints is not None:
-        if batch_size is None and slots is None:
-            raise ValueError("constraints run in the device samplers of generate_batch / generate_stream: pass "
-                             "batch_size or slots (one song: generate_batch(n_songs=1, constraints=...))")
-        if isinstance(constraints, (list, tuple)) and len(constraints) != n_songs:
-            raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
+    if constraints is not None and batch_size is None and slots is None:
+        raise ValueError("constraints run in the device samplers of generate_batch / generate_stream: pass "
+                         "batch_size or slots (one song: generate_batch(n_songs=1, constraints=...))")
+    if isinstance(constraints, (list, tuple)) and len(constraints) != n_songs:
+        raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
     if prompts is not None:
         if prompt is not None:
             raise ValueError("pass one shared prompt or per-song prompts, not both")
@@ -2011,24 +1503,24 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
 
     if slots is not None:
         start = time.time()
-        songs = generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
-                                prompt=prompt, prompts=None if prompts is None else list(prompts),
-                                constraints=constraints, return_logprobs=logprobs, grammar=grammar,
-                                reference=reference, alpha=atable)
+        songs = _generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
+                                 prompt=prompt, prompts=None if prompts is None else list(prompts),
+                                 constraints=constraints, return_logprobs=logprobs, grammar=grammar,
+                                 reference=reference, alpha=alpha, where="generate")[0]
         record(0, songs, time.time() - start, "stream on %d slots" % int(slots))
     elif batch_size is not None:
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
+        given = prompt if prompts is None else list(prompts)
+        heads, caps, plan = _batch_setup("generate", model, word2event, n_songs, bar_cond, max_tokens, given, "dqn", 128,
+                                         "blas", constraints=constraints, logprobs=logprobs, grammar=grammar,
+                                         reference=reference, alpha=alpha)
         for first in range(0, n_songs, int(batch_size)):
-            group = min(int(batch_size), n_songs - first)
+            group = slice(first, first + int(batch_size))
             start = time.time()
-            songs = generate_batch(model, word2event, group, bar_cond=bar_cond, max_tokens=max_tokens,
-                                   prompts=prompt if prompts is None else list(prompts[first:first + group]),
-                                   constraints=list(constraints[first:first + group])
-                                   if isinstance(constraints, (list, tuple)) else constraints,
-                                   return_logprobs=logprobs, grammar=grammar, reference=reference,
-                                   alpha=atable if atable is None or len(atable) == 1 else atable[first:first + group])
-            record(first, songs, time.time() - start, "batch of %d" % group)
+            songs = _run_batch(model, word2event, heads[group], caps[group], plan.songs(first, len(heads[group])),
+                               bar_cond, 128, None, None if given is None else "blas")
+            record(first, songs, time.time() - start, "batch of %d" % len(heads[group]))
     else:
         sess = DecodeSession(model)
         for sidx in range(n_songs):

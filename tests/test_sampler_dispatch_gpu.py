@@ -19,7 +19,7 @@ from test_grammar_gpu import _constraints, _small_model, _word2event  # noqa: E4
 pytestmark = pytest.mark.gpu
 
 PRE = "cwlt_sample_categorical"
-PER_TOKEN = ("cwlt_sample_", "cwlt_score_", "cwlt_count_bars", "cwlt_grammar_track", "cwlt_stream_")
+PER_TOKEN = ("cwlt_sample_", "cwlt_score_", "cwlt_count_bars", "cwlt_grammar_track", "cwlt_stream_", "cwlt_blend_logits")
 N_SONGS, SLOTS, BAR_COND, MAX_TOKENS, CHUNK = 3, 2, 3, 12, 4
 PROMPTS = [np.array([[0, 0, 1, 0, 0, 0]]),
            np.array([[0, 0, 1, 0, 0, 0], [1, 1, 2, 0, 0, 0], [0, 0, 0, 5, 3, 2]]),
@@ -28,6 +28,10 @@ PROMPTS = [np.array([[0, 0, 1, 0, 0, 0]]),
 MODES = {"plain": (False, False, False), "constraints": (True, False, False), "logprobs": (False, True, False),
          "constraints+logprobs": (True, True, False), "grammar": (False, False, True),
          "grammar+constraints+logprobs": (True, True, True)}
+# the blend with a reference model, on top of the mode it names: one more launch in front of that mode's
+BLEND = {"blend": "plain", "blend+grammar+constraints+logprobs": "grammar+constraints+logprobs"}
+MODES.update({mode: MODES[base] for mode, base in BLEND.items()})
+ALPHA = [1.0, 0.0, 0.5]                                   # one value per song
 BATCH = {"plain": [PRE + "_slots"], "constraints": [PRE + "_masked", "cwlt_count_bars"], "logprobs": [PRE + "_logp"],
          "constraints+logprobs": [PRE + "_logp", "cwlt_count_bars"],
          "grammar": [PRE + "_grammar", "cwlt_grammar_track"],
@@ -35,11 +39,21 @@ BATCH = {"plain": [PRE + "_slots"], "constraints": [PRE + "_masked", "cwlt_count
 STREAM = {"plain": [PRE + "_keyed"], "constraints": [PRE + "_masked"], "logprobs": [PRE + "_logp"],
           "constraints+logprobs": [PRE + "_logp"], "grammar": [PRE + "_grammar"],
           "grammar+constraints+logprobs": [PRE + "_grammar"]}
+for _mode, _base in BLEND.items():
+    BATCH[_mode] = ["cwlt_blend_logits"] + BATCH[_base]
+    STREAM[_mode] = STREAM[_base]
 
 
 @pytest.fixture(scope="module")
 def net(cuda):
     return _small_model(cuda)
+
+
+@pytest.fixture(scope="module")
+def ref(cuda):
+    """A second small model, of another depth and fill: the blend's reference."""
+    from test_blend_gpu import _small_model as other
+    return other(cuda, 5, layers=1)
 
 
 @pytest.fixture
@@ -56,11 +70,12 @@ def calls(monkeypatch):
     return seen
 
 
-def _mode_kw(mode, w2e):
+def _mode_kw(mode, w2e, ref):
     cons, lp, gram = MODES[mode]
     musical, beats = _constraints(w2e)
+    blend = dict(reference=ref, alpha=ALPHA) if mode in BLEND else {}
     return dict(constraints=[musical, beats, None] if cons else None, return_logprobs=lp,
-                grammar=generation.Grammar(w2e) if gram else None)
+                grammar=generation.Grammar(w2e) if gram else None, **blend)
 
 
 def _per_token(calls):
@@ -74,9 +89,9 @@ def _check(seen, pattern, tokens):
 
 @pytest.mark.parametrize("prompted", [False, True], ids=["scratch", "prompts"])
 @pytest.mark.parametrize("mode", list(MODES))
-def test_generate_batch_entries(net, calls, mode, prompted):
+def test_generate_batch_entries(net, ref, calls, mode, prompted):
     w2e = _word2event()
-    kw = _mode_kw(mode, w2e)
+    kw = _mode_kw(mode, w2e, ref)
     torch.manual_seed(7)
     out = generation.generate_batch(net, w2e, N_SONGS, bar_cond=BAR_COND, max_tokens=MAX_TOKENS, chunk=CHUNK,
                                     prompts=PROMPTS if prompted else None, prefill="gemm", **kw)
@@ -89,18 +104,21 @@ def test_generate_batch_entries(net, calls, mode, prompted):
     _check(seen, BATCH[mode], tokens)
 
 
-@pytest.mark.parametrize("prompted", [False, True], ids=["shared", "prompts"])
-@pytest.mark.parametrize("mode", list(MODES))
-def test_generate_stream_entries(net, calls, mode, prompted):
+# the blended stream starts every song from one snapshot: it refuses per-song prompts, so those cases do not exist
+@pytest.mark.parametrize("mode,prompted", [pytest.param(m, p, id="%s-%s" % (m, "prompts" if p else "shared"))
+                                           for p in (False, True) for m in MODES if not (p and m in BLEND)])
+def test_generate_stream_entries(net, ref, calls, mode, prompted):
     w2e = _word2event()
-    kw = _mode_kw(mode, w2e)
+    kw = _mode_kw(mode, w2e, ref)
     start = dict(prompts=PROMPTS) if prompted else dict(prompt=PROMPTS[1])
     torch.manual_seed(7)
     _, stats = generation._generate_stream(net, w2e, N_SONGS, slots=SLOTS, bar_cond=BAR_COND, max_tokens=MAX_TOKENS,
                                            chunk=CHUNK, **start, **kw)
     assert not stats["graph"] and stats["steps"] >= 2 * CHUNK
     bank = "_bank" if prompted else ""
-    pattern = ["cwlt_stream_refill" + bank] + STREAM[mode] + ["cwlt_stream_advance" + bank] + \
+    # under a blend the reference's pool is refilled right after the model's, then the logits are blended
+    blend = ["cwlt_stream_refill", "cwlt_blend_logits"] if mode in BLEND else []
+    pattern = ["cwlt_stream_refill" + bank] + blend + STREAM[mode] + ["cwlt_stream_advance" + bank] + \
         (["cwlt_grammar_track"] if MODES[mode][2] else [])
     seen = _per_token(calls)
     assert "cwlt_count_bars" not in seen
