@@ -606,6 +606,42 @@ int cwlt_blend_logits(const float* logits, int64_t ld, const float* ref_logits, 
                       int n_attr, const float* alpha, int64_t n_alpha, const int64_t* key, float* out, int64_t ld_out,
                       int64_t rows, void* stream);
 
+/* Soft preferences: a logit bias per class and bar and a repetition penalty (csrc/prefer.hip).
+ * Tables, all DEVICE: sched (n_songs x 2 int64 {first bias row, rows}) with bias (bias_rows x ld_bias f32), both or
+ * neither; pen (n_songs x (2 n_attr + 1) f32: frequency[n_attr], presence[n_attr], decay); seen (one f32 per class in
+ * the sampler's column layout, row stride ld_seen).  n_class is a HOST array.  Every product and sum is rounded on its
+ * own in f32 (no fused multiply-add): the results are bitwise those of the same formulas in numpy float32.
+ *
+ * cwlt_prefer_logits: out[n, c] = ((logits[n, c] + b) - f * s) - (s > 0 ? p : 0) for row n of song k = key[n] (DEVICE
+ * int64 x rows; NULL: n).  b = bias[first + min(max(bar[n] - 1, 0), rows_k - 1), c] (bar DEVICE int64 x rows, NULL: the
+ * first row), the masked sampler's row rule; a song with 0 rows, or no bias table, adds no b.  s = seen[n, c]; f, p =
+ * pen[k, a], pen[k, n_attr + a] for the attribute a of c, taken as 0 for the attribute's class 0 and when seen is NULL
+ * (then s is 0 too).  A row with k outside [0, n_songs) -- an idle (-1) or waiting (-2) stream slot -- is copied.
+ * Layout and aliasing as cwlt_blend_logits: columns at or past sum n_class are neither read nor written, out may be
+ * logits itself, 16-byte accesses when every base given is 16-byte aligned and every stride a multiple of 4.
+ * Refused: a NULL logits, out or n_class, n_attr outside 1 .. 8, a class count outside 1 .. 256, a stride below sum
+ * n_class, n_songs < 1, rows < 1 or > 2^20, bias without sched or the reverse, seen without pen, out == seen or bias.
+ *
+ * cwlt_prefer_track, after a draw: seen[n, c] = seen[n, c] * decay_k + (tokens[n, a] == c - off_a ? 1 : 0), k =
+ * song[n] (NULL: n).  fresh, song (DEVICE int64 x rows) and seen0 (DEVICE f32, n_songs x sum n_class) are given together
+ * or all NULL, as in cwlt_grammar_track: a row with fresh[n] != 0 and song[n] >= 0 takes seen0[song[n]] instead (its
+ * token belongs to the song that just ended); a row with k outside [0, n_songs) is left alone.  rows <= 2^20.
+ *
+ * cwlt_prefer_scan, for given songs: tokens (nb * Lb) x n_attr int64, song i in rows [i Lb, (i + 1) Lb); writes
+ * seen_rows (nb * Lb x ld f32), row t of a song the state after its rows 0 .. t from a zero state -- what the logits
+ * of row t, which predict row t + 1, are penalised by.  The song's decay is that of k = key[i Lb] (DEVICE int64 x nb *
+ * Lb, the per-row key of cwlt_prefer_logits; NULL: i); k outside [0, n_songs): decay 0.  One thread per (song, column)
+ * walks the rows in order with the step of cwlt_prefer_track.  nb * Lb <= 2^20. */
+int cwlt_prefer_logits(const float* logits, int64_t ld, const int* n_class, int n_attr, const int64_t* key,
+                       const int64_t* bar, const int64_t* sched, int64_t n_songs, const float* bias,
+                       int64_t bias_rows, int64_t ld_bias, const float* pen, const float* seen, int64_t ld_seen,
+                       float* out, int64_t ld_out, int64_t rows, void* stream);
+int cwlt_prefer_track(const int64_t* tokens, int64_t rows, const int* n_class, int n_attr, const float* pen,
+                      int64_t n_songs, const int64_t* fresh, const int64_t* song, const float* seen0, float* seen,
+                      int64_t ld_seen, void* stream);
+int cwlt_prefer_scan(const int64_t* tokens, int64_t nb, int64_t Lb, const int* n_class, int n_attr, const float* pen,
+                     int64_t n_songs, const int64_t* key, float* seen_rows, int64_t ld, void* stream);
+
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,
  * cwlt_stream_refill, cwlt_sample_categorical_keyed and cwlt_stream_advance.

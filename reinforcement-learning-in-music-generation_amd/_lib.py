@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -138,6 +138,10 @@ _SIGNATURES = {
     "cwlt_policy_stats": [_ptr, _ptr, _ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _c_i64] + [_ptr] * 4
     + [_c_i64, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr],
     "cwlt_blend_logits": [_ptr, _c_i64, _ptr, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr],
+    "cwlt_prefer_logits": [_ptr, _c_i64, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr, _c_i64, _c_i64, _ptr, _ptr, _c_i64,
+                           _ptr, _c_i64, _c_i64, _ptr],
+    "cwlt_prefer_track": [_ptr, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr],
+    "cwlt_prefer_scan": [_ptr, _c_i64, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr],
     "cwlt_grammar_track": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr],
     "cwlt_count_bars": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr],
     "cwlt_stream_refill": [_ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr],

@@ -1,6 +1,6 @@
 """What the device sampler draws from, compiled once: the host side of generation's sampling options.
-`Constraint`, `Grammar` and the compilers turn the options into host tables; `DrawPlan` is the one place that calls
-them and makes every refusal for them, before any device work.  Each entry of generation.py builds one plan,
+`Constraint`, `Grammar`, `Preference` and the compilers turn the options into host tables; `DrawPlan` is the one place
+that calls them and makes every refusal for them, before any device work.  Each entry of generation.py builds one plan,
 `DeviceDraw(plan, dev)` puts it on the session's device once, and the token loops, `_draw_token` and the scorers read
 that object.  Nothing here needs a GPU, a DecodeSession or ops; only `DeviceDraw` creates device tensors."""
 import copy
@@ -373,6 +373,190 @@ def compile_alpha(alpha, n_songs, n_attr):
     return np.ascontiguousarray(out)
 
 
+class Preference:
+    """What a song should rather contain: soft terms on the logits, added by cwlt_prefer_logits in front of the
+    unchanged device samplers.  generate_batch / generate_stream / generate(batch_size=... | slots=...) /
+    score_songs / policy_stats take it as `preferences=`.  A Constraint forbids; a Preference only moves mass.
+
+    bias: {attribute name: {event name or class id: float}}, a static additive logit bias for every bar.
+    per_bar: {attribute name: [{event: float}, ...]}, a schedule whose entry i applies to bar i + 1, under the generation
+    bar rule exactly as Constraint states it: the count used is the one before the row, a Bar token is drawn under the
+    bar it closes, past the end of a schedule its last entry holds, cycle=True repeats the schedule.  Classes not named
+    get 0.  Event names and ids resolve as in Constraint.
+    repeat: {attribute name: frequency} or {attribute name: (frequency, presence)}, the repetition penalty.  Each song
+    carries `seen`, one f32 per class of every attribute (sum n_class wide, the sampler's column layout): after every
+    row of the song, prompt rows included, seen = seen * decay + hit, hit 1 at the class the row carries in each
+    attribute -- as a prompt's rows move the grammar's `beat` without being constrained.  The logit of class c != 0 of
+    attribute a is lowered by frequency[a] * seen[c] + (presence[a] if seen[c] > 0 else 0).  Class 0 of every attribute,
+    the neutral class every note row carries in tempo / chord / bar-beat and every metrical row in pitch / duration /
+    velocity, is never penalised (its `seen` is still tracked).  decay in (0, 1]: 1 counts, below 1 forgets.
+    Refused (ValueError): unknown attribute or event names, ids out of range, an attribute in both bias and per_bar, an
+    empty per_bar list, any value not finite in float32 (a hard ban is a Constraint's job), decay outside (0, 1]."""
+
+    def __init__(self, word2event, bias=None, per_bar=None, cycle=False, repeat=None, decay=1.0):
+        self.keys = list(word2event.keys())
+        self.n_class = [len(word2event[k]) for k in self.keys]
+        self.cycle = bool(cycle)
+        bias = {} if bias is None else dict(bias)
+        per_bar = {} if per_bar is None else dict(per_bar)
+        both = sorted(set(bias) & set(per_bar))
+        if both:
+            raise ValueError("attribute %r is in both bias and per_bar" % both[0])
+        self.static = {self._attr(name): self._values(word2event, name, ev) for name, ev in bias.items()}
+        self.schedule = {}
+        for name, entries in per_bar.items():
+            a = self._attr(name)
+            if isinstance(entries, (str, bytes, dict)) or not hasattr(entries, "__len__") or len(entries) == 0:
+                raise ValueError("per_bar[%r] must be a non-empty list with one {event: bias} mapping per bar" % (name,))
+            self.schedule[a] = [self._values(word2event, name, ev, i) for i, ev in enumerate(entries)]
+        A = len(self.keys)
+        self.frequency, self.presence = np.zeros(A, dtype=np.float32), np.zeros(A, dtype=np.float32)
+        for name, value in ({} if repeat is None else dict(repeat)).items():
+            a = self._attr(name)
+            pair = tuple(value) if isinstance(value, (tuple, list)) else (value, 0.0)
+            if len(pair) != 2:
+                raise ValueError("repeat[%r] must be a frequency or a (frequency, presence) pair" % (name,))
+            self.frequency[a] = self._finite(pair[0], "repeat[%r]: the frequency penalty" % (name,))
+            self.presence[a] = self._finite(pair[1], "repeat[%r]: the presence penalty" % (name,))
+        self.decay = self._finite(decay, "decay")
+        if not 0.0 < float(self.decay) <= 1.0:
+            raise ValueError("decay must lie in (0, 1] (in float32), got %r" % (decay,))
+
+    def _attr(self, name):
+        if name not in self.keys:
+            raise ValueError("unknown attribute %r (attributes: %s)" % (name, ", ".join(map(str, self.keys))))
+        return self.keys.index(name)
+
+    @staticmethod
+    def _finite(value, what):
+        try:
+            with np.errstate(over="ignore"):
+                v = np.float32(value)
+        except (TypeError, ValueError):
+            v = np.float32(np.nan)
+        if isinstance(value, (bool, str, bytes)) or not np.isfinite(v):
+            raise ValueError("%s must be a number finite in float32, got %r (a hard ban is a Constraint's job)"
+                             % (what, value))
+        return v
+
+    def _values(self, word2event, name, events, bar=None):
+        where = "%r" % (name,) if bar is None else "%r, bar %d" % (name, bar + 1)
+        names = word2event[name]
+        n = len(names)
+        if not hasattr(events, "items"):
+            raise ValueError("%s: the bias is a mapping {event name or class id: float}, got %s"
+                             % (where, type(events).__name__))
+        row = np.zeros(n, dtype=np.float32)
+        for ev, value in events.items():
+            v = self._finite(value, "%s: the bias of %r" % (where, ev))
+            if isinstance(ev, (int, np.integer)) and not isinstance(ev, bool):
+                if not 0 <= int(ev) < n:
+                    raise ValueError("%s: class id %d out of range (%d classes)" % (where, int(ev), n))
+                row[int(ev)] = v
+                continue
+            ids = [i for i, e in names.items() if e == ev]
+            if not ids:
+                raise ValueError("%s: unknown event %r" % (where, ev))
+            row[ids] = v
+        return row
+
+    @property
+    def has_bias(self):
+        return bool(self.static or self.schedule)
+
+    @property
+    def has_penalty(self):
+        return bool(self.frequency.any() or self.presence.any())
+
+    def bias_row(self, bar):
+        """The (sum n_class,) f32 bias of a row drawn at bar count `bar` (the count before the row)."""
+        out = []
+        i = max(int(bar) - 1, 0)
+        for a, n in enumerate(self.n_class):
+            if a in self.static:
+                out.append(self.static[a])
+            elif a in self.schedule:
+                sch = self.schedule[a]
+                out.append(sch[i % len(sch)] if self.cycle else sch[min(i, len(sch) - 1)])
+            else:
+                out.append(np.zeros(n, dtype=np.float32))
+        return np.concatenate(out).astype(np.float32)
+
+    def bias_rows(self, bar_cond):
+        """The device table of this preference's bias for songs that end at bar `bar_cond` -> (R, sum n_class) f32, row i
+        is bar i + 1, R by the rule of Constraint.mask_rows: 1 without a schedule, bar_cond - 1 under cycle=True, else
+        the longest schedule cut at bar_cond - 1.  The device clamps to the last row."""
+        last = max(1, int(bar_cond) - 1)
+        if not self.schedule:
+            R = 1
+        elif self.cycle:
+            R = last
+        else:
+            R = min(max(len(v) for v in self.schedule.values()), last)
+        return np.stack([self.bias_row(i + 1) for i in range(R)])
+
+    def penalties(self):
+        """(2 A + 1,) f32: frequency[A], presence[A], decay -- one row of the device's penalty table."""
+        return np.concatenate([self.frequency, self.presence, [self.decay]]).astype(np.float32)
+
+    def seen_states(self, song):
+        """The repetition state after each row of `song` ((L, A) rows) -> (L, sum n_class) f32, from a zero state, in
+        np.float32 with the product and the sum as two separate operations: what cwlt_prefer_track and cwlt_prefer_scan
+        compute, bitwise.  Row L - 1 of a prompt is the seen0 its song starts from."""
+        song = np.asarray(song, dtype=np.int64).reshape(-1, len(self.n_class))
+        off = np.concatenate([[0], np.cumsum(self.n_class)[:-1]]).astype(np.int64)
+        W = int(sum(self.n_class))
+        out = np.zeros((len(song), W), dtype=np.float32)
+        s = np.zeros(W, dtype=np.float32)
+        inside = (song >= 0) & (song < np.asarray(self.n_class))
+        for t, row in enumerate(song):
+            hit = np.zeros(W, dtype=np.float32)
+            hit[(off + row)[inside[t]]] = 1.0
+            s = s * self.decay
+            s = s + hit
+            out[t] = s
+        return out
+
+
+def compile_preferences(preferences, n_songs, n_token, bar_cond):
+    """The device tables of `preferences` (one Preference for every song, or a list of n_songs entries, None = none) ->
+    None when no song has a preference, else (sched (n_songs, 2) int64 {first bias row, rows}, bias (R, sum n_class)
+    f32, pen (n_songs, 2 A + 1) f32 {frequency, presence, decay}).  One Preference object's bias rows are shared by all
+    songs that use it; a song without a bias has 0 rows, a song without a preference an all-zero pen row."""
+    if isinstance(preferences, Preference):
+        preferences = [preferences] * n_songs
+    elif isinstance(preferences, (list, tuple)):
+        if len(preferences) != n_songs:
+            raise ValueError("preferences: %d entries for %d songs" % (len(preferences), n_songs))
+    else:
+        raise ValueError("preferences must be a Preference or a list of n_songs Preference / None entries, got %s"
+                         % type(preferences).__name__)
+    if all(p is None for p in preferences):
+        return None
+    W, A = int(sum(n_token)), len(n_token)
+    sched = np.zeros((n_songs, 2), dtype=np.int64)
+    pen = np.zeros((n_songs, 2 * A + 1), dtype=np.float32)
+    parts, rows, total = [], {}, 0
+    for k, p in enumerate(preferences):
+        if p is None:
+            continue
+        if not isinstance(p, Preference):
+            raise ValueError("preferences[%d] is a %s, not a Preference or None" % (k, type(p).__name__))
+        if list(p.n_class) != list(n_token):
+            raise ValueError("preferences[%d] was built for classes %s, the model draws %s" % (k, p.n_class,
+                                                                                            list(n_token)))
+        pen[k] = p.penalties()
+        if not p.has_bias:
+            continue
+        if id(p) not in rows:
+            parts.append(p.bias_rows(bar_cond))
+            rows[id(p)] = (total, len(parts[-1]))
+            total += len(parts[-1])
+        sched[k] = rows[id(p)]
+    bias = np.concatenate(parts) if parts else np.zeros((0, W), dtype=np.float32)
+    return sched, np.ascontiguousarray(bias, dtype=np.float32), pen
+
+
 def sampler_settings(sampler):
     """sampler -> (temperature, top_p) per attribute: "dqn" forward_output_sampling's, "categorical" the plain draw."""
     if sampler not in ("dqn", "categorical"):
@@ -416,17 +600,24 @@ class DrawPlan:
     under a grammar beat0s, its position there (after its `heads` entry; no heads: none, a scorer's rows carry theirs).
     bar_cond, bar0s, max_tokens: compile_constraints'; the scorers pass their largest bar count + 1, [1] * n and the
     longest song (a given song ends: "could never end" is no refusal).  what: "generation" or "scoring", in the
-    reference's refusals.  lone_reference (policy_stats): a reference needs no alpha."""
+    reference's refusals.  lone_reference (policy_stats): a reference needs no alpha.
+    preferences: prefer = compile_preferences' (sched, bias, pen) or None; seen0s, (n_songs, sum n_class)
+    f32, each song's repetition state after its `heads` entry (Preference.seen_states; zeros without a preference), None
+    when no song has a non-zero penalty or there are no heads (a scorer's rows carry theirs); bar_mask is then also set
+    when some song's bias schedule has more than one row, so that a loop can count bars for it.  Without preferences
+    every other field is what it was."""
 
     def __init__(self, model, word2event, n_songs, where, sampler="categorical", constraints=None, grammar=None,
                  reference=None, alpha=None, logprobs=False, bar_cond=None, bar0s=None, max_tokens=None, heads=None,
-                 what="generation", lone_reference=False):
+                 what="generation", lone_reference=False, preferences=None):
         self.n_token, self.n_songs = list(model.n_token), int(n_songs)
         self.temperature, self.top_p = sampler_settings(sampler)
         self.logprobs, self.reference = bool(logprobs), reference
         self.constraints, self.grammar, self.bar_cond, self.max_tokens = constraints, grammar, bar_cond, max_tokens
         self.bar0s = [1] * self.n_songs if bar0s is None else list(bar0s)
         self.table = self.bar_mask = self.gram = self.bar_attr = self.beat0s = self.alpha = None
+        self.preferences, self.heads, self.prefer, self.seen0s = preferences, heads, None, None
+        self._bar_names = None if "bar-beat" not in word2event else word2event["bar-beat"]
         if alpha is not None and reference is None:
             raise ValueError("%salpha blends the model with a reference model: pass reference= as well"
                              % ("" if lone_reference else where + ": "))
@@ -441,22 +632,55 @@ class DrawPlan:
             self.alpha = compile_alpha(alpha, self.n_songs, len(self.n_token))
         self._compile_constraints()
         if self.table is not None:
-            names = word2event["bar-beat"]
-            self.bar_mask = np.array([names[i] == "Bar" for i in range(self.n_token[2])], dtype=np.int32)
+            self.bar_mask = self._bar_classes()
         if grammar is not None:
             self.gram = compile_grammar(grammar, constraints, self.n_songs, self.n_token, bar_cond)
             self.bar_attr = grammar.bar_attr
             at = {}                                              # one shared prompt: one walk over it
             self.beat0s = [] if heads is None else \
                 [at[id(h)] if id(h) in at else at.setdefault(id(h), grammar.beat_states(h)[1]) for h in heads]
+        if preferences is not None:
+            self._compile_preferences()
+
+    def _bar_classes(self):
+        names = self._bar_names
+        return np.array([names[i] == "Bar" for i in range(self.n_token[2])], dtype=np.int32)
+
+    @property
+    def penalised(self):
+        """True when some song has a non-zero frequency or presence penalty."""
+        return self.prefer is not None and bool(self.prefer[2][:, :-1].any())
+
+    @property
+    def bias_bars(self):
+        """True when some song's bias schedule has more than one row: its draw needs the song's bar count."""
+        return self.prefer is not None and bool((self.prefer[0][:, 1] > 1).any())
+
+    def _compile_preferences(self):
+        """prefer and seen0s of the plan's own songs (self.preferences, self.heads), and bar_mask for a bias schedule."""
+        self.prefer = compile_preferences(self.preferences, self.n_songs, self.n_token, self.bar_cond)
+        self.seen0s = None
+        self.bar_mask = self._bar_classes() if self.table is not None or self.bias_bars else None
+        if not self.penalised or self.heads is None:
+            return
+        prefs = self.preferences if isinstance(self.preferences, (list, tuple)) else [self.preferences] * self.n_songs
+        self.seen0s = np.zeros((self.n_songs, int(sum(self.n_token))), dtype=np.float32)
+        at = {}                                                  # one shared prompt and preference: one walk
+        for k, (p, h) in enumerate(zip(prefs, self.heads)):
+            if p is not None and len(h):
+                key = (id(p), id(h))
+                if key not in at:
+                    at[key] = p.seen_states(h)[-1]
+                self.seen0s[k] = at[key]
 
     def _compile_constraints(self):
         self.table = None if self.constraints is None else compile_constraints(
             self.constraints, self.n_songs, self.n_token, self.bar_cond, self.bar0s, self.max_tokens)
 
     def songs(self, first, count):
-        """The plan of songs [first, first + count): list constraints and per-song alpha rows, bar counts and positions
-        are cut (the cut list is compiled as the group's own call would), what every song shares passes through."""
+        """The plan of songs [first, first + count): list constraints and preferences, per-song alpha rows, bar counts,
+        positions and repetition states are cut (a cut list is compiled as the group's own call would), what every song
+        shares passes through."""
         p = copy.copy(self)
         cut = slice(first, first + count)
         p.n_songs, p.bar0s = count, self.bar0s[cut]
@@ -468,6 +692,11 @@ class DrawPlan:
             p._compile_constraints()
         elif self.table is not None:
             p.table = (self.table[0][cut], self.table[1])
+        if self.preferences is not None:
+            p.heads = None if self.heads is None else list(self.heads[cut])
+            if isinstance(self.preferences, (list, tuple)):
+                p.preferences = list(self.preferences[cut])
+            p._compile_preferences()
         return p
 
 
@@ -475,11 +704,15 @@ class DeviceDraw:
     """The device stage: a DrawPlan's tables on `dev`, uploaded once, for the token loops, _draw_token and the scorers:
     sched (n_songs, 2) int64 and masks (R, W) int32 (the mask words' view), or None; order (n_class[bar_attr],) int32,
     gram (3, W) int32, beat0 (n_songs,) int64 and bar_attr, or None; alpha (1 | n_songs, A) f32 or None; ref, the
-    reference's session, or None; temperature, top_p, logprobs; the host's bar0s and bar_mask.  No plan: the plain draw
-    at temperature 1.  What moves per token or row (bar counts, positions, song keys) is passed beside it."""
+    reference's session, or None; temperature, top_p, logprobs; the host's bar0s and bar_mask.  Under preferences
+     pen (n_songs, 2 A + 1) f32, with psched (n_songs, 2) int64 and bias (R, sum n_class) f32 when some
+    song has a bias (else None), seen0 (n_songs, sum n_class) f32 when some song has a penalty and the plan has heads
+    (else None), and the plan's flags penalised and bias_bars.  No plan: the plain draw at temperature 1.  What moves per
+    token or row (bar counts, positions, song keys, repetition states) is passed beside it."""
 
     temperature = top_p = sched = masks = order = gram = beat0 = bar_attr = alpha = bar0s = bar_mask = None
-    logprobs = False
+    pen = psched = bias = seen0 = None
+    logprobs = penalised = bias_bars = False
 
     def __init__(self, plan=None, dev=None, ref=None):
         self.ref = ref
@@ -496,6 +729,13 @@ class DeviceDraw:
             self.beat0 = up(np.asarray(plan.beat0s, dtype=np.int64))
         if plan.alpha is not None:
             self.alpha = up(plan.alpha)
+        if plan.prefer is not None:
+            sched, bias, pen = plan.prefer
+            self.pen, self.penalised, self.bias_bars = up(pen), plan.penalised, plan.bias_bars
+            if len(bias):
+                self.psched, self.bias = up(sched), up(bias)
+            if plan.seen0s is not None:
+                self.seen0 = up(plan.seen0s)
 
     def keywords(self, bar=None, **key):
         """The sampler settings and, at bar counts `bar`, the constraint table: keywords of ops' samplers / scorers."""

@@ -25,7 +25,8 @@ import torch
 
 from . import ops
 from .draw_plan import (DQN_TEMPERATURE, DQN_TOP_P, Constraint, DeviceDraw, DrawPlan, Grammar,  # noqa: F401
-                        check_entry, compile_alpha, compile_constraints, compile_grammar)
+                        Preference, check_entry, compile_alpha, compile_constraints, compile_grammar,
+                        compile_preferences)
 from .sampling import sample_cw
 
 INIT_CW = np.array([[0, 0, 1, 0, 0, 0]])          # "Bar" token, testing-no-type-cp.py:135-137
@@ -439,6 +440,16 @@ def _draw_token(plan, logits, n_token, tok, seed, counter=None, key=None, step=N
                                **plan.keywords())
 
 
+def _prefer_token(plan, logits, n_token, seen=None, key=None, bar=None):
+    """The preferred logits of one token or block of rows, written over `logits` (cwlt_prefer_logits): the
+    bias rows of `plan` (DeviceDraw) at bar counts `bar`, its penalties at the states `seen`, row n of song key[n]
+    (None: n).  A plan without preferences launches nothing."""
+    if plan.pen is None:
+        return logits
+    return ops.prefer_logits(logits, n_token, sched=plan.psched, bias=plan.bias, pen=plan.pen, seen=seen, key=key,
+                             bar=None if plan.bias is None else bar, out=logits)
+
+
 def _enqueue_token(loop, name):
     """Enqueue one more token of `loop` (its _one; call under torch.no_grad()): eager for the first two tokens and when
     graphs are off; at the third, after a device synchronize, _one is captured as one hipGraph -- recorded, not
@@ -470,13 +481,18 @@ class _DeviceLoop:
     sampler) log-probs into `logp` (rows, n_songs, 6, 2) f32 beside `song`, at the row `count` selects.  With a grammar
     `beat`, each song's position, from plan.beat0: cwlt_grammar_track moves it after cwlt_count_bars.  plan.ref,
     plan.alpha (the blend): `ref` (DecodeSession.shadow) steps on the same token buffer right after the
-    model and cwlt_blend_logits (alpha's row n is song n) turns the model's logits into the blend's in place."""
+    model and cwlt_blend_logits (alpha's row n is song n) turns the model's logits into the blend's in place.
+    Preferences: cwlt_prefer_logits then turns the logits into the preferred ones in place, before the
+    unchanged draw; `seen` (n_songs, sum n_class) f32, each song's repetition state from plan.seen0, is moved by
+    cwlt_prefer_track after the draw (only when some song has a penalty), and `bar` is kept, and cwlt_count_bars
+    launched, also when only a bias schedule needs the count -- which does not select the masked sampler."""
 
     def __init__(self, sess, capacity, plan=None, carry_memory=True, graph=None, ring=None):
         self.sess, self.capacity, self.carry = sess, int(capacity), carry_memory
         self.plan = plan = DeviceDraw() if plan is None else plan
         self.ref, self.bar, self.bar_mask = plan.ref, None, None
-        if plan.sched is not None:
+        self.seen = None if plan.seen0 is None else plan.seen0.clone()
+        if plan.sched is not None or plan.bias_bars:
             self.bar = torch.as_tensor(np.asarray(plan.bar0s, dtype=np.int64)).to(sess.dev)
             self.bar_mask = torch.as_tensor(plan.bar_mask).to(sess.dev)
         self.beat = None if plan.order is None else plan.beat0.clone()          # one song per row, in song order
@@ -498,12 +514,15 @@ class _DeviceLoop:
         tok = s.tok.view(self.N, self.A)
         # the plain draw writes the song row itself; every other one, and a ring, takes a copy of the token buffer
         fused = self.ring is None and self.bar is None and self.logp is None and self.beat is None
+        logits = _prefer_token(self.plan, logits, s.n_token, seen=self.seen, bar=self.bar)
         _draw_token(self.plan, logits, s.n_token, tok, self.seed, counter=self.count, bar=self.bar, beat=self.beat,
                     logp=self.logp, out_counter=self.count, song=self.song if fused else None)
         if self.bar is not None:
             ops.count_bars(tok, 2, self.bar_mask, self.bar)
         if self.beat is not None:
             ops.grammar_track(tok, self.plan.bar_attr, self.plan.order, self.beat)
+        if self.seen is not None:
+            ops.prefer_track(tok, s.n_token, self.plan.pen, self.seen)
         if not fused:
             self.song.index_copy_(0, self.count if self.ring is None else self.slot, tok.view(1, self.N, self.A))
         if self.ring is not None:
@@ -578,6 +597,9 @@ class _StreamLoop:
       the advance: (song, token, end bit) into row t % R of `ring` (R, slots, A + 2), position / bar count advanced, the
         song's end detected, finished slots handed the next song indices in slot order;
       cwlt_grammar_track (under a grammar): every slot's position after the advance.
+    Preferences add cwlt_prefer_logits in front of the draw, keyed by the slots' song indices and bar
+    counts, in place on the logits, and -- when some song has a penalty -- cwlt_prefer_track at the end: `seen` (slots,
+    sum n_class) f32 follows the slots, a slot handed a song taking that song's seen0 through `fresh`, as `beat` does.
     The ring holds two chunks: chunk k + 1 is enqueued before chunk k is read, so the device never waits on the host.
     plan.logprobs: the sampler is cwlt_sample_categorical_logp (the same tokens), writing each slot's (model, sampler)
     log-probs into `lp_ring` (2 chunk, slots, A, 2) at the row ctl[0] selects -- the row of `ring` the advance writes --
@@ -607,6 +629,7 @@ class _StreamLoop:
         self.ring = torch.zeros((2 * self.chunk, self.S, self.A + 2), dtype=torch.int64, device=dev)
         self._host = [torch.zeros((self.chunk, self.S, self.A + 2), dtype=torch.int64).pin_memory() for _ in range(2)]
         self.beat = None if plan.order is None else torch.full((self.S,), -1, dtype=torch.int64, device=dev)
+        self.seen = None if plan.seen0 is None else torch.zeros((self.S, sess.width), dtype=torch.float32, device=dev)
         self.lp_ring = torch.zeros((2 * self.chunk, self.S, self.A, 2), dtype=torch.float32, device=dev) \
             if plan.logprobs else None
         self._host_lp = [torch.zeros((self.chunk, self.S, self.A, 2), dtype=torch.float32).pin_memory()
@@ -630,6 +653,9 @@ class _StreamLoop:
         if self.beat is not None:
             k = min(self.S, self.n_songs)
             self.beat[:k] = self.plan.beat0[:k]
+        if self.seen is not None:
+            k = min(self.S, self.n_songs)
+            self.seen[:k] = self.plan.seen0[:k]
         self.ctl.copy_(torch.tensor(ctl, dtype=torch.int64))
 
     def _one(self):
@@ -637,12 +663,16 @@ class _StreamLoop:
         tok = s.tok.view(self.S, self.A)
         logits = s._device_step()
         self._refill(logits)
+        _prefer_token(self.plan, logits, s.n_token, seen=self.seen, key=self.song, bar=self.bar)
         _draw_token(self.plan, logits, s.n_token, tok, self.seed, key=self.song, step=self.pos, bar=self.bar,
                     beat=self.beat, logp=self.lp_ring, out_counter=self.ctl)
         self._advance(tok)
         if self.beat is not None:
             ops.grammar_track(tok, self.plan.bar_attr, self.plan.order, self.beat, fresh=self.fresh, song=self.song,
                               beat0=self.plan.beat0)
+        if self.seen is not None:
+            ops.prefer_track(tok, s.n_token, self.plan.pen, self.seen, fresh=self.fresh, song=self.song,
+                             seen0=self.plan.seen0)
 
     def _read(self, h):
         """The rows of ring half h that belong to songs (waiting and idle slots write song < 0), and their log-probs
@@ -890,7 +920,8 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                     return_logprobs=False, grammar=None, reference=None, alpha=None, where="generate_stream"):
+                     return_logprobs=False, grammar=None, reference=None, alpha=None, where="generate_stream",
+                     preferences=None):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
@@ -917,7 +948,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         heads, bar0s, caps = ([v[0]] * n_songs for v in _check_prompts(
             [INIT_CW[0] if prompt is None else prompt], 1, word2event, None, bar_cond, max_tokens))
     plan = DrawPlan(model, word2event, n_songs, where, sampler, constraints, grammar, reference, alpha, return_logprobs,
-                    bar_cond, bar0s, max_tokens, heads)
+                    bar_cond, bar0s, max_tokens, heads, preferences=preferences)
     if plan.reference is not None and prompts is not None:
         raise ValueError("generate_stream blends songs that start from one snapshot: per-song prompts would need a "
                          "second bank and a second prefill schedule -- generate_batch(prompts=[...], reference=..., "
@@ -968,7 +999,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                    return_logprobs=False, grammar=None, reference=None, alpha=None):
+                    return_logprobs=False, grammar=None, reference=None, alpha=None, preferences=None):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -996,11 +1027,14 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     in its bar, which cwlt_grammar_track moves after the advance (a song's own prompt sets where it starts).  Under a
     blend a second pool of `slots` decode slots runs the reference on the same tokens and cwlt_blend_logits, keyed by
     each slot's song, writes the blended logits the sampler reads: with the shared-snapshot forms only (no prompt, or
-    one shared prompt) -- per-song prompts are refused, generate_batch(prompts=[...], reference=, alpha=) takes them."""
+    one shared prompt) -- per-song prompts are refused, generate_batch(prompts=[...], reference=, alpha=) takes them.
+    preferences: as in generate_batch (Preference), with every form of the stream: each slot's logits are
+    preferred by its song's bias row for the slot's bar count and its song's repetition state, which follows the slot
+    and starts, for every song, from that song's own prompt rows."""
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
                             prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs,
-                            grammar=grammar, reference=reference, alpha=alpha)[0]
+                            grammar=grammar, reference=reference, alpha=alpha, preferences=preferences)[0]
 
 
 def _refuse_logprobs(return_logprobs, where):
@@ -1141,7 +1175,7 @@ def inference_from_prompt(model, word2event, prompt, bar_cond, max_tokens=None, 
 
 def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, prompts=None, sampler="dqn", chunk=128,
                    log=None, prefill="blas", constraints=None, return_logprobs=False, grammar=None, reference=None,
-                   alpha=None):
+                   alpha=None, preferences=None):
     """Generate `n_songs` songs in lock-step: one `DecodeSession(n_songs=N, kernel="gemm")` (the token step's
     projections as f32 MFMA GEMMs, csrc/decode_gemm.hip) and one N-song device loop, so every weight is read once per
     token for all songs.  -> list of N (L_i, 6) int64 arrays.
@@ -1178,10 +1212,16 @@ def generate_batch(model, word2event, n_songs, bar_cond=17, max_tokens=None, pro
     [..., 0] = log pi_alpha (the blended logits, temperature 1, no mask) and [..., 1] = log q of the sampler's
     distribution built on them; each model's own log-probs come from score_songs without a blend.  The reference: same
     classes, recurrent, eval(), f32, on the model's device, any width or depth.  One without the other is refused.
+    preferences: one Preference for every song, or a list of n_songs Preference / None entries: soft
+    terms on the logits, after the blend and before the unchanged draw (cwlt_prefer_logits) -- each song's bias row for
+    its bar count, and a repetition penalty by the song's own `seen` state, which starts from its prompt's rows and is
+    moved by cwlt_prefer_track after every draw.  Constraints, the grammar and the nucleus work on the preferred logits;
+    under return_logprobs [..., 0] is the log-prob of the preferred logits at temperature 1 (the blend's convention).
+    A preference with zero bias and no penalty gives bitwise the songs without it.
     All of these are compiled once, before the first token, into one plan (DrawPlan); None: nothing changes."""
     heads, caps, plan = _batch_setup("generate_batch", model, word2event, n_songs, bar_cond, max_tokens, prompts,
                                      sampler, chunk, prefill, constraints=constraints, logprobs=return_logprobs,
-                                     grammar=grammar, reference=reference, alpha=alpha)
+                                     grammar=grammar, reference=reference, alpha=alpha, preferences=preferences)
     return _run_batch(model, word2event, heads, caps, plan, bar_cond, int(chunk), log,
                       None if prompts is None else prefill)
 
@@ -1313,7 +1353,10 @@ def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
     holds song[t + 1], -1 on its last row and on padding, the plan on the device (DeviceDraw), and what each row adds
     to it: its song index `key` (under constraints or a blend), bar count `bar` (under constraints) and position `beat`
     (under a grammar), else None).  Under plan.alpha the model's logits are replaced by the blend's, alpha x +
-    (1 - alpha) r row by row (cwlt_blend_logits, keyed by `key`)."""
+    (1 - alpha) r row by row (cwlt_blend_logits, keyed by `key`).  Under preferences the model's logits
+    -- the blended ones under alpha -- are then replaced by the preferred ones (cwlt_prefer_logits with the per-row key
+    and bar), penalised by the state cwlt_prefer_scan rebuilds from the block's own tokens: row t by the state after
+    rows 0 .. t.  A reference's logits stay its own."""
     n_token, dev = plan.n_token, next(model.parameters()).device
     models = [model] if plan.reference is None else [model, plan.reference]
     A, n = len(n_token), len(songs)
@@ -1340,8 +1383,9 @@ def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
             if draw.order is not None:
                 beat[i, :len(x) - 1] = beats[a0 + i][1:]
         lgs, key = [], None
-        if draw.sched is not None or draw.alpha is not None:
+        if draw.sched is not None or draw.alpha is not None or draw.pen is not None:
             key = torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb)
+        dbar = None if draw.sched is None and draw.bias is None else torch.as_tensor(bar.reshape(-1)).to(dev)
         with torch.no_grad():
             for net in models:
                 enc = net.transformer_encoder
@@ -1354,13 +1398,16 @@ def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
                 lgs.append(lg.reshape(nb * Lb, -1))
             if draw.alpha is not None:
                 lgs[0] = ops.blend_logits(lgs[0], lgs[1], n_token, draw.alpha, out=lgs[0], key=key)
-        dbar = None if draw.sched is None else torch.as_tensor(bar.reshape(-1)).to(dev)
+            if draw.pen is not None:
+                seen = ops.prefer_scan(torch.as_tensor(toks.reshape(-1, A)).to(dev), nb, n_token, draw.pen, key) \
+                    if draw.penalised else None
+                lgs[0] = _prefer_token(draw, lgs[0], n_token, seen=seen, key=key, bar=dbar)
         dbeat = None if draw.order is None else torch.as_tensor(beat.reshape(-1)).to(dev)
         yield blk, Lb, lgs, torch.as_tensor(tgt.reshape(-1, A)).to(dev), draw, key, dbar, dbeat
 
 
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
-                prefill_rows=None, grammar=None, reference=None, alpha=None):
+                prefill_rows=None, grammar=None, reference=None, alpha=None, preferences=None):
     """Log-likelihoods of given songs under the recurrent form, as generation samples them.
     -> list of (L_i - 1, 6, 2) float32 arrays; row t is about song[t + 1] given song[:t + 1] (pe[0] on every row, as
     DecodeSession.step and prefill compute it): [..., 0] the model log-prob log_softmax(logits_t[a])[song[t + 1, a]]
@@ -1388,10 +1435,15 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     model's logits by alpha x + (1 - alpha) r, and [..., 0] is log pi_alpha (the blended logits, temperature 1, no
     mask), [..., 1] log q of the sampler's distribution built on them -- what generate_batch / generate_stream(
     reference=, alpha=, return_logprobs=True) return.  Each model's own log-probs come from a call without a blend.
+    preferences: as in generate_batch: the logits -- the blended ones under alpha -- are replaced by the
+    preferred ones before they are scored, row t with the song's bias row for song_bar_counts()[t] and the repetition
+    state after song[:t + 1] (cwlt_prefer_scan, bitwise the state generation carries), so [..., 0] is the log-prob of
+    the preferred logits at temperature 1 and both columns are what generation with the same preferences returns.
     Refused: unknown sampler or kernel, training mode, non-f32 activations, empty songs, ids out of range; reference
     without alpha or the reverse, and a reference policy_stats would refuse."""
     songs, bars, plan = _score_setup("score_songs", model, word2event, songs, mask, sampler, kernel,
-                                     constraints=constraints, grammar=grammar, reference=reference, alpha=alpha)
+                                     constraints=constraints, grammar=grammar, reference=reference, alpha=alpha,
+                                     preferences=preferences)
     out = []
     for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
         kw = d.keywords(bar, key=key)
@@ -1405,7 +1457,7 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
 
 
 def policy_stats(model, word2event, songs, reference=None, sampler="categorical", constraints=None, kernel="gemm",
-                 mask=None, prefill_rows=None, grammar=None, alpha=None):
+                 mask=None, prefill_rows=None, grammar=None, alpha=None, preferences=None):
     """Entropy of the policy along given songs, and its KL against a reference model.
     -> list of (L_i - 1, 6, 2) float32 arrays, (L_i - 1, 6, 4) with `reference`; rows as in score_songs: row t is about
     the distribution of song[t + 1] given song[:t + 1].  In nats: [..., 0] H(p), p the model's softmax (temperature 1,
@@ -1425,10 +1477,13 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
     the reference: cwlt_blend_logits replaces the model's logits by alpha x + (1 - alpha) r before the
     one cwlt_policy_stats call, so [..., 2] is KL(pi_alpha || pi_ref), the x-axis of the reward / KL frontier, and 0 at
     alpha = 0.  alpha = 1 gives the stats without it; a reference without alpha keeps that meaning.
+    preferences: as in score_songs: p and q are built on the preferred logits of the model (of the blend
+    under alpha).  The reference keeps its own logits, unpreferred: the KL columns then say how far the preferred policy
+    has moved from the reference, the question a preference added on top of a tuned policy raises.
     Refused: what score_songs refuses, a reference that fails the conditions above, alpha without a reference."""
     songs, bars, plan = _score_setup("policy_stats", model, word2event, songs, mask, sampler, kernel,
                                      constraints=constraints, grammar=grammar, reference=reference, alpha=alpha,
-                                     lone_reference=True)
+                                     lone_reference=True, preferences=preferences)
     out = []
     for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
         st = ops.policy_stats(lgs[0], plan.n_token, None if reference is None else lgs[1], grammar=d.grammar(beat),
@@ -1442,7 +1497,7 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
              batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None,
-             reference=None, alpha=None):
+             reference=None, alpha=None, preferences=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1453,9 +1508,9 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     the stream's wall time divided by n_songs.  Not together with batch_size.
     prompts: a list of n_songs (P_i, 6) arrays, song i continues prompts[i] (not together with prompt): on the stream
     with slots, each batch_size group with its own slice of the list, or one song at a time.
-    constraints, grammar, reference / alpha (generate_batch, generate_stream) and logprobs=True (their return_logprobs:
-    each song's drawn-row log-probs are saved as get_<i>_logp.npy next to the song): with slots or batch_size only, the
-    one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs)."""
+    constraints, grammar, reference / alpha, preferences (generate_batch, generate_stream) and logprobs=True (their
+    return_logprobs: each song's drawn-row log-probs are saved as get_<i>_logp.npy next to the song): with slots or
+    batch_size only, the one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs)."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
@@ -1472,6 +1527,11 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                          "batch_size or slots (one song: generate_batch(n_songs=1, constraints=...))")
     if isinstance(constraints, (list, tuple)) and len(constraints) != n_songs:
         raise ValueError("constraints: %d entries for %d songs" % (len(constraints), n_songs))
+    if preferences is not None and batch_size is None and slots is None:
+        raise ValueError("preferences run in front of the device samplers of generate_batch / generate_stream: pass "
+                         "batch_size or slots (one song: generate_batch(n_songs=1, preferences=...))")
+    if isinstance(preferences, (list, tuple)) and len(preferences) != n_songs:
+        raise ValueError("preferences: %d entries for %d songs" % (len(preferences), n_songs))
     if prompts is not None:
         if prompt is not None:
             raise ValueError("pass one shared prompt or per-song prompts, not both")
@@ -1506,7 +1566,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         songs = _generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                  prompt=prompt, prompts=None if prompts is None else list(prompts),
                                  constraints=constraints, return_logprobs=logprobs, grammar=grammar,
-                                 reference=reference, alpha=alpha, where="generate")[0]
+                                 reference=reference, alpha=alpha, where="generate", preferences=preferences)[0]
         record(0, songs, time.time() - start, "stream on %d slots" % int(slots))
     elif batch_size is not None:
         if int(batch_size) < 1:
@@ -1514,7 +1574,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         given = prompt if prompts is None else list(prompts)
         heads, caps, plan = _batch_setup("generate", model, word2event, n_songs, bar_cond, max_tokens, given, "dqn", 128,
                                          "blas", constraints=constraints, logprobs=logprobs, grammar=grammar,
-                                         reference=reference, alpha=alpha)
+                                         reference=reference, alpha=alpha, preferences=preferences)
         for first in range(0, n_songs, int(batch_size)):
             group = slice(first, first + int(batch_size))
             start = time.time()

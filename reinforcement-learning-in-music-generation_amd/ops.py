@@ -1854,6 +1854,133 @@ def blend_logits(logits, ref_logits, n_class, alpha, key=None, out=None):
     return out
 
 
+def _prefer_pen(fn, pen, A):
+    """Checks of the penalty table (n_songs, 2 A + 1) f32 -> n_songs."""
+    if pen.dtype != torch.float32 or pen.dim() != 2 or pen.shape[1] != 2 * A + 1 or pen.shape[0] < 1 or \
+            not pen.is_contiguous():
+        raise ValueError("%s: pen must be a contiguous (n_songs, %d) f32 tensor" % (fn, 2 * A + 1))
+    return pen.shape[0]
+
+
+def _prefer_seen(fn, seen, rows, W, name="seen"):
+    if seen.dtype != torch.float32 or seen.dim() != 2 or seen.shape[0] != rows or seen.shape[1] < W or \
+            seen.stride(1) != 1:
+        raise ValueError("%s: %s must be (%d, >= %d) f32 with a unit column stride" % (fn, name, rows, W))
+
+
+def prefer_logits(logits, n_class, sched=None, bias=None, pen=None, seen=None, key=None, bar=None, out=None):
+    """The preferred logits (cwlt_prefer_logits): out[n, c] = ((logits[n, c] + b) - f s) - (s > 0 ? p :
+    0).  logits (rows, >= sum n_class) f32, unit column stride.  sched (n_songs, 2) int64 {first bias row, rows} with
+    bias (R, >= sum n_class) f32, R >= 1, together or not at all; pen (n_songs, 2 A + 1) f32 {frequency, presence,
+    decay} with seen (rows, >= sum n_class) f32 (seen None: no penalty).  key (rows,) int64: the song of each row (None:
+    row n is song n), a row whose song is outside [0, n_songs) is copied; bar (rows,) int64: the bar count that picks
+    the bias row as the masked sampler picks its mask row (None: the first row).  out: None (a new tensor), `logits`
+    (in place) or a tensor that overlaps no input.  Rows go through in launches of at most 2^20."""
+    fn, W, A = "prefer_logits", sum(n_class), len(n_class)
+    for t, name in ((logits, "logits"),) + (() if out is None else ((out, "out"),)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < W or t.stride(1) != 1 or \
+                t.shape[0] != logits.shape[0] or t.device != logits.device:
+            raise ValueError("%s: %s must be (%d, >= %d) f32 with a unit column stride on the logits' device"
+                             % (fn, name, logits.shape[0], W))
+    rows = logits.shape[0]
+    if (sched is None) != (bias is None):
+        raise ValueError("%s: sched and bias go together" % fn)
+    if sched is None and pen is None:
+        raise ValueError("%s needs a bias table (sched, bias), a penalty table (pen), or both" % fn)
+    n_songs = None
+    if sched is not None:
+        if sched.dtype != torch.int64 or sched.dim() != 2 or sched.shape[1] != 2 or sched.shape[0] < 1 or \
+                not sched.is_contiguous():
+            raise ValueError("%s: sched must be a contiguous (n_songs, 2) int64 tensor" % fn)
+        if bias.dtype != torch.float32 or bias.dim() != 2 or bias.shape[0] < 1 or bias.shape[1] < W or \
+                bias.stride(1) != 1:
+            raise ValueError("%s: bias must be (R >= 1, >= %d) f32 with a unit column stride" % (fn, W))
+        n_songs = sched.shape[0]
+    if seen is not None and pen is None:
+        raise ValueError("%s: seen needs the penalty table pen" % fn)
+    if pen is not None:
+        n_pen = _prefer_pen(fn, pen, A)
+        if n_songs is not None and n_pen != n_songs:
+            raise ValueError("%s: pen has %d rows, sched %d" % (fn, n_pen, n_songs))
+        n_songs = n_pen
+    if seen is not None:
+        _prefer_seen(fn, seen, rows, W)
+    for t, name in ((key, "key"), (bar, "bar")):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != rows or not t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous (rows,) int64 tensor" % (fn, name))
+    if key is None and rows > 1 << 20:
+        raise ValueError("%s: without a key row n is song n of one launch: more than 2^20 rows need a key" % fn)
+    if out is None:
+        out = torch.empty((rows, W), dtype=torch.float32, device=logits.device)
+    for a in range(0, rows, 1 << 20):
+        z = min(rows, a + (1 << 20))
+        _call("cwlt_prefer_logits", _lib.dev(logits[a:z], "logits"), logits.stride(0), _lib.int_array(n_class), A,
+              _lib.opt(_rows(key, a, z)), _lib.opt(_rows(bar, a, z)), _lib.opt(sched), n_songs, _lib.opt(bias),
+              0 if bias is None else bias.shape[0], 0 if bias is None else bias.stride(0), _lib.opt(pen),
+              _lib.opt(_rows(seen, a, z)), 0 if seen is None else seen.stride(0), _lib.dev(out[a:z], "out"),
+              out.stride(0), z - a, _lib.stream_ptr())
+    return out
+
+
+def prefer_track(tokens, n_class, pen, seen, fresh=None, song=None, seen0=None):
+    """The repetition state after a draw (cwlt_prefer_track): seen[n] (rows, >= sum n_class) f32 becomes seen[n] * decay
+    + hit, hit 1 at the class tokens (rows, A) int64 carries in each attribute, decay from row song[n] (None: n) of pen
+    (n_songs, 2 A + 1) f32.  With fresh / song (rows,) int64 and seen0 (n_songs, sum n_class) f32, a row flagged fresh
+    with song >= 0 takes seen0[song] instead; a row whose song is outside [0, n_songs) is left alone."""
+    fn, W, A = "prefer_track", sum(n_class), len(n_class)
+    if tokens.dtype != torch.int64 or not tokens.is_contiguous() or tokens.shape[-1] != A or seen.dim() != 2 or \
+            tokens.numel() != seen.shape[0] * A:
+        raise TypeError("%s takes contiguous int64 tokens (rows, %d) and seen (rows, >= %d)" % (fn, A, W))
+    rows = seen.shape[0]
+    if rows < 1 or rows > 1 << 20:
+        raise ValueError("%s: 1 .. 2^20 rows, got %d" % (fn, rows))
+    _prefer_seen(fn, seen, rows, W)
+    n_songs = _prefer_pen(fn, pen, A)
+    opt = [fresh, song, seen0]
+    if any(t is not None for t in opt):
+        if any(t is None or not t.is_contiguous() for t in opt) or fresh.dtype != torch.int64 or \
+                song.dtype != torch.int64 or fresh.numel() != rows or song.numel() != rows or \
+                seen0.dtype != torch.float32 or tuple(seen0.shape) != (n_songs, W):
+            raise ValueError("%s: fresh and song (rows,) int64 and seen0 (n_songs, %d) f32 go together" % (fn, W))
+    _call("cwlt_prefer_track", _lib.dev(tokens, "tokens"), rows, _lib.int_array(n_class), A, _lib.dev(pen, "pen"),
+          n_songs, _lib.opt(fresh), _lib.opt(song), _lib.opt(seen0), _lib.dev(seen, "seen"), seen.stride(0),
+          _lib.stream_ptr())
+    return seen
+
+
+def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None):
+    """The repetition state along given songs (cwlt_prefer_scan): tokens (nb * Lb, A) int64, song i in rows [i Lb,
+    (i + 1) Lb) -> seen_rows (nb * Lb, sum n_class) f32, row t of a song the state after its rows 0 .. t from zero, by
+    prefer_track's step with the decay of song key[i Lb] (key (nb * Lb,) int64, the per-row key of prefer_logits; None:
+    song i) in pen (n_songs, 2 A + 1) f32.  Songs go through in launches of at most 2^20 rows."""
+    fn, W, A, nb = "prefer_scan", sum(n_class), len(n_class), int(n_songs_block)
+    if tokens.dtype != torch.int64 or not tokens.is_contiguous() or tokens.dim() != 2 or tokens.shape[1] != A:
+        raise TypeError("%s takes contiguous int64 tokens (nb * Lb, %d)" % (fn, A))
+    total = tokens.shape[0]
+    if nb < 1 or total < nb or total % nb:
+        raise ValueError("%s: %d token rows are no whole number of rows for each of %d songs" % (fn, total, nb))
+    Lb = total // nb
+    if Lb > 1 << 20:
+        raise ValueError("%s: a song of %d rows is past the 2^20 rows of one launch" % (fn, Lb))
+    n_songs = _prefer_pen(fn, pen, A)
+    if key is not None and (key.dtype != torch.int64 or key.numel() != total or not key.is_contiguous()):
+        raise ValueError("%s: key must be a contiguous (rows,) int64 tensor" % fn)
+    if key is None and nb > n_songs:
+        raise ValueError("%s: without a key song i reads row i of pen: %d songs, %d rows" % (fn, nb, n_songs))
+    if out is None:
+        out = torch.empty((total, W), dtype=torch.float32, device=tokens.device)
+    else:
+        _prefer_seen(fn, out, total, W, "out")
+    per = max(1, (1 << 20) // Lb)
+    for a in range(0, nb, per):
+        z = min(nb, a + per)
+        pn = pen if key is not None else pen[a:]
+        _call("cwlt_prefer_scan", _lib.dev(tokens[a * Lb:z * Lb], "tokens"), z - a, Lb, _lib.int_array(n_class), A,
+              _lib.dev(pn, "pen"), pn.shape[0], _lib.opt(_rows(key, a * Lb, z * Lb)),
+              _lib.dev(out[a * Lb:z * Lb], "seen_rows"), out.stride(0), _lib.stream_ptr())
+    return out
+
+
 def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):
     """The row grammar's position after a draw (cwlt_grammar_track): beat[n] (rows,) int64 moves by the bar-beat class
     of tokens (rows, A) int64 through order (int32: -1 Bar, k >= 0 Beat_k, else unchanged); with fresh / song (rows,)

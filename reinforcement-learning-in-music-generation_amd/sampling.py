@@ -169,6 +169,32 @@ def blend_logits_f64(logits, ref_logits, n_class, alpha):
     return w * x[:, :W] + (1.0 - w) * r[:, :W]
 
 
+def prefer_logits_f32(logits, n_class, bias_row=None, pen=None, seen=None):
+    """Numpy float32 restatement of cwlt_prefer_logits for the rows of ONE song: logits (rows, >= sum
+    n_class) or (sum n_class,) -> float32 of the same leading shape, ((x + b) - f s) - (s > 0 ? p : 0) with every
+    operation rounded on its own, as the kernel rounds it: the result is bitwise the kernel's.  bias_row: (sum n_class,)
+    or one row per row of logits, None: no b is added; pen: Preference.penalties(), (2 A + 1,) {frequency, presence,
+    decay}; seen: the state per row, shaped like the result, None: no penalty.  Class 0 of every attribute is never
+    penalised."""
+    A, W = len(n_class), int(sum(n_class))
+    x = np.asarray(logits, dtype=np.float32)[..., :W]
+    out = x.copy()
+    if bias_row is not None:
+        out = out + np.asarray(bias_row, dtype=np.float32)[..., :W]
+    if seen is None:
+        return out
+    pen = np.asarray(pen, dtype=np.float32).reshape(2 * A + 1)
+    f = np.repeat(pen[:A], [int(n) for n in n_class])
+    p = np.repeat(pen[A:2 * A], [int(n) for n in n_class])
+    first = np.concatenate([[0], np.cumsum(n_class)[:-1]]).astype(np.int64)
+    f[first], p[first] = 0.0, 0.0
+    s = np.asarray(seen, dtype=np.float32)[..., :W]
+    with np.errstate(over="ignore", invalid="ignore"):
+        out = out - f * s
+        out = out - np.where(s > 0, p, np.float32(0.0))
+    return out.astype(np.float32, copy=False)
+
+
 def grammar_allowed_f64(bar_class, beat, order, gram, bar_attr, allowed=None):
     """The allowed sets of one row under the row grammar -> list of (n,) bool arrays, one per attribute.
     order: per class of attribute bar_attr, -2 class 0 (a note row), -1 a Bar class, k >= 0 Beat_k, -3 never allowed;
