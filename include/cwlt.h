@@ -686,6 +686,47 @@ int cwlt_stream_advance_bank(const int64_t* tokens, int n_attr, int64_t slots, i
                              int64_t bank, int64_t n_songs, int64_t* song, int64_t* pos, int64_t* bar, int64_t* cap,
                              int64_t* fresh, int64_t* ctl, int64_t* ring, int64_t ring_rows, void* stream);
 
+/* ---- particle generation: SMC resampling of lock-step songs (csrc/particles.hip) ---------------------------
+ * K consecutive rows of a cwlt_decode_step_rows pool are the particles of one song.  Per token, after the draw of
+ * cwlt_sample_categorical_logp / _grammar, cwlt_particle_weigh; every few tokens cwlt_particle_resample and, per family
+ * of per-row buffers, cwlt_particle_gather twice (state -> scratch, scratch -> state).  One launch each, no host
+ * synchronisation, no allocation.  Every pointer is DEVICE memory.
+ *
+ * cwlt_particle_weigh (one thread per row): for every row n with done[n] == 0,
+ *     lw[n] += sum_a (logp[o, n, a, 0] - logp[o, n, a, 1]),  o = *out_counter % out_rows (NULL: 0, out_rows 1),
+ * logp the (out_rows, rows, n_attr, 2) f32 ring of cwlt_sample_categorical_logp and out_counter the counter that draw was
+ * given; the attributes' differences are added in order from 0.0f and the row's sum is then added to lw[n], each
+ * difference and sum rounded on its own in f32.  Then len[n] += 1 and done[n] = 1 when bar[n] >= bar_cond (bar after
+ * cwlt_count_bars) or len[n] >= cap[n], else 0: the row that ends a song counts.  A row with done[n] != 0 is not
+ * touched.  lw f32, bar / cap / len / done int64, all x rows.  rows <= 2^20, n_attr 1 .. 8.
+ *
+ * cwlt_particle_resample (one workgroup per group of `particles` = K consecutive rows, 2 <= K <= 1024): with m = max lw,
+ * e_i = expf(lw_i - m), s = sum e_i and ess = s^2 / sum e_i^2 of the group's rows, a group whose rows are all done, or
+ * with ess >= ess_frac * K (compared in f32), keeps anc[i] = i (the row's own index in the whole pool) and its lw.  Any
+ * other group is resampled systematically: anc[g K + j] = g K + the first i whose inclusive prefix sum of e exceeds
+ * (j + u) / K * s, K - 1 when none does; log_z[g] += m + logf(s / K); every lw of the group becomes 0.  u in [0, 1) is
+ * the counter-based generator's draw for (seed, event, g): it does not depend on `groups`.  Written for every group:
+ * anc (groups * K int64), u and ess (groups f32), resampled (groups int32, 1 where the group was resampled).
+ * done int64 x rows, log_z f32 x groups.  0 <= ess_frac <= 1, 0 <= event < 2^32, groups * K <= 2^20.
+ *
+ * cwlt_particle_gather: dst[b][n] = src[b][anc[n]] for blocks b < n_blocks and rows n < rows with anc[n] != n; row n of
+ * block b lies at byte b * block_stride + n * row_bytes of dst and of src alike.  A row with anc[n] == n, or with anc[n]
+ * outside [0, rows), is neither read nor written.  row_bytes (and block_stride when n_blocks > 1) multiples of 4, both
+ * bases 4-byte aligned; 16-byte accesses when both bases, row_bytes and block_stride are multiples of 16, 8-byte ones
+ * when of 8.  dst == src is refused: a permutation in place would read rows it has overwritten (a swap 0 <-> 1), so a
+ * caller moves a state through a scratch buffer of the same layout in two calls, moved rows only: state -> scratch with
+ * copy_back = 0, then scratch -> state with copy_back = 1, which copies dst[b][n] = src[b][n] for the same rows n (the
+ * rows the first call wrote); the launch boundary between the two is the barrier.  rows <= 2^20, block_stride >= rows *
+ * row_bytes when n_blocks > 1, copy_back 0 or 1. */
+int cwlt_particle_weigh(const float* logp, const int64_t* out_counter, int64_t out_rows, int64_t rows, int n_attr,
+                        const int64_t* bar, int64_t bar_cond, const int64_t* cap, float* lw, int64_t* len,
+                        int64_t* done, void* stream);
+int cwlt_particle_resample(float* lw, const int64_t* done, int64_t groups, int particles, float ess_frac,
+                           uint64_t seed, int64_t event, int64_t* anc, float* u, float* ess, int* resampled,
+                           float* log_z, void* stream);
+int cwlt_particle_gather(void* dst, const void* src, const int64_t* anc, int64_t rows, int64_t row_bytes, int n_blocks,
+                         int64_t block_stride, int copy_back, void* stream);
+
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass
  * (dqn_policy/IRL_dqn_train.py:267-345 `DQN.update`, ppo_policy/ppo_train.py:365-417 `update_policy`): ~970 launches of

@@ -27,7 +27,7 @@ from . import ops
 from .draw_plan import (DQN_TEMPERATURE, DQN_TOP_P, Constraint, DeviceDraw, DrawPlan, Grammar,  # noqa: F401
                         Preference, check_entry, compile_alpha, compile_constraints, compile_grammar,
                         compile_preferences)
-from .sampling import sample_cw
+from .sampling import logmeanexp, sample_cw
 
 INIT_CW = np.array([[0, 0, 1, 0, 0, 0]])          # "Bar" token, testing-no-type-cp.py:135-137
 PREFILL_ROWS = 32768        # default token-row budget of one gemm prefill block (prompts x the block's longest prompt)
@@ -527,7 +527,11 @@ class _DeviceLoop:
             self.song.index_copy_(0, self.count if self.ring is None else self.slot, tok.view(1, self.N, self.A))
         if self.ring is not None:
             self.slot.add_(1).remainder_(self.ring)
+        self._after_draw(tok)
         self.count.add_(1)
+
+    def _after_draw(self, tok):
+        """What a loop adds to a token after the draw and its tracks, before the counter moves (none here)."""
 
     def _blend(self, logits, ref_logits):
         """The blended logits, written over the model's (ref_logits None: the model's own, untouched)."""
@@ -583,6 +587,99 @@ class _DeviceLoop:
             return self.logp[start:stop].cpu().numpy()
         idx = torch.arange(start, stop, device=self.logp.device) % self.ring
         return self.logp.index_select(0, idx).cpu().numpy()
+
+
+class _ParticleLoop(_DeviceLoop):
+    """The lock-step loop with K particles per song: row g K + k of the pool is particle k of song g.
+    Per token, inside the captured token and before the counter moves: cwlt_count_bars (into a count of the loop's own
+    when the plan keeps none -- ending is decided on the device) and cwlt_particle_weigh, which adds the draw's
+    lp_model - lp_sampler to `lw`, counts the row in `len` and sets `done` by the bar rule and `cap`.  After every
+    `every` tokens resample(): lw is copied into row e of h_lw (E, N) f32 (the weights the event saw), then
+    cwlt_particle_resample into row e of the device histories (anc (E, N) int64, u, ess (E, G) f32, resampled (E, G)
+    int32), then the two-phase cwlt_particle_gather of every per-row state the loop
+    carries -- the model's decode state and the reference's, the token buffer, bar, beat, seen, len, done, cap --
+    through scratch buffers of the same shapes: eager launches on the loop's stream, no sync.  lw is not gathered: the
+    resampling kernel set it.  timed=True records HIP events around the resampling and each gather phase."""
+
+    def __init__(self, sess, capacity, plan, particles, every, ess, bar_cond, caps, bar_mask, graph=None, ring=None,
+                 timed=False):
+        super().__init__(sess, capacity, plan, graph=graph, ring=ring)
+        dev, N = sess.dev, self.N
+        self.K, self.every, self.ess_frac, self.bar_cond = int(particles), int(every), float(ess), int(bar_cond)
+        self.G = N // self.K
+        self.pbar, self.pbar_mask = self.bar, self.bar_mask
+        if self.pbar is None:
+            self.pbar = torch.as_tensor(np.asarray(self.plan.bar0s, dtype=np.int64)).to(dev)
+            self.pbar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32)).to(dev)
+        self.lw = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.len = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.done = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.cap = torch.as_tensor(np.asarray(caps, dtype=np.int64)).to(dev)
+        self.log_z = torch.zeros(self.G, dtype=torch.float32, device=dev)
+        E = -(-self.capacity // self.every)
+        self.h_anc = torch.zeros((E, N), dtype=torch.int64, device=dev)
+        self.h_lw = torch.zeros((E, N), dtype=torch.float32, device=dev)
+        self.h_u = torch.zeros((E, self.G), dtype=torch.float32, device=dev)
+        self.h_ess = torch.zeros((E, self.G), dtype=torch.float32, device=dev)
+        self.h_res = torch.zeros((E, self.G), dtype=torch.int32, device=dev)
+        self.n_events = 0
+        # (state, scratch, row bytes, blocks, block stride in bytes) of every family of per-row buffers
+        self.families = []
+        for s in (sess, self.ref):
+            if s is None:
+                continue
+            scratch = torch.empty_like(s._state)
+            sf, zf = s.memory[0][0][0].numel(), s.memory[0][1][0].numel()
+            stride = 4 * N * (sf + zf)
+            self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
+            self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
+        for t in (sess.tok, self.pbar, self.beat, self.seen, self.len, self.done, self.cap):
+            if t is not None:
+                self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
+        self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)      # what one moved row copies per phase
+        self.timed = [] if timed else None
+
+    def _after_draw(self, tok):
+        if self.pbar is not self.bar:
+            ops.count_bars(tok, 2, self.pbar_mask, self.pbar)
+        ops.particle_weigh(self.logp, self.count, self.pbar, self.bar_cond, self.cap, self.lw, self.len, self.done)
+
+    def resample(self):
+        """One resampling event, enqueued: the decision and ancestors, then every family state -> scratch -> state."""
+        e = self.n_events
+        anc = self.h_anc[e]
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.timed is not None else None
+        mark = (lambda i: marks[i].record()) if marks else (lambda i: None)
+        self.h_lw[e].copy_(self.lw)
+        mark(0)
+        ops.particle_resample(self.lw, self.done, self.K, self.ess_frac, self.seed, e, anc, self.h_u[e], self.h_ess[e],
+                              self.h_res[e], self.log_z)
+        mark(1)
+        for state, scratch, rb, nb, stride in self.families:
+            ops.particle_gather(scratch, state, anc, rb, nb, stride)
+        mark(2)
+        for state, scratch, rb, nb, stride in self.families:
+            ops.particle_gather(state, scratch, anc, rb, nb, stride, copy_back=True)
+        mark(3)
+        if marks:
+            self.timed.append(marks)
+        self.n_events += 1
+
+    def run(self, n):
+        """Enqueue n more tokens, with a resampling event after every `every`-th token of the run (no host sync)."""
+        n = min(n, self.capacity - self.enqueued)
+        with torch.no_grad():
+            for _ in range(n):
+                _enqueue_token(self, "particle loop")
+                if self.enqueued % self.every == 0:
+                    self.resample()
+        return n
+
+    def start(self, logits, ref_logits=None):
+        super().start(logits, ref_logits)
+        if self.every == 1:
+            with torch.no_grad():
+                self.resample()
 
 
 class _StreamLoop:
@@ -1290,6 +1387,209 @@ def _run_batch(model, word2event, heads, caps, plan, bar_cond, chunk, log, prefi
     return songs
 
 
+PARTICLE_ROWS = 4096        # most rows (songs x particles) of one generate_particles pool: the GEMM step's row limit
+
+
+def particle_lineage(ancestors, rows=None):
+    """Where each final row's song lived between the resampling events.  ancestors: (E, N) pool rows,
+    event e's ancestor vector (row n continues row ancestors[e, n]'s song).  -> (E + 1, N) int64: entry [e, n] is the
+    pool row that drew final row n's tokens of segment e, the rows after event e - 1 and up to event e; the last
+    segment is the row itself, and segment e is ancestors[e] taken at segment e + 1's rows.  A row no final row
+    descends from appears in no later segment.  rows (default N): the rows of a pool with no event."""
+    anc = np.asarray(ancestors, dtype=np.int64)
+    if anc.ndim != 2:
+        anc = anc.reshape(0, int(rows or 0))
+    E, N = anc.shape
+    if E and ((anc < 0) | (anc >= N)).any():
+        raise ValueError("ancestors must be rows of the pool, 0 .. %d" % (N - 1))
+    out = np.empty((E + 1, N), dtype=np.int64)
+    out[E] = np.arange(N)
+    for e in range(E - 1, -1, -1):
+        out[e] = anc[e][out[e + 1]]
+    return out
+
+
+class ParticleSet:
+    """The K weighted particles generate_particles returns for one song.
+    songs: K (L_i, 6) int64 arrays, prompt included; logprobs: K (L_i - P, 6, 2) f32 arrays, the (model, sampler) pairs
+    of each song's drawn rows along its lineage (generate_batch(return_logprobs=True)'s layout); log_weights: (K,) f32,
+    each particle's weight since the group was last resampled (the sum of lp_model - lp_sampler over those rows);
+    log_evidence: the estimate of log P(the song obeys what the sampler enforces) under the target's unrestricted
+    model, the resampling events' increments + logmeanexp(log_weights); per event that happened while the song had a
+    live particle, ess (E,) f32, resampled (E,) bool, ancestors (E, K) int64 in-group indices (the identity where
+    resampled is False) and event_log_weights (E, K) f32, the weights of the song's K pool rows as the event saw
+    them."""
+
+    def __init__(self, songs, logprobs, log_weights, log_evidence, ess, resampled, ancestors, event_log_weights=None):
+        self.songs, self.logprobs = songs, logprobs
+        self.log_weights, self.log_evidence = log_weights, float(log_evidence)
+        self.ess, self.resampled, self.ancestors = ess, resampled, ancestors
+        self.event_log_weights = event_log_weights
+
+    def weights(self):
+        """The normalised weights, (K,) float64."""
+        w = self.log_weights.astype(np.float64)
+        w = np.exp(w - w.max())
+        return w / w.sum()
+
+    def draw(self, rng, return_index=False):
+        """One song by final weight (rng: a numpy Generator) -> the song, or (song, its index)."""
+        k = int(rng.choice(len(self.songs), p=self.weights()))
+        return (self.songs[k], k) if return_index else self.songs[k]
+
+
+def _repeat_per_song(value, n_songs, K):
+    """A per-song list repeated K times entry by entry (row g K + k is song g); anything else passes through."""
+    if isinstance(value, (list, tuple)) and len(value) == n_songs:
+        return [v for v in value for _ in range(K)]
+    return value
+
+
+def _particle_setup(where, model, word2event, n_songs, particles, resample_every, ess, bar_cond, max_tokens, prompts,
+                    sampler, chunk, prefill, constraints, grammar, reference, alpha, preferences, pool=None):
+    """generate_particles' refusals, then generate_batch's for the n_songs x particles rows (_batch_setup), every
+    per-song entry repeated `particles` times -> (heads, caps, plan) of the rows.  pool: the songs that share one
+    pool (default: all)."""
+    K = int(particles)
+    if not 2 <= K <= 1024:
+        raise ValueError("particles must be 2 .. 1024, got %r" % (particles,))
+    pool = int(n_songs) if pool is None else int(pool)
+    if pool * K > PARTICLE_ROWS:
+        raise ValueError("n_songs x particles = %d x %d rows, the step takes at most %d" % (pool, K, PARTICLE_ROWS))
+    if int(resample_every) < 1:
+        raise ValueError("resample_every must be >= 1, got %r" % (resample_every,))
+    if not 0.0 <= float(ess) <= 1.0:
+        raise ValueError("ess must lie in [0, 1] (the fraction of `particles` below which a song is resampled), got %r"
+                         % (ess,))
+    n = int(n_songs)
+    if alpha is not None and reference is not None and n >= 1:
+        try:
+            table = compile_alpha(alpha, n, len(word2event))
+            alpha = np.repeat(table, K, axis=0) if len(table) > 1 else table
+        except ValueError:
+            pass                                                       # the plan refuses it, in its place
+    return _batch_setup(where, model, word2event, n * K, bar_cond, max_tokens, _repeat_per_song(prompts, n, K),
+                        sampler, chunk, prefill, constraints=_repeat_per_song(constraints, n, K), logprobs=True,
+                        grammar=grammar, reference=reference, alpha=alpha,
+                        preferences=_repeat_per_song(preferences, n, K))
+
+
+def _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, chunk, log, prefill,
+                   stats=None):
+    """generate_particles after its refusals: the rows of `plan` (particles consecutive rows per song) -> ParticleSets.
+    stats (a dict, optional): filled with steps, events, seconds, the rows every event moved and what one moved row
+    copies per phase; a stats that comes with {"timed": True} also gets the HIP-event times of every event's resampling
+    and two gather phases."""
+    N, K, R, A = plan.n_songs, int(particles), int(resample_every), len(word2event)
+    cap = max(caps)
+    start = time.perf_counter()
+    sess = DecodeSession(model, n_songs=N, kernel="gemm")
+    sess.reset()
+    ref = sess.shadow(plan.reference)
+    bar_mask = plan.bar_mask if plan.bar_mask is not None else plan._bar_classes()
+    loop = _ParticleLoop(sess, cap, DeviceDraw(plan, sess.dev, ref), K, R, ess, bar_cond, caps, bar_mask,
+                         graph=sess.use_graph, ring=chunk, timed=bool(stats and stats.get("timed")))
+    if prefill is None:
+        sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (N, 1)), dtype=torch.int64).view(N, 1, A).to(sess.dev))
+    else:
+        P = max(len(p) for p in heads)
+        toks = np.zeros((N, P, A), dtype=np.int64)
+        for i, p in enumerate(heads):
+            toks[i, :len(p)] = p
+        lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
+        loop.start(sess._prefill(toks, lengths, kernel=prefill),
+                   None if ref is None else ref._prefill(toks, lengths, kernel=prefill))
+    rows, lps = [], []
+    done = 0
+    while done < cap:
+        stop = min(cap, done + chunk)
+        loop.run(stop - loop.enqueued)
+        rows.append(loop.tokens(done, stop))                           # (stop - done, N, 6)
+        lps.append(loop.logprobs(done, stop))
+        done = stop
+        if bool(loop.done.all().item()):
+            break
+    rows, lps = np.concatenate(rows), np.concatenate(lps)
+    lens, lw, log_z = loop.len.cpu().numpy(), loop.lw.cpu().numpy(), loop.log_z.cpu().numpy()
+    E = loop.n_events
+    h_anc = loop.h_anc[:E].cpu().numpy()
+    h_ess, h_res = loop.h_ess[:E].cpu().numpy(), loop.h_res[:E].cpu().numpy()
+    h_lw = loop.h_lw[:E].cpu().numpy()
+    line = particle_lineage(h_anc, N)
+    seg = np.minimum(np.arange(len(rows)) // R, E)                     # the segment each drawn row belongs to
+    out = []
+    for g in range(N // K):
+        songs, logps = [], []
+        for n in range(g * K, (g + 1) * K):
+            t = np.arange(int(lens[n]))
+            src = line[seg[t], n]
+            songs.append(np.concatenate([heads[n], rows[t, src]]))
+            logps.append(lps[t, src].astype(np.float32).reshape(-1, A, 2))
+        w = lw[g * K:(g + 1) * K].astype(np.float32)
+        # events after the song's last particle ended are not its own: they depend on the other songs of the pool.  The
+        # song had a live particle up to its last resampling (which may have replaced the last live one by copies of
+        # finished ones) and, after it, until the longest final particle ended
+        hit = np.nonzero(h_res[:, g])[0]
+        live = max(int(np.count_nonzero((np.arange(E) + 1) * R < int(lens[g * K:(g + 1) * K].max()))),
+                   int(hit.max()) + 1 if len(hit) else 0)
+        out.append(ParticleSet(songs, logps, w, float(log_z[g]) + logmeanexp(w), h_ess[:live, g].copy(),
+                               h_res[:live, g] != 0, h_anc[:live, g * K:(g + 1) * K] - g * K,
+                               h_lw[:live, g * K:(g + 1) * K].copy()))
+    if log is not None:
+        log("%d songs x %d particles: %d tokens, %d steps, %d resampling events"
+            % (N // K, K, sum(len(x) for s in out for x in s.songs), done, E))
+    if stats is not None:
+        torch.cuda.synchronize(sess.dev)
+        moved = (h_anc != np.arange(N)).sum(1)
+        stats.update(steps=done, events=E, seconds=time.perf_counter() - start, graph=loop._graph is not None,
+                     drawn=int(lens.sum()), row_bytes=loop.row_bytes, moved_rows=[int(m) for m in moved],
+                     resampled_groups=[int(r.sum()) for r in h_res], groups=N // K,
+                     event_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)] for m in loop.timed or []])
+    return out
+
+
+def generate_particles(model, word2event, n_songs, particles, resample_every=16, ess=0.5, bar_cond=17, max_tokens=None,
+                       prompts=None, sampler="dqn", chunk=128, log=None, prefill="blas", constraints=None,
+                       grammar=None, reference=None, alpha=None, preferences=None):
+    """Generate `n_songs` songs with `particles` = K weighted particles each, by sequential Monte Carlo with the device
+    sampler as the proposal.  -> list of n_songs ParticleSet.
+
+    Constraints, the row grammar and the nucleus act row by row: the sampler removes classes and renormalises, so a
+    prefix the model rarely continues inside the allowed set is kept as readily as one it continues there with
+    probability 0.9.  The pair the sampler writes for every drawn class gives the exact local error: lp_model -
+    lp_sampler is, at temperature 1 without a nucleus, the log of the allowed mass of that draw -- the importance weight
+    of the local proposal against the model restricted to allowed rows.  Here K particles per song run in lock-step in
+    one pool (row g K + k is particle k of song g; one DecodeSession(n_songs x K, kernel="gemm") and the lock-step
+    device loop), cwlt_particle_weigh accumulates the weights inside the captured token, and after every
+    `resample_every` rows cwlt_particle_resample looks at each song: when its effective sample size (sum w)^2 / sum w^2
+    is below ess x K, its particles are resampled systematically -- low-weight particles replaced by copies of
+    high-weight ones -- and cwlt_particle_gather moves every per-row state of the loop (the decode state of the model
+    and of a blend's reference, token, bar count, grammar position, repetition state, length, end flag, cap) from
+    ancestor to descendant, through scratch.  A song ends by generate_batch's rule, decided on the device; a finished
+    particle keeps its weight and takes part in later resamplings of its song.
+
+    The target is the distribution of the logits the plan builds (blended, preferred), restricted to rows the mask and
+    the grammar allow, and conditioned on the WHOLE song being allowed.  The weighted particles are exact for it in the
+    limit of K at temperature 1 without a nucleus (sampler="categorical"); ParticleSet.log_evidence then estimates
+    log P(the song obeys the constraints) under those logits.  With a temperature, the weights also carry the ratio of
+    the model's distribution to the tempered one.  With a nucleus (sampler="dqn"), classes outside the kept set stay
+    unreachable: the weights then correct only the renormalisation, not the cut.
+
+    ess=0 never resamples: the run is generate_batch(n_songs x K, ..., return_logprobs=True) with every per-song entry
+    repeated K times, bit for bit, plus the weights.  prompts, constraints, preferences (one for all, or a list of
+    n_songs), alpha, grammar, reference, sampler, bar_cond, max_tokens, chunk, prefill: as in generate_batch.  Each
+    prompt is prefilled K times: sharing one prefill among a song's particles is left out.  Draws are keyed by (torch
+    seed, step, row) and the resampling draw by (seed, event, song), so song g's set is the same whatever the other
+    songs.  The continuous-batching stream (slots=) and reward terms in the weights are out of scope.
+    Refused, before anything runs: particles outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit),
+    resample_every < 1, ess outside [0, 1], then everything generate_batch refuses."""
+    heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
+                                        ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
+                                        grammar, reference, alpha, preferences)
+    return _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, int(chunk),
+                          log, None if prompts is None else prefill)
+
+
 SCORE_BLOCK_SONGS = 1024    # most songs in one score_songs block: bounds its scratch decode state (1.6 MB a song at repo dims)
 
 
@@ -1497,7 +1797,7 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
              batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None,
-             reference=None, alpha=None, preferences=None):
+             reference=None, alpha=None, preferences=None, particles=None, resample_every=16, ess=0.5):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1510,9 +1810,15 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     with slots, each batch_size group with its own slice of the list, or one song at a time.
     constraints, grammar, reference / alpha, preferences (generate_batch, generate_stream) and logprobs=True (their
     return_logprobs: each song's drawn-row log-probs are saved as get_<i>_logp.npy next to the song): with slots or
-    batch_size only, the one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs)."""
+    batch_size only, the one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs).
+    particles=K (with batch_size; resample_every, ess: generate_particles'): each group is made by
+    generate_particles with K particles a song, and each song kept is ParticleSet.draw -- one particle by final weight --
+    with a numpy generator seeded from the torch seed.  None (the default): nothing changes."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if particles is not None and batch_size is None:
+        raise ValueError("particles run in generate_particles' lock-step pool: pass batch_size (the songs of one pool; "
+                         "the stream, slots=, takes no particles)")
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
         raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
                          "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
@@ -1572,15 +1878,33 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
         if int(batch_size) < 1:
             raise ValueError("batch_size must be >= 1")
         given = prompt if prompts is None else list(prompts)
-        heads, caps, plan = _batch_setup("generate", model, word2event, n_songs, bar_cond, max_tokens, given, "dqn", 128,
-                                         "blas", constraints=constraints, logprobs=logprobs, grammar=grammar,
-                                         reference=reference, alpha=alpha, preferences=preferences)
+        K = 1 if particles is None else int(particles)
+        if particles is None:
+            heads, caps, plan = _batch_setup("generate", model, word2event, n_songs, bar_cond, max_tokens, given, "dqn",
+                                             128, "blas", constraints=constraints, logprobs=logprobs, grammar=grammar,
+                                             reference=reference, alpha=alpha, preferences=preferences)
+        else:
+            heads, caps, plan = _particle_setup("generate", model, word2event, n_songs, particles, resample_every, ess,
+                                                bar_cond, max_tokens, given, "dqn", 128, "blas", constraints, grammar,
+                                                reference, alpha, preferences, pool=min(n_songs, int(batch_size)))
+            rng = None
         for first in range(0, n_songs, int(batch_size)):
-            group = slice(first, first + int(batch_size))
+            rows = slice(first * K, (first + int(batch_size)) * K)
+            count = len(heads[rows]) // K
             start = time.time()
-            songs = _run_batch(model, word2event, heads[group], caps[group], plan.songs(first, len(heads[group])),
-                               bar_cond, 128, None, None if given is None else "blas")
-            record(first, songs, time.time() - start, "batch of %d" % len(heads[group]))
+            if particles is None:
+                songs = _run_batch(model, word2event, heads[rows], caps[rows], plan.songs(first, count), bar_cond, 128,
+                                   None, None if given is None else "blas")
+            else:
+                sets = _run_particles(model, word2event, heads[rows], caps[rows], plan.songs(first * K, count * K), K,
+                                      resample_every, ess, bar_cond, 128, None, None if given is None else "blas")
+                if rng is None:                                        # after the first pool's seed: that pool is
+                    rng = np.random.default_rng(ops.next_seed())      # generate_particles' with the same torch seed
+                picks = [s.draw(rng, return_index=True) for s in sets]
+                songs = [p[0] for p in picks]
+                if logprobs:
+                    songs = (songs, [s.logprobs[p[1]] for s, p in zip(sets, picks)])
+            record(first, songs, time.time() - start, "batch of %d" % count)
     else:
         sess = DecodeSession(model)
         for sidx in range(n_songs):

@@ -2016,6 +2016,72 @@ def count_bars(tokens, bar_attr, bar_mask, bar):
     return bar
 
 
+def particle_weigh(logp, out_counter, bar, bar_cond, cap, lw, length, done):
+    """One token of the particles' weights (cwlt_particle_weigh): for every row n with done[n] == 0,
+    lw[n] += sum_a (logp[o, n, a, 0] - logp[o, n, a, 1]) with o = *out_counter % R (logp the (R, rows, A, 2) f32 ring of
+    sample_categorical_logp, out_counter its device int64 counter; None needs R == 1), length[n] += 1, and done[n] = 1
+    when bar[n] >= bar_cond or length[n] >= cap[n].  lw (rows,) f32; bar, cap, length, done (rows,) int64."""
+    rows = lw.numel()
+    if logp.dtype != torch.float32 or lw.dtype != torch.float32 or not logp.is_contiguous() or not lw.is_contiguous():
+        raise TypeError("particle_weigh takes a contiguous f32 log-prob ring and f32 weights")
+    if logp.dim() != 4 or logp.shape[1] != rows or logp.shape[3] != 2:
+        raise ValueError("particle_weigh: logp must be (R, rows = %d, A, 2), got %s" % (rows, tuple(logp.shape)))
+    for t in (bar, cap, length, done):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != rows:
+            raise TypeError("particle_weigh takes contiguous int64 bar, cap, length and done of %d rows" % rows)
+    if out_counter is None and logp.shape[0] != 1:
+        raise ValueError("particle_weigh: a ring of %d rows needs its counter" % logp.shape[0])
+    if out_counter is not None and out_counter.dtype != torch.int64:
+        raise TypeError("particle_weigh: out_counter must be a device int64")
+    _call("cwlt_particle_weigh", _lib.dev(logp, "logp"), _lib.opt(out_counter), logp.shape[0], rows, logp.shape[2],
+          _lib.dev(bar, "bar"), int(bar_cond), _lib.dev(cap, "cap"), _lib.dev(lw, "lw"), _lib.dev(length, "length"),
+          _lib.dev(done, "done"), _lib.stream_ptr())
+    return lw
+
+
+def particle_resample(lw, done, particles, ess_frac, seed, event, anc, u, ess, resampled, log_z):
+    """One resampling event (cwlt_particle_resample): lw, done (rows,) in groups of `particles` consecutive
+    rows; a group below ess_frac * particles effective samples (and not all done) is resampled systematically.  Written:
+    anc (rows,) int64 global ancestor rows (the identity for a kept group), u, ess (groups,) f32, resampled (groups,)
+    int32; log_z (groups,) f32 gains the group's evidence increment and its lw become 0.  u is keyed by (seed, event,
+    group)."""
+    rows, K = lw.numel(), int(particles)
+    if K < 1 or rows % K:
+        raise ValueError("particle_resample: %d rows are no whole groups of %d particles" % (rows, K))
+    groups = rows // K
+    for t, dt, n in ((lw, torch.float32, rows), (done, torch.int64, rows), (anc, torch.int64, rows),
+                     (u, torch.float32, groups), (ess, torch.float32, groups), (resampled, torch.int32, groups),
+                     (log_z, torch.float32, groups)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("particle_resample takes contiguous lw f32 / done, anc int64 (rows,) and u, ess, log_z f32 / "
+                            "resampled int32 (groups,)")
+    _call("cwlt_particle_resample", _lib.dev(lw, "lw"), _lib.dev(done, "done"), groups, K, float(ess_frac),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), _lib.dev(anc, "anc"), _lib.dev(u, "u"), _lib.dev(ess, "ess"),
+          _lib.dev(resampled, "resampled"), _lib.dev(log_z, "log_z"), _lib.stream_ptr())
+    return anc
+
+
+def particle_gather(dst, src, anc, row_bytes, n_blocks=1, block_stride=0, copy_back=False):
+    """dst[b][n] = src[b][anc[n]] for the rows n with anc[n] != n (cwlt_particle_gather): dst and src are
+    contiguous tensors (or views: the family starts at their first element) of one layout, row n of block b at byte
+    b * block_stride + n * row_bytes; anc (rows,) int64.  Rows that stay, and rows whose ancestor is out of range, are
+    neither read nor written.  dst must not be src: move a state through a scratch buffer, in two calls, the second
+    with copy_back=True (dst[b][n] = src[b][n] for the same rows)."""
+    rows = anc.numel()
+    if anc.dtype != torch.int64 or not anc.is_contiguous():
+        raise TypeError("particle_gather takes a contiguous int64 ancestor vector")
+    if not dst.is_contiguous() or not src.is_contiguous():
+        raise TypeError("particle_gather takes contiguous buffers")
+    need = (int(n_blocks) - 1) * int(block_stride) + rows * int(row_bytes)
+    for t, name in ((dst, "dst"), (src, "src")):
+        if t.numel() * t.element_size() < need:
+            raise ValueError("particle_gather: %s holds %d bytes, the family %d (%d blocks, stride %d, %d rows x %d B)"
+                             % (name, t.numel() * t.element_size(), need, n_blocks, block_stride, rows, row_bytes))
+    _call("cwlt_particle_gather", _lib.dev(dst, "dst"), _lib.dev(src, "src"), _lib.dev(anc, "anc"), rows,
+          int(row_bytes), int(n_blocks), int(block_stride), int(bool(copy_back)), _lib.stream_ptr())
+    return dst
+
+
 def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):
     """Copy the one-slot snapshot (state, logits) into every slot whose fresh flag is set (cwlt_stream_refill).
     state: flat f32 of n_layer x [S (slots, s_floats), Z (slots, z_floats)] (DecodeSession._state); snap_state: the same

@@ -235,3 +235,62 @@ def grammar_logprobs_f64(logits, target, beat, order, gram, bar_attr, temperatur
         p = None if top_p is None else top_p[a]
         out[a] = logprobs_f64(logits[a], target[a], t, p, sets[a])
     return out
+
+
+def particle_weigh_f32(lw, pairs, done=None):
+    """Numpy float32 restatement of cwlt_particle_weigh's weight update for one token: lw (rows,) and the
+    token's log-prob pairs (rows, A, 2) -> the new (rows,) float32 weights, bitwise the kernel's.  Per row the
+    differences model - sampler are added in attribute order from 0, then the row's sum is added to lw, every
+    operation rounded on its own.  done (rows,), optional: rows with done != 0 keep their weight."""
+    lw = np.asarray(lw, dtype=np.float32)
+    p = np.asarray(pairs, dtype=np.float32)
+    s = np.zeros(lw.shape, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        for a in range(p.shape[-2]):
+            s = (s + (p[..., a, 0] - p[..., a, 1]).astype(np.float32)).astype(np.float32)
+        out = (lw + s).astype(np.float32)
+    return out if done is None else np.where(np.asarray(done) != 0, lw, out)
+
+
+def logmeanexp(x):
+    """log(mean(exp(x))) of a vector in float64, by the max subtraction; -inf for all -inf."""
+    x = np.asarray(x, dtype=np.float64)
+    m = x.max()
+    return float(m) if not np.isfinite(m) else float(m + np.log(np.exp(x - m).mean()))
+
+
+class Resampled:
+    """What systematic_resample decides for one group: anc (K,) int64 in-group ancestors, ess, resampled (0 / 1), log_z
+    (the evidence increment, 0.0 for a kept group), lw (K,) the weights after the event; and, for a comparison with
+    float32 arithmetic, the scaled prefix sums `prefix` (K,), the thresholds (K,) they were searched with and s."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def systematic_resample(lw, u, ess_frac, done=None):
+    """Float64 restatement of cwlt_particle_resample for ONE group: lw (K,) log-weights, u in [0, 1) ->
+    Resampled.  m = max lw, e = exp(lw - m), s = sum e, ess = s^2 / sum e^2.  A group whose rows are all done, or with
+    ess >= ess_frac * K, is kept: the identity, resampled 0, weights unchanged.  Otherwise ancestor j is the first row
+    whose inclusive prefix sum of e exceeds (j + u) / K * s (the last row when none does), the increment of the log
+    evidence is m + log(s / K) and every weight becomes 0."""
+    x = np.asarray(lw, dtype=np.float64).reshape(-1)
+    K = len(x)
+    if K < 2:
+        raise ValueError("a group has at least 2 particles, got %d" % K)
+    if not 0.0 <= float(u) < 1.0:
+        raise ValueError("u must lie in [0, 1), got %r" % (u,))
+    m = x.max()
+    e = np.exp(x - m) if np.isfinite(m) else np.zeros(K)
+    prefix = np.cumsum(e)
+    s = float(prefix[-1])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ess = s * s / float((e * e).sum())
+    thresholds = (np.arange(K) + float(u)) / K * s
+    all_done = done is not None and bool(np.all(np.asarray(done) != 0))
+    if all_done or not s > 0.0 or ess >= float(ess_frac) * K:
+        return Resampled(anc=np.arange(K, dtype=np.int64), ess=ess, resampled=0, log_z=0.0, lw=x.copy(),
+                         prefix=prefix, thresholds=thresholds, s=s)
+    anc = np.minimum(np.searchsorted(prefix, thresholds, side="right"), K - 1).astype(np.int64)
+    return Resampled(anc=anc, ess=ess, resampled=1, log_z=float(m + np.log(s / K)), lw=np.zeros(K), prefix=prefix,
+                     thresholds=thresholds, s=s)
