@@ -727,6 +727,34 @@ int cwlt_particle_resample(float* lw, const int64_t* done, int64_t groups, int p
 int cwlt_particle_gather(void* dst, const void* src, const int64_t* anc, int64_t rows, int64_t row_bytes, int n_blocks,
                          int64_t block_stride, int copy_back, void* stream);
 
+/* ---- reward terms in the particles' weights (csrc/reward.hip) ----------------------------------------------
+ * Each pool row keeps a ring of its particle's last `window` = W drawn rows, recent (rows, W, n_attr) int64, and of
+ * whether the particle was alive when each was drawn, live (rows, W) int64.  Both are per-row state: a caller hands them
+ * to cwlt_particle_gather with everything else, so a descendant inherits its ancestor's window.  One launch each, no host
+ * synchronisation, no allocation, no atomics.  Every pointer is DEVICE memory.  rows 1 .. 2^20, n_attr 1 .. 8,
+ * W 1 .. 2^16; anything else, and a null pointer, is refused with CWLT_ERR_ARG before any launch.
+ *
+ * cwlt_reward_push (per token, after the draw and BEFORE cwlt_particle_weigh): with s = *counter % W,
+ *     recent[n, s, :] = tok[n, :],  live[n, s] = (done[n] == 0),
+ * tok (rows, n_attr) int64 the token just drawn, done as the previous token's cwlt_particle_weigh left it (so the row
+ * that ends a song is live), counter the loop's device int64 row counter.
+ *
+ * cwlt_reward_window (per reward event; the slots 0 .. filled - 1 of the ring hold the window's rows in time order,
+ * 1 <= filled <= W): for slot j of row n, when j < filled and live[n, j] != 0, win[n, j, :] = recent[n, j, :] and
+ * mask[n, j] = 1; elsewhere win[n, j, :] = 0 and mask[n, j] = 0.  any[n] = 1 when row n has such a slot, else 0, and
+ * then mask[n, 0] = 1 (tokens 0): no consumer sees an empty window.  win (rows, W, n_attr), mask (rows, W), any (rows,)
+ * int64.
+ *
+ * cwlt_reward_apply: for the rows with any[n] != 0, lw[n] = lw[n] + (beta * r[n]), the product rounded to f32 and then
+ * the sum (no fma), and h_r[n] = r[n]; for the others lw[n] is not written and h_r[n] = 0 whatever r[n] holds (a
+ * select: r[n] may be NaN).  r, lw, h_r f32 x rows. */
+int cwlt_reward_push(const int64_t* tok, const int64_t* done, const int64_t* counter, int64_t rows, int n_attr,
+                     int64_t window, int64_t* recent, int64_t* live, void* stream);
+int cwlt_reward_window(const int64_t* recent, const int64_t* live, int64_t rows, int n_attr, int64_t window,
+                       int64_t filled, int64_t* win, int64_t* mask, int64_t* any, void* stream);
+int cwlt_reward_apply(const float* r, const int64_t* any, float beta, int64_t rows, float* lw, float* h_r,
+                      void* stream);
+
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass
  * (dqn_policy/IRL_dqn_train.py:267-345 `DQN.update`, ppo_policy/ppo_train.py:365-417 `update_policy`): ~970 launches of

@@ -599,10 +599,19 @@ class _ParticleLoop(_DeviceLoop):
     int32), then the two-phase cwlt_particle_gather of every per-row state the loop
     carries -- the model's decode state and the reference's, the token buffer, bar, beat, seen, len, done, cap --
     through scratch buffers of the same shapes: eager launches on the loop's stream, no sync.  lw is not gathered: the
-    resampling kernel set it.  timed=True records HIP events around the resampling and each gather phase."""
+    resampling kernel set it.  timed=True records HIP events around the resampling and each gather phase.
+
+    reward (a _reward_spec: callable, window W, beta): two more per-row states, the ring `recent`
+    (N, W, A) int64 of each particle's last W drawn rows and `live` (N, W) int64, whether the particle was alive at each,
+    both gather families -- so a descendant inherits its ancestor's window together with its `done` flag, although the
+    `song` ring is never gathered.  cwlt_reward_push fills slot count % W inside the captured token, ahead of
+    cwlt_particle_weigh (it reads `done` as it was before the row).  After every W-th token, and ahead of a resampling
+    event of the same token, reward_event(): cwlt_reward_window cuts the rings into win / mask / any, the callable
+    scores them, cwlt_reward_apply adds beta r to lw and writes r into row j of h_r (ceil(capacity / W), N) f32 --
+    eager launches on the loop's stream, no sync.  timed=True records HIP events around the three steps too."""
 
     def __init__(self, sess, capacity, plan, particles, every, ess, bar_cond, caps, bar_mask, graph=None, ring=None,
-                 timed=False):
+                 timed=False, reward=None):
         super().__init__(sess, capacity, plan, graph=graph, ring=ring)
         dev, N = sess.dev, self.N
         self.K, self.every, self.ess_frac, self.bar_cond = int(particles), int(every), float(ess), int(bar_cond)
@@ -623,6 +632,14 @@ class _ParticleLoop(_DeviceLoop):
         self.h_ess = torch.zeros((E, self.G), dtype=torch.float32, device=dev)
         self.h_res = torch.zeros((E, self.G), dtype=torch.int32, device=dev)
         self.n_events = 0
+        self.reward, self.recent, self.live, self.n_rewards = reward, None, None, 0
+        if reward is not None:
+            W = reward[1]
+            self.recent = torch.zeros((N, W, self.A), dtype=torch.int64, device=dev)
+            self.live = torch.zeros((N, W), dtype=torch.int64, device=dev)
+            self.win, self.mask = torch.zeros_like(self.recent), torch.zeros_like(self.live)
+            self.any = torch.zeros(N, dtype=torch.int64, device=dev)
+            self.h_r = torch.zeros((-(-self.capacity // W), N), dtype=torch.float32, device=dev)
         # (state, scratch, row bytes, blocks, block stride in bytes) of every family of per-row buffers
         self.families = []
         for s in (sess, self.ref):
@@ -633,16 +650,47 @@ class _ParticleLoop(_DeviceLoop):
             stride = 4 * N * (sf + zf)
             self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
             self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
-        for t in (sess.tok, self.pbar, self.beat, self.seen, self.len, self.done, self.cap):
+        for t in (sess.tok, self.pbar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live):
             if t is not None:
                 self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
         self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)      # what one moved row copies per phase
         self.timed = [] if timed else None
+        self.reward_timed = [] if timed and reward is not None else None
 
     def _after_draw(self, tok):
         if self.pbar is not self.bar:
             ops.count_bars(tok, 2, self.pbar_mask, self.pbar)
+        if self.reward is not None:
+            ops.reward_push(tok, self.done, self.count, self.recent, self.live)
         ops.particle_weigh(self.logp, self.count, self.pbar, self.bar_cond, self.cap, self.lw, self.len, self.done)
+
+    def reward_event(self, filled=None):
+        """One reward event, enqueued: the window the callable sees, the callable, beta r into the weights.  filled:
+        the ring's slots that belong to the window (default: all W, the ring has just wrapped)."""
+        fn, W, beta = self.reward
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.reward_timed is not None else None
+        mark = (lambda i: marks[i].record()) if marks else (lambda i: None)
+        mark(0)
+        ops.reward_window(self.recent, self.live, W if filled is None else filled, self.win, self.mask, self.any)
+        mark(1)
+        r = fn(self.win, self.mask)
+        if not torch.is_tensor(r) or not r.is_cuda or r.dtype != torch.float32 or tuple(r.shape) != (self.N,):
+            raise TypeError("reward(windows, mask) must return a (%d,) float32 tensor on the GPU, got %s"
+                            % (self.N, "%s %s" % (tuple(r.shape), r.dtype) if torch.is_tensor(r) else type(r).__name__))
+        mark(2)
+        ops.reward_apply(r.contiguous(), self.any, beta, self.lw, self.h_r[self.n_rewards])
+        mark(3)
+        if marks:
+            self.reward_timed.append(marks)
+        self.n_rewards += 1
+
+    def _events(self):
+        """What follows a token between replays: the reward event first, so that a resampling of the same token sees
+        it."""
+        if self.reward is not None and self.enqueued % self.reward[1] == 0:
+            self.reward_event()
+        if self.enqueued % self.every == 0:
+            self.resample()
 
     def resample(self):
         """One resampling event, enqueued: the decision and ancestors, then every family state -> scratch -> state."""
@@ -666,20 +714,19 @@ class _ParticleLoop(_DeviceLoop):
         self.n_events += 1
 
     def run(self, n):
-        """Enqueue n more tokens, with a resampling event after every `every`-th token of the run (no host sync)."""
+        """Enqueue n more tokens, with a resampling event after every `every`-th token of the run and, under a reward, a
+        reward event after every W-th (no host sync)."""
         n = min(n, self.capacity - self.enqueued)
         with torch.no_grad():
             for _ in range(n):
                 _enqueue_token(self, "particle loop")
-                if self.enqueued % self.every == 0:
-                    self.resample()
+                self._events()
         return n
 
     def start(self, logits, ref_logits=None):
         super().start(logits, ref_logits)
-        if self.every == 1:
-            with torch.no_grad():
-                self.resample()
+        with torch.no_grad():
+            self._events()                                             # only an `every` or a W of 1 has one here
 
 
 class _StreamLoop:
@@ -1418,13 +1465,19 @@ class ParticleSet:
     model, the resampling events' increments + logmeanexp(log_weights); per event that happened while the song had a
     live particle, ess (E,) f32, resampled (E,) bool, ancestors (E, K) int64 in-group indices (the identity where
     resampled is False) and event_log_weights (E, K) f32, the weights of the song's K pool rows as the event saw
-    them."""
+    them.  Under a reward rewards: K (n_windows_i,) f32 arrays, the window rewards applied along each
+    particle's lineage (n_windows_i = ceil((L_i - P) / reward_window)); log_weights then carry beta x them as well and
+    log_evidence estimates the log of the constrained expectation of exp(beta sum r); event_rewards (R, K) f32 is what
+    each reward event that happened while the song had a live particle recorded for the song's K pool rows (0 for a
+    row without a live row in the window).  Both None without a reward."""
 
-    def __init__(self, songs, logprobs, log_weights, log_evidence, ess, resampled, ancestors, event_log_weights=None):
+    def __init__(self, songs, logprobs, log_weights, log_evidence, ess, resampled, ancestors, event_log_weights=None,
+                 rewards=None, event_rewards=None):
         self.songs, self.logprobs = songs, logprobs
         self.log_weights, self.log_evidence = log_weights, float(log_evidence)
         self.ess, self.resampled, self.ancestors = ess, resampled, ancestors
         self.event_log_weights = event_log_weights
+        self.rewards, self.event_rewards = rewards, event_rewards
 
     def weights(self):
         """The normalised weights, (K,) float64."""
@@ -1443,6 +1496,60 @@ def _repeat_per_song(value, n_songs, K):
     if isinstance(value, (list, tuple)) and len(value) == n_songs:
         return [v for v in value for _ in range(K)]
     return value
+
+
+REWARD_FORMS = ("log_odds", "log", "score")
+
+
+class WindowReward:
+    """A reward callable for generate_particles(reward=) from an AIRL discriminator (dqn_policy.AIRL_model.LongFormer:
+    forward(data (B, W, 6), masks (B, W)) -> (B, 1) scores D in (0, 1)); DESIGN §4.6n.
+    form="log_odds" (default): log D - log(1 - D) with D clamped to [eps, 1 - eps], the AIRL reward; "log": log D (D
+    clamped the same way); "score": D itself.  The transform is plain torch on the (N,) scores.
+
+    The call runs under torch.no_grad() with every module of `disc` in eval() mode, and puts each module's mode back
+    afterwards.  The reference scores its windows in train() mode, with live dropout and the score classifier's
+    BatchNorm1d on batch statistics: there a window's score depends on the other windows of the batch -- here, on the
+    other particles and songs of the pool -- and moves the running statistics.  In eval() every entry depends on its own
+    window alone, which is what reward weights need, and the module is left as it was found."""
+
+    def __init__(self, disc, form="log_odds", eps=1e-6):
+        if form not in REWARD_FORMS:
+            raise ValueError("form must be one of %s, got %r" % (", ".join(repr(f) for f in REWARD_FORMS), form))
+        if not callable(disc):
+            raise TypeError("disc must be a discriminator module: (windows, mask) -> (N, 1) scores")
+        eps = float(eps)
+        if not 0.0 < eps < 0.5:
+            raise ValueError("eps must lie in (0, 0.5), got %r" % (eps,))
+        self.disc, self.form, self.eps = disc, form, eps
+
+    def __call__(self, windows, mask):
+        modules = list(self.disc.modules()) if hasattr(self.disc, "modules") else []
+        modes = [m.training for m in modules]
+        try:
+            if modules:
+                self.disc.eval()
+            with torch.no_grad():
+                d = self.disc(windows, mask).reshape(-1).float()
+        finally:
+            for m, was in zip(modules, modes):
+                m.training = was
+        if self.form == "score":
+            return d
+        d = d.clamp(self.eps, 1.0 - self.eps)
+        return torch.log(d) if self.form == "log" else torch.log(d) - torch.log(1.0 - d)
+
+
+def _reward_spec(reward, reward_window, beta):
+    """generate_particles' reward refusals -> None without a reward, else (callable, W, beta)."""
+    if reward is not None and not callable(reward):
+        raise TypeError("reward must be a callable (windows (N, W, A) int64, mask (N, W) int64) -> (N,) float32, got %r"
+                        % (type(reward).__name__,))
+    if int(reward_window) < 1:
+        raise ValueError("reward_window must be >= 1, got %r" % (reward_window,))
+    if not np.isfinite(float(beta)):
+        raise ValueError("beta must be finite, got %r" % (beta,))
+    return None if reward is None else (reward, int(reward_window), float(beta))
 
 
 def _particle_setup(where, model, word2event, n_songs, particles, resample_every, ess, bar_cond, max_tokens, prompts,
@@ -1475,11 +1582,12 @@ def _particle_setup(where, model, word2event, n_songs, particles, resample_every
 
 
 def _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, chunk, log, prefill,
-                   stats=None):
+                   stats=None, reward=None):
     """generate_particles after its refusals: the rows of `plan` (particles consecutive rows per song) -> ParticleSets.
     stats (a dict, optional): filled with steps, events, seconds, the rows every event moved and what one moved row
     copies per phase; a stats that comes with {"timed": True} also gets the HIP-event times of every event's resampling
-    and two gather phases."""
+    and two gather phases (and of every reward event's window kernel, callable and apply kernel).
+    reward: a _reward_spec; a run that ends inside a window closes it with one partial reward event."""
     N, K, R, A = plan.n_songs, int(particles), int(resample_every), len(word2event)
     cap = max(caps)
     start = time.perf_counter()
@@ -1488,7 +1596,7 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
     ref = sess.shadow(plan.reference)
     bar_mask = plan.bar_mask if plan.bar_mask is not None else plan._bar_classes()
     loop = _ParticleLoop(sess, cap, DeviceDraw(plan, sess.dev, ref), K, R, ess, bar_cond, caps, bar_mask,
-                         graph=sess.use_graph, ring=chunk, timed=bool(stats and stats.get("timed")))
+                         graph=sess.use_graph, ring=chunk, timed=bool(stats and stats.get("timed")), reward=reward)
     if prefill is None:
         sess.tok.copy_(torch.as_tensor(np.tile(INIT_CW[0], (N, 1)), dtype=torch.int64).view(N, 1, A).to(sess.dev))
     else:
@@ -1510,6 +1618,10 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
         if bool(loop.done.all().item()):
             break
     rows, lps = np.concatenate(rows), np.concatenate(lps)
+    W = None if reward is None else reward[1]
+    if W is not None and done % W:                                     # the open window: rows already done add nothing
+        with torch.no_grad():
+            loop.reward_event(filled=done % W)
     lens, lw, log_z = loop.len.cpu().numpy(), loop.lw.cpu().numpy(), loop.log_z.cpu().numpy()
     E = loop.n_events
     h_anc = loop.h_anc[:E].cpu().numpy()
@@ -1517,14 +1629,19 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
     h_lw = loop.h_lw[:E].cpu().numpy()
     line = particle_lineage(h_anc, N)
     seg = np.minimum(np.arange(len(rows)) // R, E)                     # the segment each drawn row belongs to
+    h_r = None if W is None else loop.h_r[:loop.n_rewards].cpu().numpy()
     out = []
     for g in range(N // K):
-        songs, logps = [], []
+        songs, logps, rewards = [], [], None if W is None else []
         for n in range(g * K, (g + 1) * K):
             t = np.arange(int(lens[n]))
             src = line[seg[t], n]
             songs.append(np.concatenate([heads[n], rows[t, src]]))
             logps.append(lps[t, src].astype(np.float32).reshape(-1, A, 2))
+            if W is not None:                                          # window j's event followed step (j + 1) W, or the
+                j = np.arange(-(-int(lens[n]) // W))                   # run's last: the row the lineage lived in then
+                at = np.minimum((j + 1) * W, len(rows)) - 1
+                rewards.append(h_r[j, line[seg[at], n]].astype(np.float32))
         w = lw[g * K:(g + 1) * K].astype(np.float32)
         # events after the song's last particle ended are not its own: they depend on the other songs of the pool.  The
         # song had a live particle up to its last resampling (which may have replaced the last live one by copies of
@@ -1534,7 +1651,10 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
                    int(hit.max()) + 1 if len(hit) else 0)
         out.append(ParticleSet(songs, logps, w, float(log_z[g]) + logmeanexp(w), h_ess[:live, g].copy(),
                                h_res[:live, g] != 0, h_anc[:live, g * K:(g + 1) * K] - g * K,
-                               h_lw[:live, g * K:(g + 1) * K].copy()))
+                               h_lw[:live, g * K:(g + 1) * K].copy(), rewards))
+        if W is not None:                                              # the reward events of the same span of steps
+            n_r = max(-(-int(lens[g * K:(g + 1) * K].max()) // W), (int(hit.max()) + 1) * R // W if len(hit) else 0)
+            out[-1].event_rewards = h_r[:n_r, g * K:(g + 1) * K].copy()
     if log is not None:
         log("%d songs x %d particles: %d tokens, %d steps, %d resampling events"
             % (N // K, K, sum(len(x) for s in out for x in s.songs), done, E))
@@ -1545,12 +1665,16 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
                      drawn=int(lens.sum()), row_bytes=loop.row_bytes, moved_rows=[int(m) for m in moved],
                      resampled_groups=[int(r.sum()) for r in h_res], groups=N // K,
                      event_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)] for m in loop.timed or []])
+        if W is not None:
+            stats.update(reward_events=loop.n_rewards, reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
+                                                                  for m in loop.reward_timed or []])
     return out
 
 
 def generate_particles(model, word2event, n_songs, particles, resample_every=16, ess=0.5, bar_cond=17, max_tokens=None,
                        prompts=None, sampler="dqn", chunk=128, log=None, prefill="blas", constraints=None,
-                       grammar=None, reference=None, alpha=None, preferences=None):
+                       grammar=None, reference=None, alpha=None, preferences=None, reward=None, reward_window=50,
+                       beta=1.0):
     """Generate `n_songs` songs with `particles` = K weighted particles each, by sequential Monte Carlo with the device
     sampler as the proposal.  -> list of n_songs ParticleSet.
 
@@ -1580,14 +1704,30 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     n_songs), alpha, grammar, reference, sampler, bar_cond, max_tokens, chunk, prefill: as in generate_batch.  Each
     prompt is prefilled K times: sharing one prefill among a song's particles is left out.  Draws are keyed by (torch
     seed, step, row) and the resampling draw by (seed, event, song), so song g's set is the same whatever the other
-    songs.  The continuous-batching stream (slots=) and reward terms in the weights are out of scope.
-    Refused, before anything runs: particles outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit),
-    resample_every < 1, ess outside [0, 1], then everything generate_batch refuses."""
+    songs.  The continuous-batching stream (slots=) is out of scope.
+
+    reward, reward_window = W, beta: reward terms in the weights.  Each particle's drawn rows (not its
+    prompt) are cut into consecutive windows of W rows, the last one possibly partial; after the last row of each
+    window the log-weight of every particle with a live row in it gains beta x r, r = reward(windows (N, W, 6) int64
+    cuda, mask (N, W) int64 cuda)[n] -- the window's tokens, zero-padded, and a 0/1 mask of its live rows (the row that
+    ends a song is live) -- and a resampling event of the same step sees it.  The target becomes the one above times
+    exp(beta x sum of the song's window rewards): the optimum of KL-regularised RL with KL coefficient 1 / beta, sampled
+    without a backward pass; log_evidence estimates the log of that expectation and ParticleSet.rewards records each
+    lineage's rewards.  reward is any callable whose entry n depends on row n's window alone (WindowReward wraps the
+    AIRL discriminator, whose window is the default 50); a row without a live row in the window is shown mask[n, 0] = 1
+    over zero tokens and its result is discarded.  The windows live per pool row on the device (cwlt_reward_push per
+    token, cwlt_reward_window and cwlt_reward_apply per event) and are gathered with every other per-row state.
+    beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  Rewards on the stream, per-song
+    beta and the PPO reward model's per-attribute heads are left out.
+    Refused, before anything runs: a reward that is not callable, reward_window < 1, a beta that is not finite, particles
+    outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit), resample_every < 1, ess outside [0, 1], then
+    everything generate_batch refuses."""
+    spec = _reward_spec(reward, reward_window, beta)
     heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                         ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                         grammar, reference, alpha, preferences)
     return _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, int(chunk),
-                          log, None if prompts is None else prefill)
+                          log, None if prompts is None else prefill, reward=spec)
 
 
 SCORE_BLOCK_SONGS = 1024    # most songs in one score_songs block: bounds its scratch decode state (1.6 MB a song at repo dims)
@@ -1797,7 +1937,8 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
 def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis", write_midi=None,
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
              batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None,
-             reference=None, alpha=None, preferences=None, particles=None, resample_every=16, ess=0.5):
+             reference=None, alpha=None, preferences=None, particles=None, resample_every=16, ess=0.5, reward=None,
+             reward_window=50, beta=1.0):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -1813,9 +1954,15 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     batch_size only, the one-song path samples on the host.  Per-song entries are cut per batch_size group like prompts (DrawPlan.songs).
     particles=K (with batch_size; resample_every, ess: generate_particles'): each group is made by
     generate_particles with K particles a song, and each song kept is ParticleSet.draw -- one particle by final weight --
-    with a numpy generator seeded from the torch seed.  None (the default): nothing changes."""
+    with a numpy generator seeded from the torch seed.  None (the default): nothing changes.
+    reward, reward_window, beta (with particles; generate_particles', DESIGN §4.6n): window rewards in the particles'
+    weights.  reward=None (the default): nothing changes."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
+    if reward is not None and particles is None:
+        raise ValueError("reward terms act on the weights of generate_particles' particles: pass particles= (and "
+                         "batch_size); the one-song path, plain batches and the stream take no reward")
+    spec = _reward_spec(reward, reward_window, beta)
     if particles is not None and batch_size is None:
         raise ValueError("particles run in generate_particles' lock-step pool: pass batch_size (the songs of one pool; "
                          "the stream, slots=, takes no particles)")
@@ -1897,7 +2044,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                                    None, None if given is None else "blas")
             else:
                 sets = _run_particles(model, word2event, heads[rows], caps[rows], plan.songs(first * K, count * K), K,
-                                      resample_every, ess, bar_cond, 128, None, None if given is None else "blas")
+                                      resample_every, ess, bar_cond, 128, None, None if given is None else "blas",
+                                      reward=spec)
                 if rng is None:                                        # after the first pool's seed: that pool is
                     rng = np.random.default_rng(ops.next_seed())      # generate_particles' with the same torch seed
                 picks = [s.draw(rng, return_index=True) for s in sets]

@@ -269,8 +269,20 @@ def capture_hip_graph(body, mode=torch.no_grad, name="step"):
                           "hipGraph capture is off, steps run eagerly")
         return None, None, {}, 0
     graph = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(graph), mode():
-        out = body()
+    # No cyclic garbage collection while the stream captures.  A collection that starts inside the capture (in this
+    # thread or in autograd's) may reach a dead cycle that still holds an earlier hipGraph -- a GraphedCall and the
+    # object whose bound method it wraps, say; torch.cuda.graph no longer collects before it begins -- and a CUDAGraph's
+    # destructor synchronises the device on ROCm, which a capture in the global error mode turns into an error thrown
+    # from a destructor: the process aborts.  Such garbage waits for the first collection after the capture.
+    import gc
+    collecting = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph), mode():
+            out = body()
+    finally:
+        if collecting:
+            gc.enable()
     raw = graph.raw_cuda_graph()
     census = _lib.graph_node_census(raw)
     replaced = 0
@@ -2080,6 +2092,60 @@ def particle_gather(dst, src, anc, row_bytes, n_blocks=1, block_stride=0, copy_b
     _call("cwlt_particle_gather", _lib.dev(dst, "dst"), _lib.dev(src, "src"), _lib.dev(anc, "anc"), rows,
           int(row_bytes), int(n_blocks), int(block_stride), int(bool(copy_back)), _lib.stream_ptr())
     return dst
+
+
+def _reward_ring(where, recent, live):
+    """(rows, W, A) of a reward ring: recent (rows, W, A) and live (rows, W), contiguous int64."""
+    if recent.dtype != torch.int64 or live.dtype != torch.int64 or not recent.is_contiguous() or not live.is_contiguous():
+        raise TypeError("%s takes contiguous int64 recent and live" % where)
+    if recent.dim() != 3 or tuple(live.shape) != tuple(recent.shape[:2]):
+        raise ValueError("%s: recent must be (rows, W, A) and live (rows, W), got %s and %s"
+                         % (where, tuple(recent.shape), tuple(live.shape)))
+    return tuple(recent.shape)
+
+
+def reward_push(tok, done, counter, recent, live):
+    """One token into the particles' reward windows (cwlt_reward_push): with s = *counter % W,
+    recent[n, s] = tok[n] and live[n, s] = (done[n] == 0).  tok (rows, A) int64, the token just drawn; done (rows,)
+    int64 as it was BEFORE this token (call ahead of particle_weigh); counter the loop's device int64 row counter;
+    recent (rows, W, A), live (rows, W) int64."""
+    rows, W, A = _reward_ring("reward_push", recent, live)
+    for t, n in ((tok, rows * A), (done, rows)):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("reward_push takes contiguous int64 tok (%d, %d) and done (%d,)" % (rows, A, rows))
+    if counter.dtype != torch.int64 or counter.numel() != 1:
+        raise TypeError("reward_push: counter must be one device int64")
+    _call("cwlt_reward_push", _lib.dev(tok, "tok"), _lib.dev(done, "done"), _lib.dev(counter, "counter"), rows, A, W,
+          _lib.dev(recent, "recent"), _lib.dev(live, "live"), _lib.stream_ptr())
+
+
+def reward_window(recent, live, filled, win, mask, any_live):
+    """The particles' windows as a reward callable sees them (cwlt_reward_window): slots 0 .. filled - 1
+    of the rings hold the window's rows in time order.  win[n, j] = recent[n, j] and mask[n, j] = 1 where j < filled and
+    live[n, j], else token 0 and mask 0; any_live[n] = whether row n has such a slot; a row with none gets
+    mask[n, 0] = 1.  win (rows, W, A), mask (rows, W), any_live (rows,) int64."""
+    rows, W, A = _reward_ring("reward_window", recent, live)
+    for t, shape in ((win, (rows, W, A)), (mask, (rows, W)), (any_live, (rows,))):
+        if t.dtype != torch.int64 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise TypeError("reward_window takes contiguous int64 win (rows, W, A), mask (rows, W) and any (rows,)")
+    _call("cwlt_reward_window", _lib.dev(recent, "recent"), _lib.dev(live, "live"), rows, A, W, int(filled),
+          _lib.dev(win, "win"), _lib.dev(mask, "mask"), _lib.dev(any_live, "any"), _lib.stream_ptr())
+    return win, mask, any_live
+
+
+def reward_apply(r, any_live, beta, lw, h_r):
+    """The window rewards into the log-weights (cwlt_reward_apply): rows with any_live[n] != 0 get
+    lw[n] = lw[n] + (beta * r[n]) (two f32 roundings, bitwise sampling.reward_apply_f32) and h_r[n] = r[n]; the others
+    keep lw and get h_r[n] = 0, whatever r[n] holds.  r, lw, h_r (rows,) f32, any_live (rows,) int64."""
+    rows = lw.numel()
+    for t in (r, lw, h_r):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
+            raise TypeError("reward_apply takes contiguous f32 r, lw and h_r of %d rows" % rows)
+    if any_live.dtype != torch.int64 or not any_live.is_contiguous() or any_live.numel() != rows:
+        raise TypeError("reward_apply takes a contiguous int64 any of %d rows" % rows)
+    _call("cwlt_reward_apply", _lib.dev(r, "r"), _lib.dev(any_live, "any"), float(beta), rows, _lib.dev(lw, "lw"),
+          _lib.dev(h_r, "h_r"), _lib.stream_ptr())
+    return lw
 
 
 def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):

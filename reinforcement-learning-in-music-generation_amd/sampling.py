@@ -252,6 +252,19 @@ def particle_weigh_f32(lw, pairs, done=None):
     return out if done is None else np.where(np.asarray(done) != 0, lw, out)
 
 
+def reward_apply_f32(lw, r, any_live, beta):
+    """Numpy float32 restatement of cwlt_reward_apply: lw, r (rows,), any_live (rows,) 0 / 1 -> (the new
+    (rows,) float32 weights, the (rows,) float32 rewards recorded), both bitwise the kernel's.  A row with any_live != 0
+    gets lw + (beta * r), the product rounded to float32 and then the sum, and records r; every other row keeps its
+    weight and records 0 -- selected, not multiplied: r may be NaN or infinite there."""
+    lw = np.asarray(lw, dtype=np.float32)
+    r = np.asarray(r, dtype=np.float32)
+    on = np.asarray(any_live) != 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = (lw + (np.float32(beta) * r).astype(np.float32)).astype(np.float32)
+    return np.where(on, out, lw), np.where(on, r, np.float32(0))
+
+
 def logmeanexp(x):
     """log(mean(exp(x))) of a vector in float64, by the max subtraction; -inf for all -inf."""
     x = np.asarray(x, dtype=np.float64)
