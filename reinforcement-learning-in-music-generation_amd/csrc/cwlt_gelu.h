@@ -10,6 +10,17 @@
 // bf16 result carries 2^-9 relative (2e-3 at |y| = 1), and where the output is small the error is too (it scales
 // with x e(x)).  Round 2's Abramowitz-Stegun 7.1.26 form (1.5e-7) needed v_rcp_f32 besides the v_exp_f32 and 23
 // instruction slots per element where this needs 17.
+//
+// Domain.  Q(|x|) is evaluated for every |x|; its degree-5 Horner chain overflows f32 to -inf once |x|^5 |Q5| passes
+// FLT_MAX, i.e. for |x| above about 1.75e8 (the f32 emulation in oracle/elementwise_f64.py first returns NaN at 1.7496e8),
+// while e = exp2(-x^2 c) is long 0 there: fma(-0, -inf, c0) is NaN, so value AND derivative are NaN where exact-erf GELU is
+// x or 0 and 1 or 0 (the f32 path, libm erff, stays finite).  Through |x| = 2^26 = 6.7e7 (oracle GELU_BF16_MAX_ABS, pinned
+// on the GPU by tests/test_elementwise_f64_gpu.py over a magnitude ladder in both signs) the results are finite and right:
+// x, 0 / 1, 0 within rounding.  Deliberately NOT clamped: an activation of 1e8 means the model is already lost, and a
+// v_min_f32 per element is an instruction in the very epilogue whose count gemm_nt.hip was tuned on.
+// "Within rounding" for large negative x: y = fma(|x|, us, c0 x) with us = c0 cancels two terms of magnitude s |x| / 2, and
+// c0 x is rounded when s (the keep scale) is no power of two, so y is that rounding, up to 2^-25 s |x| (0.025 at x = -1e6, s = 1.1111), not -0:
+// above |x| = 4.5e3 the absolute 1.5e-4 holds relative to the uncancelled magnitude only.
 #pragma once
 #include "cwlt_common.h"
 
