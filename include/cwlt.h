@@ -727,6 +727,46 @@ int cwlt_particle_resample(float* lw, const int64_t* done, int64_t groups, int p
 int cwlt_particle_gather(void* dst, const void* src, const int64_t* anc, int64_t rows, int64_t row_bytes, int n_blocks,
                          int64_t block_stride, int copy_back, void* stream);
 
+/* ---- particle generation on the stream (csrc/particles.hip, csrc/particles_stream.hip) -------------------
+ * A pool of `groups` groups of `particles` = K consecutive rows; group g holds song song[g] (< 0: none), row g K + k its
+ * particle k with id[row] = song K + k (-1: none).  pos[row] is the row's clock: tokens since its song started, ticked
+ * for every row with a song, done or not.  One launch each, no host synchronisation, no allocation, no atomics.  Every
+ * pointer is DEVICE memory; a null pointer or a size out of range is refused with CWLT_ERR_ARG before any launch.
+ *
+ * cwlt_particle_resample_keyed: cwlt_particle_resample with u drawn for (seed, event, song[g]) where event =
+ * pos[g * pos_stride] / every - 1, the song's own event index, instead of (seed, event, g).  A group with song[g] < 0 or
+ * event < 0 gets anc[i] = i, u = ess = 0, resampled = 0 and its lw and log_z are neither read nor written; a group whose
+ * rows are all done is kept as in cwlt_particle_resample.  With song[g] = g and pos = (e + 1) * every every output is
+ * bitwise cwlt_particle_resample's at event e.  song int64 x groups, pos int64, 1 <= pos_stride <= 2^20, every >= 1.
+ *
+ * cwlt_particle_advance (per token, after cwlt_particle_weigh; one workgroup): row ctl[0] % ring_rows of ring
+ * (ring_rows, rows, n_attr + 2) int64 gets, per row, {id (-1 without a song), the n_attr tokens, done != 0 (0 without a
+ * song)}; pos += 1 for rows with a song; every fresh flag becomes 0; ctl[0] += 1.  rows <= 2^20, n_attr 1 .. 8.
+ *
+ * cwlt_particle_release (per event, after the gather; one workgroup, groups <= 4096): a group is a candidate when
+ * song[g] < 0 or all its K rows have done != 0.  A candidate with song[g] >= 0 is finished: out_logz[song] = log_z[g],
+ * and out_lw[id] = lw, out_len[id] = len for its K rows; ctl[2] += the finished groups.  Candidate number r in group
+ * order takes song ctl[1] + r while that is < n_songs: its rows get id = song K + k, pos 0, bar bar0, cap cap0, len 0,
+ * done 0, lw 0, fresh 1 and log_z[g] = 0; the others get song -1, id -1, done 1.  ctl[1] = min(ctl[1] + candidates,
+ * n_songs).  Nothing of a group that is no candidate is written.  out_lw f32 / out_len int64 x n_songs K, out_logz f32 x
+ * n_songs; n_songs K <= 2^20, cap0 >= 1.
+ *
+ * cwlt_particle_fill: for rows with fresh != 0 and 0 <= id < n_src, row_bytes bytes of dst row n (rows ld_dst bytes
+ * apart) = those of src row id (ld_src apart).  row_bytes, ld_dst, ld_src multiples of 4, bases 4-byte aligned, dst !=
+ * src. */
+int cwlt_particle_resample_keyed(float* lw, const int64_t* done, int64_t groups, int particles, float ess_frac,
+                                 uint64_t seed, const int64_t* song, const int64_t* pos, int64_t pos_stride,
+                                 int64_t every, int64_t* anc, float* u, float* ess, int* resampled, float* log_z,
+                                 void* stream);
+int cwlt_particle_advance(const int64_t* tokens, int n_attr, int64_t rows, const int64_t* id, const int64_t* done,
+                          int64_t* pos, int64_t* fresh, int64_t* ctl, int64_t* ring, int64_t ring_rows, void* stream);
+int cwlt_particle_release(int64_t groups, int particles, int64_t n_songs, int64_t bar0, int64_t cap0, int64_t* song,
+                          int64_t* id, int64_t* pos, int64_t* bar, int64_t* cap, int64_t* len, int64_t* done,
+                          int64_t* fresh, float* lw, float* log_z, int64_t* ctl, float* out_lw, int64_t* out_len,
+                          float* out_logz, void* stream);
+int cwlt_particle_fill(void* dst, const void* src, const int64_t* fresh, const int64_t* id, int64_t rows, int64_t n_src,
+                       int64_t row_bytes, int64_t ld_dst, int64_t ld_src, void* stream);
+
 /* ---- reward terms in the particles' weights (csrc/reward.hip) ----------------------------------------------
  * Each pool row keeps a ring of its particle's last `window` = W drawn rows, recent (rows, W, n_attr) int64, and of
  * whether the particle was alive when each was drawn, live (rows, W) int64.  Both are per-row state: a caller hands them

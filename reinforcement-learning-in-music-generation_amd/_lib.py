@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 33
+ABI_VERSION = 34
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -153,6 +153,10 @@ _SIGNATURES = {
     "cwlt_particle_weigh": [_ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr],
     "cwlt_particle_resample": [_ptr, _ptr, _c_i64, _c_int, _c_f32, _c_u64, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
     "cwlt_particle_gather": [_ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _c_i64, _c_int, _ptr],
+    "cwlt_particle_resample_keyed": [_ptr, _ptr, _c_i64, _c_int, _c_f32, _c_u64, _ptr, _ptr, _c_i64, _c_i64] + [_ptr] * 6,
+    "cwlt_particle_advance": [_ptr, _c_int, _c_i64] + [_ptr] * 6 + [_c_i64, _ptr],
+    "cwlt_particle_release": [_c_i64, _c_int, _c_i64, _c_i64, _c_i64] + [_ptr] * 15,
+    "cwlt_particle_fill": [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _ptr],
     "cwlt_reward_push": [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_i64, _ptr, _ptr, _ptr],
     "cwlt_reward_window": [_ptr, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr],
     "cwlt_reward_apply": [_ptr, _ptr, _c_f32, _c_i64, _ptr, _ptr, _ptr],

@@ -39,10 +39,18 @@ constexpr uint64_t RESAMPLE_STREAM = 0x7061727469636c65ull;     // keeps u off t
 // One workgroup per group of K consecutive rows, one thread per row (blockDim = K rounded up to whole waves).
 // The prefix sums are sequential per wave and over the wave totals, so the prefix array never decreases and the binary
 // search below is the "first row whose prefix exceeds the threshold" of the restatement.
+// KEYED (cwlt_particle_resample_keyed, the particle stream of DESIGN §4.6o): u is keyed by the group's song and the
+// song's own event index, pos[g * pos_stride] / every - 1, not by the group's place and the run's event; a group
+// without a song (or before its first event) is left alone, workgroup-uniformly and ahead of every barrier.  song, pos,
+// pos_stride and every are KEYED's alone; everything after the key is the one body of both entries.
+template <bool KEYED>
 __global__ __launch_bounds__(1024) void particle_resample_kernel(float* __restrict__ lw,
                                                                  const int64_t* __restrict__ done, int K,
                                                                  float ess_frac, uint64_t seed, long event,
-                                                                 int64_t* __restrict__ anc, float* __restrict__ u_out,
+                                                                 const int64_t* __restrict__ song,
+                                                                 const int64_t* __restrict__ pos, long pos_stride,
+                                                                 long every, int64_t* __restrict__ anc,
+                                                                 float* __restrict__ u_out,
                                                                  float* __restrict__ ess_out,
                                                                  int* __restrict__ resampled,
                                                                  float* __restrict__ log_z) {
@@ -51,6 +59,20 @@ __global__ __launch_bounds__(1024) void particle_resample_kernel(float* __restri
     __shared__ int live_s[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n_wave = blockDim.x >> 6;
     const long g = blockIdx.x, row0 = g * K;
+    long key = g;
+    if (KEYED) {
+        key = song[g];
+        event = pos[g * pos_stride] / every - 1;
+        if (key < 0 || event < 0) {                  // the same for the whole workgroup
+            if (tid < K) anc[row0 + tid] = row0 + tid;
+            if (tid == 0) {
+                u_out[g] = 0.f;
+                ess_out[g] = 0.f;
+                resampled[g] = 0;
+            }
+            return;
+        }
+    }
     const bool own = tid < K;
     const float x = own ? lw[row0 + tid] : -INFINITY;
     const bool live = own && done[row0 + tid] == 0;
@@ -92,7 +114,7 @@ __global__ __launch_bounds__(1024) void particle_resample_kernel(float* __restri
     __syncthreads();
     const float s = c_s[K - 1];
     const float ess = s * s / s2;
-    const uint32_t r = rng_pair(seed ^ RESAMPLE_STREAM, ((uint64_t)event << 32) + (uint64_t)g);
+    const uint32_t r = rng_pair(seed ^ RESAMPLE_STREAM, ((uint64_t)event << 32) + (uint64_t)key);
     const float u = (float)(r >> 8) * (1.0f / 16777216.0f);      // [0, 1)
     const bool keep = !any_live || !(s > 0.f) || ess >= ess_frac * (float)K;      // workgroup-uniform
     if (tid == 0) {
@@ -178,8 +200,25 @@ extern "C" int cwlt_particle_resample(float* lw, const int64_t* done, int64_t gr
         event > 0xffffffffL || !(ess_frac >= 0.f && ess_frac <= 1.f))
         return CWLT_ERR_ARG;
     const int threads = (particles + 63) / 64 * 64;
-    hipLaunchKernelGGL(particle_resample_kernel, dim3((unsigned)groups), dim3(threads), 0, (hipStream_t)stream, lw,
-                       done, particles, ess_frac, seed, (long)event, anc, u, ess, resampled, log_z);
+    hipLaunchKernelGGL(particle_resample_kernel<false>, dim3((unsigned)groups), dim3(threads), 0, (hipStream_t)stream,
+                       lw, done, particles, ess_frac, seed, (long)event, nullptr, nullptr, 0L, 1L, anc, u, ess,
+                       resampled, log_z);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cwlt_particle_resample_keyed(float* lw, const int64_t* done, int64_t groups, int particles,
+                                            float ess_frac, uint64_t seed, const int64_t* song, const int64_t* pos,
+                                            int64_t pos_stride, int64_t every, int64_t* anc, float* u, float* ess,
+                                            int* resampled, float* log_z, void* stream) {
+    using namespace cwlt;
+    if (!lw || !done || !song || !pos || !anc || !u || !ess || !resampled || !log_z) return CWLT_ERR_ARG;
+    if (particles < 2 || particles > 1024 || groups < 1 || groups * particles > (1L << 20) || pos_stride < 1 ||
+        pos_stride > (1L << 20) || every < 1 || !(ess_frac >= 0.f && ess_frac <= 1.f))
+        return CWLT_ERR_ARG;
+    const int threads = (particles + 63) / 64 * 64;
+    hipLaunchKernelGGL(particle_resample_kernel<true>, dim3((unsigned)groups), dim3(threads), 0, (hipStream_t)stream,
+                       lw, done, particles, ess_frac, seed, 0L, song, pos, (long)pos_stride, (long)every, anc, u, ess,
+                       resampled, log_z);
     return (int)hipGetLastError();
 }
 

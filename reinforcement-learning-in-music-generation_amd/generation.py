@@ -846,6 +846,10 @@ class _StreamLoop:
         self._events[h].synchronize()
         self.wait_s += time.perf_counter() - t
 
+    def _step_limit(self):
+        """The most steps run() enqueues before it gives up: every slot's songs, one by one."""
+        return -(-self.n_songs // self.S) * (self.song_cap + 1) + 2 * self.chunk
+
     def _between_chunks(self, ctl, limit):
         """Between two chunks of run(), with the counters of the chunk just read: the step limit."""
         if self.enqueued > limit:
@@ -854,7 +858,7 @@ class _StreamLoop:
     def run(self):
         """Run until the device's finished counter reaches n_songs -> (rows (n, A + 2) of every song, time-ordered)."""
         parts = []
-        limit = -(-self.n_songs // self.S) * (self.song_cap + 1) + 2 * self.chunk     # every slot's songs, one by one
+        limit = self._step_limit()
         self.start()
         h = self._enqueue_chunk()
         while True:
@@ -912,6 +916,139 @@ class _SnapshotStreamLoop(_StreamLoop):
     def _advance(self, tok):
         ops.stream_advance(tok, 2, self.bar_mask, self.bar_cond, self.bar0, self.cap, self.n_songs, self.song,
                            self.pos, self.bar, self.fresh, self.ctl, self.ring)
+
+
+class _ParticleStreamLoop(_StreamLoop):
+    """The stream whose unit of refill is a group of K rows: `sess` (DecodeSession(S K, kernel="gemm"))
+    runs S songs with K particles each, row g K + k particle k of group g's song, and a group takes the next song once
+    all its K particles have ended -- at the next resampling boundary, so that every song sees its own events after its
+    own rows R, 2 R, ...  `song` (rows,) holds the rows' particle ids (song K + k, the plan's rows; -1: none), `gsong`
+    (S,) the groups' songs.  Per token, one captured sequence: the decode step (and the reference's), cwlt_stream_refill
+    of the fresh rows from the snapshot(s), the blend, the preferences, the draw keyed by (particle id, position in
+    song) with its log-probs, cwlt_count_bars, the tracks (which never see a fresh flag), cwlt_particle_weigh and
+    cwlt_particle_advance.  After every R-th token, eagerly on the same stream (_event): lw into its history, the keyed
+    resampling, the two-phase gather of every family (_ParticleLoop's, through scratch), cwlt_particle_release and the
+    fill of the new particles' beat / seen rows.  The event histories are rings of two chunks' events, copied out with
+    the token rows behind the chunk's event; rows are kept per (step, row): the lineage needs the row index."""
+
+    def __init__(self, sess, snap, ref_snap, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0, cap, chunk,
+                 **kw):
+        super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
+        dev, N = sess.dev, self.S
+        self.K, self.every, self.ess_frac = int(particles), int(every), float(ess)
+        self.G = N // self.K
+        self.snap, self.ref_snap, self.bar0, self.cap0 = snap, ref_snap, int(bar0), int(cap)
+        self.song_cap = self.cap0
+        i64 = lambda n, v=0: torch.full((n,), v, dtype=torch.int64, device=dev)
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        self.gsong, self.len, self.done, self.cap, self.no_fresh = i64(self.G, -1), i64(N), i64(N, 1), i64(N, 1), i64(N)
+        self.song.fill_(-1)
+        self.lw, self.log_z = f32(N), f32(self.G)
+        P = self.n_songs * self.K
+        self.out_lw, self.out_len, self.out_logz = f32(P), i64(P), f32(self.n_songs)
+        self.EC = self.chunk // self.every                       # events per chunk; the history rings hold two chunks'
+        E2 = 2 * self.EC
+        self.h_anc = torch.zeros((E2, N), dtype=torch.int64, device=dev)
+        self.h_lw, self.h_u, self.h_ess = f32(E2, N), f32(E2, self.G), f32(E2, self.G)
+        self.h_res = torch.zeros((E2, self.G), dtype=torch.int32, device=dev)
+        self._hist = (self.h_anc, self.h_lw, self.h_ess, self.h_res)
+        self._host_hist = [[torch.zeros((self.EC,) + tuple(t.shape[1:]), dtype=t.dtype).pin_memory()
+                            for t in self._hist] for _ in range(2)]
+        self.hist_parts = [[] for _ in self._hist]
+        self.n_events = 0
+        self.families = []                                       # _ParticleLoop's: (state, scratch, row bytes, blocks, stride)
+        for s in (sess, self.plan.ref):
+            if s is None:
+                continue
+            scratch = torch.empty_like(s._state)
+            sf, zf = s.memory[0][0][0].numel(), s.memory[0][1][0].numel()
+            stride = 4 * N * (sf + zf)
+            self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
+            self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
+        for t in (sess.tok, self.bar, self.beat, self.seen, self.len, self.done, self.cap):
+            if t is not None:
+                self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
+        self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)
+
+    def _step_limit(self):
+        """List scheduling: the songs' total over the groups plus one longest song, each rounded up to a boundary."""
+        per = -(-self.cap0 // self.every) * self.every + self.every
+        return (-(-self.n_songs // self.G) + 1) * per + 2 * self.chunk
+
+    def _release(self):
+        ops.particle_release(self.K, self.n_songs, self.bar0, self.cap0, self.gsong, self.song, self.pos, self.bar,
+                             self.cap, self.len, self.done, self.fresh, self.lw, self.log_z, self.ctl, self.out_lw,
+                             self.out_len, self.out_logz)
+        if self.beat is not None:
+            ops.particle_fill(self.beat, self.plan.beat0, self.fresh, self.song)
+        if self.seen is not None:
+            ops.particle_fill(self.seen, self.plan.seen0, self.fresh, self.song)
+
+    def start(self):
+        """Every group is without a song; the first release hands out songs 0, 1, ... in group order."""
+        self.ctl.zero_()
+        self._release()
+
+    def _one(self):
+        s, plan = self.sess, self.plan
+        tok = s.tok.view(self.S, self.A)
+        logits = s._device_step()
+        ops.stream_refill(s._state, self.snap[0], self.n_layer, self.s_floats, self.z_floats, logits, self.snap[1],
+                          self.fresh)
+        ref = plan.ref
+        if ref is not None:
+            ref_logits = ref._device_step()
+            ops.stream_refill(ref._state, self.ref_snap[0], len(ref.memory), ref.memory[0][0][0].numel(),
+                              ref.memory[0][1][0].numel(), ref_logits, self.ref_snap[1], self.fresh)
+            ops.blend_logits(logits, ref_logits, s.n_token, plan.alpha, key=self.song, out=logits)
+        _prefer_token(plan, logits, s.n_token, seen=self.seen, key=self.song, bar=self.bar)
+        _draw_token(plan, logits, s.n_token, tok, self.seed, key=self.song, step=self.pos, bar=self.bar, beat=self.beat,
+                    logp=self.lp_ring, out_counter=self.ctl)
+        ops.count_bars(tok, 2, self.bar_mask, self.bar)
+        if self.beat is not None:
+            ops.grammar_track(tok, plan.bar_attr, plan.order, self.beat)
+        if self.seen is not None:                             # keyed by the particle id; the release filled the fresh rows
+            ops.prefer_track(tok, s.n_token, plan.pen, self.seen, fresh=self.no_fresh, song=self.song,
+                             seen0=plan.seen0)
+        # weigh reads the log-prob row ctl[0] selects: ahead of the advance, which moves it
+        ops.particle_weigh(self.lp_ring, self.ctl, self.bar, self.bar_cond, self.cap, self.lw, self.len, self.done)
+        ops.particle_advance(tok, self.song, self.done, self.pos, self.fresh, self.ctl, self.ring)
+
+    def _event(self):
+        """One boundary, enqueued: the resampling of every group with a live song, the gather, then the release."""
+        r = self.n_events % (2 * self.EC)
+        anc = self.h_anc[r]
+        self.h_lw[r].copy_(self.lw)
+        ops.particle_resample_keyed(self.lw, self.done, self.K, self.ess_frac, self.seed, self.gsong, self.pos,
+                                    self.every, anc, self.h_u[r], self.h_ess[r], self.h_res[r], self.log_z)
+        for state, scratch, rb, nb, stride in self.families:
+            ops.particle_gather(scratch, state, anc, rb, nb, stride)
+        for state, scratch, rb, nb, stride in self.families:
+            ops.particle_gather(state, scratch, anc, rb, nb, stride, copy_back=True)
+        self._release()
+        self.n_events += 1
+
+    def _enqueue_chunk(self):
+        with torch.no_grad():
+            for _ in range(self.chunk):
+                _enqueue_token(self, "particle stream step")
+                if self.enqueued % self.every == 0:
+                    self._event()
+        h = (self.enqueued // self.chunk - 1) % 2
+        self._host[h].copy_(self.ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
+        self._host_lp[h].copy_(self.lp_ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
+        for host, t in zip(self._host_hist[h], self._hist):
+            host.copy_(t[h * self.EC:(h + 1) * self.EC], non_blocking=True)
+        self._host_ctl[h].copy_(self.ctl, non_blocking=True)
+        self._events[h].record()
+        return h
+
+    def _read(self, h):
+        """Ring half h whole, (chunk, rows, A + 2), and its log-probs and event histories into their lists."""
+        self.lp_parts.append(self._host_lp[h].numpy().copy())
+        for parts, host in zip(self.hist_parts, self._host_hist[h]):
+            parts.append(host.numpy().copy())
+        return self._host[h].numpy().copy()
 
 
 class _BankStreamLoop(_StreamLoop):
@@ -1019,9 +1156,10 @@ class _BankStreamLoop(_StreamLoop):
                 "prefill_blocks": self.next_block, "gated_chunks": self.gated_chunks}
 
 
-def _stream_snapshot(model, prompt, A):
+def _stream_snapshot(model, prompt, A, kernel="blas"):
     """The state and logits every song of a stream starts from, on a one-slot GEMM session: one step of INIT_CW from
-    zero state (bitwise any row of the many-slot step, by batch invariance), or a one-row prefill of the prompt."""
+    zero state (bitwise any row of the many-slot step, by batch invariance), or a one-row prefill of the prompt with
+    prefill kernel `kernel` ("gemm": batch invariant, bitwise any row of a many-song gemm prefill of the same prompt)."""
     snap = DecodeSession(model, n_songs=1, kernel="gemm", graph=False)
     snap.reset()
     with torch.no_grad():
@@ -1029,7 +1167,7 @@ def _stream_snapshot(model, prompt, A):
             snap.tok.copy_(torch.as_tensor(INIT_CW[0], dtype=torch.int64).view(1, 1, A).to(snap.dev))
             logits = snap._device_step()
         else:
-            logits = snap._prefill(prompt)
+            logits = snap._prefill(prompt, kernel=kernel)
     return snap._state.clone(), logits.reshape(-1).clone()
 
 
@@ -1671,10 +1809,136 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
     return out
 
 
+def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len, out_logz, particles, every, n_songs,
+                         head, stats=None):
+    """The ParticleSets of a particle stream from what the device wrote; numpy only.
+    rows (T, N, A + 2) int64, the ring rows of T steps: per pool row {particle id or -1, the A tokens, done}; logps
+    (T, N, A, 2) f32 beside them; the run's events e = 0, 1, ..., event e after step (e + 1) R: h_anc (E, N) int64 pool-row
+    ancestors, h_lw (E, N) f32, h_ess (E, G) f32, h_res (E, G) int32; what the release wrote: out_lw, out_len (n_songs K,)
+    by particle id and out_logz (n_songs,).  K = particles, R = every, head: the (P, A) rows every song starts with.
+    The song of group g at step t is rows[t, g K, 0] // K; it held the group over the steps [t0, t1) that show it, t0 a
+    multiple of R, and its own events j = 0, 1, ... are the run's events t0 / R + j, (t1 - t0) // R of them.  Lineage:
+    particle_lineage on the in-group ancestors of those events; row tau of final particle k was drawn by pool row
+    g K + lineage[min(tau // R, events), k] at step t0 + tau.  The event fields are cut as in the lock-step pool: while the
+    song had a live particle (up to its last resampling, or the end of its longest final particle).
+    stats (a dict, optional) gains wait_group_steps -- steps groups spent with every particle done, waiting for the
+    boundary --, idle_group_steps, steps of groups without a song, and start_steps, the step each song's first row was
+    drawn at."""
+    rows = np.asarray(rows)
+    T, N = rows.shape[:2]
+    K, R, A = int(particles), int(every), rows.shape[2] - 2
+    G = N // K
+    ids = rows[:, ::K, 0]
+    gsong = np.where(ids >= 0, ids // K, -1)
+    out, starts = [None] * int(n_songs), [None] * int(n_songs)
+    wait = idle = 0
+    for g in range(G):
+        col = gsong[:, g]
+        cuts = np.nonzero(np.diff(col, prepend=np.int64(-2)))[0]
+        for t0, t1 in zip(cuts, list(cuts[1:]) + [T]):
+            s = int(col[t0])
+            if s < 0:
+                idle += int(t1 - t0)
+                continue
+            if t0 % R or out[s] is not None:
+                raise RuntimeError("particle stream output is inconsistent: song %d starts at step %d (every %d)%s"
+                                   % (s, t0, R, "" if out[s] is None else ", a second time"))
+            e0 = int(t0) // R
+            E = min(int(t1 - t0) // R, len(h_anc) - e0)
+            span, own = slice(e0, e0 + E), slice(g * K, (g + 1) * K)
+            anc = np.asarray(h_anc[span, own], dtype=np.int64) - g * K
+            line = particle_lineage(anc, K)
+            lens = np.asarray(out_len[s * K:(s + 1) * K], dtype=np.int64)
+            longest = int(lens.max())
+            if longest < 1 or longest > t1 - t0:
+                raise RuntimeError("particle stream output is inconsistent: song %d has lengths %s in %d steps"
+                                   % (s, list(lens), t1 - t0))
+            songs, lps = [], []
+            for k in range(K):
+                tau = np.arange(int(lens[k]))
+                src = g * K + line[np.minimum(tau // R, E), k]
+                songs.append(np.concatenate([head, rows[t0 + tau, src, 1:1 + A]]))
+                lps.append(np.asarray(logps[t0 + tau, src], dtype=np.float32).reshape(-1, A, 2))
+            w = np.asarray(out_lw[s * K:(s + 1) * K], dtype=np.float32).copy()
+            hit = np.nonzero(h_res[span, g])[0]
+            live = max(int(np.count_nonzero((np.arange(E) + 1) * R < longest)), int(hit.max()) + 1 if len(hit) else 0)
+            cut = slice(e0, e0 + live)
+            out[s] = ParticleSet(songs, lps, w, float(out_logz[s]) + logmeanexp(w), np.array(h_ess[cut, g]),
+                                 np.asarray(h_res[cut, g]) != 0, anc[:live], np.array(h_lw[cut, own]))
+            wait += int(t1 - t0) - longest
+            starts[s] = int(t0)
+    missing = [s for s, ps in enumerate(out) if ps is None]
+    if missing:
+        raise RuntimeError("particle stream output is inconsistent: no rows of songs %s" % missing[:8])
+    if stats is not None:
+        stats.update(wait_group_steps=wait, idle_group_steps=idle, start_steps=starts)
+    return out
+
+
+def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward):
+    """What generate_particles(slots=) refuses ahead of the lock-step path's own refusals."""
+    if reward is not None:
+        raise ValueError("reward= with slots=: windows of reward_window rows and resampling events of resample_every "
+                         "rows do not share boundaries, and a group takes a song only at an event's; rewards run in "
+                         "the lock-step pool (slots=None)")
+    if isinstance(prompts, (list, tuple)):
+        raise ValueError("slots= takes one shared (P, 6) prompt, prefilled once for all songs: per-song prompt lists "
+                         "would need a prompt bank (generate_particles without slots takes them)")
+    if int(slots) < 1:
+        raise ValueError("slots must be >= 1, got %r" % (slots,))
+    K = int(particles)
+    if int(slots) * K > PARTICLE_ROWS:
+        raise ValueError("slots x particles = %d x %d rows, the step takes at most %d" % (int(slots), K, PARTICLE_ROWS))
+    if int(n_songs) * K > 1 << 20:
+        raise ValueError("n_songs x particles must be <= 2**20 (the sampler's key layout), got %d x %d"
+                         % (int(n_songs), K))
+    if int(resample_every) >= 1 and int(chunk) >= 1 and int(chunk) % int(resample_every):
+        raise ValueError("chunk (%d) must be a multiple of resample_every (%d): a chunk's ring half holds whole event "
+                         "segments" % (int(chunk), int(resample_every)))
+
+
+def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particles, slots, resample_every, ess, bar_cond,
+                         chunk, log, prompt, stats=None):
+    """generate_particles(slots=) after its refusals: the rows of `plan` (particles consecutive rows per song), S =
+    min(slots, n_songs) songs in flight -> n_songs ParticleSets.  stats (a dict, optional): steps, events, seconds (all
+    of it) and run_seconds (up to the last chunk read, before the host rebuilds the sets), graph, drawn, the pool rows
+    every event moved, the group-steps spent waiting for a boundary and idle at the tail."""
+    K, R, A = int(particles), int(resample_every), len(word2event)
+    S = min(int(slots), int(n_songs))
+    start = time.perf_counter()
+    sess = DecodeSession(model, n_songs=S * K, kernel="gemm")
+    sess.reset()
+    seed = ops.next_seed()                                    # where _generate_stream and _DeviceLoop take it
+    bar_mask = plan.bar_mask if plan.bar_mask is not None else plan._bar_classes()
+    draw = DeviceDraw(plan, sess.dev, sess.shadow(plan.reference))
+    snap = _stream_snapshot(model, prompt, A, "gemm")
+    ref_snap = None if plan.reference is None else _stream_snapshot(plan.reference, prompt, A, "gemm")
+    loop = _ParticleStreamLoop(sess, snap, ref_snap, n_songs, K, R, ess, seed, bar_mask, bar_cond, plan.bar0s[0],
+                               caps[0], chunk, plan=draw, graph=sess.use_graph)
+    rows = loop.run()
+    ran = time.perf_counter()
+    lps = np.concatenate(loop.lp_parts)
+    h_anc, h_lw, h_ess, h_res = (np.concatenate(p) for p in loop.hist_parts)
+    more = {}
+    sets = particle_stream_sets(rows, lps, h_anc, h_lw, h_ess, h_res, loop.out_lw.cpu().numpy(),
+                                loop.out_len.cpu().numpy(), loop.out_logz.cpu().numpy(), K, R, n_songs, heads[0], more)
+    if log is not None:
+        log("%d songs x %d particles on %d slots: %d tokens, %d steps, %d resampling events"
+            % (n_songs, K, S, sum(len(x) for s in sets for x in s.songs), len(rows), len(h_anc)))
+    if stats is not None:
+        torch.cuda.synchronize(sess.dev)
+        moved = (h_anc != np.arange(S * K)).sum(1)
+        stats.update(steps=len(rows), events=len(h_anc), seconds=time.perf_counter() - start,
+                     graph=loop._graph is not None, drawn=int(loop.out_len.sum().item()), row_bytes=loop.row_bytes,
+                     moved_rows=[int(m) for m in moved], groups=S, wait_seconds=loop.wait_s,
+                     run_seconds=ran - start, **more)
+    return sets
+
+
 def generate_particles(model, word2event, n_songs, particles, resample_every=16, ess=0.5, bar_cond=17, max_tokens=None,
                        prompts=None, sampler="dqn", chunk=128, log=None, prefill="blas", constraints=None,
                        grammar=None, reference=None, alpha=None, preferences=None, reward=None, reward_window=50,
-                       beta=1.0):
+                       beta=1.0, slots=None):
     """Generate `n_songs` songs with `particles` = K weighted particles each, by sequential Monte Carlo with the device
     sampler as the proposal.  -> list of n_songs ParticleSet.
 
@@ -1704,7 +1968,22 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     n_songs), alpha, grammar, reference, sampler, bar_cond, max_tokens, chunk, prefill: as in generate_batch.  Each
     prompt is prefilled K times: sharing one prefill among a song's particles is left out.  Draws are keyed by (torch
     seed, step, row) and the resampling draw by (seed, event, song), so song g's set is the same whatever the other
-    songs.  The continuous-batching stream (slots=) is out of scope.
+    songs.
+
+    slots=S (None, the default: the lock-step pool above, unchanged): the particle stream.  S songs are in
+    flight on S K rows of one session and n_songs may be far larger than S: a group of K consecutive rows takes the next
+    song once all its K particles have ended, at the next multiple of resample_every steps, from a snapshot refilled on
+    the device (cwlt_stream_refill, cwlt_particle_release), so the pool never drains to its longest song.  Everything
+    about a song is relative to that song: draws are keyed by (particle id = song K + k, position in song), the song's
+    events follow its own rows R, 2 R, ... and their draw is keyed by (seed, the song's own event index, song)
+    (cwlt_particle_resample_keyed).  A song's ParticleSet is therefore bit for bit the one the lock-step pool makes after
+    the same torch.manual_seed, whatever `slots` and whatever the other songs.  Starts: from scratch, or from ONE shared
+    (P, 6) `prompts` array, prefilled once -- not n_songs K times -- by the batch-invariant prefill (the lock-step twin
+    is prefill="gemm"; `prefill` itself is not used); a list of per-song prompts is refused (the bank form of
+    generate_stream is left out here).  constraints, grammar, preferences, reference / alpha as above.  Refused with
+    slots: reward= (windows and events do not share boundaries: rewards on the stream stay left out), per-song prompt
+    lists, slots < 1, slots x particles > 4096, n_songs x particles > 2**20 (the sampler's key layout), and a chunk that
+    is no multiple of resample_every (a chunk's ring half holds whole event segments).
 
     reward, reward_window = W, beta: reward terms in the weights.  Each particle's drawn rows (not its
     prompt) are cut into consecutive windows of W rows, the last one possibly partial; after the last row of each
@@ -1717,12 +1996,20 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     AIRL discriminator, whose window is the default 50); a row without a live row in the window is shown mask[n, 0] = 1
     over zero tokens and its result is discarded.  The windows live per pool row on the device (cwlt_reward_push per
     token, cwlt_reward_window and cwlt_reward_apply per event) and are gathered with every other per-row state.
-    beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  Rewards on the stream, per-song
-    beta and the PPO reward model's per-attribute heads are left out.
+    beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  Rewards on the particle stream
+    (reward= with slots=, refused), per-song beta and the PPO reward model's per-attribute heads are left out.
     Refused, before anything runs: a reward that is not callable, reward_window < 1, a beta that is not finite, particles
     outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit), resample_every < 1, ess outside [0, 1], then
     everything generate_batch refuses."""
     spec = _reward_spec(reward, reward_window, beta)
+    if slots is not None:
+        _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward)
+        heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
+                                            ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
+                                            grammar, reference, alpha, preferences,
+                                            pool=min(int(slots), max(int(n_songs), 1)))
+        return _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
+                                    ess, bar_cond, int(chunk), log, None if prompts is None else heads[0])
     heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                         ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                         grammar, reference, alpha, preferences)
@@ -1955,17 +2242,24 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     particles=K (with batch_size; resample_every, ess: generate_particles'): each group is made by
     generate_particles with K particles a song, and each song kept is ParticleSet.draw -- one particle by final weight --
     with a numpy generator seeded from the torch seed.  None (the default): nothing changes.
-    reward, reward_window, beta (with particles; generate_particles', DESIGN §4.6n): window rewards in the particles'
-    weights.  reward=None (the default): nothing changes."""
+    particles=K with slots=S: the songs are made by generate_particles(slots=S), the particle stream --
+    S songs in flight, a group of K rows taking the next song when its particles have ended -- from scratch or from the
+    one shared `prompt`, and each song kept is ParticleSet.draw as above; resample_every must divide 128, the chunk.
+    reward, reward_window, beta (with particles and batch_size; generate_particles'): window rewards in
+    the particles' weights; refused with slots.  reward=None (the default): nothing changes."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
     if reward is not None and particles is None:
         raise ValueError("reward terms act on the weights of generate_particles' particles: pass particles= (and "
                          "batch_size); the one-song path, plain batches and the stream take no reward")
     spec = _reward_spec(reward, reward_window, beta)
-    if particles is not None and batch_size is None:
-        raise ValueError("particles run in generate_particles' lock-step pool: pass batch_size (the songs of one pool; "
-                         "the stream, slots=, takes no particles)")
+    if particles is not None and batch_size is None and slots is None:
+        raise ValueError("particles run in generate_particles' lock-step pool or its stream: pass batch_size or slots "
+                         "(the songs of one pool, or the songs in flight)")
+    if particles is not None and slots is not None:
+        if prompts is not None:
+            raise ValueError("slots= with particles= takes one shared prompt (prompt=), not per-song prompts")
+        _particle_stream_refusals(n_songs, particles, slots, resample_every, 128, None, reward)
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
         raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
                          "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
@@ -2014,7 +2308,20 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
             words_len_list.append(len(res))
             log("song %d: %d tokens in %.3f s (%s)" % (first + j, len(res), song_time_list[-1], how))
 
-    if slots is not None:
+    if slots is not None and particles is not None:
+        start = time.time()
+        heads, caps, plan = _particle_setup("generate", model, word2event, n_songs, particles, resample_every, ess,
+                                            bar_cond, max_tokens, prompt, "dqn", 128, "blas", constraints, grammar,
+                                            reference, alpha, preferences, pool=min(int(slots), max(int(n_songs), 1)))
+        sets = _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
+                                    ess, bar_cond, 128, None, None if prompt is None else heads[0])
+        rng = np.random.default_rng(ops.next_seed())             # after the run's seed, as the batch_size path
+        picks = [s.draw(rng, return_index=True) for s in sets]
+        songs = [p[0] for p in picks]
+        if logprobs:
+            songs = (songs, [s.logprobs[p[1]] for s, p in zip(sets, picks)])
+        record(0, songs, time.time() - start, "particle stream on %d slots" % int(slots))
+    elif slots is not None:
         start = time.time()
         songs = _generate_stream(model, word2event, n_songs, slots=int(slots), bar_cond=bar_cond, max_tokens=max_tokens,
                                  prompt=prompt, prompts=None if prompts is None else list(prompts),

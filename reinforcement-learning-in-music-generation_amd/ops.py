@@ -2094,6 +2094,90 @@ def particle_gather(dst, src, anc, row_bytes, n_blocks=1, block_stride=0, copy_b
     return dst
 
 
+def _int64_rows(fn, rows, **tensors):
+    """Every tensor a contiguous int64 of `rows` elements."""
+    for name, t in tensors.items():
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != rows:
+            raise TypeError("%s: %s must be a contiguous int64 tensor of %d elements" % (fn, name, rows))
+
+
+def particle_resample_keyed(lw, done, particles, ess_frac, seed, song, pos, every, anc, u, ess, resampled, log_z,
+                            pos_stride=None):
+    """particle_resample for the particle stream (cwlt_particle_resample_keyed): u is keyed by (seed, the
+    song's own event index pos / every - 1, song[g]); song (groups,) int64 (< 0: no song: the group is left alone, anc
+    the identity, u = ess = 0); pos int64, group g's clock at pos[g * pos_stride] (default: particles, pos per row)."""
+    fn, rows, K = "particle_resample_keyed", lw.numel(), int(particles)
+    if K < 1 or rows % K:
+        raise ValueError("%s: %d rows are no whole groups of %d particles" % (fn, rows, K))
+    groups = rows // K
+    stride = K if pos_stride is None else int(pos_stride)
+    for t, dt, n in ((lw, torch.float32, rows), (done, torch.int64, rows), (anc, torch.int64, rows),
+                     (u, torch.float32, groups), (ess, torch.float32, groups), (resampled, torch.int32, groups),
+                     (log_z, torch.float32, groups), (song, torch.int64, groups)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("%s takes contiguous lw f32 / done, anc int64 (rows,) and u, ess, log_z f32 / resampled "
+                            "int32 / song int64 (groups,)" % fn)
+    if pos.dtype != torch.int64 or not pos.is_contiguous() or stride < 1 or pos.numel() < (groups - 1) * stride + 1:
+        raise TypeError("%s: pos must be a contiguous int64 tensor with group g's clock at g * %d" % (fn, stride))
+    _call("cwlt_particle_resample_keyed", _lib.dev(lw, "lw"), _lib.dev(done, "done"), groups, K, float(ess_frac),
+          int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.dev(song, "song"), _lib.dev(pos, "pos"), stride, int(every),
+          _lib.dev(anc, "anc"), _lib.dev(u, "u"), _lib.dev(ess, "ess"), _lib.dev(resampled, "resampled"),
+          _lib.dev(log_z, "log_z"), _lib.stream_ptr())
+    return anc
+
+
+def particle_advance(tokens, pid, done, pos, fresh, ctl, ring):
+    """One token of the particle stream's bookkeeping (cwlt_particle_advance): (pid or -1, tokens, done)
+    of every row into row ctl[0] % R of ring (R, rows, A + 2) int64; pos += 1 for rows with pid >= 0; fresh = 0;
+    ctl[0] += 1.  tokens (rows, A), pid / done / pos / fresh (rows,) int64; ctl int64, its element 0 the counter."""
+    fn, rows, A = "particle_advance", pid.numel(), tokens.shape[-1]
+    _int64_rows(fn, rows, pid=pid, done=done, pos=pos, fresh=fresh)
+    _int64_rows(fn, rows * A, tokens=tokens)
+    if ctl.dtype != torch.int64 or ctl.numel() < 1 or ring.dtype != torch.int64 or not ring.is_contiguous() or \
+            ring.dim() != 3 or tuple(ring.shape[1:]) != (rows, A + 2):
+        raise ValueError("%s: ctl int64 and ring a contiguous (R, %d, %d) int64" % (fn, rows, A + 2))
+    _call("cwlt_particle_advance", _lib.dev(tokens, "tokens"), A, rows, _lib.dev(pid), _lib.dev(done), _lib.dev(pos),
+          _lib.dev(fresh), _lib.dev(ctl), _lib.dev(ring), ring.shape[0], _lib.stream_ptr())
+
+
+def particle_release(particles, n_songs, bar0, cap0, song, pid, pos, bar, cap, length, done, fresh, lw, log_z, ctl,
+                     out_lw, out_len, out_logz):
+    """The release / hand-out of the particle stream (cwlt_particle_release; sampling.particle_release is
+    its numpy restatement): groups without a song or with every row done are candidates; finished ones write out_lw,
+    out_len (n_songs * particles,) and out_logz (n_songs,); candidates take the next songs from ctl[1] in group order.
+    song, log_z (groups,); pid, pos, bar, cap, length, done, fresh, lw (rows,); ctl (>= 3,) int64."""
+    fn, K, groups = "particle_release", int(particles), song.numel()
+    rows = groups * K
+    _int64_rows(fn, groups, song=song)
+    _int64_rows(fn, rows, pid=pid, pos=pos, bar=bar, cap=cap, length=length, done=done, fresh=fresh)
+    _int64_rows(fn, int(n_songs) * K, out_len=out_len)
+    for t, n in ((lw, rows), (log_z, groups), (out_lw, int(n_songs) * K), (out_logz, int(n_songs))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("%s takes contiguous f32 lw (rows,), log_z (groups,), out_lw (n_songs * K,) and out_logz "
+                            "(n_songs,)" % fn)
+    if ctl.dtype != torch.int64 or ctl.numel() < 3:
+        raise TypeError("%s: ctl must hold the int64 counters {tokens, assigned, finished}" % fn)
+    _call("cwlt_particle_release", groups, K, int(n_songs), int(bar0), int(cap0), _lib.dev(song), _lib.dev(pid),
+          _lib.dev(pos), _lib.dev(bar), _lib.dev(cap), _lib.dev(length), _lib.dev(done), _lib.dev(fresh), _lib.dev(lw),
+          _lib.dev(log_z), _lib.dev(ctl), _lib.dev(out_lw), _lib.dev(out_len), _lib.dev(out_logz), _lib.stream_ptr())
+
+
+def particle_fill(dst, src, fresh, pid):
+    """dst[n] = src[pid[n]] for the rows with fresh[n] != 0 and 0 <= pid[n] < len(src) (cwlt_particle_fill): the new
+    particles' start rows.  dst (rows, ...) and src (n_src, ...) of one dtype and row width (4-byte multiples), unit
+    stride inside a row; fresh, pid (rows,) int64."""
+    fn, rows = "particle_fill", fresh.numel()
+    _int64_rows(fn, rows, fresh=fresh, pid=pid)
+    if dst.dtype != src.dtype or dst.shape[0] != rows or dst.dim() > 2 or src.dim() != dst.dim() or \
+            dst.shape[1:] != src.shape[1:] or (dst.dim() == 2 and (dst.stride(1) != 1 or src.stride(1) != 1)):
+        raise TypeError("%s takes dst (rows, w) and src (n_src, w) of one dtype, rows %d" % (fn, rows))
+    es = dst.element_size()
+    width = es * (dst.shape[1] if dst.dim() == 2 else 1)
+    _call("cwlt_particle_fill", _lib.dev(dst, "dst"), _lib.dev(src, "src"), _lib.dev(fresh), _lib.dev(pid), rows,
+          src.shape[0], width, es * dst.stride(0), es * src.stride(0), _lib.stream_ptr())
+    return dst
+
+
 def _reward_ring(where, recent, live):
     """(rows, W, A) of a reward ring: recent (rows, W, A) and live (rows, W), contiguous int64."""
     if recent.dtype != torch.int64 or live.dtype != torch.int64 or not recent.is_contiguous() or not live.is_contiguous():

@@ -307,3 +307,30 @@ def systematic_resample(lw, u, ess_frac, done=None):
     anc = np.minimum(np.searchsorted(prefix, thresholds, side="right"), K - 1).astype(np.int64)
     return Resampled(anc=anc, ess=ess, resampled=1, log_z=float(m + np.log(s / K)), lw=np.zeros(K), prefix=prefix,
                      thresholds=thresholds, s=s)
+
+
+def particle_release(song, done, particles, assigned, finished, n_songs):
+    """Numpy restatement of cwlt_particle_release's decision.  song (groups,): each group's song, < 0
+    none; done (groups * K,): the rows' end flags; assigned, finished: the counters before; n_songs: the run's songs.
+    A group is a candidate when it has no song or all its K rows are done; a candidate with a song is finished.
+    Candidate number r, in group order, takes song assigned + r while that is < n_songs, else none (-1).
+    -> (take (groups,) int64: -2 for a group that is no candidate (nothing of it is written), else its new song or -1;
+    released (groups,) bool: the finished groups, whose old song's outputs are written; assigned, finished after)."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1)
+    K = int(particles)
+    all_done = (np.asarray(done).reshape(len(song), K) != 0).all(1)
+    cand = (song < 0) | all_done
+    released = (song >= 0) & all_done
+    idx = int(assigned) + np.cumsum(cand) - 1
+    take = np.where(cand, np.where(idx < int(n_songs), idx, -1), -2).astype(np.int64)
+    return take, released, min(int(assigned) + int(cand.sum()), int(n_songs)), int(finished) + int(released.sum())
+
+
+def particle_event_keys(song, pos, every):
+    """Numpy restatement of cwlt_particle_resample_keyed's bookkeeping: song (groups,) and the groups'
+    clocks pos (groups,) -> (event (groups,) int64: the song's own event index pos // every - 1; skip (groups,) bool:
+    groups the kernel leaves alone -- no song, or no whole segment yet).  Group g's u is cwlt_particle_resample's for
+    (seed, event[g], song[g]) in place of (seed, the run's event, g)."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1)
+    event = np.asarray(pos, dtype=np.int64).reshape(-1) // int(every) - 1
+    return event, (song < 0) | (event < 0)
