@@ -787,13 +787,22 @@ int cwlt_particle_fill(void* dst, const void* src, const int64_t* fresh, const i
  *
  * cwlt_reward_apply: for the rows with any[n] != 0, lw[n] = lw[n] + (beta * r[n]), the product rounded to f32 and then
  * the sum (no fma), and h_r[n] = r[n]; for the others lw[n] is not written and h_r[n] = 0 whatever r[n] holds (a
- * select: r[n] may be NaN).  r, lw, h_r f32 x rows. */
+ * select: r[n] may be NaN).  r, lw, h_r f32 x rows.
+ *
+ * cwlt_reward_apply_keyed: cwlt_reward_apply with a reward weight per song.  Row n belongs to song
+ * s = id / particles, id = key[n], or n when key is NULL (the lock-step pool, where the row index is the particle id;
+ * the particle stream passes its id array).  A row is on when any[n] != 0, id >= 0 and s < n_beta: it gets
+ * lw[n] = lw[n] + (beta[s] * r[n]), by the same two roundings, and h_r[n] = r[n].  Every other row keeps lw[n]
+ * unwritten and gets h_r[n] = 0 by a select; beta is not read for it.  beta f32 x n_beta (n_beta >= 1), key int64 x rows
+ * or NULL, particles >= 1. */
 int cwlt_reward_push(const int64_t* tok, const int64_t* done, const int64_t* counter, int64_t rows, int n_attr,
                      int64_t window, int64_t* recent, int64_t* live, void* stream);
 int cwlt_reward_window(const int64_t* recent, const int64_t* live, int64_t rows, int n_attr, int64_t window,
                        int64_t filled, int64_t* win, int64_t* mask, int64_t* any, void* stream);
 int cwlt_reward_apply(const float* r, const int64_t* any, float beta, int64_t rows, float* lw, float* h_r,
                       void* stream);
+int cwlt_reward_apply_keyed(const float* r, const int64_t* any, const float* beta, int64_t n_beta, const int64_t* key,
+                            int particles, int64_t rows, float* lw, float* h_r, void* stream);
 
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass

@@ -6,9 +6,11 @@
 // per reward event (the ring wrapped, or the run ended inside a window)
 //   cwlt_reward_window  the ring as the reward callable sees it: tokens and a 0/1 mask of the live slots, zero elsewhere,
 //                       and per row whether it has a live slot at all;
-//   cwlt_reward_apply   lw += beta * r for the rows that have one, and the reward into the event's history row.
-// None of the three synchronises with the host or allocates: push sits inside the captured token, the other two are
-// enqueued between replays around the callable.  No cross-workgroup communication, no atomics, no barriers.
+//   cwlt_reward_apply   lw += beta * r for the rows that have one, and the reward into the event's history row;
+//   cwlt_reward_apply_keyed  the same with the reward weight of the row's own song: beta[s], s the row's
+//                       particle id / K -- the row index in the lock-step pool, the stream's id array otherwise.
+// None of the four synchronises with the host or allocates: push sits inside the captured token; the window kernel and
+// one of the two apply kernels are enqueued between replays, around the callable.  No cross-workgroup communication, no atomics, no barriers.
 #include "cwlt_common.h"
 
 namespace cwlt {
@@ -72,6 +74,24 @@ __global__ __launch_bounds__(256) void reward_apply_kernel(const float* __restri
     if (on) lw[n] = reward_term(lw[n], beta, x);
 }
 
+// One thread per row, cwlt_reward_apply's arithmetic (reward_term) with beta[s] of the row's song s = id / K, id the
+// row's key (NULL: the row index).  A row is on when it has a live slot, an id and a table entry; beta is read for on
+// rows only, and an off row is skipped by a select: its r may be anything.  Bitwise sampling.reward_apply_keyed_f32.
+__global__ __launch_bounds__(256) void reward_apply_keyed_kernel(const float* __restrict__ r,
+                                                                 const int64_t* __restrict__ any,
+                                                                 const float* __restrict__ beta, long n_beta,
+                                                                 const int64_t* __restrict__ key, long K, long rows,
+                                                                 float* __restrict__ lw, float* __restrict__ h_r) {
+    const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= rows) return;
+    const long id = key ? (long)key[n] : n;
+    const long s = id >= 0 ? id / K : -1;
+    const bool on = any[n] != 0 && id >= 0 && s < n_beta;
+    const float x = r[n];
+    h_r[n] = on ? x : 0.f;
+    if (on) lw[n] = reward_term(lw[n], beta[s], x);
+}
+
 constexpr long REWARD_MAX_ROWS = 1L << 20, REWARD_MAX_WINDOW = 1L << 16;
 
 }  // namespace cwlt
@@ -108,5 +128,16 @@ extern "C" int cwlt_reward_apply(const float* r, const int64_t* any, float beta,
     if (rows < 1 || rows > REWARD_MAX_ROWS) return CWLT_ERR_ARG;
     hipLaunchKernelGGL(reward_apply_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r,
                        any, beta, (long)rows, lw, h_r);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cwlt_reward_apply_keyed(const float* r, const int64_t* any, const float* beta, int64_t n_beta,
+                                       const int64_t* key, int particles, int64_t rows, float* lw, float* h_r,
+                                       void* stream) {
+    using namespace cwlt;
+    if (!r || !any || !beta || !lw || !h_r) return CWLT_ERR_ARG;
+    if (rows < 1 || rows > REWARD_MAX_ROWS || n_beta < 1 || particles < 1) return CWLT_ERR_ARG;
+    hipLaunchKernelGGL(reward_apply_keyed_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, r, any, beta, (long)n_beta, key, (long)particles, (long)rows, lw, h_r);
     return (int)hipGetLastError();
 }

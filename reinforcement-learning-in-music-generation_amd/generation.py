@@ -17,6 +17,7 @@ Sampling stays on the host with numpy, in the reference's order of draws, so tha
 """
 import ctypes
 import json
+import math
 import os
 import time
 
@@ -589,6 +590,34 @@ class _DeviceLoop:
         return self.logp.index_select(0, idx).cpu().numpy()
 
 
+def _reward_event(loop, filled, key, h_row):
+    """One reward event of a particle loop (_ParticleLoop, _ParticleStreamLoop), enqueued on the current stream, no
+    sync: cwlt_reward_window cuts the loop's rings into win / mask / any (filled: the ring's slots that belong to the
+    window), the callable scores every row, and beta r goes into loop.lw and r into h_row -- cwlt_reward_apply, or with
+    a beta per song cwlt_reward_apply_keyed, row n of song key[n] // K (key None: n // K).  A loop with a reward_timed
+    list gets the four HIP events around the three steps appended."""
+    fn, _, beta = loop.reward
+    rows = loop.lw.numel()
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if loop.reward_timed is not None else None
+    mark = (lambda i: marks[i].record()) if marks else (lambda i: None)
+    mark(0)
+    ops.reward_window(loop.recent, loop.live, filled, loop.win, loop.mask, loop.any)
+    mark(1)
+    r = fn(loop.win, loop.mask)
+    if not torch.is_tensor(r) or not r.is_cuda or r.dtype != torch.float32 or tuple(r.shape) != (rows,):
+        raise TypeError("reward(windows, mask) must return a (%d,) float32 tensor on the GPU, got %s"
+                        % (rows, "%s %s" % (tuple(r.shape), r.dtype) if torch.is_tensor(r) else type(r).__name__))
+    mark(2)
+    if loop.beta_t is None:
+        ops.reward_apply(r.contiguous(), loop.any, beta, loop.lw, h_row)
+    else:
+        ops.reward_apply_keyed(r.contiguous(), loop.any, loop.beta_t, key, loop.K, loop.lw, h_row)
+    mark(3)
+    if marks:
+        loop.reward_timed.append(marks)
+    loop.n_rewards += 1
+
+
 class _ParticleLoop(_DeviceLoop):
     """The lock-step loop with K particles per song: row g K + k of the pool is particle k of song g.
     Per token, inside the captured token and before the counter moves: cwlt_count_bars (into a count of the loop's own
@@ -608,7 +637,8 @@ class _ParticleLoop(_DeviceLoop):
     cwlt_particle_weigh (it reads `done` as it was before the row).  After every W-th token, and ahead of a resampling
     event of the same token, reward_event(): cwlt_reward_window cuts the rings into win / mask / any, the callable
     scores them, cwlt_reward_apply adds beta r to lw and writes r into row j of h_r (ceil(capacity / W), N) f32 --
-    eager launches on the loop's stream, no sync.  timed=True records HIP events around the three steps too."""
+    eager launches on the loop's stream, no sync.  timed=True records HIP events around the three steps too.  A beta per
+    song (a tuple, DESIGN §4.6p): cwlt_reward_apply_keyed with the device table `beta_t`, row n of song n // K."""
 
     def __init__(self, sess, capacity, plan, particles, every, ess, bar_cond, caps, bar_mask, graph=None, ring=None,
                  timed=False, reward=None):
@@ -640,6 +670,7 @@ class _ParticleLoop(_DeviceLoop):
             self.win, self.mask = torch.zeros_like(self.recent), torch.zeros_like(self.live)
             self.any = torch.zeros(N, dtype=torch.int64, device=dev)
             self.h_r = torch.zeros((-(-self.capacity // W), N), dtype=torch.float32, device=dev)
+            self.beta_t = _beta_table(reward[2], dev)                 # a per-song beta: row n is of song n // K
         # (state, scratch, row bytes, blocks, block stride in bytes) of every family of per-row buffers
         self.families = []
         for s in (sess, self.ref):
@@ -667,22 +698,7 @@ class _ParticleLoop(_DeviceLoop):
     def reward_event(self, filled=None):
         """One reward event, enqueued: the window the callable sees, the callable, beta r into the weights.  filled:
         the ring's slots that belong to the window (default: all W, the ring has just wrapped)."""
-        fn, W, beta = self.reward
-        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if self.reward_timed is not None else None
-        mark = (lambda i: marks[i].record()) if marks else (lambda i: None)
-        mark(0)
-        ops.reward_window(self.recent, self.live, W if filled is None else filled, self.win, self.mask, self.any)
-        mark(1)
-        r = fn(self.win, self.mask)
-        if not torch.is_tensor(r) or not r.is_cuda or r.dtype != torch.float32 or tuple(r.shape) != (self.N,):
-            raise TypeError("reward(windows, mask) must return a (%d,) float32 tensor on the GPU, got %s"
-                            % (self.N, "%s %s" % (tuple(r.shape), r.dtype) if torch.is_tensor(r) else type(r).__name__))
-        mark(2)
-        ops.reward_apply(r.contiguous(), self.any, beta, self.lw, self.h_r[self.n_rewards])
-        mark(3)
-        if marks:
-            self.reward_timed.append(marks)
-        self.n_rewards += 1
+        _reward_event(self, self.reward[1] if filled is None else filled, None, self.h_r[self.n_rewards])
 
     def _events(self):
         """What follows a token between replays: the reward event first, so that a resampling of the same token sees
@@ -929,10 +945,21 @@ class _ParticleStreamLoop(_StreamLoop):
     cwlt_particle_advance.  After every R-th token, eagerly on the same stream (_event): lw into its history, the keyed
     resampling, the two-phase gather of every family (_ParticleLoop's, through scratch), cwlt_particle_release and the
     fill of the new particles' beat / seen rows.  The event histories are rings of two chunks' events, copied out with
-    the token rows behind the chunk's event; rows are kept per (step, row): the lineage needs the row index."""
+    the token rows behind the chunk's event; rows are kept per (step, row): the lineage needs the row index.
+
+    reward (a _reward_spec: callable, window W, beta): _ParticleLoop's rings `recent` (S K, W, A) and
+    `live` (S K, W) join the gather families, and cwlt_reward_push, with the stream's step counter ctl[0] as its counter,
+    sits in the captured token ahead of cwlt_particle_weigh.  A group then takes a song only at run steps that are
+    multiples of B = lcm(R, W) -- the release and the fills run at those boundaries alone, a finished group waits for
+    the next one -- so that every song starts at t0 = 0 (mod B) and slot ctl[0] % W is the song's own pos % W: its
+    windows close after its own rows W, 2 W, ...  After every W-th token, ahead of a resampling of the same token
+    (_reward_event): cwlt_reward_window (always the whole ring: it has just wrapped), the callable on all S K rows,
+    cwlt_reward_apply -- or cwlt_reward_apply_keyed with a beta per song, keyed by the rows' particle ids -- into a ring
+    `h_r` of two chunks' reward events, copied out with the chunk.  timed=True records HIP events around the three steps of
+    every reward event.  reward=None: launch for launch the loop without this paragraph."""
 
     def __init__(self, sess, snap, ref_snap, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0, cap, chunk,
-                 **kw):
+                 reward=None, timed=False, **kw):
         super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
         dev, N = sess.dev, self.S
         self.K, self.every, self.ess_frac = int(particles), int(every), float(ess)
@@ -956,6 +983,22 @@ class _ParticleStreamLoop(_StreamLoop):
                             for t in self._hist] for _ in range(2)]
         self.hist_parts = [[] for _ in self._hist]
         self.n_events = 0
+        self.reward, self.recent, self.live, self.n_rewards = reward, None, None, 0
+        self.hand_every = self.every                             # a group takes a song at multiples of this many steps
+        self.reward_timed = [] if timed and reward is not None else None
+        if reward is not None:
+            W = reward[1]
+            self.hand_every = _lcm(self.every, W)
+            self.recent = torch.zeros((N, W, self.A), dtype=torch.int64, device=dev)
+            self.live = torch.zeros((N, W), dtype=torch.int64, device=dev)
+            self.win, self.mask = torch.zeros_like(self.recent), torch.zeros_like(self.live)
+            self.any = i64(N)
+            self.step = self.ctl[:1]                             # the run's step counter, cwlt_reward_push's
+            self.RC = self.chunk // W                            # reward events per chunk; a ring of two chunks' again
+            self.h_r = f32(2 * self.RC, N)
+            self._host_r = [torch.zeros((self.RC, N), dtype=torch.float32).pin_memory() for _ in range(2)]
+            self.r_parts = []
+            self.beta_t = _beta_table(reward[2], dev)            # a per-song beta: n_songs entries, keyed by particle id
         self.families = []                                       # _ParticleLoop's: (state, scratch, row bytes, blocks, stride)
         for s in (sess, self.plan.ref):
             if s is None:
@@ -965,14 +1008,15 @@ class _ParticleStreamLoop(_StreamLoop):
             stride = 4 * N * (sf + zf)
             self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
             self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
-        for t in (sess.tok, self.bar, self.beat, self.seen, self.len, self.done, self.cap):
+        for t in (sess.tok, self.bar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live):
             if t is not None:
                 self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
         self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)
 
     def _step_limit(self):
-        """List scheduling: the songs' total over the groups plus one longest song, each rounded up to a boundary."""
-        per = -(-self.cap0 // self.every) * self.every + self.every
+        """List scheduling: the songs' total over the groups plus one longest song, each rounded up to a boundary at
+        which groups take songs."""
+        per = -(-self.cap0 // self.hand_every) * self.hand_every + self.hand_every
         return (-(-self.n_songs // self.G) + 1) * per + 2 * self.chunk
 
     def _release(self):
@@ -1010,12 +1054,21 @@ class _ParticleStreamLoop(_StreamLoop):
         if self.seen is not None:                             # keyed by the particle id; the release filled the fresh rows
             ops.prefer_track(tok, s.n_token, plan.pen, self.seen, fresh=self.no_fresh, song=self.song,
                              seen0=plan.seen0)
+        if self.reward is not None:                            # slot ctl[0] % W; reads `done` as it was before the row
+            ops.reward_push(tok, self.done, self.step, self.recent, self.live)
         # weigh reads the log-prob row ctl[0] selects: ahead of the advance, which moves it
         ops.particle_weigh(self.lp_ring, self.ctl, self.bar, self.bar_cond, self.cap, self.lw, self.len, self.done)
         ops.particle_advance(tok, self.song, self.done, self.pos, self.fresh, self.ctl, self.ring)
 
+    def _reward_event(self):
+        """One reward event, enqueued on the stream's own stream, no sync: the windows of all S K rows, the callable,
+        beta r into the weights and r into the history ring.  Rows without a live slot -- finished, waiting, parked --
+        are shown mask[n, 0] = 1 and their result is discarded."""
+        _reward_event(self, self.reward[1], self.song, self.h_r[self.n_rewards % (2 * self.RC)])
+
     def _event(self):
-        """One boundary, enqueued: the resampling of every group with a live song, the gather, then the release."""
+        """One boundary, enqueued: the resampling of every group with a live song, the gather, then -- at a boundary at
+        which groups take songs (every one without a reward) -- the release."""
         r = self.n_events % (2 * self.EC)
         anc = self.h_anc[r]
         self.h_lw[r].copy_(self.lw)
@@ -1025,13 +1078,16 @@ class _ParticleStreamLoop(_StreamLoop):
             ops.particle_gather(scratch, state, anc, rb, nb, stride)
         for state, scratch, rb, nb, stride in self.families:
             ops.particle_gather(state, scratch, anc, rb, nb, stride, copy_back=True)
-        self._release()
+        if self.enqueued % self.hand_every == 0:
+            self._release()
         self.n_events += 1
 
     def _enqueue_chunk(self):
         with torch.no_grad():
             for _ in range(self.chunk):
                 _enqueue_token(self, "particle stream step")
+                if self.reward is not None and self.enqueued % self.reward[1] == 0:
+                    self._reward_event()                              # ahead of a resampling of the same step
                 if self.enqueued % self.every == 0:
                     self._event()
         h = (self.enqueued // self.chunk - 1) % 2
@@ -1039,6 +1095,8 @@ class _ParticleStreamLoop(_StreamLoop):
         self._host_lp[h].copy_(self.lp_ring[h * self.chunk:(h + 1) * self.chunk], non_blocking=True)
         for host, t in zip(self._host_hist[h], self._hist):
             host.copy_(t[h * self.EC:(h + 1) * self.EC], non_blocking=True)
+        if self.reward is not None:
+            self._host_r[h].copy_(self.h_r[h * self.RC:(h + 1) * self.RC], non_blocking=True)
         self._host_ctl[h].copy_(self.ctl, non_blocking=True)
         self._events[h].record()
         return h
@@ -1048,6 +1106,8 @@ class _ParticleStreamLoop(_StreamLoop):
         self.lp_parts.append(self._host_lp[h].numpy().copy())
         for parts, host in zip(self.hist_parts, self._host_hist[h]):
             parts.append(host.numpy().copy())
+        if self.reward is not None:
+            self.r_parts.append(self._host_r[h].numpy().copy())
         return self._host[h].numpy().copy()
 
 
@@ -1607,15 +1667,16 @@ class ParticleSet:
     particle's lineage (n_windows_i = ceil((L_i - P) / reward_window)); log_weights then carry beta x them as well and
     log_evidence estimates the log of the constrained expectation of exp(beta sum r); event_rewards (R, K) f32 is what
     each reward event that happened while the song had a live particle recorded for the song's K pool rows (0 for a
-    row without a live row in the window).  Both None without a reward."""
+    row without a live row in the window); beta: the song's own reward weight.  All three None without a
+    reward."""
 
     def __init__(self, songs, logprobs, log_weights, log_evidence, ess, resampled, ancestors, event_log_weights=None,
-                 rewards=None, event_rewards=None):
+                 rewards=None, event_rewards=None, beta=None):
         self.songs, self.logprobs = songs, logprobs
         self.log_weights, self.log_evidence = log_weights, float(log_evidence)
         self.ess, self.resampled, self.ancestors = ess, resampled, ancestors
         self.event_log_weights = event_log_weights
-        self.rewards, self.event_rewards = rewards, event_rewards
+        self.rewards, self.event_rewards, self.beta = rewards, event_rewards, beta
 
     def weights(self):
         """The normalised weights, (K,) float64."""
@@ -1678,16 +1739,47 @@ class WindowReward:
         return torch.log(d) if self.form == "log" else torch.log(d) - torch.log(1.0 - d)
 
 
-def _reward_spec(reward, reward_window, beta):
-    """generate_particles' reward refusals -> None without a reward, else (callable, W, beta)."""
+def _reward_spec(reward, reward_window, beta, n_songs=None):
+    """generate_particles' reward refusals -> None without a reward, else (callable, W, beta).  beta: a float, or -- for
+    a sequence of n_songs reward weights, one per song -- a tuple of floats."""
     if reward is not None and not callable(reward):
         raise TypeError("reward must be a callable (windows (N, W, A) int64, mask (N, W) int64) -> (N,) float32, got %r"
                         % (type(reward).__name__,))
     if int(reward_window) < 1:
         raise ValueError("reward_window must be >= 1, got %r" % (reward_window,))
-    if not np.isfinite(float(beta)):
-        raise ValueError("beta must be finite, got %r" % (beta,))
-    return None if reward is None else (reward, int(reward_window), float(beta))
+    sequence = isinstance(beta, (list, tuple)) or (isinstance(beta, np.ndarray) and beta.ndim > 0)
+    if sequence and reward is None:                                    # reward=None: nothing changes, beta is not used
+        return None
+    if sequence:
+        table = tuple(float(b) for b in np.asarray(beta, dtype=np.float64).reshape(-1))
+        if n_songs is not None and len(table) != int(n_songs):
+            raise ValueError("beta: %d entries for %d songs (one reward weight per song, or one float for all)"
+                             % (len(table), int(n_songs)))
+        if not table:
+            raise ValueError("beta: an empty sequence (one reward weight per song, or one float for all)")
+        for i, b in enumerate(table):
+            if not np.isfinite(b):
+                raise ValueError("every entry of beta must be finite, got %r for song %d" % (b, i))
+        beta = table
+    else:
+        if not np.isfinite(float(beta)):
+            raise ValueError("beta must be finite, got %r" % (beta,))
+        beta = float(beta)
+    return None if reward is None else (reward, int(reward_window), beta)
+
+
+def _beta_table(beta, dev):
+    """A per-song beta (a tuple) as the f32 device table cwlt_reward_apply_keyed reads; None for one float."""
+    return torch.tensor(beta, dtype=torch.float32, device=dev) if isinstance(beta, tuple) else None
+
+
+def _song_beta(reward, s):
+    """Song s's own reward weight under the _reward_spec `reward`."""
+    return float(reward[2][s]) if isinstance(reward[2], tuple) else float(reward[2])
+
+
+def _lcm(a, b):
+    return int(a) * int(b) // math.gcd(int(a), int(b))
 
 
 def _particle_setup(where, model, word2event, n_songs, particles, resample_every, ess, bar_cond, max_tokens, prompts,
@@ -1793,6 +1885,7 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
         if W is not None:                                              # the reward events of the same span of steps
             n_r = max(-(-int(lens[g * K:(g + 1) * K].max()) // W), (int(hit.max()) + 1) * R // W if len(hit) else 0)
             out[-1].event_rewards = h_r[:n_r, g * K:(g + 1) * K].copy()
+            out[-1].beta = _song_beta(reward, g)
     if log is not None:
         log("%d songs x %d particles: %d tokens, %d steps, %d resampling events"
             % (N // K, K, sum(len(x) for s in out for x in s.songs), done, E))
@@ -1810,7 +1903,7 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
 
 
 def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len, out_logz, particles, every, n_songs,
-                         head, stats=None):
+                         head, stats=None, h_r=None, window=None):
     """The ParticleSets of a particle stream from what the device wrote; numpy only.
     rows (T, N, A + 2) int64, the ring rows of T steps: per pool row {particle id or -1, the A tokens, done}; logps
     (T, N, A, 2) f32 beside them; the run's events e = 0, 1, ..., event e after step (e + 1) R: h_anc (E, N) int64 pool-row
@@ -1823,11 +1916,22 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
     song had a live particle (up to its last resampling, or the end of its longest final particle).
     stats (a dict, optional) gains wait_group_steps -- steps groups spent with every particle done, waiting for the
     boundary --, idle_group_steps, steps of groups without a song, and start_steps, the step each song's first row was
-    drawn at."""
+    drawn at.
+    h_r (the run's reward events, event i after step (i + 1) W: (n, N) f32) and window = W: the run carried
+    a reward.  Songs then start at multiples of B = lcm(R, W) only, and ParticleSet.rewards and event_rewards are filled:
+    window j of final particle k is the run's reward event t0 / W + j, read at pool row
+    g K + lineage[min(tau // R, events), k] with tau = (j + 1) W - 1, the row the lineage lived in when the event ran;
+    ceil(L_k / W) windows; event_rewards is cut like the lock-step pool's, with the song's own event indices.  A song
+    that starts off a multiple of B, or a group released before its song's last window closed, is inconsistent.  stats
+    then also gains boundary_wait_group_steps: the group-steps waited for a multiple of B beyond the next multiple of
+    R."""
     rows = np.asarray(rows)
     T, N = rows.shape[:2]
     K, R, A = int(particles), int(every), rows.shape[2] - 2
     G = N // K
+    W = None if window is None or h_r is None else int(window)
+    B = R if W is None else _lcm(R, W)
+    beyond = 0
     ids = rows[:, ::K, 0]
     gsong = np.where(ids >= 0, ids // K, -1)
     out, starts = [None] * int(n_songs), [None] * int(n_songs)
@@ -1840,9 +1944,9 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
             if s < 0:
                 idle += int(t1 - t0)
                 continue
-            if t0 % R or out[s] is not None:
+            if t0 % B or out[s] is not None:
                 raise RuntimeError("particle stream output is inconsistent: song %d starts at step %d (every %d)%s"
-                                   % (s, t0, R, "" if out[s] is None else ", a second time"))
+                                   % (s, t0, B, "" if out[s] is None else ", a second time"))
             e0 = int(t0) // R
             E = min(int(t1 - t0) // R, len(h_anc) - e0)
             span, own = slice(e0, e0 + E), slice(g * K, (g + 1) * K)
@@ -1865,6 +1969,20 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
             cut = slice(e0, e0 + live)
             out[s] = ParticleSet(songs, lps, w, float(out_logz[s]) + logmeanexp(w), np.array(h_ess[cut, g]),
                                  np.asarray(h_res[cut, g]) != 0, anc[:live], np.array(h_lw[cut, own]))
+            if W is not None:
+                w0, n_win = int(t0) // W, -(-longest // W)
+                if n_win * W > t1 - t0 or w0 + n_win > len(h_r):
+                    raise RuntimeError("particle stream output is inconsistent: song %d held its group for %d steps, "
+                                       "its last window of %d rows closes after %d" % (s, t1 - t0, W, n_win * W))
+                out[s].rewards = []
+                for k in range(K):
+                    j = np.arange(-(-int(lens[k]) // W))
+                    tau = (j + 1) * W - 1
+                    out[s].rewards.append(np.asarray(h_r[w0 + j, g * K + line[np.minimum(tau // R, E), k]],
+                                                     dtype=np.float32))
+                n_r = max(n_win, (int(hit.max()) + 1) * R // W if len(hit) else 0)
+                out[s].event_rewards = np.array(h_r[w0:w0 + n_r, own], dtype=np.float32)
+                beyond += int(t1 - t0) - -(-longest // R) * R
             wait += int(t1 - t0) - longest
             starts[s] = int(t0)
     missing = [s for s, ps in enumerate(out) if ps is None]
@@ -1872,15 +1990,26 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
         raise RuntimeError("particle stream output is inconsistent: no rows of songs %s" % missing[:8])
     if stats is not None:
         stats.update(wait_group_steps=wait, idle_group_steps=idle, start_steps=starts)
+        if W is not None:
+            stats.update(boundary_wait_group_steps=beyond)
     return out
 
 
-def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward):
-    """What generate_particles(slots=) refuses ahead of the lock-step path's own refusals."""
-    if reward is not None:
-        raise ValueError("reward= with slots=: windows of reward_window rows and resampling events of resample_every "
-                         "rows do not share boundaries, and a group takes a song only at an event's; rewards run in "
-                         "the lock-step pool (slots=None)")
+def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window=50):
+    """What generate_particles(slots=) refuses ahead of the lock-step path's own refusals.  Under a reward (DESIGN
+    §4.6p) a group takes a song only at multiples of B = lcm(resample_every, reward_window) steps, and a chunk holds
+    whole stretches of B."""
+    if reward is not None and int(resample_every) >= 1 and int(reward_window) >= 1 and int(chunk) >= 1:
+        B = _lcm(resample_every, reward_window)
+        if int(chunk) % B:
+            raise ValueError("reward= with slots=: chunk (%d) must be a multiple of lcm(resample_every, reward_window) = "
+                             "lcm(%d, %d) = %d -- windows of reward_window rows and resampling events of resample_every "
+                             "rows share only every %d-th step as a boundary, a group takes a song only there, and a "
+                             "chunk's ring half holds whole such stretches.  Choose a resample_every that divides "
+                             "reward_window, or the other way round, and a chunk that both divide: for example "
+                             "resample_every = 10 or 25 with reward_window = 50 and chunk = 100 (generate's chunk is "
+                             "128: resample_every = 16 with reward_window = 32); or run the lock-step pool (slots=None)"
+                             % (int(chunk), int(resample_every), int(reward_window), B, B))
     if isinstance(prompts, (list, tuple)):
         raise ValueError("slots= takes one shared (P, 6) prompt, prefilled once for all songs: per-song prompt lists "
                          "would need a prompt bank (generate_particles without slots takes them)")
@@ -1898,11 +2027,14 @@ def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, 
 
 
 def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particles, slots, resample_every, ess, bar_cond,
-                         chunk, log, prompt, stats=None):
+                         chunk, log, prompt, stats=None, reward=None):
     """generate_particles(slots=) after its refusals: the rows of `plan` (particles consecutive rows per song), S =
     min(slots, n_songs) songs in flight -> n_songs ParticleSets.  stats (a dict, optional): steps, events, seconds (all
     of it) and run_seconds (up to the last chunk read, before the host rebuilds the sets), graph, drawn, the pool rows
-    every event moved, the group-steps spent waiting for a boundary and idle at the tail."""
+    every event moved, the group-steps spent waiting for a boundary and idle at the tail.
+    reward: a _reward_spec; stats then also gets reward_events and the group-steps waited for a multiple
+    of lcm(R, W) beyond the next multiple of R, and a stats that comes with {"timed": True} the HIP-event milliseconds
+    of every reward event's window kernel, callable and apply kernel (reward_ms, as _run_particles')."""
     K, R, A = int(particles), int(resample_every), len(word2event)
     S = min(int(slots), int(n_songs))
     start = time.perf_counter()
@@ -1914,14 +2046,20 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
     snap = _stream_snapshot(model, prompt, A, "gemm")
     ref_snap = None if plan.reference is None else _stream_snapshot(plan.reference, prompt, A, "gemm")
     loop = _ParticleStreamLoop(sess, snap, ref_snap, n_songs, K, R, ess, seed, bar_mask, bar_cond, plan.bar0s[0],
-                               caps[0], chunk, plan=draw, graph=sess.use_graph)
+                               caps[0], chunk, reward=reward, timed=bool(stats and stats.get("timed")), plan=draw,
+                               graph=sess.use_graph)
     rows = loop.run()
     ran = time.perf_counter()
     lps = np.concatenate(loop.lp_parts)
     h_anc, h_lw, h_ess, h_res = (np.concatenate(p) for p in loop.hist_parts)
     more = {}
+    h_r = None if reward is None else np.concatenate(loop.r_parts)
     sets = particle_stream_sets(rows, lps, h_anc, h_lw, h_ess, h_res, loop.out_lw.cpu().numpy(),
-                                loop.out_len.cpu().numpy(), loop.out_logz.cpu().numpy(), K, R, n_songs, heads[0], more)
+                                loop.out_len.cpu().numpy(), loop.out_logz.cpu().numpy(), K, R, n_songs, heads[0], more,
+                                h_r=h_r, window=None if reward is None else reward[1])
+    if reward is not None:
+        for s, ps in enumerate(sets):
+            ps.beta = _song_beta(reward, s)
     if log is not None:
         log("%d songs x %d particles on %d slots: %d tokens, %d steps, %d resampling events"
             % (n_songs, K, S, sum(len(x) for s in sets for x in s.songs), len(rows), len(h_anc)))
@@ -1932,6 +2070,10 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
                      graph=loop._graph is not None, drawn=int(loop.out_len.sum().item()), row_bytes=loop.row_bytes,
                      moved_rows=[int(m) for m in moved], groups=S, wait_seconds=loop.wait_s,
                      run_seconds=ran - start, **more)
+        if reward is not None:
+            stats.update(reward_events=len(h_r),
+                         reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
+                                    for m in loop.reward_timed or []])
     return sets
 
 
@@ -1981,9 +2123,9 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     (P, 6) `prompts` array, prefilled once -- not n_songs K times -- by the batch-invariant prefill (the lock-step twin
     is prefill="gemm"; `prefill` itself is not used); a list of per-song prompts is refused (the bank form of
     generate_stream is left out here).  constraints, grammar, preferences, reference / alpha as above.  Refused with
-    slots: reward= (windows and events do not share boundaries: rewards on the stream stay left out), per-song prompt
-    lists, slots < 1, slots x particles > 4096, n_songs x particles > 2**20 (the sampler's key layout), and a chunk that
-    is no multiple of resample_every (a chunk's ring half holds whole event segments).
+    slots: per-song prompt lists, slots < 1, slots x particles > 4096, n_songs x particles > 2**20 (the sampler's key
+    layout), a chunk that is no multiple of resample_every (a chunk's ring half holds whole event segments) and, with a
+    reward, a chunk that is no multiple of lcm(resample_every, reward_window) (below).
 
     reward, reward_window = W, beta: reward terms in the weights.  Each particle's drawn rows (not its
     prompt) are cut into consecutive windows of W rows, the last one possibly partial; after the last row of each
@@ -1996,20 +2138,32 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     AIRL discriminator, whose window is the default 50); a row without a live row in the window is shown mask[n, 0] = 1
     over zero tokens and its result is discarded.  The windows live per pool row on the device (cwlt_reward_push per
     token, cwlt_reward_window and cwlt_reward_apply per event) and are gathered with every other per-row state.
-    beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  Rewards on the particle stream
-    (reward= with slots=, refused), per-song beta and the PPO reward model's per-attribute heads are left out.
-    Refused, before anything runs: a reward that is not callable, reward_window < 1, a beta that is not finite, particles
+    beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  The PPO reward model's
+    per-attribute heads are left out.
+    beta: one finite float, or a sequence of n_songs finite floats, song g's windows weighted by beta[g]
+    (cwlt_reward_apply_keyed; a sweep of the KL coefficient over the songs of one run); ParticleSet.beta is the song's
+    own value.  A list of equal entries gives the scalar's run bit for bit.
+    reward= with slots=: with B = lcm(resample_every, reward_window), a group takes its next song only at
+    run steps that are multiples of B -- a finished group waits for one -- so that every song's windows and events
+    fall after its own rows W, 2 W, ... and R, 2 R, ...; resampling events stay at every R-th step and reward events
+    follow every W-th, ahead of a resampling of the same step.  The sets, rewards and event_rewards included, are bit
+    for bit the lock-step pool's.  The callable is given all slots x particles rows on the stream's own HIP stream.
+    chunk must be a multiple of B: choose resample_every and reward_window so that one divides the other and both divide
+    chunk, for example resample_every = 10 or 25 with reward_window = 50 and chunk = 100; the defaults (16, 50, 128: B =
+    400) are refused.
+    Refused, before anything runs: a reward that is not callable, reward_window < 1, a beta that is not finite or a beta
+    sequence of another length than n_songs, particles
     outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit), resample_every < 1, ess outside [0, 1], then
     everything generate_batch refuses."""
-    spec = _reward_spec(reward, reward_window, beta)
+    spec = _reward_spec(reward, reward_window, beta, n_songs)
     if slots is not None:
-        _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward)
+        _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window)
         heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                             ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                             grammar, reference, alpha, preferences,
                                             pool=min(int(slots), max(int(n_songs), 1)))
         return _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
-                                    ess, bar_cond, int(chunk), log, None if prompts is None else heads[0])
+                                    ess, bar_cond, int(chunk), log, None if prompts is None else heads[0], reward=spec)
     heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                         ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                         grammar, reference, alpha, preferences)
@@ -2245,21 +2399,23 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     particles=K with slots=S: the songs are made by generate_particles(slots=S), the particle stream --
     S songs in flight, a group of K rows taking the next song when its particles have ended -- from scratch or from the
     one shared `prompt`, and each song kept is ParticleSet.draw as above; resample_every must divide 128, the chunk.
-    reward, reward_window, beta (with particles and batch_size; generate_particles'): window rewards in
-    the particles' weights; refused with slots.  reward=None (the default): nothing changes."""
+    reward, reward_window, beta (with particles and batch_size or slots; generate_particles'): window
+    rewards in the particles' weights; beta one float or a list of n_songs, cut per batch_size group.  With slots the
+    chunk of 128 must be a multiple of lcm(resample_every, reward_window): for example resample_every = 16 with
+    reward_window = 32 (the default window of 50 is refused there).  reward=None (the default): nothing changes."""
     if batch_size is not None and slots is not None:
         raise ValueError("pass batch_size or slots, not both")
     if reward is not None and particles is None:
         raise ValueError("reward terms act on the weights of generate_particles' particles: pass particles= (and "
-                         "batch_size); the one-song path, plain batches and the stream take no reward")
-    spec = _reward_spec(reward, reward_window, beta)
+                         "batch_size or slots); the one-song path, plain batches and the plain stream take no reward")
+    spec = _reward_spec(reward, reward_window, beta, n_songs)
     if particles is not None and batch_size is None and slots is None:
         raise ValueError("particles run in generate_particles' lock-step pool or its stream: pass batch_size or slots "
                          "(the songs of one pool, or the songs in flight)")
     if particles is not None and slots is not None:
         if prompts is not None:
             raise ValueError("slots= with particles= takes one shared prompt (prompt=), not per-song prompts")
-        _particle_stream_refusals(n_songs, particles, slots, resample_every, 128, None, reward)
+        _particle_stream_refusals(n_songs, particles, slots, resample_every, 128, None, reward, reward_window)
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
         raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
                          "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
@@ -2314,7 +2470,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
                                             bar_cond, max_tokens, prompt, "dqn", 128, "blas", constraints, grammar,
                                             reference, alpha, preferences, pool=min(int(slots), max(int(n_songs), 1)))
         sets = _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
-                                    ess, bar_cond, 128, None, None if prompt is None else heads[0])
+                                    ess, bar_cond, 128, None, None if prompt is None else heads[0], reward=spec)
         rng = np.random.default_rng(ops.next_seed())             # after the run's seed, as the batch_size path
         picks = [s.draw(rng, return_index=True) for s in sets]
         songs = [p[0] for p in picks]
@@ -2352,7 +2508,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
             else:
                 sets = _run_particles(model, word2event, heads[rows], caps[rows], plan.songs(first * K, count * K), K,
                                       resample_every, ess, bar_cond, 128, None, None if given is None else "blas",
-                                      reward=spec)
+                                      reward=spec if spec is None or not isinstance(spec[2], tuple) else
+                                      spec[:2] + (spec[2][first:first + count],))
                 if rng is None:                                        # after the first pool's seed: that pool is
                     rng = np.random.default_rng(ops.next_seed())      # generate_particles' with the same torch seed
                 picks = [s.draw(rng, return_index=True) for s in sets]

@@ -2232,6 +2232,29 @@ def reward_apply(r, any_live, beta, lw, h_r):
     return lw
 
 
+def reward_apply_keyed(r, any_live, beta, key, particles, lw, h_r):
+    """reward_apply with a reward weight per song (cwlt_reward_apply_keyed): row n is a row of song
+    s = id // particles, id = key[n] (key None: n, the lock-step pool's rows).  Rows with any_live[n] != 0, id >= 0 and
+    s < len(beta) get lw[n] = lw[n] + (beta[s] * r[n]) (two f32 roundings, bitwise sampling.reward_apply_keyed_f32) and
+    h_r[n] = r[n]; the others keep lw and get h_r[n] = 0, whatever r[n] holds.  r, lw, h_r (rows,) f32, any_live (rows,)
+    int64, beta (n_beta,) f32 on the device, key (rows,) int64 or None."""
+    rows = lw.numel()
+    for t in (r, lw, h_r):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
+            raise TypeError("reward_apply_keyed takes contiguous f32 r, lw and h_r of %d rows" % rows)
+    if any_live.dtype != torch.int64 or not any_live.is_contiguous() or any_live.numel() != rows:
+        raise TypeError("reward_apply_keyed takes a contiguous int64 any of %d rows" % rows)
+    if beta.dtype != torch.float32 or not beta.is_contiguous() or beta.dim() != 1 or beta.numel() < 1:
+        raise TypeError("reward_apply_keyed takes a contiguous (n_beta,) f32 beta table")
+    if key is not None and (key.dtype != torch.int64 or not key.is_contiguous() or key.numel() != rows):
+        raise TypeError("reward_apply_keyed takes a contiguous int64 key of %d rows, or None" % rows)
+    if int(particles) < 1:
+        raise ValueError("reward_apply_keyed: particles must be >= 1, got %r" % (particles,))
+    _call("cwlt_reward_apply_keyed", _lib.dev(r, "r"), _lib.dev(any_live, "any"), _lib.dev(beta, "beta"), beta.numel(),
+          _lib.opt(key, "key"), int(particles), rows, _lib.dev(lw, "lw"), _lib.dev(h_r, "h_r"), _lib.stream_ptr())
+    return lw
+
+
 def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):
     """Copy the one-slot snapshot (state, logits) into every slot whose fresh flag is set (cwlt_stream_refill).
     state: flat f32 of n_layer x [S (slots, s_floats), Z (slots, z_floats)] (DecodeSession._state); snap_state: the same

@@ -265,6 +265,24 @@ def reward_apply_f32(lw, r, any_live, beta):
     return np.where(on, out, lw), np.where(on, r, np.float32(0))
 
 
+def reward_apply_keyed_f32(lw, r, any_live, beta, key, particles):
+    """Numpy float32 restatement of cwlt_reward_apply_keyed: reward_apply_f32 with the reward weight of
+    the row's own song.  beta (n_beta,); key (rows,) particle ids, or None: the row indices; row n is of song
+    s = key[n] // particles.  A row is on when any_live != 0, key >= 0 and s < n_beta: it gets lw + (beta[s] * r), the
+    product rounded to float32 and then the sum, and records r.  Every other row keeps its weight and records 0 --
+    selected: r may be NaN or infinite there, and no entry of beta is read for it.  Both outputs bitwise the kernel's."""
+    lw = np.asarray(lw, dtype=np.float32)
+    r = np.asarray(r, dtype=np.float32)
+    table = np.asarray(beta, dtype=np.float32).reshape(-1)
+    ids = np.arange(len(lw), dtype=np.int64) if key is None else np.asarray(key, dtype=np.int64).reshape(-1)
+    song = np.where(ids >= 0, ids // int(particles), -1)
+    on = (np.asarray(any_live) != 0) & (ids >= 0) & (song < len(table))
+    b = table[np.where(on, song, 0)]
+    with np.errstate(invalid="ignore", over="ignore"):
+        out = (lw + (b * r).astype(np.float32)).astype(np.float32)
+    return np.where(on, out, lw), np.where(on, r, np.float32(0))
+
+
 def logmeanexp(x):
     """log(mean(exp(x))) of a vector in float64, by the max subtraction; -inf for all -inf."""
     x = np.asarray(x, dtype=np.float64)
