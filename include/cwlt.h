@@ -767,6 +767,34 @@ int cwlt_particle_release(int64_t groups, int particles, int64_t n_songs, int64_
 int cwlt_particle_fill(void* dst, const void* src, const int64_t* fresh, const int64_t* id, int64_t rows, int64_t n_src,
                        int64_t row_bytes, int64_t ld_dst, int64_t ld_src, void* stream);
 
+/* ---- per-song prompts on the particle stream (csrc/particles_bank.hip) -----------------------------------
+ * Every song starts from its own entry, song % bank, of cwlt_stream_refill_bank's bank, and the K particles of a song
+ * share that one prefill.  One launch each, no host synchronisation, no allocation, no atomics.  Every pointer is
+ * DEVICE memory; a null pointer or a size out of range is refused with CWLT_ERR_ARG before any launch.
+ *
+ * cwlt_particle_refill_bank (per token, in the place of cwlt_stream_refill): row n of the pool belongs to group
+ * n / particles; a row with fresh[n] != 0 and id[n] >= 0 takes the state and the n_logits logits of bank entry
+ * e = (id[n] / particles) % bank -- state, bank_state, bank_logits and logits laid out as for cwlt_stream_refill_bank with
+ * `rows` slots.  Every other row is not written.  A workgroup that serves a group loads each float4 of the entry once
+ * and stores it to every fresh row of the group that takes it.  rows <= 2^20 and a multiple of particles, particles
+ * 2 .. 1024, bank >= 1, s_floats and z_floats multiples of 4, state and bank_state 16-byte aligned.
+ *
+ * cwlt_particle_release_bank (per hand-out boundary, in the place of cwlt_particle_release): ctl (DEVICE int64 x 4) =
+ * {tokens advanced, songs assigned, songs finished, songs ready}.  With limit = min(ctl[3], n_songs), candidate number r
+ * takes song ctl[1] + r only while that is < limit; a candidate past it is parked (song -1, id -1, done 1) and is a
+ * candidate again at the next boundary.  A finished song's out_lw / out_len / out_logz are written whether or not its
+ * group gets a new song.  ctl[1] = min(ctl[1] + candidates, max(limit, ctl[1])); ctl[2] += the finished groups.  A row
+ * handed song v gets bar bar0_all[v] and cap cap_all[v], two tables of n_songs int64, in the place of bar0 and cap0.
+ * With ctl[3] >= n_songs and constant tables every array comes out bitwise as cwlt_particle_release leaves it. */
+int cwlt_particle_refill_bank(float* state, const float* bank_state, int64_t bank, int n_layer, int64_t s_floats,
+                              int64_t z_floats, float* logits, const float* bank_logits, int64_t n_logits,
+                              int64_t ld_logits, int64_t ld_bank_logits, const int64_t* fresh, const int64_t* id,
+                              int64_t rows, int particles, void* stream);
+int cwlt_particle_release_bank(int64_t groups, int particles, int64_t n_songs, const int64_t* bar0_all,
+                               const int64_t* cap_all, int64_t* song, int64_t* id, int64_t* pos, int64_t* bar,
+                               int64_t* cap, int64_t* len, int64_t* done, int64_t* fresh, float* lw, float* log_z,
+                               int64_t* ctl, float* out_lw, int64_t* out_len, float* out_logz, void* stream);
+
 /* ---- reward terms in the particles' weights (csrc/reward.hip) ----------------------------------------------
  * Each pool row keeps a ring of its particle's last `window` = W drawn rows, recent (rows, W, n_attr) int64, and of
  * whether the particle was alive when each was drawn, live (rows, W) int64.  Both are per-row state: a caller hands them

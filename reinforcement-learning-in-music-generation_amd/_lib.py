@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -157,6 +157,9 @@ _SIGNATURES = {
     "cwlt_particle_advance": [_ptr, _c_int, _c_i64] + [_ptr] * 6 + [_c_i64, _ptr],
     "cwlt_particle_release": [_c_i64, _c_int, _c_i64, _c_i64, _c_i64] + [_ptr] * 15,
     "cwlt_particle_fill": [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _ptr],
+    "cwlt_particle_refill_bank": [_ptr, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _c_i64, _ptr,
+                                  _ptr, _c_i64, _c_int, _ptr],
+    "cwlt_particle_release_bank": [_c_i64, _c_int, _c_i64] + [_ptr] * 17,
     "cwlt_reward_push": [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_i64, _ptr, _ptr, _ptr],
     "cwlt_reward_window": [_ptr, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr],
     "cwlt_reward_apply": [_ptr, _ptr, _c_f32, _c_i64, _ptr, _ptr, _ptr],

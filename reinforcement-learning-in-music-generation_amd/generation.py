@@ -1019,10 +1019,14 @@ class _ParticleStreamLoop(_StreamLoop):
         per = -(-self.cap0 // self.hand_every) * self.hand_every + self.hand_every
         return (-(-self.n_songs // self.G) + 1) * per + 2 * self.chunk
 
-    def _release(self):
+    def _hand_out_songs(self):
         ops.particle_release(self.K, self.n_songs, self.bar0, self.cap0, self.gsong, self.song, self.pos, self.bar,
                              self.cap, self.len, self.done, self.fresh, self.lw, self.log_z, self.ctl, self.out_lw,
                              self.out_len, self.out_logz)
+
+    def _release(self):
+        """The release, then the new particles' grammar positions and repetition states by particle id."""
+        self._hand_out_songs()
         if self.beat is not None:
             ops.particle_fill(self.beat, self.plan.beat0, self.fresh, self.song)
         if self.seen is not None:
@@ -1033,17 +1037,21 @@ class _ParticleStreamLoop(_StreamLoop):
         self.ctl.zero_()
         self._release()
 
+    def _refill(self, sess, logits, ref=False):
+        """The fresh rows of `sess` (the model's pool, or ref: the reference's) and of its logits take their start."""
+        snap = self.ref_snap if ref else self.snap
+        ops.stream_refill(sess._state, snap[0], len(sess.memory), sess.memory[0][0][0].numel(),
+                          sess.memory[0][1][0].numel(), logits, snap[1], self.fresh)
+
     def _one(self):
         s, plan = self.sess, self.plan
         tok = s.tok.view(self.S, self.A)
         logits = s._device_step()
-        ops.stream_refill(s._state, self.snap[0], self.n_layer, self.s_floats, self.z_floats, logits, self.snap[1],
-                          self.fresh)
+        self._refill(s, logits)
         ref = plan.ref
         if ref is not None:
             ref_logits = ref._device_step()
-            ops.stream_refill(ref._state, self.ref_snap[0], len(ref.memory), ref.memory[0][0][0].numel(),
-                              ref.memory[0][1][0].numel(), ref_logits, self.ref_snap[1], self.fresh)
+            self._refill(ref, ref_logits, ref=True)
             ops.blend_logits(logits, ref_logits, s.n_token, plan.alpha, key=self.song, out=logits)
         _prefer_token(plan, logits, s.n_token, seen=self.seen, key=self.song, bar=self.bar)
         _draw_token(plan, logits, s.n_token, tok, self.seed, key=self.song, step=self.pos, bar=self.bar, beat=self.beat,
@@ -1111,34 +1119,36 @@ class _ParticleStreamLoop(_StreamLoop):
         return self._host[h].numpy().copy()
 
 
-class _BankStreamLoop(_StreamLoop):
-    """The stream with a prompt of its own for every song.  Song k starts from entry k % bank of a device bank laid out
-    like a `bank`-slot DecodeSession._state (per layer the S rows of all entries, then their Z rows), with its next-token
-    logits, bar count and cap beside it.  Blocks of B consecutive songs are prefilled (CWTrunk._prefill_gemm, batch
-    invariant) straight into their entries between chunks, on the stream's own stream, each followed by a device write
-    of ctl[3] = songs ready, the counter this form adds.  cwlt_stream_refill_bank and cwlt_stream_advance_bank: a slot
-    takes a song only below ctl[3], otherwise it waits (song -2), and keeps its song's cap in `cap`."""
+class _PromptBank:
+    """What the two streams with a prompt of its own for every song share (mixed in ahead of their _StreamLoop): the
+    device bank.  Song k starts from entry k % bank of a bank laid out like a `bank`-slot DecodeSession._state (per
+    layer the S rows of all entries, then their Z rows), with its next-token logits beside it.  Blocks of B consecutive
+    songs are prefilled (CWTrunk._prefill_gemm, batch invariant) straight into their entries between chunks, on the
+    stream's own stream, each followed by a device write of ctl[3] = songs ready, the counter these forms add; a block
+    is written only once the reuse rule (bank_may_prefill) allows it.  ref (a DecodeSession, the blend's reference):
+    a second bank, `ref_bank`, prefilled by the reference model in the same block step."""
 
     n_ctl = 4
 
-    def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, prefill_rows=None,
-                 **kw):
-        super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
-        dev = sess.dev
-        self.cap = torch.ones(self.S, dtype=torch.int64, device=dev)
+    def _bank_buffers(self, sess):
+        """(state, per-layer [S, Z] views, logits) of a bank for `sess`'s model."""
+        H, d = sess.memory[0][1].shape[1:]
+        sf, zf, n_layer = sess.memory[0][0][0].numel(), sess.memory[0][1][0].numel(), len(sess.memory)
+        per = self.bank * (sf + zf)
+        state = torch.zeros(per * n_layer, dtype=torch.float32, device=sess.dev)
+        mem = [[state[i * per:i * per + self.bank * sf].view(self.bank, H, d, d),
+                state[i * per + self.bank * sf:(i + 1) * per].view(self.bank, H, d)] for i in range(n_layer)]
+        return state, mem, torch.zeros((self.bank, sess.width), dtype=torch.float32, device=sess.dev)
+
+    def _init_bank(self, heads, bar0s, caps, B, bank, prefill_rows=None, ref=None):
+        """heads, bar0s, caps: one entry per song."""
+        sess, dev = self.sess, self.sess.dev
         self.song_cap = int(max(caps))
         self.B, self.bank = int(B), int(bank)
         self.nb = self.bank // self.B
         self.n_blocks = -(-self.n_songs // self.B)
-        H, d = sess.memory[0][1].shape[1:]
-        per = self.bank * (self.s_floats + self.z_floats)
-        self.bank_state = torch.zeros(per * self.n_layer, dtype=torch.float32, device=dev)
-        self.bank_mem = [[self.bank_state[i * per:i * per + self.bank * self.s_floats].view(self.bank, H, d, d),
-                          self.bank_state[i * per + self.bank * self.s_floats:(i + 1) * per].view(self.bank, H, d)]
-                         for i in range(self.n_layer)]
-        self.bank_logits = torch.zeros((self.bank, sess.width), dtype=torch.float32, device=dev)
-        self.bank_bar0 = torch.zeros(self.bank, dtype=torch.int64, device=dev)
-        self.bank_cap = torch.ones(self.bank, dtype=torch.int64, device=dev)
+        self.bank_state, self.bank_mem, self.bank_logits = self._bank_buffers(sess)
+        self.ref_bank = None if ref is None else (ref.model,) + self._bank_buffers(ref)
         # every prompt on the device once, padded to the longest: no host copy (and no sync) inside the stream
         lens = np.array([len(h) for h in heads], dtype=np.int64)
         self.lens = lens
@@ -1154,6 +1164,20 @@ class _BankStreamLoop(_StreamLoop):
         self.prefill_events = []                                   # (start, stop) CUDA events of every block
         self.gated_chunks = 0                                      # chunks that ended with every ready song assigned
 
+    def _prefill_into(self, model, bank_mem, bank_logits, a, z, e0, e1):
+        """Songs [a, z) through `model`'s batch-invariant prefill into the entries [e0, e1) of one bank."""
+        mem = [[S[e0:e1], Z[e0:e1]] for S, Z in bank_mem]
+        for S, Z in mem:
+            S.zero_()
+            Z.zero_()
+        P = int(self.lens[a:z].max())
+        dl = self.dev_len[a:z]
+        _, logits = model._prefill_gemm(self.toks[a:z, :P].contiguous(), mem, dl, dl.to(torch.int64) - 1)
+        bank_logits[e0:e1].copy_(logits)
+
+    def _block_written(self, a, z, e0, e1):
+        """What a form writes beside a block's entries, ahead of the ready counter (nothing here)."""
+
     def _prefill_block(self):
         """Enqueue block next_block's prefill into its bank entries, then ctl[3] = its last song + 1."""
         j = self.next_block
@@ -1162,17 +1186,11 @@ class _BankStreamLoop(_StreamLoop):
         e1 = e0 + (z - a)
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-        mem = [[S[e0:e1], Z[e0:e1]] for S, Z in self.bank_mem]
         with torch.no_grad():
-            for S, Z in mem:
-                S.zero_()
-                Z.zero_()
-            P = int(self.lens[a:z].max())
-            dl = self.dev_len[a:z]
-            _, logits = self.sess.model._prefill_gemm(self.toks[a:z, :P].contiguous(), mem, dl, dl.to(torch.int64) - 1)
-            self.bank_logits[e0:e1].copy_(logits)
-            self.bank_bar0[e0:e1].copy_(self.bar0_all[a:z])
-            self.bank_cap[e0:e1].copy_(self.cap_all[a:z])
+            self._prefill_into(self.sess.model, self.bank_mem, self.bank_logits, a, z, e0, e1)
+            if self.ref_bank is not None:
+                self._prefill_into(self.ref_bank[0], self.ref_bank[2], self.ref_bank[3], a, z, e0, e1)
+            self._block_written(a, z, e0, e1)
             self.ctl[3:4].fill_(z)                                 # ordered after the block's writes: same stream
         ev[1].record()
         self.prefill_events.append(ev)
@@ -1182,6 +1200,38 @@ class _BankStreamLoop(_StreamLoop):
         """Prefill every block the reuse rule allows (bank_may_prefill) given the copied assigned counter."""
         while self.next_block < self.n_blocks and bank_may_prefill(self.next_block, self.B, self.bank, assigned):
             self._prefill_block()
+
+    def _between_chunks(self, ctl, limit):
+        """A chunk that ended with every ready song assigned counts as gated (slots may have waited for a prefill: a
+        chunk more for the step limit); after the limit's check, prefill every block the reuse rule allows."""
+        if ctl[1] < self.n_songs and ctl[1] >= ctl[3]:
+            self.gated_chunks += 1
+        super()._between_chunks(ctl, limit + self.gated_chunks * self.chunk)
+        self._prefill_allowed(int(ctl[1]))
+
+    def stats(self):
+        """After run(): the block size, bank entries, GPU seconds of the block prefills, blocks, gated chunks."""
+        return {"block": self.B, "bank": self.bank,
+                "prefill_seconds": sum(a.elapsed_time(b) for a, b in self.prefill_events) / 1e3,
+                "prefill_blocks": self.next_block, "gated_chunks": self.gated_chunks}
+
+
+class _BankStreamLoop(_PromptBank, _StreamLoop):
+    """The stream with a prompt of its own for every song (_PromptBank), each entry with its song's bar count and cap
+    beside it.  cwlt_stream_refill_bank and cwlt_stream_advance_bank: a slot takes a song only below ctl[3], otherwise
+    it waits (song -2), and keeps its song's cap in `cap`."""
+
+    def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, prefill_rows=None,
+                 **kw):
+        super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
+        self.cap = torch.ones(self.S, dtype=torch.int64, device=sess.dev)
+        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows)
+        self.bank_bar0 = torch.zeros(self.bank, dtype=torch.int64, device=sess.dev)
+        self.bank_cap = torch.ones(self.bank, dtype=torch.int64, device=sess.dev)
+
+    def _block_written(self, a, z, e0, e1):
+        self.bank_bar0[e0:e1].copy_(self.bar0_all[a:z])
+        self.bank_cap[e0:e1].copy_(self.cap_all[a:z])
 
     def start(self):
         """Prefill the first nb blocks and hand the ready songs to slots 0, 1, ... in order; slots past them wait while
@@ -1201,19 +1251,39 @@ class _BankStreamLoop(_StreamLoop):
         ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
                                 self.song, self.pos, self.bar, self.cap, self.fresh, self.ctl, self.ring)
 
-    def _between_chunks(self, ctl, limit):
-        """A chunk that ended with every ready song assigned counts as gated (slots may have waited for a prefill: a
-        chunk more for the step limit); after the limit's check, prefill every block the reuse rule allows."""
-        if ctl[1] < self.n_songs and ctl[1] >= ctl[3]:
-            self.gated_chunks += 1
-        super()._between_chunks(ctl, limit + self.gated_chunks * self.chunk)
-        self._prefill_allowed(int(ctl[1]))
 
-    def stats(self):
-        """After run(): the block size, bank entries, GPU seconds of the block prefills, blocks, gated chunks."""
-        return {"block": self.B, "bank": self.bank,
-                "prefill_seconds": sum(a.elapsed_time(b) for a, b in self.prefill_events) / 1e3,
-                "prefill_blocks": self.next_block, "gated_chunks": self.gated_chunks}
+class _ParticleBankStreamLoop(_PromptBank, _ParticleStreamLoop):
+    """The particle stream with a prompt of its own for every song: _ParticleStreamLoop on _PromptBank's
+    bank, one entry -- one prefill -- per song for all its K particles.  Per token cwlt_particle_refill_bank in the
+    place of cwlt_stream_refill (a second one from `ref_bank` for the blend's reference, as the snapshot form does with
+    ref_snap); per hand-out boundary cwlt_particle_release_bank in the place of cwlt_particle_release: a group takes a
+    song only below ctl[3], else it is parked until the next boundary, and its rows start from the song's own bar count
+    and cap (bar0_all, cap_all: tables of n_songs entries, not bank-sized, so no reuse hazard arises).
+    The reuse rule carries over from _BankStreamLoop: a song assigned by a release at the end of chunk k is copied out
+    by the refill of the first token of chunk k + 1, and that token is already on the stream when the host reads chunk
+    k's counters and enqueues the next block's prefill behind it."""
+
+    def __init__(self, sess, heads, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0s, caps, B, bank,
+                 chunk, prefill_rows=None, **kw):
+        super().__init__(sess, None, None, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0s[0],
+                         max(caps), chunk, **kw)                 # cap0, the step limit's: the largest cap
+        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows, ref=self.plan.ref)
+
+    def _hand_out_songs(self):
+        ops.particle_release_bank(self.K, self.n_songs, self.bar0_all, self.cap_all, self.gsong, self.song, self.pos,
+                                  self.bar, self.cap, self.len, self.done, self.fresh, self.lw, self.log_z, self.ctl,
+                                  self.out_lw, self.out_len, self.out_logz)
+
+    def start(self):
+        """Prefill the first nb blocks; then the first release hands the ready songs out in group order."""
+        self.ctl.zero_()
+        self._prefill_allowed(0)
+        self._release()
+
+    def _refill(self, sess, logits, ref=False):
+        state, blogits = (self.ref_bank[1], self.ref_bank[3]) if ref else (self.bank_state, self.bank_logits)
+        ops.particle_refill_bank(sess._state, state, len(sess.memory), sess.memory[0][0][0].numel(),
+                                 sess.memory[0][1][0].numel(), logits, blogits, self.fresh, self.song, self.K)
 
 
 def _stream_snapshot(model, prompt, A, kernel="blas"):
@@ -1811,13 +1881,33 @@ def _particle_setup(where, model, word2event, n_songs, particles, resample_every
                         preferences=_repeat_per_song(preferences, n, K))
 
 
+def _shared_prefill(sess, toks, lengths, K):
+    """The lock-step pool's prefill, once a song: row g K of toks (N, P, A) -- every song's K rows hold
+    the same prompt -- goes through the batch-invariant prefill on a scratch session of N / K songs, whose state is a
+    bank of N / K entries, and cwlt_particle_refill_bank broadcasts entry g to rows g K .. g K + K - 1 of `sess` (ids
+    arange(N), every row fresh) -> (N, width) logits, bitwise sess._prefill(toks, lengths, "gemm")'s, as is the state."""
+    N = sess.n_songs
+    scratch = DecodeSession(sess.model, n_songs=N // K, kernel="gemm", graph=False)
+    scratch.reset()
+    bank_logits = scratch._prefill(toks[::K], None if lengths is None else lengths[::K], kernel="gemm")
+    logits = torch.empty((N, sess.width), dtype=torch.float32, device=sess.dev)
+    ops.particle_refill_bank(sess._state, scratch._state, len(sess.memory), sess.memory[0][0][0].numel(),
+                             sess.memory[0][1][0].numel(), logits, bank_logits,
+                             torch.ones(N, dtype=torch.int64, device=sess.dev),
+                             torch.arange(N, dtype=torch.int64, device=sess.dev), K)
+    sess.n_steps += scratch.n_steps
+    return logits
+
+
 def _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, chunk, log, prefill,
-                   stats=None, reward=None):
+                   stats=None, reward=None, share_prefill=False):
     """generate_particles after its refusals: the rows of `plan` (particles consecutive rows per song) -> ParticleSets.
     stats (a dict, optional): filled with steps, events, seconds, the rows every event moved and what one moved row
     copies per phase; a stats that comes with {"timed": True} also gets the HIP-event times of every event's resampling
     and two gather phases (and of every reward event's window kernel, callable and apply kernel).
-    reward: a _reward_spec; a run that ends inside a window closes it with one partial reward event."""
+    reward: a _reward_spec; a run that ends inside a window closes it with one partial reward event.
+    share_prefill: every song's K rows hold one prompt and prefill is "gemm": prefill it once (_shared_prefill);
+    stats' prefilled_prompts is then the songs, not the rows."""
     N, K, R, A = plan.n_songs, int(particles), int(resample_every), len(word2event)
     cap = max(caps)
     start = time.perf_counter()
@@ -1835,8 +1925,12 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
         for i, p in enumerate(heads):
             toks[i, :len(p)] = p
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
-        loop.start(sess._prefill(toks, lengths, kernel=prefill),
-                   None if ref is None else ref._prefill(toks, lengths, kernel=prefill))
+        if share_prefill:
+            loop.start(_shared_prefill(sess, toks, lengths, K),
+                       None if ref is None else _shared_prefill(ref, toks, lengths, K))
+        else:
+            loop.start(sess._prefill(toks, lengths, kernel=prefill),
+                       None if ref is None else ref._prefill(toks, lengths, kernel=prefill))
     rows, lps = [], []
     done = 0
     while done < cap:
@@ -1895,6 +1989,7 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
         stats.update(steps=done, events=E, seconds=time.perf_counter() - start, graph=loop._graph is not None,
                      drawn=int(lens.sum()), row_bytes=loop.row_bytes, moved_rows=[int(m) for m in moved],
                      resampled_groups=[int(r.sum()) for r in h_res], groups=N // K,
+                     prefilled_prompts=0 if prefill is None else N // K if share_prefill else N,
                      event_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)] for m in loop.timed or []])
         if W is not None:
             stats.update(reward_events=loop.n_rewards, reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
@@ -1908,7 +2003,9 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
     rows (T, N, A + 2) int64, the ring rows of T steps: per pool row {particle id or -1, the A tokens, done}; logps
     (T, N, A, 2) f32 beside them; the run's events e = 0, 1, ..., event e after step (e + 1) R: h_anc (E, N) int64 pool-row
     ancestors, h_lw (E, N) f32, h_ess (E, G) f32, h_res (E, G) int32; what the release wrote: out_lw, out_len (n_songs K,)
-    by particle id and out_logz (n_songs,).  K = particles, R = every, head: the (P, A) rows every song starts with.
+    by particle id and out_logz (n_songs,).  K = particles, R = every, head: the (P, A) rows every song starts with, or
+     a list of n_songs arrays, each song's own; stats then also gains gate_wait_group_steps, the steps
+    groups spent without a song while songs were still unassigned (the bank's gate), kept out of idle_group_steps.
     The song of group g at step t is rows[t, g K, 0] // K; it held the group over the steps [t0, t1) that show it, t0 a
     multiple of R, and its own events j = 0, 1, ... are the run's events t0 / R + j, (t1 - t0) // R of them.  Lineage:
     particle_lineage on the in-group ancestors of those events; row tau of final particle k was drawn by pool row
@@ -1935,7 +2032,11 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
     ids = rows[:, ::K, 0]
     gsong = np.where(ids >= 0, ids // K, -1)
     out, starts = [None] * int(n_songs), [None] * int(n_songs)
+    per_song = isinstance(head, (list, tuple))
+    if per_song and len(head) != int(n_songs):
+        raise ValueError("head: %d arrays for %d songs" % (len(head), int(n_songs)))
     wait = idle = 0
+    parked = []                                                          # the stretches groups spent without a song
     for g in range(G):
         col = gsong[:, g]
         cuts = np.nonzero(np.diff(col, prepend=np.int64(-2)))[0]
@@ -1943,6 +2044,7 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
             s = int(col[t0])
             if s < 0:
                 idle += int(t1 - t0)
+                parked.append((int(t0), int(t1)))
                 continue
             if t0 % B or out[s] is not None:
                 raise RuntimeError("particle stream output is inconsistent: song %d starts at step %d (every %d)%s"
@@ -1961,7 +2063,7 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
             for k in range(K):
                 tau = np.arange(int(lens[k]))
                 src = g * K + line[np.minimum(tau // R, E), k]
-                songs.append(np.concatenate([head, rows[t0 + tau, src, 1:1 + A]]))
+                songs.append(np.concatenate([head[s] if per_song else head, rows[t0 + tau, src, 1:1 + A]]))
                 lps.append(np.asarray(logps[t0 + tau, src], dtype=np.float32).reshape(-1, A, 2))
             w = np.asarray(out_lw[s * K:(s + 1) * K], dtype=np.float32).copy()
             hit = np.nonzero(h_res[span, g])[0]
@@ -1989,16 +2091,45 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
     if missing:
         raise RuntimeError("particle stream output is inconsistent: no rows of songs %s" % missing[:8])
     if stats is not None:
+        if per_song:        # parked while songs were still unassigned: the bank's gate, not the idle tail
+            last = max(starts)
+            gate = sum(max(0, min(t1, last) - t0) for t0, t1 in parked)
+            idle -= gate
+            stats.update(gate_wait_group_steps=gate)
         stats.update(wait_group_steps=wait, idle_group_steps=idle, start_steps=starts)
         if W is not None:
             stats.update(boundary_wait_group_steps=beyond)
     return out
 
 
-def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window=50):
+def _bank_choice(bank):
+    """bank= of the particle entries -> None for "auto" (stream_bank_plan's choice), else the int."""
+    if isinstance(bank, str):
+        if bank != "auto":
+            raise ValueError("bank must be \"auto\" or a number of entries, got %r" % (bank,))
+        return None
+    return int(bank)
+
+
+def _particle_bank_refusals(n_songs, slots, prompts, bank, prefill_rows, word2event, bar_cond, max_tokens):
+    """What bank= / prefill_rows= of the particle entries refuse, before the model is looked at: either of them without
+    slots= and a prompt list; then, in the bank form, what _check_prompts and stream_bank_plan refuse.  -> whether the
+    run is the bank form (slots=, a prompt list and bank=)."""
+    listed = isinstance(prompts, (list, tuple))
+    if (bank is not None or prefill_rows is not None) and (slots is None or not listed):
+        raise ValueError("bank and prefill_rows belong to slots= with per-song prompts (prompts=[...])")
+    if bank is None or not listed:
+        return False
+    heads = _check_prompts(prompts, int(n_songs), word2event, None, bar_cond, max_tokens)[0]
+    stream_bank_plan([len(h) for h in heads], max(1, min(int(slots), int(n_songs))), prefill_rows, _bank_choice(bank))
+    return True
+
+
+def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window=50,
+                              bank=None):
     """What generate_particles(slots=) refuses ahead of the lock-step path's own refusals.  Under a reward (DESIGN
     §4.6p) a group takes a song only at multiples of B = lcm(resample_every, reward_window) steps, and a chunk holds
-    whole stretches of B."""
+    whole stretches of B.  bank: the opt-in to per-song prompt lists."""
     if reward is not None and int(resample_every) >= 1 and int(reward_window) >= 1 and int(chunk) >= 1:
         B = _lcm(resample_every, reward_window)
         if int(chunk) % B:
@@ -2010,9 +2141,10 @@ def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, 
                              "resample_every = 10 or 25 with reward_window = 50 and chunk = 100 (generate's chunk is "
                              "128: resample_every = 16 with reward_window = 32); or run the lock-step pool (slots=None)"
                              % (int(chunk), int(resample_every), int(reward_window), B, B))
-    if isinstance(prompts, (list, tuple)):
+    if isinstance(prompts, (list, tuple)) and bank is None:
         raise ValueError("slots= takes one shared (P, 6) prompt, prefilled once for all songs: per-song prompt lists "
-                         "would need a prompt bank (generate_particles without slots takes them)")
+                         "would need a prompt bank (generate_particles without slots takes them); bank=\"auto\" opts "
+                         "into that bank")
     if int(slots) < 1:
         raise ValueError("slots must be >= 1, got %r" % (slots,))
     K = int(particles)
@@ -2027,11 +2159,14 @@ def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, 
 
 
 def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particles, slots, resample_every, ess, bar_cond,
-                         chunk, log, prompt, stats=None, reward=None):
+                         chunk, log, prompt, stats=None, reward=None, bank=None, prefill_rows=None):
     """generate_particles(slots=) after its refusals: the rows of `plan` (particles consecutive rows per song), S =
     min(slots, n_songs) songs in flight -> n_songs ParticleSets.  stats (a dict, optional): steps, events, seconds (all
     of it) and run_seconds (up to the last chunk read, before the host rebuilds the sets), graph, drawn, the pool rows
     every event moved, the group-steps spent waiting for a boundary and idle at the tail.
+    bank ("auto" or an int; None: the songs share `prompt`) and prefill_rows: every song continues its
+    own heads[s K] from a device bank of prefilled prompts, one entry per song (stream_bank_plan with slots = groups);
+    stats then also gets _PromptBank.stats and the group-steps parked by the bank's gate.
     reward: a _reward_spec; stats then also gets reward_events and the group-steps waited for a multiple
     of lcm(R, W) beyond the next multiple of R, and a stats that comes with {"timed": True} the HIP-event milliseconds
     of every reward event's window kernel, callable and apply kernel (reward_ms, as _run_particles')."""
@@ -2043,11 +2178,21 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
     seed = ops.next_seed()                                    # where _generate_stream and _DeviceLoop take it
     bar_mask = plan.bar_mask if plan.bar_mask is not None else plan._bar_classes()
     draw = DeviceDraw(plan, sess.dev, sess.shadow(plan.reference))
-    snap = _stream_snapshot(model, prompt, A, "gemm")
-    ref_snap = None if plan.reference is None else _stream_snapshot(plan.reference, prompt, A, "gemm")
-    loop = _ParticleStreamLoop(sess, snap, ref_snap, n_songs, K, R, ess, seed, bar_mask, bar_cond, plan.bar0s[0],
-                               caps[0], chunk, reward=reward, timed=bool(stats and stats.get("timed")), plan=draw,
-                               graph=sess.use_graph)
+    kw = dict(reward=reward, timed=bool(stats and stats.get("timed")), plan=draw, graph=sess.use_graph)
+    if bank is not None:
+        song_heads = heads[::K]
+        per_entry = 4 * (sess._state.numel() // (S * K) + sess.width) * (1 if plan.reference is None else 2)
+        B, entries = stream_bank_plan([len(h) for h in song_heads], S, prefill_rows, _bank_choice(bank), per_entry,
+                                      torch.cuda.mem_get_info(sess.dev)[0])
+        loop = _ParticleBankStreamLoop(sess, song_heads, n_songs, K, R, ess, seed, bar_mask, bar_cond,
+                                       list(plan.bar0s[::K]), caps[::K], B, entries, chunk, prefill_rows=prefill_rows,
+                                       **kw)
+    else:
+        song_heads = heads[0]
+        snap = _stream_snapshot(model, prompt, A, "gemm")
+        ref_snap = None if plan.reference is None else _stream_snapshot(plan.reference, prompt, A, "gemm")
+        loop = _ParticleStreamLoop(sess, snap, ref_snap, n_songs, K, R, ess, seed, bar_mask, bar_cond, plan.bar0s[0],
+                                   caps[0], chunk, **kw)
     rows = loop.run()
     ran = time.perf_counter()
     lps = np.concatenate(loop.lp_parts)
@@ -2055,7 +2200,7 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
     more = {}
     h_r = None if reward is None else np.concatenate(loop.r_parts)
     sets = particle_stream_sets(rows, lps, h_anc, h_lw, h_ess, h_res, loop.out_lw.cpu().numpy(),
-                                loop.out_len.cpu().numpy(), loop.out_logz.cpu().numpy(), K, R, n_songs, heads[0], more,
+                                loop.out_len.cpu().numpy(), loop.out_logz.cpu().numpy(), K, R, n_songs, song_heads, more,
                                 h_r=h_r, window=None if reward is None else reward[1])
     if reward is not None:
         for s, ps in enumerate(sets):
@@ -2070,6 +2215,8 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
                      graph=loop._graph is not None, drawn=int(loop.out_len.sum().item()), row_bytes=loop.row_bytes,
                      moved_rows=[int(m) for m in moved], groups=S, wait_seconds=loop.wait_s,
                      run_seconds=ran - start, **more)
+        if bank is not None:
+            stats.update(loop.stats())
         if reward is not None:
             stats.update(reward_events=len(h_r),
                          reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
@@ -2080,7 +2227,7 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
 def generate_particles(model, word2event, n_songs, particles, resample_every=16, ess=0.5, bar_cond=17, max_tokens=None,
                        prompts=None, sampler="dqn", chunk=128, log=None, prefill="blas", constraints=None,
                        grammar=None, reference=None, alpha=None, preferences=None, reward=None, reward_window=50,
-                       beta=1.0, slots=None):
+                       beta=1.0, slots=None, bank=None, prefill_rows=None, share_prefill=None):
     """Generate `n_songs` songs with `particles` = K weighted particles each, by sequential Monte Carlo with the device
     sampler as the proposal.  -> list of n_songs ParticleSet.
 
@@ -2107,10 +2254,14 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
 
     ess=0 never resamples: the run is generate_batch(n_songs x K, ..., return_logprobs=True) with every per-song entry
     repeated K times, bit for bit, plus the weights.  prompts, constraints, preferences (one for all, or a list of
-    n_songs), alpha, grammar, reference, sampler, bar_cond, max_tokens, chunk, prefill: as in generate_batch.  Each
-    prompt is prefilled K times: sharing one prefill among a song's particles is left out.  Draws are keyed by (torch
-    seed, step, row) and the resampling draw by (seed, event, song), so song g's set is the same whatever the other
-    songs.
+    n_songs), alpha, grammar, reference, sampler, bar_cond, max_tokens, chunk, prefill: as in generate_batch.  Draws
+    are keyed by (torch seed, step, row) and the resampling draw by (seed, event, song), so song g's set is the same
+    whatever the other songs.
+    share_prefill, for a list of per-song prompts: None (the default) shares one prefill among a song's K
+    particles exactly when prefill="gemm" -- each prompt is prefilled once into a scratch bank of n_songs entries (a
+    second one for a reference) and cwlt_particle_refill_bank broadcasts every entry to its song's K rows; the gemm
+    prefill is batch invariant, so the sets are bitwise those of the K-fold prefill.  False: every row is prefilled, K
+    times a prompt.  True with prefill="blas" is refused: that prefill is not batch invariant.
 
     slots=S (None, the default: the lock-step pool above, unchanged): the particle stream.  S songs are in
     flight on S K rows of one session and n_songs may be far larger than S: a group of K consecutive rows takes the next
@@ -2121,11 +2272,22 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     (cwlt_particle_resample_keyed).  A song's ParticleSet is therefore bit for bit the one the lock-step pool makes after
     the same torch.manual_seed, whatever `slots` and whatever the other songs.  Starts: from scratch, or from ONE shared
     (P, 6) `prompts` array, prefilled once -- not n_songs K times -- by the batch-invariant prefill (the lock-step twin
-    is prefill="gemm"; `prefill` itself is not used); a list of per-song prompts is refused (the bank form of
-    generate_stream is left out here).  constraints, grammar, preferences, reference / alpha as above.  Refused with
-    slots: per-song prompt lists, slots < 1, slots x particles > 4096, n_songs x particles > 2**20 (the sampler's key
+    is prefill="gemm"; `prefill` itself is not used); a list of per-song prompts is refused unless bank= opts into the
+    prompt bank (below).  constraints, grammar, preferences, reference / alpha as above.  Refused with slots: per-song
+    prompt lists without bank=, slots < 1, slots x particles > 4096, n_songs x particles > 2**20 (the sampler's key
     layout), a chunk that is no multiple of resample_every (a chunk's ring half holds whole event segments) and, with a
     reward, a chunk that is no multiple of lcm(resample_every, reward_window) (below).
+
+    slots=S with prompts=[...] and bank=: song s continues prompts[s].  bank="auto" (stream_bank_plan's
+    choice, with slots = the groups in flight) or a number of entries; prefill_rows: the token-row budget of one prefill
+    block.  Each prompt is prefilled ONCE, by the batch-invariant prefill, into entry s % bank of a device bank (a
+    second bank for a reference), in blocks between chunks as in generate_stream(prompts=[...]); a group takes song s
+    only once its entry is written (cwlt_particle_release_bank: it is parked until the next boundary otherwise), starts
+    from the song's own bar count and cap, and its K rows are filled from the one entry (cwlt_particle_refill_bank).  A
+    song's ParticleSet -- rewards, event_rewards and beta included -- is bit for bit the lock-step pool's with
+    prefill="gemm" after the same torch.manual_seed, whatever slots, bank, prefill_rows and the other songs.  bank or
+    prefill_rows without slots= and a prompt list are refused, and what stream_bank_plan and the prompts' own checks
+    refuse, before the model is looked at.
 
     reward, reward_window = W, beta: reward terms in the weights.  Each particle's drawn rows (not its
     prompt) are cut into consecutive windows of W rows, the last one possibly partial; after the last row of each
@@ -2156,19 +2318,27 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit), resample_every < 1, ess outside [0, 1], then
     everything generate_batch refuses."""
     spec = _reward_spec(reward, reward_window, beta, n_songs)
+    if share_prefill and prefill != "gemm":
+        raise ValueError("share_prefill=True needs prefill=\"gemm\": the %r prefill is not batch invariant, so one "
+                         "prefill a song would not give the bits of one a particle" % (prefill,))
     if slots is not None:
-        _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window)
+        _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window,
+                                  bank=bank)
+    banked = _particle_bank_refusals(n_songs, slots, prompts, bank, prefill_rows, word2event, bar_cond, max_tokens)
+    if slots is not None:
         heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                             ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                             grammar, reference, alpha, preferences,
                                             pool=min(int(slots), max(int(n_songs), 1)))
         return _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
-                                    ess, bar_cond, int(chunk), log, None if prompts is None else heads[0], reward=spec)
+                                    ess, bar_cond, int(chunk), log, None if prompts is None else heads[0], reward=spec,
+                                    bank=bank if banked else None, prefill_rows=prefill_rows)
     heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                         ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                         grammar, reference, alpha, preferences)
+    share = isinstance(prompts, (list, tuple)) and prefill == "gemm" and (share_prefill is None or bool(share_prefill))
     return _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, int(chunk),
-                          log, None if prompts is None else prefill, reward=spec)
+                          log, None if prompts is None else prefill, reward=spec, share_prefill=share)
 
 
 SCORE_BLOCK_SONGS = 1024    # most songs in one score_songs block: bounds its scratch decode state (1.6 MB a song at repo dims)
@@ -2379,7 +2549,7 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
              max_tokens=None, stats_path="runtime_stats.json", log=print, device_sampling=False, prompt=None,
              batch_size=None, slots=None, prompts=None, constraints=None, logprobs=False, grammar=None,
              reference=None, alpha=None, preferences=None, particles=None, resample_every=16, ess=0.5, reward=None,
-             reward_window=50, beta=1.0):
+             reward_window=50, beta=1.0, bank=None):
     """testing-no-type-cp.py:182-223 / agent_pretrain.py:663-706: generate `n_songs`, time them, write
     runtime_stats.json with the reference's keys.  `write_midi(res, path, word2event)` is the caller's MIDI writer
     (miditoolkit-based in the reference; out of scope here) -- when None the token array is saved as .npy.
@@ -2399,6 +2569,8 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     particles=K with slots=S: the songs are made by generate_particles(slots=S), the particle stream --
     S songs in flight, a group of K rows taking the next song when its particles have ended -- from scratch or from the
     one shared `prompt`, and each song kept is ParticleSet.draw as above; resample_every must divide 128, the chunk.
+    bank ("auto" or a number of entries) with particles, slots and `prompts`: song i continues prompts[i]
+    on the particle stream, from generate_particles' prompt bank; a prompt list without bank= is refused there.
     reward, reward_window, beta (with particles and batch_size or slots; generate_particles'): window
     rewards in the particles' weights; beta one float or a list of n_songs, cut per batch_size group.  With slots the
     chunk of 128 must be a multiple of lcm(resample_every, reward_window): for example resample_every = 16 with
@@ -2412,10 +2584,17 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
     if particles is not None and batch_size is None and slots is None:
         raise ValueError("particles run in generate_particles' lock-step pool or its stream: pass batch_size or slots "
                          "(the songs of one pool, or the songs in flight)")
+    if bank is not None and (particles is None or slots is None or prompts is None):
+        raise ValueError("bank belongs to slots= with particles= and per-song prompts (prompts=[...])")
     if particles is not None and slots is not None:
-        if prompts is not None:
-            raise ValueError("slots= with particles= takes one shared prompt (prompt=), not per-song prompts")
+        if prompts is not None and bank is None:
+            raise ValueError("slots= with particles= takes one shared prompt (prompt=), not per-song prompts; "
+                             "bank=\"auto\" opts into the prompt bank")
         _particle_stream_refusals(n_songs, particles, slots, resample_every, 128, None, reward, reward_window)
+        if prompts is not None:
+            if prompt is not None:
+                raise ValueError("pass one shared prompt or per-song prompts, not both")
+            _particle_bank_refusals(n_songs, slots, list(prompts), bank, None, word2event, bar_cond, max_tokens)
     if (reference is not None or alpha is not None) and batch_size is None and slots is None:
         raise ValueError("the blend with a reference model runs in the device loops of generate_batch / generate_stream: "
                          "pass batch_size or slots (one song: generate_batch(n_songs=1, reference=..., alpha=...))")
@@ -2466,11 +2645,13 @@ def generate(model, word2event, n_songs=1, bar_cond=17, path_gendir="./gen_midis
 
     if slots is not None and particles is not None:
         start = time.time()
+        given = prompt if prompts is None else list(prompts)
         heads, caps, plan = _particle_setup("generate", model, word2event, n_songs, particles, resample_every, ess,
-                                            bar_cond, max_tokens, prompt, "dqn", 128, "blas", constraints, grammar,
+                                            bar_cond, max_tokens, given, "dqn", 128, "blas", constraints, grammar,
                                             reference, alpha, preferences, pool=min(int(slots), max(int(n_songs), 1)))
         sets = _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
-                                    ess, bar_cond, 128, None, None if prompt is None else heads[0], reward=spec)
+                                    ess, bar_cond, 128, None, None if given is None else heads[0], reward=spec,
+                                    bank=bank)
         rng = np.random.default_rng(ops.next_seed())             # after the run's seed, as the batch_size path
         picks = [s.draw(rng, return_index=True) for s in sets]
         songs = [p[0] for p in picks]

@@ -2178,6 +2178,56 @@ def particle_fill(dst, src, fresh, pid):
     return dst
 
 
+def particle_refill_bank(state, bank_state, n_layer, s_floats, z_floats, logits, bank_logits, fresh, pid, particles):
+    """The fresh rows of a particle pool take their song's bank entry (cwlt_particle_refill_bank): row n
+    with fresh[n] and pid[n] >= 0 gets entry (pid[n] // particles) % bank, each float4 of an entry loaded once for the
+    group's fresh rows.  state: flat f32 n_layer x [S (rows, s_floats), Z (rows, z_floats)]; bank_state the same for
+    `bank` entries; logits (rows, >= n) and bank_logits (bank, n) f32; fresh, pid (rows,) int64."""
+    fn, rows, per, K = "particle_refill_bank", fresh.numel(), s_floats + z_floats, int(particles)
+    bank = bank_logits.shape[0]
+    if state.dtype != torch.float32 or bank_state.dtype != torch.float32 or bank_logits.dtype != torch.float32 or \
+            logits.dtype != torch.float32:
+        raise TypeError("%s takes f32 state / logits" % fn)
+    _int64_rows(fn, rows, fresh=fresh, pid=pid)
+    if K < 1 or rows % K:
+        raise ValueError("%s: %d rows are no whole groups of %d particles" % (fn, rows, K))
+    if state.numel() != n_layer * rows * per or bank_state.numel() != n_layer * bank * per:
+        raise ValueError("%s: state holds %d floats, bank %d, for %d layers x %d rows / %d entries x %d"
+                         % (fn, state.numel(), bank_state.numel(), n_layer, rows, bank, per))
+    if logits.shape[0] != rows or logits.stride(-1) != 1 or bank_logits.stride(-1) != 1 or \
+            bank_logits.shape[1] > logits.shape[1]:
+        raise ValueError("%s: logits must be (rows, >= n_logits), bank_logits (bank, n_logits), unit column strides"
+                         % fn)
+    _call("cwlt_particle_refill_bank", _lib.dev(state, "state"), _lib.dev(bank_state, "bank_state"), bank, int(n_layer),
+          int(s_floats), int(z_floats), _lib.dev(logits, "logits"), _lib.dev(bank_logits, "bank_logits"),
+          bank_logits.shape[1], logits.stride(0), bank_logits.stride(0), _lib.dev(fresh, "fresh"), _lib.dev(pid, "pid"),
+          rows, K, _lib.stream_ptr())
+
+
+def particle_release_bank(particles, n_songs, bar0_all, cap_all, song, pid, pos, bar, cap, length, done, fresh, lw,
+                          log_z, ctl, out_lw, out_len, out_logz):
+    """particle_release gated by the songs the bank has ready, each song with its own start (cwlt_particle_release_bank,
+    DESIGN §4.6q; sampling.particle_release_bank restates the decision): songs are handed out only below
+    min(ctl[3], n_songs), a candidate past that is parked until the next boundary, and a row handed song v starts from
+    bar0_all[v] and cap_all[v] ((n_songs,) int64).  ctl (4,) int64 {tokens, assigned, finished, ready}."""
+    fn, K, groups = "particle_release_bank", int(particles), song.numel()
+    rows = groups * K
+    _int64_rows(fn, groups, song=song)
+    _int64_rows(fn, rows, pid=pid, pos=pos, bar=bar, cap=cap, length=length, done=done, fresh=fresh)
+    _int64_rows(fn, int(n_songs) * K, out_len=out_len)
+    _int64_rows(fn, int(n_songs), bar0_all=bar0_all, cap_all=cap_all)
+    for t, n in ((lw, rows), (log_z, groups), (out_lw, int(n_songs) * K), (out_logz, int(n_songs))):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("%s takes contiguous f32 lw (rows,), log_z (groups,), out_lw (n_songs * K,) and out_logz "
+                            "(n_songs,)" % fn)
+    if ctl.dtype != torch.int64 or not ctl.is_contiguous() or ctl.numel() < 4:
+        raise TypeError("%s: ctl must hold the int64 counters {tokens, assigned, finished, ready}" % fn)
+    _call("cwlt_particle_release_bank", groups, K, int(n_songs), _lib.dev(bar0_all), _lib.dev(cap_all), _lib.dev(song),
+          _lib.dev(pid), _lib.dev(pos), _lib.dev(bar), _lib.dev(cap), _lib.dev(length), _lib.dev(done), _lib.dev(fresh),
+          _lib.dev(lw), _lib.dev(log_z), _lib.dev(ctl), _lib.dev(out_lw), _lib.dev(out_len), _lib.dev(out_logz),
+          _lib.stream_ptr())
+
+
 def _reward_ring(where, recent, live):
     """(rows, W, A) of a reward ring: recent (rows, W, A) and live (rows, W), contiguous int64."""
     if recent.dtype != torch.int64 or live.dtype != torch.int64 or not recent.is_contiguous() or not live.is_contiguous():

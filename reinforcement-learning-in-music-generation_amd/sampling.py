@@ -344,6 +344,25 @@ def particle_release(song, done, particles, assigned, finished, n_songs):
     return take, released, min(int(assigned) + int(cand.sum()), int(n_songs)), int(finished) + int(released.sum())
 
 
+def particle_release_bank(song, done, particles, assigned, finished, ready, n_songs):
+    """Numpy restatement of cwlt_particle_release_bank's decision: particle_release under the gate of
+    the bank.  ready: the songs whose bank entries are written (ctl[3]).  With limit = min(ready, n_songs), candidate
+    number r takes song assigned + r only while that is < limit, else none (-1: parked, a candidate again at the next
+    boundary); finished groups are released whether or not they take a song; assigned becomes
+    min(assigned + candidates, max(limit, assigned)), so it never decreases.  -> particle_release's four values; with
+    ready >= n_songs they are particle_release's."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1)
+    K = int(particles)
+    all_done = (np.asarray(done).reshape(len(song), K) != 0).all(1)
+    cand = (song < 0) | all_done
+    released = (song >= 0) & all_done
+    limit = min(int(ready), int(n_songs))
+    idx = int(assigned) + np.cumsum(cand) - 1
+    take = np.where(cand, np.where(idx < limit, idx, -1), -2).astype(np.int64)
+    return (take, released, min(int(assigned) + int(cand.sum()), max(limit, int(assigned))),
+            int(finished) + int(released.sum()))
+
+
 def particle_event_keys(song, pos, every):
     """Numpy restatement of cwlt_particle_resample_keyed's bookkeeping: song (groups,) and the groups'
     clocks pos (groups,) -> (event (groups,) int64: the song's own event index pos // every - 1; skip (groups,) bool:
