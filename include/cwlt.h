@@ -832,6 +832,51 @@ int cwlt_reward_apply(const float* r, const int64_t* any, float beta, int64_t ro
 int cwlt_reward_apply_keyed(const float* r, const int64_t* any, const float* beta, int64_t n_beta, const int64_t* key,
                             int particles, int64_t rows, float* lw, float* h_r, void* stream);
 
+/* ---- song metrics and rule-based rewards (csrc/metrics.hip) ------------------------------------------------
+ * cwlt_song_metrics: F = 11 measures per song from its token rows, bit for bit sampling.song_metrics_f32.  One launch,
+ * no host synchronisation, no allocation, no cross-workgroup communication.  Every pointer is DEVICE memory.
+ *
+ * tok (N, L, n_attr) int64; mask (N, L) int64 or NULL (nonzero: live); lengths (N) int32 or NULL (rows at or past a
+ * song's length are not live).  order (n_order), pitch (n_pitch), chord (n_chord) int32: the tables of the classes of
+ * bar_attr, pitch_attr and chord_attr (chord_attr = -1: no chord feature, chord may be NULL).  order: -2 class 0,
+ * -1 Bar, k >= 0 Beat_k (k < Q <= 64); pitch: a MIDI pitch 0..127, or -1; chord: -1 keep the current chord, else a 12-bit
+ * mask of pitch classes (0: no chord).  xlog2x (n_table >= L + 1) f32: T[c] = float32(c log2 c), T[0] = T[1] = 0.
+ *
+ * A song is walked in row order from beat = -1, chord mask 0, slot 0.  A row that is not live is nothing.  A live row
+ * whose class in one of the (two or three) attributes lies outside its table only counts as a live row.  Otherwise, with
+ * o = order[class]: o == -1 opens the next bar slot and sets beat = -1; o >= 0 sets beat = o and, when chord[class] >= 0,
+ * the chord mask; o == -2 with pitch[class] in 0..127 is a note at (slot, beat, chord mask); anything else is nothing.
+ * Slot s >= 1 is the s-th Bar row's bar; slot 0 exists only if a live row precedes the first Bar row.  B is the number of
+ * existing slots, `first` the lowest (0 or 1).  A note in slot s >= max_bars is dropped from every output, and the
+ * per-slot measures run over the Bk existing slots below max_bars; bars[n] and n_bars report the true B.
+ * Per slot: hist[12] note counts per pitch class (pitch % 12), groove: bit k set when a note sits at beat k (0 <= k < 64;
+ * a note at beat -1 sets none), and the note count.
+ *
+ * ent(c) = (T[n] - (((0 + T[c_0]) + T[c_1]) + ... + T[c_11])) / (float)n with n = sum c, 0 for n = 0; every float
+ * operation here and below is rounded to f32 on its own (no fma), in the order written.  feat (N, 11) f32:
+ *   0 n_notes   1 n_bars = B
+ *   2 h1: over the kept slots in order, for each slot with notes sum += ent(hist), count += 1; sum / count, 0 without
+ *   3 h4: the same over every run of 4 consecutive kept slots (the run's histogram the integer sum; runs without notes
+ *     skipped)       4 h_all: ent of the integer sum of all kept slots
+ *   5 groove: P = Bk (Bk - 1) / 2, S = sum over kept i < j of popcount(g_i ^ g_j); 1 - (float)S / (float)(P Q), 0 for P = 0
+ *   6 in_chord: of the notes under a chord mask != 0, the share whose pitch class is in the mask; 0 without such notes
+ *   7 pitch_range: max - min pitch   8 distinct_pitches   9 notes_per_bar = n_notes / Bk   10 empty_bars = the share of
+ *     kept slots without notes (both 0 for Bk = 0).
+ * weights (11) f32 or NULL; reward (N) f32 or NULL: r = 0, then for f = 0..10 m = weights[f] * feat[f], r = r + m.
+ * bars (N) int32, hist (N, max_bars, 12) int32, groove (N, max_bars) int64 (indexed by slot, zero outside the kept
+ * slots), each or NULL.
+ *
+ * CWLT_ERR_ARG before any launch: a null tok / order / pitch / xlog2x / feat (chord with chord_attr >= 0), N < 1 or
+ * > 2^24, L < 1 or >= 2^24, n_attr outside 1..8, an attribute index outside n_attr (chord_attr below -1), an empty
+ * table, Q outside 1..64, max_bars outside 1..512, n_table < L + 1, reward without weights.
+ * Songs of at most 128 rows with max_bars <= 64 take a wave each, four to a workgroup; the others 256 threads each. */
+#define CWLT_SONG_METRICS 11
+int cwlt_song_metrics(const int64_t* tok, const int64_t* mask, const int32_t* lengths, int64_t N, int64_t L, int n_attr,
+                      int bar_attr, int pitch_attr, int chord_attr, const int32_t* order, int n_order,
+                      const int32_t* pitch, int n_pitch, const int32_t* chord, int n_chord, int Q, const float* xlog2x,
+                      int64_t n_table, int max_bars, float* feat, const float* weights, float* reward, int32_t* bars,
+                      int32_t* hist, int64_t* groove, void* stream);
+
 /* ---- the dense projections at few token rows, and a whole encoder layer per host call ---------------------------------
  * The reference's own RL setting is 30 windows x 50 tokens = 1 500 token rows per network pass
  * (dqn_policy/IRL_dqn_train.py:267-345 `DQN.update`, ppo_policy/ppo_train.py:365-417 `update_policy`): ~970 launches of

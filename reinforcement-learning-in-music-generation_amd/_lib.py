@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 36
+ABI_VERSION = 37
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -164,6 +164,8 @@ _SIGNATURES = {
     "cwlt_reward_window": [_ptr, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr],
     "cwlt_reward_apply": [_ptr, _ptr, _c_f32, _c_i64, _ptr, _ptr, _ptr],
     "cwlt_reward_apply_keyed": [_ptr, _ptr, _ptr, _c_i64, _ptr, _c_int, _c_i64, _ptr, _ptr, _ptr],
+    "cwlt_song_metrics": [_ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _c_int,
+                          _ptr, _c_int, _c_int, _ptr, _c_i64, _c_int] + [_ptr] * 7,
     "cwlt_heads_blocks": [_c_i64],
     "cwlt_heads_tiled": [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr],
     "cwlt_heads_fwd": [_ptr, _ptr, _c_int] + [_ptr] * 7 + [_c_i64, _c_i64, _c_i64, _c_int, _ptr],

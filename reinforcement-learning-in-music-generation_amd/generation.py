@@ -28,6 +28,7 @@ from . import ops
 from .draw_plan import (DQN_TEMPERATURE, DQN_TOP_P, Constraint, DeviceDraw, DrawPlan, Grammar,  # noqa: F401
                         Preference, check_entry, compile_alpha, compile_constraints, compile_grammar,
                         compile_preferences)
+from .metrics import METRICS, MetricReward, SongMetricSpec, song_metrics  # noqa: F401
 from .sampling import logmeanexp, sample_cw
 
 INIT_CW = np.array([[0, 0, 1, 0, 0, 0]])          # "Bar" token, testing-no-type-cp.py:135-137
@@ -2297,7 +2298,8 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     exp(beta x sum of the song's window rewards): the optimum of KL-regularised RL with KL coefficient 1 / beta, sampled
     without a backward pass; log_evidence estimates the log of that expectation and ParticleSet.rewards records each
     lineage's rewards.  reward is any callable whose entry n depends on row n's window alone (WindowReward wraps the
-    AIRL discriminator, whose window is the default 50); a row without a live row in the window is shown mask[n, 0] = 1
+    AIRL discriminator, whose window is the default 50; MetricReward is a rule-based one, a weighted sum of song
+    measures such as in_chord, groove and h1 over the window); a row without a live row in the window is shown mask[n, 0] = 1
     over zero tokens and its result is discarded.  The windows live per pool row on the device (cwlt_reward_push per
     token, cwlt_reward_window and cwlt_reward_apply per event) and are gathered with every other per-row state.
     beta = 0 gives bitwise the run without a reward; reward=None enqueues nothing new.  The PPO reward model's

@@ -2305,6 +2305,48 @@ def reward_apply_keyed(r, any_live, beta, key, particles, lw, h_r):
     return lw
 
 
+def song_metrics(tok, mask, lengths, attrs, order, pitch, chord, Q, xlog2x, max_bars, feat, weights=None, reward=None,
+                 bars=None, hist=None, groove=None):
+    """The 11 song measures of metrics.METRICS per song (cwlt_song_metrics; bitwise
+    sampling.song_metrics_f32), one launch on the current stream, no sync.  tok (N, L, A) int64; mask (N, L) int64 or
+    None; lengths (N,) int32 or None; attrs = (bar_attr, pitch_attr, chord_attr) column indices, chord_attr -1 (then
+    chord may be None) for no chord feature; order / pitch / chord int32 tables and xlog2x (>= L + 1,) f32 as
+    metrics.SongMetricSpec builds them.  Written: feat (N, 11) f32; with weights (11,) f32, reward (N,) f32; bars (N,)
+    int32, hist (N, max_bars, 12) int32 and groove (N, max_bars) int64 where given."""
+    if tok.dtype != torch.int64 or not tok.is_contiguous() or tok.dim() != 3:
+        raise TypeError("song_metrics takes a contiguous int64 tok (N, L, A)")
+    N, L, A = tok.shape
+    MB = int(max_bars)
+    if mask is not None and (mask.dtype != torch.int64 or not mask.is_contiguous() or tuple(mask.shape) != (N, L)):
+        raise TypeError("song_metrics takes a contiguous int64 mask (%d, %d), or None" % (N, L))
+    if lengths is not None and (lengths.dtype != torch.int32 or not lengths.is_contiguous()
+                                or tuple(lengths.shape) != (N,)):
+        raise TypeError("song_metrics takes contiguous int32 lengths (%d,), or None" % N)
+    for t, name in ((order, "order"), (pitch, "pitch"), (chord, "chord")):
+        if t is None and name == "chord":
+            continue
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+            raise TypeError("song_metrics takes a contiguous int32 %s table" % name)
+    for t, shape, name in ((xlog2x, None, "xlog2x"), (feat, (N, 11), "feat"), (weights, (11,), "weights"),
+                           (reward, (N,), "reward")):
+        if t is None and name in ("weights", "reward"):
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise TypeError("song_metrics takes a contiguous f32 %s%s" % (name, "" if shape is None else " %s" % (shape,)))
+    for t, dt, shape, name in ((bars, torch.int32, (N,), "bars"), (hist, torch.int32, (N, MB, 12), "hist"),
+                               (groove, torch.int64, (N, MB), "groove")):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise TypeError("song_metrics takes a contiguous %s %s %s, or None" % (dt, name, shape))
+    bar_attr, pitch_attr, chord_attr = (int(x) for x in attrs)
+    _call("cwlt_song_metrics", _lib.dev(tok, "tok"), _lib.opt(mask, "mask"), _lib.opt(lengths, "lengths"), N, L, A,
+          bar_attr, pitch_attr, chord_attr, _lib.dev(order, "order"), order.numel(), _lib.dev(pitch, "pitch"),
+          pitch.numel(), _lib.opt(chord, "chord"), 0 if chord is None else chord.numel(), int(Q),
+          _lib.dev(xlog2x, "xlog2x"), xlog2x.numel(), MB, _lib.dev(feat, "feat"), _lib.opt(weights, "weights"),
+          _lib.opt(reward, "reward"), _lib.opt(bars, "bars"), _lib.opt(hist, "hist"), _lib.opt(groove, "groove"),
+          _lib.stream_ptr())
+    return feat
+
+
 def stream_refill(state, snap_state, n_layer, s_floats, z_floats, logits, snap_logits, fresh):
     """Copy the one-slot snapshot (state, logits) into every slot whose fresh flag is set (cwlt_stream_refill).
     state: flat f32 of n_layer x [S (slots, s_floats), Z (slots, z_floats)] (DecodeSession._state); snap_state: the same

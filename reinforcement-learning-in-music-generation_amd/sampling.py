@@ -371,3 +371,133 @@ def particle_event_keys(song, pos, every):
     song = np.asarray(song, dtype=np.int64).reshape(-1)
     event = np.asarray(pos, dtype=np.int64).reshape(-1) // int(every) - 1
     return event, (song < 0) | (event < 0)
+
+
+SONG_METRICS = 11
+
+
+def _song_metrics(tok, mask, lengths, spec, weights, max_bars, exact):
+    """song_metrics_f32 (exact False) and song_metrics_f64 (exact True): the walk and every integer are shared."""
+    tok = np.asarray(tok, dtype=np.int64)
+    N, L, _ = tok.shape
+    MB = int(spec.max_bars if max_bars is None else max_bars)
+    idx = np.arange(L, dtype=np.int64)
+    live = np.ones((N, L), dtype=bool) if mask is None else np.asarray(mask).reshape(N, L) != 0
+    if lengths is not None:
+        live = live & (idx[None, :] < np.asarray(lengths, dtype=np.int64).reshape(N, 1))
+    order, pitch = spec.order.astype(np.int64), spec.pitch.astype(np.int64)
+    cb, cp = tok[:, :, spec.bar_attr], tok[:, :, spec.pitch_attr]
+    inside = live & (cb >= 0) & (cb < len(order)) & (cp >= 0) & (cp < len(pitch))
+    if spec.chord_attr >= 0:
+        chord, cc = spec.chord.astype(np.int64), tok[:, :, spec.chord_attr]
+        inside = inside & (cc >= 0) & (cc < len(chord))
+    o = np.where(inside, order[np.where(inside, cb, 0)], -3)
+    pit = np.where(inside, pitch[np.where(inside, cp, 0)], -1)
+    ch = np.where(inside, chord[np.where(inside, cc, 0)], -1) if spec.chord_attr >= 0 else np.full((N, L), -1)
+
+    def last_set(setter, value, start):
+        # the value of the last setter at or before each row (Grammar.beat_states' max-scan), `start` without one
+        last = np.maximum.accumulate(np.where(setter, idx[None, :], -1), axis=1)
+        return np.where(last >= 0, np.take_along_axis(value, np.maximum(last, 0), axis=1), start)
+
+    slot = np.cumsum(o == -1, axis=1)
+    beat = last_set(o >= -1, o, -1)
+    cur = last_set((o >= 0) & (ch >= 0), ch, 0)
+    note = (o == -2) & (pit >= 0) & (pit < 128)
+    head = (live & (slot == 0)).any(axis=1)
+    keep = note & (slot < MB)
+
+    ft = np.float64 if exact else np.float32
+    T = None if exact else np.asarray(spec.xlog2x(L + 1), dtype=np.float32)
+
+    def ent(c):
+        # c (..., 12) integer counts -> the entropies in bits
+        c = np.asarray(c, dtype=np.int64)
+        n = c.sum(axis=-1)
+        safe = np.maximum(n, 1)
+        if exact:
+            xl = lambda v: v * np.log2(np.maximum(v, 1).astype(np.float64))    # noqa: E731
+            return np.where(n > 0, (xl(n) - xl(c).sum(axis=-1)) / safe, 0.0)
+        s = np.zeros(n.shape, dtype=np.float32)
+        for k in range(12):
+            s = (s + T[c[..., k]]).astype(np.float32)
+        return np.where(n > 0, ((T[n] - s).astype(np.float32) / safe.astype(np.float32)).astype(np.float32),
+                        np.float32(0))
+
+    def mean(values):
+        if not len(values):
+            return ft(0)
+        total = values.sum() if exact else np.add.accumulate(values.astype(np.float32), dtype=np.float32)[-1]
+        return ft(total / ft(len(values)))
+
+    def ratio(a, b):
+        return ft(ft(a) / ft(b)) if b else ft(0)
+
+    feat = np.zeros((N, SONG_METRICS), dtype=ft)
+    bars = np.zeros(N, dtype=np.int32)
+    hist = np.zeros((N, MB, 12), dtype=np.int32)
+    groove = np.zeros((N, MB), dtype=np.uint64)
+    for n in range(N):
+        k = np.nonzero(keep[n])[0]
+        s_k, p_k, b_k, c_k = slot[n, k], pit[n, k], beat[n, k], cur[n, k]
+        pc = p_k % 12
+        np.add.at(hist[n], (s_k, pc), 1)
+        on = (b_k >= 0) & (b_k < 64)
+        np.bitwise_or.at(groove[n], s_k[on], np.uint64(1) << b_k[on].astype(np.uint64))
+        c_bars = int(slot[n, -1])
+        first = 0 if head[n] else 1
+        B = c_bars + 1 - first
+        hi = min(c_bars + 1, MB)
+        Bk = max(hi - first, 0)
+        bars[n] = B
+        h = hist[n, first:hi].astype(np.int64)
+        cnt = h.sum(axis=1)
+        notes = int(cnt.sum())
+        e1 = ent(h)
+        feat[n, 0], feat[n, 1] = notes, B
+        feat[n, 2] = mean(e1[cnt > 0])
+        if Bk >= 4:
+            h4 = h[:-3] + h[1:-2] + h[2:-1] + h[3:]
+            feat[n, 3] = mean(ent(h4)[h4.sum(axis=1) > 0])
+        feat[n, 4] = ent(h.sum(axis=0))
+        P = Bk * (Bk - 1) // 2
+        if P:
+            bits = np.unpackbits(groove[n, first:hi].view(np.uint8).reshape(Bk, 8), axis=1).astype(np.int64)
+            ones = bits.sum(axis=0)
+            S = int((ones * (Bk - ones)).sum())
+            feat[n, 5] = 1.0 - S / (P * spec.Q) if exact else np.float32(1) - ratio(S, P * spec.Q)
+        under = c_k != 0
+        feat[n, 6] = ratio(int((((c_k >> pc) & 1) != 0)[under].sum()), int(under.sum()))
+        feat[n, 7] = int(p_k.max() - p_k.min()) if notes else 0
+        feat[n, 8] = len(np.unique(p_k))
+        feat[n, 9] = ratio(notes, Bk)
+        feat[n, 10] = ratio(int((cnt == 0).sum()), Bk)
+    reward = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=ft).reshape(SONG_METRICS)
+        reward = np.zeros(N, dtype=ft)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for f in range(SONG_METRICS):
+                reward = (reward + (w[f] * feat[:, f]).astype(ft)).astype(ft)
+    return {"feat": feat, "reward": reward, "bars": bars, "hist": hist, "groove": groove.view(np.int64)}
+
+
+def song_metrics_f32(tok, mask, lengths, spec, weights=None, max_bars=None):
+    """Numpy float32 restatement of cwlt_song_metrics, bitwise what the kernel produces.  tok (N, L, A)
+    int64; mask (N, L) or None (nonzero: live); lengths (N,) or None; spec a metrics.SongMetricSpec (its order, pitch and
+    chord tables, its Q and its xlog2x table; max_bars: the spec's unless given).  -> a dict: feat (N, 11) float32 in
+    metrics.METRICS' order, reward (N,) float32 (None without weights (11,)), bars (N,) int32, hist (N, max_bars, 12)
+    int32 and groove (N, max_bars) int64, indexed by slot.
+    The walk: a row that is not live is nothing; a live row with a class outside its table only counts as a live row;
+    a Bar row opens the next slot and sets beat = -1; a Beat_k row sets beat = k and, unless its chord entry is -1, the
+    chord mask; a class-0 row with a pitch is a note at (slot, beat, chord mask).  Slot 0 exists only when a live row
+    precedes the first Bar row.  Every entropy is (T[n] - sum_k T[c_k]) / n with the float32 table T[c] = c log2 c, the
+    sum taken from 0 in the order k = 0..11, each operation rounded on its own; means are sequential float32 sums in
+    slot order divided once; the reward is r = r + (w[f] * feat[f]) for f = 0..10 from 0."""
+    return _song_metrics(tok, mask, lengths, spec, weights, max_bars, False)
+
+
+def song_metrics_f64(tok, mask, lengths, spec, weights=None, max_bars=None):
+    """song_metrics_f32's definitions in float64: c log2 c evaluated in float64 (no table), exact divisions, float64
+    sums.  The integers (bars, hist, groove, and the features that are counts) are the same arrays."""
+    return _song_metrics(tok, mask, lengths, spec, weights, max_bars, True)
