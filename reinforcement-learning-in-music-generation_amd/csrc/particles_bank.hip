@@ -3,18 +3,15 @@
 // per-song form keeps (stream.hip), and the K particles of a song share that one prefill.
 //   cwlt_particle_refill_bank   per token, inside the captured token, in the place of cwlt_stream_refill: the fresh rows
 //                               of a group take the state and logits of their song's entry -- each float4 of the entry
-//                               loaded once and stored to every fresh row of the group;
-//   cwlt_particle_release_bank  per hand-out boundary, in the place of cwlt_particle_release: the same ranking of the
-//                               groups that can take a song, but songs are handed out only below min(ctl[3], n_songs),
-//                               ctl[3] the songs whose entries the host has marked written, and a row handed song v starts
-//                               from bar0_all[v] and cap_all[v], two tables of n_songs entries, not from two scalars.
-// One launch each, no host synchronisation, no allocation, no atomics, no cross-workgroup communication; every barrier
+//                               loaded once and stored to every fresh row of the group.
+// The hand-out of songs at a boundary, cwlt_particle_release_bank, is particle_release_kernel<true> in
+// particles_stream.hip.
+// One launch, no host synchronisation, no allocation, no atomics, no cross-workgroup communication; every barrier
 // is workgroup-uniform; all index arithmetic is 64-bit.
 #include "cwlt_common.h"
 
 namespace cwlt {
 
-constexpr int BANK_RELEASE_GROUPS = 4096;            // groups of one release: its decisions live in LDS
 constexpr int GROUP_WORDS = 16;                      // 64-row words of one group's flags: K <= 1024
 
 // Every block walks the rows' flags, a ballot per 64 rows (stream_refill_kernel's scan); nothing fresh: nothing else.
@@ -109,96 +106,6 @@ __global__ __launch_bounds__(256) void particle_refill_bank_kernel(
     }
 }
 
-// particle_release_kernel (particles_stream.hip) with the gate and the tables, and nothing else changed: one workgroup;
-// phase 1, one thread per group, ranks the candidates -- no song, or every row done -- in group order, and candidate
-// number r takes song ctl[1] + r while that lies below limit = min(ctl[3], n_songs), else none (-1: parked, a candidate
-// again at the next boundary); a candidate that had a song is finished and its outputs are written whether or not the
-// group gets a new one.  Phase 2, one thread per row: a handed row starts from bar0_all / cap_all of its new song.
-__global__ __launch_bounds__(1024) void particle_release_bank_kernel(
-    long groups, int K, long n_songs, const int64_t* __restrict__ bar0_all, const int64_t* __restrict__ cap_all,
-    int64_t* __restrict__ song, int64_t* __restrict__ id, int64_t* __restrict__ pos, int64_t* __restrict__ bar,
-    int64_t* __restrict__ cap, int64_t* __restrict__ len, int64_t* __restrict__ done, int64_t* __restrict__ fresh,
-    float* __restrict__ lw, float* __restrict__ log_z, int64_t* __restrict__ ctl, float* __restrict__ out_lw,
-    int64_t* __restrict__ out_len, float* __restrict__ out_logz) {
-    __shared__ int take_s[BANK_RELEASE_GROUPS];      // -2: no candidate; -1: parked; else the song handed out
-    __shared__ int wave_n[16], wave_f[16];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n_wave = blockDim.x >> 6;
-    const long assigned = ctl[1], ready = ctl[3];
-    const long limit = ready < n_songs ? ready : n_songs;
-    long carry = 0, carry_f = 0;                     // candidates / finished songs before this chunk
-    for (long base = 0; base < groups; base += blockDim.x) {
-        const long g = base + tid;
-        const bool active = g < groups;
-        int cand = 0, fin = 0;
-        long sg = -1;
-        if (active) {
-            sg = song[g];
-            int all = 1;
-            for (int k = 0; k < K; ++k) all &= done[g * K + k] != 0 ? 1 : 0;
-            cand = (sg < 0 || all) ? 1 : 0;
-            fin = (sg >= 0 && all) ? 1 : 0;
-        }
-        const unsigned long long m = __ballot(cand != 0);
-        const unsigned long long mf = __ballot(fin != 0);
-        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) {
-            wave_n[w] = __popcll(m);
-            wave_f[w] = __popcll(mf);
-        }
-        __syncthreads();
-        int before = 0, chunk_n = 0, chunk_f = 0;
-        for (int q = 0; q < n_wave; ++q) {
-            before += q < w ? wave_n[q] : 0;
-            chunk_n += wave_n[q];
-            chunk_f += wave_f[q];
-        }
-        __syncthreads();                             // wave_n / wave_f are rewritten by the next chunk
-        if (active) {
-            int v = -2;
-            if (cand) {
-                const long idx = assigned + carry + before + rank;
-                v = idx < limit ? (int)idx : -1;
-                if (fin && sg < n_songs) out_logz[sg] = log_z[g];
-                song[g] = v;
-                if (v >= 0) log_z[g] = 0.f;
-            }
-            take_s[g] = v;
-        }
-        carry += chunk_n;
-        carry_f += chunk_f;
-    }
-    __syncthreads();
-    const long rows = groups * K;
-    for (long n = tid; n < rows; n += blockDim.x) {
-        const long g = n / K;
-        const int v = take_s[g];
-        if (v == -2) continue;
-        const long old = id[n];
-        if (old >= 0 && old < n_songs * K) {       // the output arrays hold n_songs * K particles
-            out_lw[old] = lw[n];
-            out_len[old] = len[n];
-        }
-        if (v >= 0) {                                // v < limit <= n_songs: inside the tables
-            id[n] = (long)v * K + (n - g * K);
-            pos[n] = 0;
-            bar[n] = bar0_all[v];
-            cap[n] = cap_all[v];
-            len[n] = 0;
-            done[n] = 0;
-            lw[n] = 0.f;
-            fresh[n] = 1;
-        } else {
-            id[n] = -1;
-            done[n] = 1;
-        }
-    }
-    if (tid == 0) {
-        const long next = assigned + carry, top = limit > assigned ? limit : assigned;
-        ctl[1] = next > top ? top : next;            // never decreases
-        ctl[2] = ctl[2] + carry_f;
-    }
-}
-
 }  // namespace cwlt
 
 extern "C" int cwlt_particle_refill_bank(float* state, const float* bank_state, int64_t bank, int n_layer,
@@ -220,23 +127,5 @@ extern "C" int cwlt_particle_refill_bank(float* state, const float* bank_state, 
                        (float4*)state, (const float4*)bank_state, (long)bank, (long)rows, particles, n_layer,
                        (long)s_floats / 4, (long)z_floats / 4, logits, bank_logits, (long)n_logits, (long)ld_logits,
                        (long)ld_bank_logits, fresh, id);
-    return (int)hipGetLastError();
-}
-
-extern "C" int cwlt_particle_release_bank(int64_t groups, int particles, int64_t n_songs, const int64_t* bar0_all,
-                                          const int64_t* cap_all, int64_t* song, int64_t* id, int64_t* pos,
-                                          int64_t* bar, int64_t* cap, int64_t* len, int64_t* done, int64_t* fresh,
-                                          float* lw, float* log_z, int64_t* ctl, float* out_lw, int64_t* out_len,
-                                          float* out_logz, void* stream) {
-    using namespace cwlt;
-    if (!bar0_all || !cap_all || !song || !id || !pos || !bar || !cap || !len || !done || !fresh || !lw || !log_z ||
-        !ctl || !out_lw || !out_len || !out_logz)
-        return CWLT_ERR_ARG;
-    if (particles < 2 || particles > 1024 || groups < 1 || groups > BANK_RELEASE_GROUPS ||
-        groups * particles > (1L << 20) || n_songs < 0 || n_songs * particles > (1L << 20))
-        return CWLT_ERR_ARG;
-    hipLaunchKernelGGL(particle_release_bank_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (long)groups,
-                       particles, (long)n_songs, bar0_all, cap_all, song, id, pos, bar, cap, len, done, fresh, lw, log_z,
-                       ctl, out_lw, out_len, out_logz);
     return (int)hipGetLastError();
 }

@@ -8,6 +8,9 @@
 //   cwlt_particle_release  per event, after the gather: one workgroup ranks the groups that can take a song -- every row
 //                          done, or no song -- in group order, writes a finished song's final weights, lengths and
 //                          evidence into the run's output arrays and hands out the next song indices;
+//   cwlt_particle_release_bank  the same kernel's other instantiation, for per-song prompts (particles_bank.hip, DESIGN
+//                          §4.6q): songs are handed out only below min(ctl[3], n_songs), and a row handed song v starts
+//                          from bar0_all[v] and cap_all[v], two tables of n_songs entries, not from two scalars;
 //   cwlt_particle_fill     per event, after the release: dst[n] = src[id[n]] for the rows flagged fresh -- the new
 //                          particles' grammar positions and repetition states.
 // One launch each, no host synchronisation, no allocation, no atomics, no cross-workgroup communication; every barrier
@@ -40,15 +43,35 @@ __global__ __launch_bounds__(1024) void particle_advance_kernel(const int64_t* _
     if (threadIdx.x == 0) ctl[0] = t + 1;
 }
 
+// Where a handed-out row's bar count and cap come from: two scalars, or (BANK) two tables of n_songs entries.
+template <bool BANK>
+struct ParticleStart {
+    long bar0, cap;
+};
+template <>
+struct ParticleStart<true> {
+    const int64_t* bar0;                             // [n_songs]
+    const int64_t* cap;                              // [n_songs]
+};
+
+// A row takes song v -> the bar count and the cap it starts from.
+__device__ inline long bar_of(const ParticleStart<false>& st, long) { return st.bar0; }
+__device__ inline long bar_of(const ParticleStart<true>& st, long v) { return st.bar0[v]; }
+__device__ inline long cap_of(const ParticleStart<false>& st, long) { return st.cap; }
+__device__ inline long cap_of(const ParticleStart<true>& st, long v) { return st.cap[v]; }
+
 // One workgroup.  Phase 1, one thread per group, groups in chunks of blockDim: a group is a candidate for a song when it
 // has none or when its K rows are all done; candidates are ranked in group order by a ballot prefix per wave, the wave
 // totals and the chunks before (stream_advance_kernel's ranking), and candidate number r takes song ctl[1] + r while
-// that lies below n_songs, else none (-1).  A candidate that had a song is finished: its log_z goes to out_logz[song].
+// that lies below limit, else none (-1: parked, a candidate again at the next boundary).  limit is n_songs, lowered
+// (BANK) to ctl[3], the songs whose bank entries the host has marked written; the plain form's ctl has no ctl[3].  A
+// candidate that had a song is finished: its log_z goes to out_logz[song], whether or not the group gets a new one.
 // Phase 2, after the barrier, one thread per row: a candidate group's rows write their particle's final lw and len to
 // out_lw / out_len[id] (when they had one) and are then set up for the new song, or parked (id -1, done 1).  The rows of
 // a group that is no candidate, and its song and log_z, are not written.
+template <bool BANK>
 __global__ __launch_bounds__(1024) void particle_release_kernel(
-    long groups, int K, long n_songs, long bar0, long cap0, int64_t* __restrict__ song, int64_t* __restrict__ id,
+    long groups, int K, long n_songs, ParticleStart<BANK> st, int64_t* __restrict__ song, int64_t* __restrict__ id,
     int64_t* __restrict__ pos, int64_t* __restrict__ bar, int64_t* __restrict__ cap, int64_t* __restrict__ len,
     int64_t* __restrict__ done, int64_t* __restrict__ fresh, float* __restrict__ lw, float* __restrict__ log_z,
     int64_t* __restrict__ ctl, float* __restrict__ out_lw, int64_t* __restrict__ out_len,
@@ -57,6 +80,8 @@ __global__ __launch_bounds__(1024) void particle_release_kernel(
     __shared__ int wave_n[16], wave_f[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, n_wave = blockDim.x >> 6;
     const long assigned = ctl[1];
+    long limit = n_songs;                            // song indices below this may be handed out
+    if (BANK && ctl[3] < limit) limit = ctl[3];
     long carry = 0, carry_f = 0;                     // candidates / finished songs before this chunk
     for (long base = 0; base < groups; base += blockDim.x) {
         const long g = base + tid;
@@ -89,7 +114,7 @@ __global__ __launch_bounds__(1024) void particle_release_kernel(
             int v = -2;
             if (cand) {
                 const long idx = assigned + carry + before + rank;
-                v = idx < n_songs ? (int)idx : -1;
+                v = idx < limit ? (int)idx : -1;
                 if (fin && sg < n_songs) out_logz[sg] = log_z[g];
                 song[g] = v;
                 if (v >= 0) log_z[g] = 0.f;
@@ -110,11 +135,11 @@ __global__ __launch_bounds__(1024) void particle_release_kernel(
             out_lw[old] = lw[n];
             out_len[old] = len[n];
         }
-        if (v >= 0) {
+        if (v >= 0) {                                // v < limit <= n_songs: inside the tables
             id[n] = (long)v * K + (n - g * K);
             pos[n] = 0;
-            bar[n] = bar0;
-            cap[n] = cap0;
+            bar[n] = bar_of(st, v);
+            cap[n] = cap_of(st, v);
             len[n] = 0;
             done[n] = 0;
             lw[n] = 0.f;
@@ -126,7 +151,8 @@ __global__ __launch_bounds__(1024) void particle_release_kernel(
     }
     if (tid == 0) {
         const long next = assigned + carry;
-        ctl[1] = next > n_songs ? n_songs : next;
+        const long top = BANK && assigned > limit ? assigned : limit;   // BANK: the counter never decreases
+        ctl[1] = next > top ? top : next;
         ctl[2] = ctl[2] + carry_f;
     }
 }
@@ -147,6 +173,24 @@ __global__ __launch_bounds__(256) void particle_fill_kernel(uint32_t* __restrict
     }
 }
 
+// The checks and the launch the two release entries share.
+template <bool BANK>
+static int particle_release(int64_t groups, int particles, int64_t n_songs, ParticleStart<BANK> st, int64_t* song,
+                            int64_t* id, int64_t* pos, int64_t* bar, int64_t* cap, int64_t* len, int64_t* done,
+                            int64_t* fresh, float* lw, float* log_z, int64_t* ctl, float* out_lw, int64_t* out_len,
+                            float* out_logz, void* stream) {
+    if (!song || !id || !pos || !bar || !cap || !len || !done || !fresh || !lw || !log_z || !ctl || !out_lw ||
+        !out_len || !out_logz)
+        return CWLT_ERR_ARG;
+    if (particles < 2 || particles > 1024 || groups < 1 || groups > RELEASE_GROUPS ||
+        groups * particles > (1L << 20) || n_songs < 0 || n_songs * particles > (1L << 20))
+        return CWLT_ERR_ARG;
+    hipLaunchKernelGGL(particle_release_kernel<BANK>, dim3(1), dim3(1024), 0, (hipStream_t)stream, (long)groups,
+                       particles, (long)n_songs, st, song, id, pos, bar, cap, len, done, fresh, lw, log_z, ctl, out_lw,
+                       out_len, out_logz);
+    return (int)hipGetLastError();
+}
+
 }  // namespace cwlt
 
 extern "C" int cwlt_particle_advance(const int64_t* tokens, int n_attr, int64_t rows, const int64_t* id,
@@ -164,17 +208,19 @@ extern "C" int cwlt_particle_release(int64_t groups, int particles, int64_t n_so
                                      int64_t* song, int64_t* id, int64_t* pos, int64_t* bar, int64_t* cap,
                                      int64_t* len, int64_t* done, int64_t* fresh, float* lw, float* log_z,
                                      int64_t* ctl, float* out_lw, int64_t* out_len, float* out_logz, void* stream) {
-    using namespace cwlt;
-    if (!song || !id || !pos || !bar || !cap || !len || !done || !fresh || !lw || !log_z || !ctl || !out_lw ||
-        !out_len || !out_logz)
-        return CWLT_ERR_ARG;
-    if (particles < 2 || particles > 1024 || groups < 1 || groups > RELEASE_GROUPS ||
-        groups * particles > (1L << 20) || n_songs < 0 || n_songs * particles > (1L << 20) || cap0 < 1)
-        return CWLT_ERR_ARG;
-    hipLaunchKernelGGL(particle_release_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (long)groups, particles,
-                       (long)n_songs, (long)bar0, (long)cap0, song, id, pos, bar, cap, len, done, fresh, lw, log_z, ctl,
-                       out_lw, out_len, out_logz);
-    return (int)hipGetLastError();
+    if (cap0 < 1) return CWLT_ERR_ARG;
+    return cwlt::particle_release<false>(groups, particles, n_songs, {(long)bar0, (long)cap0}, song, id, pos, bar, cap,
+                                         len, done, fresh, lw, log_z, ctl, out_lw, out_len, out_logz, stream);
+}
+
+extern "C" int cwlt_particle_release_bank(int64_t groups, int particles, int64_t n_songs, const int64_t* bar0_all,
+                                          const int64_t* cap_all, int64_t* song, int64_t* id, int64_t* pos,
+                                          int64_t* bar, int64_t* cap, int64_t* len, int64_t* done, int64_t* fresh,
+                                          float* lw, float* log_z, int64_t* ctl, float* out_lw, int64_t* out_len,
+                                          float* out_logz, void* stream) {
+    if (!bar0_all || !cap_all) return CWLT_ERR_ARG;
+    return cwlt::particle_release<true>(groups, particles, n_songs, {bar0_all, cap_all}, song, id, pos, bar, cap, len,
+                                        done, fresh, lw, log_z, ctl, out_lw, out_len, out_logz, stream);
 }
 
 extern "C" int cwlt_particle_fill(void* dst, const void* src, const int64_t* fresh, const int64_t* id, int64_t rows,

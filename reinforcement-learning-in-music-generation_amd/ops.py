@@ -2051,22 +2051,28 @@ def particle_weigh(logp, out_counter, bar, bar_cond, cap, lw, length, done):
     return lw
 
 
+def _resample_groups(fn, lw, done, particles, anc, u, ess, resampled, log_z, song=None):
+    """(groups, K) of a resampling event, its per-row and per-group tensors checked (song: the keyed form's)."""
+    rows, K = lw.numel(), int(particles)
+    if K < 1 or rows % K:
+        raise ValueError("%s: %d rows are no whole groups of %d particles" % (fn, rows, K))
+    groups = rows // K
+    for t, dt, n in ((lw, torch.float32, rows), (done, torch.int64, rows), (anc, torch.int64, rows),
+                     (u, torch.float32, groups), (ess, torch.float32, groups), (resampled, torch.int32, groups),
+                     (log_z, torch.float32, groups)) + (() if song is None else ((song, torch.int64, groups),)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("%s takes contiguous lw f32 / done, anc int64 (rows,) and u, ess, log_z f32 / resampled "
+                            "int32%s (groups,)" % (fn, "" if song is None else " / song int64"))
+    return groups, K
+
+
 def particle_resample(lw, done, particles, ess_frac, seed, event, anc, u, ess, resampled, log_z):
     """One resampling event (cwlt_particle_resample): lw, done (rows,) in groups of `particles` consecutive
     rows; a group below ess_frac * particles effective samples (and not all done) is resampled systematically.  Written:
     anc (rows,) int64 global ancestor rows (the identity for a kept group), u, ess (groups,) f32, resampled (groups,)
     int32; log_z (groups,) f32 gains the group's evidence increment and its lw become 0.  u is keyed by (seed, event,
     group)."""
-    rows, K = lw.numel(), int(particles)
-    if K < 1 or rows % K:
-        raise ValueError("particle_resample: %d rows are no whole groups of %d particles" % (rows, K))
-    groups = rows // K
-    for t, dt, n in ((lw, torch.float32, rows), (done, torch.int64, rows), (anc, torch.int64, rows),
-                     (u, torch.float32, groups), (ess, torch.float32, groups), (resampled, torch.int32, groups),
-                     (log_z, torch.float32, groups)):
-        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-            raise TypeError("particle_resample takes contiguous lw f32 / done, anc int64 (rows,) and u, ess, log_z f32 / "
-                            "resampled int32 (groups,)")
+    groups, K = _resample_groups("particle_resample", lw, done, particles, anc, u, ess, resampled, log_z)
     _call("cwlt_particle_resample", _lib.dev(lw, "lw"), _lib.dev(done, "done"), groups, K, float(ess_frac),
           int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), _lib.dev(anc, "anc"), _lib.dev(u, "u"), _lib.dev(ess, "ess"),
           _lib.dev(resampled, "resampled"), _lib.dev(log_z, "log_z"), _lib.stream_ptr())
@@ -2094,11 +2100,14 @@ def particle_gather(dst, src, anc, row_bytes, n_blocks=1, block_stride=0, copy_b
     return dst
 
 
+_INT64_ROWS = "%s: %s must be a contiguous int64 tensor of %d elements"
+
+
 def _int64_rows(fn, rows, **tensors):
     """Every tensor a contiguous int64 of `rows` elements."""
     for name, t in tensors.items():
         if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != rows:
-            raise TypeError("%s: %s must be a contiguous int64 tensor of %d elements" % (fn, name, rows))
+            raise TypeError(_INT64_ROWS % (fn, name, rows))
 
 
 def particle_resample_keyed(lw, done, particles, ess_frac, seed, song, pos, every, anc, u, ess, resampled, log_z,
@@ -2106,17 +2115,9 @@ def particle_resample_keyed(lw, done, particles, ess_frac, seed, song, pos, ever
     """particle_resample for the particle stream (cwlt_particle_resample_keyed): u is keyed by (seed, the
     song's own event index pos / every - 1, song[g]); song (groups,) int64 (< 0: no song: the group is left alone, anc
     the identity, u = ess = 0); pos int64, group g's clock at pos[g * pos_stride] (default: particles, pos per row)."""
-    fn, rows, K = "particle_resample_keyed", lw.numel(), int(particles)
-    if K < 1 or rows % K:
-        raise ValueError("%s: %d rows are no whole groups of %d particles" % (fn, rows, K))
-    groups = rows // K
+    fn = "particle_resample_keyed"
+    groups, K = _resample_groups(fn, lw, done, particles, anc, u, ess, resampled, log_z, song)
     stride = K if pos_stride is None else int(pos_stride)
-    for t, dt, n in ((lw, torch.float32, rows), (done, torch.int64, rows), (anc, torch.int64, rows),
-                     (u, torch.float32, groups), (ess, torch.float32, groups), (resampled, torch.int32, groups),
-                     (log_z, torch.float32, groups), (song, torch.int64, groups)):
-        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-            raise TypeError("%s takes contiguous lw f32 / done, anc int64 (rows,) and u, ess, log_z f32 / resampled "
-                            "int32 / song int64 (groups,)" % fn)
     if pos.dtype != torch.int64 or not pos.is_contiguous() or stride < 1 or pos.numel() < (groups - 1) * stride + 1:
         raise TypeError("%s: pos must be a contiguous int64 tensor with group g's clock at g * %d" % (fn, stride))
     _call("cwlt_particle_resample_keyed", _lib.dev(lw, "lw"), _lib.dev(done, "done"), groups, K, float(ess_frac),
@@ -2140,21 +2141,34 @@ def particle_advance(tokens, pid, done, pos, fresh, ctl, ring):
           _lib.dev(fresh), _lib.dev(ctl), _lib.dev(ring), ring.shape[0], _lib.stream_ptr())
 
 
+def _release_groups(fn, particles, n_songs, song, pid, pos, bar, cap, length, done, fresh, lw, log_z, out_lw, out_len,
+                    out_logz, tables=()):
+    """(groups, K) of a release, its state and output tensors checked in one pass (_int64_rows' check and message, one
+    call for all sizes: the wrappers' Python time is the release's cost on the stream); tables: (name, tensor) pairs of
+    (n_songs,) int64, the bank form's."""
+    K, groups, N = int(particles), song.numel(), int(n_songs)
+    rows = groups * K
+    for name, t, n in (("song", song, groups), ("pid", pid, rows), ("pos", pos, rows), ("bar", bar, rows),
+                       ("cap", cap, rows), ("length", length, rows), ("done", done, rows), ("fresh", fresh, rows),
+                       ("out_len", out_len, N * K)) + tuple((name, t, N) for name, t in tables):
+        if t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != n:
+            raise TypeError(_INT64_ROWS % (fn, name, n))
+    for t, n in ((lw, rows), (log_z, groups), (out_lw, N * K), (out_logz, N)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+            raise TypeError("%s takes contiguous f32 lw (rows,), log_z (groups,), out_lw (n_songs * K,) and out_logz "
+                            "(n_songs,)" % fn)
+    return groups, K
+
+
 def particle_release(particles, n_songs, bar0, cap0, song, pid, pos, bar, cap, length, done, fresh, lw, log_z, ctl,
                      out_lw, out_len, out_logz):
     """The release / hand-out of the particle stream (cwlt_particle_release; sampling.particle_release is
     its numpy restatement): groups without a song or with every row done are candidates; finished ones write out_lw,
     out_len (n_songs * particles,) and out_logz (n_songs,); candidates take the next songs from ctl[1] in group order.
     song, log_z (groups,); pid, pos, bar, cap, length, done, fresh, lw (rows,); ctl (>= 3,) int64."""
-    fn, K, groups = "particle_release", int(particles), song.numel()
-    rows = groups * K
-    _int64_rows(fn, groups, song=song)
-    _int64_rows(fn, rows, pid=pid, pos=pos, bar=bar, cap=cap, length=length, done=done, fresh=fresh)
-    _int64_rows(fn, int(n_songs) * K, out_len=out_len)
-    for t, n in ((lw, rows), (log_z, groups), (out_lw, int(n_songs) * K), (out_logz, int(n_songs))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise TypeError("%s takes contiguous f32 lw (rows,), log_z (groups,), out_lw (n_songs * K,) and out_logz "
-                            "(n_songs,)" % fn)
+    fn = "particle_release"
+    groups, K = _release_groups(fn, particles, n_songs, song, pid, pos, bar, cap, length, done, fresh, lw, log_z, out_lw,
+                                out_len, out_logz)
     if ctl.dtype != torch.int64 or ctl.numel() < 3:
         raise TypeError("%s: ctl must hold the int64 counters {tokens, assigned, finished}" % fn)
     _call("cwlt_particle_release", groups, K, int(n_songs), int(bar0), int(cap0), _lib.dev(song), _lib.dev(pid),
@@ -2210,16 +2224,9 @@ def particle_release_bank(particles, n_songs, bar0_all, cap_all, song, pid, pos,
     DESIGN §4.6q; sampling.particle_release_bank restates the decision): songs are handed out only below
     min(ctl[3], n_songs), a candidate past that is parked until the next boundary, and a row handed song v starts from
     bar0_all[v] and cap_all[v] ((n_songs,) int64).  ctl (4,) int64 {tokens, assigned, finished, ready}."""
-    fn, K, groups = "particle_release_bank", int(particles), song.numel()
-    rows = groups * K
-    _int64_rows(fn, groups, song=song)
-    _int64_rows(fn, rows, pid=pid, pos=pos, bar=bar, cap=cap, length=length, done=done, fresh=fresh)
-    _int64_rows(fn, int(n_songs) * K, out_len=out_len)
-    _int64_rows(fn, int(n_songs), bar0_all=bar0_all, cap_all=cap_all)
-    for t, n in ((lw, rows), (log_z, groups), (out_lw, int(n_songs) * K), (out_logz, int(n_songs))):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
-            raise TypeError("%s takes contiguous f32 lw (rows,), log_z (groups,), out_lw (n_songs * K,) and out_logz "
-                            "(n_songs,)" % fn)
+    fn = "particle_release_bank"
+    groups, K = _release_groups(fn, particles, n_songs, song, pid, pos, bar, cap, length, done, fresh, lw, log_z, out_lw,
+                                out_len, out_logz, (("bar0_all", bar0_all), ("cap_all", cap_all)))
     if ctl.dtype != torch.int64 or not ctl.is_contiguous() or ctl.numel() < 4:
         raise TypeError("%s: ctl must hold the int64 counters {tokens, assigned, finished, ready}" % fn)
     _call("cwlt_particle_release_bank", groups, K, int(n_songs), _lib.dev(bar0_all), _lib.dev(cap_all), _lib.dev(song),
@@ -2267,16 +2274,22 @@ def reward_window(recent, live, filled, win, mask, any_live):
     return win, mask, any_live
 
 
+def _reward_rows(fn, r, any_live, lw, h_r):
+    """The rows of a reward_apply: r, lw, h_r contiguous f32 and any_live contiguous int64, all of lw's length."""
+    rows = lw.numel()
+    for t in (r, lw, h_r):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
+            raise TypeError("%s takes contiguous f32 r, lw and h_r of %d rows" % (fn, rows))
+    if any_live.dtype != torch.int64 or not any_live.is_contiguous() or any_live.numel() != rows:
+        raise TypeError("%s takes a contiguous int64 any of %d rows" % (fn, rows))
+    return rows
+
+
 def reward_apply(r, any_live, beta, lw, h_r):
     """The window rewards into the log-weights (cwlt_reward_apply): rows with any_live[n] != 0 get
     lw[n] = lw[n] + (beta * r[n]) (two f32 roundings, bitwise sampling.reward_apply_f32) and h_r[n] = r[n]; the others
     keep lw and get h_r[n] = 0, whatever r[n] holds.  r, lw, h_r (rows,) f32, any_live (rows,) int64."""
-    rows = lw.numel()
-    for t in (r, lw, h_r):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
-            raise TypeError("reward_apply takes contiguous f32 r, lw and h_r of %d rows" % rows)
-    if any_live.dtype != torch.int64 or not any_live.is_contiguous() or any_live.numel() != rows:
-        raise TypeError("reward_apply takes a contiguous int64 any of %d rows" % rows)
+    rows = _reward_rows("reward_apply", r, any_live, lw, h_r)
     _call("cwlt_reward_apply", _lib.dev(r, "r"), _lib.dev(any_live, "any"), float(beta), rows, _lib.dev(lw, "lw"),
           _lib.dev(h_r, "h_r"), _lib.stream_ptr())
     return lw
@@ -2288,12 +2301,7 @@ def reward_apply_keyed(r, any_live, beta, key, particles, lw, h_r):
     s < len(beta) get lw[n] = lw[n] + (beta[s] * r[n]) (two f32 roundings, bitwise sampling.reward_apply_keyed_f32) and
     h_r[n] = r[n]; the others keep lw and get h_r[n] = 0, whatever r[n] holds.  r, lw, h_r (rows,) f32, any_live (rows,)
     int64, beta (n_beta,) f32 on the device, key (rows,) int64 or None."""
-    rows = lw.numel()
-    for t in (r, lw, h_r):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows:
-            raise TypeError("reward_apply_keyed takes contiguous f32 r, lw and h_r of %d rows" % rows)
-    if any_live.dtype != torch.int64 or not any_live.is_contiguous() or any_live.numel() != rows:
-        raise TypeError("reward_apply_keyed takes a contiguous int64 any of %d rows" % rows)
+    rows = _reward_rows("reward_apply_keyed", r, any_live, lw, h_r)
     if beta.dtype != torch.float32 or not beta.is_contiguous() or beta.dim() != 1 or beta.numel() < 1:
         raise TypeError("reward_apply_keyed takes a contiguous (n_beta,) f32 beta table")
     if key is not None and (key.dtype != torch.int64 or not key.is_contiguous() or key.numel() != rows):

@@ -327,6 +327,18 @@ def systematic_resample(lw, u, ess_frac, done=None):
                      thresholds=thresholds, s=s)
 
 
+def _particle_release(song, done, particles, assigned, finished, limit, top):
+    """The release's decision: songs are handed out below `limit`, and the counter of assigned songs stops at `top`."""
+    song = np.asarray(song, dtype=np.int64).reshape(-1)
+    K = int(particles)
+    all_done = (np.asarray(done).reshape(len(song), K) != 0).all(1)
+    cand = (song < 0) | all_done
+    released = (song >= 0) & all_done
+    idx = int(assigned) + np.cumsum(cand) - 1
+    take = np.where(cand, np.where(idx < limit, idx, -1), -2).astype(np.int64)
+    return take, released, min(int(assigned) + int(cand.sum()), top), int(finished) + int(released.sum())
+
+
 def particle_release(song, done, particles, assigned, finished, n_songs):
     """Numpy restatement of cwlt_particle_release's decision.  song (groups,): each group's song, < 0
     none; done (groups * K,): the rows' end flags; assigned, finished: the counters before; n_songs: the run's songs.
@@ -334,14 +346,7 @@ def particle_release(song, done, particles, assigned, finished, n_songs):
     Candidate number r, in group order, takes song assigned + r while that is < n_songs, else none (-1).
     -> (take (groups,) int64: -2 for a group that is no candidate (nothing of it is written), else its new song or -1;
     released (groups,) bool: the finished groups, whose old song's outputs are written; assigned, finished after)."""
-    song = np.asarray(song, dtype=np.int64).reshape(-1)
-    K = int(particles)
-    all_done = (np.asarray(done).reshape(len(song), K) != 0).all(1)
-    cand = (song < 0) | all_done
-    released = (song >= 0) & all_done
-    idx = int(assigned) + np.cumsum(cand) - 1
-    take = np.where(cand, np.where(idx < int(n_songs), idx, -1), -2).astype(np.int64)
-    return take, released, min(int(assigned) + int(cand.sum()), int(n_songs)), int(finished) + int(released.sum())
+    return _particle_release(song, done, particles, assigned, finished, int(n_songs), int(n_songs))
 
 
 def particle_release_bank(song, done, particles, assigned, finished, ready, n_songs):
@@ -351,16 +356,8 @@ def particle_release_bank(song, done, particles, assigned, finished, ready, n_so
     boundary); finished groups are released whether or not they take a song; assigned becomes
     min(assigned + candidates, max(limit, assigned)), so it never decreases.  -> particle_release's four values; with
     ready >= n_songs they are particle_release's."""
-    song = np.asarray(song, dtype=np.int64).reshape(-1)
-    K = int(particles)
-    all_done = (np.asarray(done).reshape(len(song), K) != 0).all(1)
-    cand = (song < 0) | all_done
-    released = (song >= 0) & all_done
     limit = min(int(ready), int(n_songs))
-    idx = int(assigned) + np.cumsum(cand) - 1
-    take = np.where(cand, np.where(idx < limit, idx, -1), -2).astype(np.int64)
-    return (take, released, min(int(assigned) + int(cand.sum()), max(limit, int(assigned))),
-            int(finished) + int(released.sum()))
+    return _particle_release(song, done, particles, assigned, finished, limit, max(limit, int(assigned)))
 
 
 def particle_event_keys(song, pos, every):

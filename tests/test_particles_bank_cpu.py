@@ -56,6 +56,11 @@ def test_release_bank_restatement_hand_cases():
     # the gate below n_songs, the songs running out above it
     take, _, assigned, _ = sampling.particle_release_bank([-1] * 4, [1] * 8, 2, 0, 0, 5, 3)
     assert take.tolist() == [0, 1, 2, -1] and assigned == 3
+    # a counter that came in above n_songs: every candidate parks, as in particle_release, but the counter stays
+    for ready in (5, 9, 100):
+        take, rel, assigned, finished = sampling.particle_release_bank(song, done, 2, 12, 3, ready, 9)
+        assert take.tolist() == [-1, -2, -1, -1, -2] and rel.tolist() == [True, False, False, True, False]
+        assert (assigned, finished) == (12, 5)
 
 
 # ---- 2. ABI ----------------------------------------------------------------------------------------------------------------

@@ -172,7 +172,7 @@ def _release(cuda, c, ready=None, bar0_all=None, cap_all=None, scalars=None):
     return {k: v.cpu().numpy() for k, v in dev.items()}
 
 
-@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2)])
+@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2), (4096, 2)])
 def test_release_bank_against_restatement(cuda, groups, K):
     rng = np.random.default_rng([groups, K, 36])
     c = _release_inputs(groups, K, rng)
@@ -217,7 +217,7 @@ def test_release_bank_against_restatement(cuda, groups, K):
     assert np.array_equal(got["ctl"], [77, assigned, finished, c2["n_songs"] + 3]) and assigned == c2["n_songs"]
 
 
-@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2)])
+@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2), (4096, 2)])
 def test_release_bank_open_gate_is_the_plain_release(cuda, groups, K):
     rng = np.random.default_rng([groups, K, 37])
     c = _release_inputs(groups, K, rng)

@@ -49,6 +49,10 @@ def test_release_restatement_hand_cases():
     # nothing to do
     take, rel, assigned, finished = sampling.particle_release([0, 1], [0, 1, 1, 0], K, 2, 0, 5)
     assert take.tolist() == [-2, -2] and not rel.any() and (assigned, finished) == (2, 0)
+    # a counter that came in above n_songs: every candidate parks and the counter is clamped down to n_songs
+    take, rel, assigned, finished = sampling.particle_release(song, done, K, 12, 3, 9)
+    assert take.tolist() == [-1, -2, -1, -1, -2] and rel.tolist() == [True, False, False, True, False]
+    assert (assigned, finished) == (9, 5)
 
 
 def test_event_keys_restatement():

@@ -184,7 +184,7 @@ def _release_case(cuda, groups, K, how, rng):
         assert (take[:-1] != -1).all()
 
 
-@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2)])
+@pytest.mark.parametrize("groups,K", [(1, 2), (3, 64), (130, 7), (1025, 2), (4096, 2)])
 def test_release_against_restatement(cuda, groups, K):
     rng = np.random.default_rng([groups, K])
     for how in ("enough", "last", "middle"):
