@@ -243,7 +243,10 @@ class DecodeSession:
         self.memory = [[self._state[i * per:i * per + n * H * d * d].view(n, H, d, d),
                         self._state[i * per + n * H * d * d:(i + 1) * per].view(n, H, d)]
                        for i in range(len(enc.layers))]
-        self._host_tok = torch.zeros((n, 1, A), dtype=torch.int64).pin_memory()
+        # _state's layout as the refill and gather kernels take it: layers, one song's S floats (H x d x d), Z (H x d)
+        self.n_layer = len(self.memory)
+        self.s_floats, self.z_floats = self.memory[0][0][0].numel(), self.memory[0][1][0].numel()
+        self._host_tok =torch.zeros((n, 1, A), dtype=torch.int64).pin_memory()
         self._host_logits = torch.zeros((n, self.width), dtype=torch.float32).pin_memory()
         self.use_graph = ops.GRAPHS_ENABLED if graph is None else bool(graph)
         self._graph, self._out, self._plan = None, None, None
@@ -591,6 +594,56 @@ class _DeviceLoop:
         return self.logp.index_select(0, idx).cpu().numpy()
 
 
+def _gather_families(sessions, tensors, N):
+    """The per-row buffers a resampling event of a particle loop moves, N rows each -> (families, row_bytes).  families:
+    (state, scratch, row bytes, blocks, block stride in bytes) of, in launch order, the decode state of every session
+    that is not None -- its S rows, then its Z rows, a block per layer -- and then every tensor that is not None, each
+    with a scratch buffer of its own shape; row_bytes: what one moved row copies per phase."""
+    families = []
+    for s in sessions:
+        if s is None:
+            continue
+        scratch = torch.empty_like(s._state)
+        stride = 4 * N * (s.s_floats + s.z_floats)
+        families.append((s._state, scratch, 4 * s.s_floats, s.n_layer, stride))
+        families.append((s._state[N * s.s_floats:], scratch[N * s.s_floats:], 4 * s.z_floats, s.n_layer, stride))
+    for t in tensors:
+        if t is not None:
+            families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
+    return families, sum(rb * nb for _, _, rb, nb, _ in families)
+
+
+def _gather(families, anc, copy_back=False):
+    """One phase of the two-phase cwlt_particle_gather over `families`, enqueued: every state's moved rows into its
+    scratch, taken at the ancestors `anc`; copy_back: the same rows from the scratch back into the state."""
+    for state, scratch, rb, nb, stride in families:
+        dst, src = (state, scratch) if copy_back else (scratch, state)
+        ops.particle_gather(dst, src, anc, rb, nb, stride, copy_back=copy_back)
+
+
+def _event_ms(marks):
+    """The milliseconds between the four HIP events of every timed event of a loop (None: not timed, none)."""
+    return [[m[i].elapsed_time(m[i + 1]) for i in range(3)] for m in marks or []]
+
+
+def _reward_buffers(loop, reward, N, A, dev, timed):
+    """What both particle loops keep for a reward (`reward`: a _reward_spec or None) over N rows of A attributes, as
+    _reward_event reads it off the loop: the rings `recent` (N, W, A) int64 of each row's last W drawn rows and `live`
+    (N, W) int64, whether the particle was alive at each -- both gather families --, the window the callable sees (win,
+    mask, any), beta_t (the device table of a beta per song, else None), the count n_rewards and, when timed, the list
+    reward_timed.  Without a reward the buffers are None.  The history `h_r` is the loop's own."""
+    loop.recent = loop.live = loop.win = loop.mask = loop.any = loop.beta_t = None
+    loop.n_rewards = 0
+    loop.reward_timed = [] if timed and reward is not None else None
+    if reward is not None:
+        W = reward[1]
+        loop.recent = torch.zeros((N, W, A), dtype=torch.int64, device=dev)
+        loop.live = torch.zeros((N, W), dtype=torch.int64, device=dev)
+        loop.win, loop.mask = torch.zeros_like(loop.recent), torch.zeros_like(loop.live)
+        loop.any = torch.zeros(N, dtype=torch.int64, device=dev)
+        loop.beta_t = _beta_table(reward[2], dev)
+
+
 def _reward_event(loop, filled, key, h_row):
     """One reward event of a particle loop (_ParticleLoop, _ParticleStreamLoop), enqueued on the current stream, no
     sync: cwlt_reward_window cuts the loop's rings into win / mask / any (filled: the ring's slots that belong to the
@@ -626,20 +679,20 @@ class _ParticleLoop(_DeviceLoop):
     lp_model - lp_sampler to `lw`, counts the row in `len` and sets `done` by the bar rule and `cap`.  After every
     `every` tokens resample(): lw is copied into row e of h_lw (E, N) f32 (the weights the event saw), then
     cwlt_particle_resample into row e of the device histories (anc (E, N) int64, u, ess (E, G) f32, resampled (E, G)
-    int32), then the two-phase cwlt_particle_gather of every per-row state the loop
-    carries -- the model's decode state and the reference's, the token buffer, bar, beat, seen, len, done, cap --
-    through scratch buffers of the same shapes: eager launches on the loop's stream, no sync.  lw is not gathered: the
-    resampling kernel set it.  timed=True records HIP events around the resampling and each gather phase.
+    int32), then the two-phase cwlt_particle_gather (_gather) of every per-row state the loop carries
+    (_gather_families) -- the model's decode state and the reference's, the token buffer, bar, beat, seen, len, done,
+    cap -- through scratch buffers of the same shapes: eager launches on the loop's stream, no sync.  lw is not
+    gathered: the resampling kernel set it.  timed=True records HIP events around the resampling and each gather phase.
 
-    reward (a _reward_spec: callable, window W, beta): two more per-row states, the ring `recent`
-    (N, W, A) int64 of each particle's last W drawn rows and `live` (N, W) int64, whether the particle was alive at each,
-    both gather families -- so a descendant inherits its ancestor's window together with its `done` flag, although the
-    `song` ring is never gathered.  cwlt_reward_push fills slot count % W inside the captured token, ahead of
-    cwlt_particle_weigh (it reads `done` as it was before the row).  After every W-th token, and ahead of a resampling
-    event of the same token, reward_event(): cwlt_reward_window cuts the rings into win / mask / any, the callable
-    scores them, cwlt_reward_apply adds beta r to lw and writes r into row j of h_r (ceil(capacity / W), N) f32 --
-    eager launches on the loop's stream, no sync.  timed=True records HIP events around the three steps too.  A beta per
-    song (a tuple, DESIGN §4.6p): cwlt_reward_apply_keyed with the device table `beta_t`, row n of song n // K."""
+    reward (a _reward_spec: callable, window W, beta): two more per-row states (_reward_buffers), the
+    rings `recent` and `live`, both gather families -- so a descendant inherits its ancestor's window together with its
+    `done` flag, although the `song` ring is never gathered.  cwlt_reward_push fills slot count % W inside the captured
+    token, ahead of cwlt_particle_weigh (it reads `done` as it was before the row).  After every W-th token, and ahead
+    of a resampling event of the same token, reward_event(): cwlt_reward_window cuts the rings into win / mask / any,
+    the callable scores them, cwlt_reward_apply adds beta r to lw and writes r into row j of h_r (ceil(capacity / W),
+    N) f32 -- eager launches on the loop's stream, no sync.  timed=True records HIP events around the three steps too.
+    A beta per song (a tuple): cwlt_reward_apply_keyed with the device table `beta_t`, row n of song
+    n // K."""
 
     def __init__(self, sess, capacity, plan, particles, every, ess, bar_cond, caps, bar_mask, graph=None, ring=None,
                  timed=False, reward=None):
@@ -663,31 +716,13 @@ class _ParticleLoop(_DeviceLoop):
         self.h_ess = torch.zeros((E, self.G), dtype=torch.float32, device=dev)
         self.h_res = torch.zeros((E, self.G), dtype=torch.int32, device=dev)
         self.n_events = 0
-        self.reward, self.recent, self.live, self.n_rewards = reward, None, None, 0
+        self.reward = reward
+        _reward_buffers(self, reward, N, self.A, dev, timed)          # beta_t, a beta per song: row n is of song n // K
         if reward is not None:
-            W = reward[1]
-            self.recent = torch.zeros((N, W, self.A), dtype=torch.int64, device=dev)
-            self.live = torch.zeros((N, W), dtype=torch.int64, device=dev)
-            self.win, self.mask = torch.zeros_like(self.recent), torch.zeros_like(self.live)
-            self.any = torch.zeros(N, dtype=torch.int64, device=dev)
-            self.h_r = torch.zeros((-(-self.capacity // W), N), dtype=torch.float32, device=dev)
-            self.beta_t = _beta_table(reward[2], dev)                 # a per-song beta: row n is of song n // K
-        # (state, scratch, row bytes, blocks, block stride in bytes) of every family of per-row buffers
-        self.families = []
-        for s in (sess, self.ref):
-            if s is None:
-                continue
-            scratch = torch.empty_like(s._state)
-            sf, zf = s.memory[0][0][0].numel(), s.memory[0][1][0].numel()
-            stride = 4 * N * (sf + zf)
-            self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
-            self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
-        for t in (sess.tok, self.pbar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live):
-            if t is not None:
-                self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
-        self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)      # what one moved row copies per phase
+            self.h_r = torch.zeros((-(-self.capacity // reward[1]), N), dtype=torch.float32, device=dev)
+        self.families, self.row_bytes = _gather_families((sess, self.ref), (
+            sess.tok, self.pbar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live), N)
         self.timed = [] if timed else None
-        self.reward_timed = [] if timed and reward is not None else None
 
     def _after_draw(self, tok):
         if self.pbar is not self.bar:
@@ -720,11 +755,9 @@ class _ParticleLoop(_DeviceLoop):
         ops.particle_resample(self.lw, self.done, self.K, self.ess_frac, self.seed, e, anc, self.h_u[e], self.h_ess[e],
                               self.h_res[e], self.log_z)
         mark(1)
-        for state, scratch, rb, nb, stride in self.families:
-            ops.particle_gather(scratch, state, anc, rb, nb, stride)
+        _gather(self.families, anc)
         mark(2)
-        for state, scratch, rb, nb, stride in self.families:
-            ops.particle_gather(state, scratch, anc, rb, nb, stride, copy_back=True)
+        _gather(self.families, anc, copy_back=True)
         mark(3)
         if marks:
             self.timed.append(marks)
@@ -776,9 +809,6 @@ class _StreamLoop:
         self.sess, self.n_songs, self.chunk = sess, int(n_songs), int(chunk)
         self.S, self.A = sess.n_songs, len(sess.n_token)
         dev = sess.dev
-        self.n_layer = len(sess.memory)
-        self.s_floats = sess.memory[0][0][0].numel()             # one slot's S of one layer (H x d x d)
-        self.z_floats = sess.memory[0][1][0].numel()             # one slot's Z (H x d)
         self.seed = seed
         self.plan = plan = DeviceDraw() if plan is None else plan
         self.bar_mask = torch.as_tensor(np.asarray(bar_mask, dtype=np.int32), device=dev)
@@ -921,13 +951,13 @@ class _SnapshotStreamLoop(_StreamLoop):
         self.bar.fill_(self.bar0)
 
     def _refill(self, logits):
-        ops.stream_refill(self.sess._state, self.snap_state, self.n_layer, self.s_floats, self.z_floats, logits,
-                          self.snap_logits, self.fresh)
-        ref = self.plan.ref
+        s, ref = self.sess, self.plan.ref
+        ops.stream_refill(s._state, self.snap_state, s.n_layer, s.s_floats, s.z_floats, logits, self.snap_logits,
+                          self.fresh)
         if ref is not None:                                     # the reference's pool, then the blend over `logits`
             ref_logits = ref._device_step()
-            ops.stream_refill(ref._state, self.ref_snap[0], len(ref.memory), ref.memory[0][0][0].numel(),
-                              ref.memory[0][1][0].numel(), ref_logits, self.ref_snap[1], self.fresh)
+            ops.stream_refill(ref._state, self.ref_snap[0], ref.n_layer, ref.s_floats, ref.z_floats, ref_logits,
+                              self.ref_snap[1], self.fresh)
             ops.blend_logits(logits, ref_logits, self.sess.n_token, self.plan.alpha, key=self.song, out=logits)
 
     def _advance(self, tok):
@@ -944,15 +974,15 @@ class _ParticleStreamLoop(_StreamLoop):
     of the fresh rows from the snapshot(s), the blend, the preferences, the draw keyed by (particle id, position in
     song) with its log-probs, cwlt_count_bars, the tracks (which never see a fresh flag), cwlt_particle_weigh and
     cwlt_particle_advance.  After every R-th token, eagerly on the same stream (_event): lw into its history, the keyed
-    resampling, the two-phase gather of every family (_ParticleLoop's, through scratch), cwlt_particle_release and the
+    resampling, the two-phase gather (_gather) of every family (_gather_families), cwlt_particle_release and the
     fill of the new particles' beat / seen rows.  The event histories are rings of two chunks' events, copied out with
     the token rows behind the chunk's event; rows are kept per (step, row): the lineage needs the row index.
 
-    reward (a _reward_spec: callable, window W, beta): _ParticleLoop's rings `recent` (S K, W, A) and
-    `live` (S K, W) join the gather families, and cwlt_reward_push, with the stream's step counter ctl[0] as its counter,
-    sits in the captured token ahead of cwlt_particle_weigh.  A group then takes a song only at run steps that are
-    multiples of B = lcm(R, W) -- the release and the fills run at those boundaries alone, a finished group waits for
-    the next one -- so that every song starts at t0 = 0 (mod B) and slot ctl[0] % W is the song's own pos % W: its
+    reward (a _reward_spec: callable, window W, beta): the rings `recent` (S K, W, A) and `live` (S K, W)
+    of _reward_buffers join the gather families, and cwlt_reward_push, with the stream's step counter ctl[0] as its
+    counter, sits in the captured token ahead of cwlt_particle_weigh.  A group then takes a song only at run steps that
+    are multiples of B = lcm(R, W) -- the release and the fills run at those boundaries alone, a finished group waits
+    for the next one -- so that every song starts at t0 = 0 (mod B) and slot ctl[0] % W is the song's own pos % W: its
     windows close after its own rows W, 2 W, ...  After every W-th token, ahead of a resampling of the same token
     (_reward_event): cwlt_reward_window (always the whole ring: it has just wrapped), the callable on all S K rows,
     cwlt_reward_apply -- or cwlt_reward_apply_keyed with a beta per song, keyed by the rows' particle ids -- into a ring
@@ -984,35 +1014,19 @@ class _ParticleStreamLoop(_StreamLoop):
                             for t in self._hist] for _ in range(2)]
         self.hist_parts = [[] for _ in self._hist]
         self.n_events = 0
-        self.reward, self.recent, self.live, self.n_rewards = reward, None, None, 0
+        self.reward = reward
+        _reward_buffers(self, reward, N, self.A, dev, timed)     # beta_t, a beta per song: keyed by particle id
         self.hand_every = self.every                             # a group takes a song at multiples of this many steps
-        self.reward_timed = [] if timed and reward is not None else None
         if reward is not None:
             W = reward[1]
             self.hand_every = _lcm(self.every, W)
-            self.recent = torch.zeros((N, W, self.A), dtype=torch.int64, device=dev)
-            self.live = torch.zeros((N, W), dtype=torch.int64, device=dev)
-            self.win, self.mask = torch.zeros_like(self.recent), torch.zeros_like(self.live)
-            self.any = i64(N)
             self.step = self.ctl[:1]                             # the run's step counter, cwlt_reward_push's
             self.RC = self.chunk // W                            # reward events per chunk; a ring of two chunks' again
             self.h_r = f32(2 * self.RC, N)
             self._host_r = [torch.zeros((self.RC, N), dtype=torch.float32).pin_memory() for _ in range(2)]
             self.r_parts = []
-            self.beta_t = _beta_table(reward[2], dev)            # a per-song beta: n_songs entries, keyed by particle id
-        self.families = []                                       # _ParticleLoop's: (state, scratch, row bytes, blocks, stride)
-        for s in (sess, self.plan.ref):
-            if s is None:
-                continue
-            scratch = torch.empty_like(s._state)
-            sf, zf = s.memory[0][0][0].numel(), s.memory[0][1][0].numel()
-            stride = 4 * N * (sf + zf)
-            self.families.append((s._state, scratch, 4 * sf, len(s.memory), stride))
-            self.families.append((s._state[N * sf:], scratch[N * sf:], 4 * zf, len(s.memory), stride))
-        for t in (sess.tok, self.bar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live):
-            if t is not None:
-                self.families.append((t, torch.empty_like(t), t.numel() // N * t.element_size(), 1, 0))
-        self.row_bytes = sum(rb * nb for _, _, rb, nb, _ in self.families)
+        self.families, self.row_bytes = _gather_families((sess, self.plan.ref), (
+            sess.tok, self.bar, self.beat, self.seen, self.len, self.done, self.cap, self.recent, self.live), N)
 
     def _step_limit(self):
         """List scheduling: the songs' total over the groups plus one longest song, each rounded up to a boundary at
@@ -1041,8 +1055,7 @@ class _ParticleStreamLoop(_StreamLoop):
     def _refill(self, sess, logits, ref=False):
         """The fresh rows of `sess` (the model's pool, or ref: the reference's) and of its logits take their start."""
         snap = self.ref_snap if ref else self.snap
-        ops.stream_refill(sess._state, snap[0], len(sess.memory), sess.memory[0][0][0].numel(),
-                          sess.memory[0][1][0].numel(), logits, snap[1], self.fresh)
+        ops.stream_refill(sess._state, snap[0], sess.n_layer, sess.s_floats, sess.z_floats, logits, snap[1], self.fresh)
 
     def _one(self):
         s, plan = self.sess, self.plan
@@ -1083,10 +1096,8 @@ class _ParticleStreamLoop(_StreamLoop):
         self.h_lw[r].copy_(self.lw)
         ops.particle_resample_keyed(self.lw, self.done, self.K, self.ess_frac, self.seed, self.gsong, self.pos,
                                     self.every, anc, self.h_u[r], self.h_ess[r], self.h_res[r], self.log_z)
-        for state, scratch, rb, nb, stride in self.families:
-            ops.particle_gather(scratch, state, anc, rb, nb, stride)
-        for state, scratch, rb, nb, stride in self.families:
-            ops.particle_gather(state, scratch, anc, rb, nb, stride, copy_back=True)
+        _gather(self.families, anc)
+        _gather(self.families, anc, copy_back=True)
         if self.enqueued % self.hand_every == 0:
             self._release()
         self.n_events += 1
@@ -1134,7 +1145,7 @@ class _PromptBank:
     def _bank_buffers(self, sess):
         """(state, per-layer [S, Z] views, logits) of a bank for `sess`'s model."""
         H, d = sess.memory[0][1].shape[1:]
-        sf, zf, n_layer = sess.memory[0][0][0].numel(), sess.memory[0][1][0].numel(), len(sess.memory)
+        sf, zf, n_layer = sess.s_floats, sess.z_floats, sess.n_layer
         per = self.bank * (sf + zf)
         state = torch.zeros(per * n_layer, dtype=torch.float32, device=sess.dev)
         mem = [[state[i * per:i * per + self.bank * sf].view(self.bank, H, d, d),
@@ -1245,8 +1256,9 @@ class _BankStreamLoop(_PromptBank, _StreamLoop):
         self.cap[:first] = self.cap_all[:first]
 
     def _refill(self, logits):
-        ops.stream_refill_bank(self.sess._state, self.bank_state, self.n_layer, self.s_floats, self.z_floats, logits,
-                               self.bank_logits, self.fresh, self.song)
+        s = self.sess
+        ops.stream_refill_bank(s._state, self.bank_state, s.n_layer, s.s_floats, s.z_floats, logits, self.bank_logits,
+                               self.fresh, self.song)
 
     def _advance(self, tok):
         ops.stream_advance_bank(tok, 2, self.bar_mask, self.bar_cond, self.bank_bar0, self.bank_cap, self.n_songs,
@@ -1283,8 +1295,8 @@ class _ParticleBankStreamLoop(_PromptBank, _ParticleStreamLoop):
 
     def _refill(self, sess, logits, ref=False):
         state, blogits = (self.ref_bank[1], self.ref_bank[3]) if ref else (self.bank_state, self.bank_logits)
-        ops.particle_refill_bank(sess._state, state, len(sess.memory), sess.memory[0][0][0].numel(),
-                                 sess.memory[0][1][0].numel(), logits, blogits, self.fresh, self.song, self.K)
+        ops.particle_refill_bank(sess._state, state, sess.n_layer, sess.s_floats, sess.z_floats, logits, blogits,
+                                 self.fresh, self.song, self.K)
 
 
 def _stream_snapshot(model, prompt, A, kernel="blas"):
@@ -1892,9 +1904,8 @@ def _shared_prefill(sess, toks, lengths, K):
     scratch.reset()
     bank_logits = scratch._prefill(toks[::K], None if lengths is None else lengths[::K], kernel="gemm")
     logits = torch.empty((N, sess.width), dtype=torch.float32, device=sess.dev)
-    ops.particle_refill_bank(sess._state, scratch._state, len(sess.memory), sess.memory[0][0][0].numel(),
-                             sess.memory[0][1][0].numel(), logits, bank_logits,
-                             torch.ones(N, dtype=torch.int64, device=sess.dev),
+    ops.particle_refill_bank(sess._state, scratch._state, sess.n_layer, sess.s_floats, sess.z_floats, logits,
+                             bank_logits, torch.ones(N, dtype=torch.int64, device=sess.dev),
                              torch.arange(N, dtype=torch.int64, device=sess.dev), K)
     sess.n_steps += scratch.n_steps
     return logits
@@ -1952,35 +1963,11 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
     h_anc = loop.h_anc[:E].cpu().numpy()
     h_ess, h_res = loop.h_ess[:E].cpu().numpy(), loop.h_res[:E].cpu().numpy()
     h_lw = loop.h_lw[:E].cpu().numpy()
-    line = particle_lineage(h_anc, N)
-    seg = np.minimum(np.arange(len(rows)) // R, E)                     # the segment each drawn row belongs to
     h_r = None if W is None else loop.h_r[:loop.n_rewards].cpu().numpy()
-    out = []
-    for g in range(N // K):
-        songs, logps, rewards = [], [], None if W is None else []
-        for n in range(g * K, (g + 1) * K):
-            t = np.arange(int(lens[n]))
-            src = line[seg[t], n]
-            songs.append(np.concatenate([heads[n], rows[t, src]]))
-            logps.append(lps[t, src].astype(np.float32).reshape(-1, A, 2))
-            if W is not None:                                          # window j's event followed step (j + 1) W, or the
-                j = np.arange(-(-int(lens[n]) // W))                   # run's last: the row the lineage lived in then
-                at = np.minimum((j + 1) * W, len(rows)) - 1
-                rewards.append(h_r[j, line[seg[at], n]].astype(np.float32))
-        w = lw[g * K:(g + 1) * K].astype(np.float32)
-        # events after the song's last particle ended are not its own: they depend on the other songs of the pool.  The
-        # song had a live particle up to its last resampling (which may have replaced the last live one by copies of
-        # finished ones) and, after it, until the longest final particle ended
-        hit = np.nonzero(h_res[:, g])[0]
-        live = max(int(np.count_nonzero((np.arange(E) + 1) * R < int(lens[g * K:(g + 1) * K].max()))),
-                   int(hit.max()) + 1 if len(hit) else 0)
-        out.append(ParticleSet(songs, logps, w, float(log_z[g]) + logmeanexp(w), h_ess[:live, g].copy(),
-                               h_res[:live, g] != 0, h_anc[:live, g * K:(g + 1) * K] - g * K,
-                               h_lw[:live, g * K:(g + 1) * K].copy(), rewards))
-        if W is not None:                                              # the reward events of the same span of steps
-            n_r = max(-(-int(lens[g * K:(g + 1) * K].max()) // W), (int(hit.max()) + 1) * R // W if len(hit) else 0)
-            out[-1].event_rewards = h_r[:n_r, g * K:(g + 1) * K].copy()
-            out[-1].beta = _song_beta(reward, g)
+    out = particle_pool_sets(heads, rows, lps, lens, lw, log_z, h_anc, h_lw, h_ess, h_res, K, R, h_r=h_r, window=W)
+    if W is not None:
+        for g, ps in enumerate(out):
+            ps.beta = _song_beta(reward, g)
     if log is not None:
         log("%d songs x %d particles: %d tokens, %d steps, %d resampling events"
             % (N // K, K, sum(len(x) for s in out for x in s.songs), done, E))
@@ -1991,10 +1978,67 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
                      drawn=int(lens.sum()), row_bytes=loop.row_bytes, moved_rows=[int(m) for m in moved],
                      resampled_groups=[int(r.sum()) for r in h_res], groups=N // K,
                      prefilled_prompts=0 if prefill is None else N // K if share_prefill else N,
-                     event_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)] for m in loop.timed or []])
+                     event_ms=_event_ms(loop.timed))
         if W is not None:
-            stats.update(reward_events=loop.n_rewards, reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
-                                                                  for m in loop.reward_timed or []])
+            stats.update(reward_events=loop.n_rewards, reward_ms=_event_ms(loop.reward_timed))
+    return out
+
+
+def _song_particle_set(head, toks, lps, lens, w, logz, anc, h_lw, h_ess, h_res, R, h_r=None, W=None):
+    """One song's ParticleSet (beta aside) from its group's columns over the T steps it held the group: the rules the
+    lock-step pool and the stream share; numpy only.  head (P, A): its prompt rows; toks (T, K, A),
+    lps (T, K, A, 2): what the group's K rows drew; lens (K,), w (K,), logz: the final particles' drawn rows and weights
+    and the events' evidence; the song's own events, event e after its row (e + 1) R: anc (E, K) in-group, h_lw (E, K),
+    h_ess (E,), h_res (E,).  Row tau of final particle k was drawn by group row lineage[min(tau // R, E), k].  The event
+    fields are cut to the events at which the song had a live particle, the first max(#{e : (e + 1) R < longest}, last
+    hit + 1): up to its last resampling (which may have replaced the last live particle by copies of finished ones) and,
+    after it, until the longest final particle ended; later events depend on the other songs of the run.
+    h_r (n, K) f32, the reward events from the song's first window on, and W: window j < ceil(lens[k] / W) of particle k
+    is read at the group row its lineage lived in at the song's row min((j + 1) W, T) - 1 (T: the event of a run that
+    ended inside the window followed its last step); event_rewards spans the same steps, max(ceil(longest / W), (last
+    hit + 1) R // W) events."""
+    K, A, E = len(lens), toks.shape[2], len(anc)
+    line = particle_lineage(anc, K)
+    songs, logps, rewards = [], [], None if W is None else []
+    for k in range(K):
+        tau = np.arange(int(lens[k]))
+        src = line[np.minimum(tau // R, E), k]
+        songs.append(np.concatenate([head, toks[tau, src]]))
+        logps.append(np.asarray(lps[tau, src], dtype=np.float32).reshape(-1, A, 2))
+        if W is not None:
+            j = np.arange(-(-int(lens[k]) // W))
+            at = np.minimum((j + 1) * W, len(toks)) - 1
+            rewards.append(np.asarray(h_r[j, line[np.minimum(at // R, E), k]], dtype=np.float32))
+    longest = int(np.max(lens))
+    hit = np.nonzero(h_res)[0]
+    last = int(hit.max()) + 1 if len(hit) else 0
+    live = max(int(np.count_nonzero((np.arange(E) + 1) * R < longest)), last)
+    w = np.array(w, dtype=np.float32)
+    ps = ParticleSet(songs, logps, w, float(logz) + logmeanexp(w), np.array(h_ess[:live]), np.asarray(h_res[:live]) != 0,
+                     anc[:live], np.array(h_lw[:live]), rewards)
+    if W is not None:
+        ps.event_rewards = np.array(h_r[:max(-(-longest // W), last * R // W)], dtype=np.float32)
+    return ps
+
+
+def particle_pool_sets(heads, rows, logps, lens, lw, log_z, h_anc, h_lw, h_ess, h_res, particles, every, h_r=None,
+                       window=None):
+    """The ParticleSets of a lock-step particle pool from what the device wrote; numpy only.
+    heads: the N pool rows' prompt rows, a song's K rows holding one prompt (row g K's is read); rows (T, N, A) int64,
+    the rows of T steps, logps (T, N, A, 2) f32 beside them; lens (N,) int64, lw (N,) f32, log_z (G,) f32: the rows each
+    pool row drew, the final weights, the events' evidence; the run's events e = 0, 1, ..., event e after step (e + 1) R:
+    h_anc (E, N) int64 pool-row ancestors, h_lw (E, N) f32, h_ess (E, G) f32, h_res (E, G) int32.  K = particles, R =
+    every.  Song g holds rows g K .. g K + K - 1 from step 0 on and every event of the run is one of its own:
+    _song_particle_set on those columns.  h_r (n, N) f32, reward event i after step (i + 1) W, the last one after step
+    T where the run ended inside a window, and window = W: the run carried a reward."""
+    K, R = int(particles), int(every)
+    W = None if window is None or h_r is None else int(window)
+    out = []
+    for g in range(len(heads) // K):
+        own = slice(g * K, (g + 1) * K)
+        out.append(_song_particle_set(heads[g * K], rows[:, own], logps[:, own], lens[own], lw[own], log_z[g],
+                                      h_anc[:, own] - g * K, h_lw[:, own], h_ess[:, g], h_res[:, g], R,
+                                      None if W is None else h_r[:, own], W))
     return out
 
 
@@ -2008,21 +2052,18 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
      a list of n_songs arrays, each song's own; stats then also gains gate_wait_group_steps, the steps
     groups spent without a song while songs were still unassigned (the bank's gate), kept out of idle_group_steps.
     The song of group g at step t is rows[t, g K, 0] // K; it held the group over the steps [t0, t1) that show it, t0 a
-    multiple of R, and its own events j = 0, 1, ... are the run's events t0 / R + j, (t1 - t0) // R of them.  Lineage:
-    particle_lineage on the in-group ancestors of those events; row tau of final particle k was drawn by pool row
-    g K + lineage[min(tau // R, events), k] at step t0 + tau.  The event fields are cut as in the lock-step pool: while the
-    song had a live particle (up to its last resampling, or the end of its longest final particle).
+    multiple of R, and its own events j = 0, 1, ... are the run's events t0 / R + j, (t1 - t0) // R of them.  Its set is
+    _song_particle_set's, the lock-step pool's rules, on the columns [t0:t1, g K .. g K + K - 1] and those events, once
+    they are found consistent: row tau of final particle k was drawn at step t0 + tau.
     stats (a dict, optional) gains wait_group_steps -- steps groups spent with every particle done, waiting for the
     boundary --, idle_group_steps, steps of groups without a song, and start_steps, the step each song's first row was
     drawn at.
     h_r (the run's reward events, event i after step (i + 1) W: (n, N) f32) and window = W: the run carried
-    a reward.  Songs then start at multiples of B = lcm(R, W) only, and ParticleSet.rewards and event_rewards are filled:
-    window j of final particle k is the run's reward event t0 / W + j, read at pool row
-    g K + lineage[min(tau // R, events), k] with tau = (j + 1) W - 1, the row the lineage lived in when the event ran;
-    ceil(L_k / W) windows; event_rewards is cut like the lock-step pool's, with the song's own event indices.  A song
-    that starts off a multiple of B, or a group released before its song's last window closed, is inconsistent.  stats
-    then also gains boundary_wait_group_steps: the group-steps waited for a multiple of B beyond the next multiple of
-    R."""
+    a reward.  Songs then start at multiples of B = lcm(R, W) only, and ParticleSet.rewards and event_rewards are filled,
+    by the same rules: the song's window j is the run's reward event t0 / W + j, and every window closes while the song
+    holds the group.  A song that starts off a multiple of B, or a group released before its song's last window closed,
+    is inconsistent.  stats then also gains boundary_wait_group_steps: the group-steps waited for a multiple of B beyond
+    the next multiple of R."""
     rows = np.asarray(rows)
     T, N = rows.shape[:2]
     K, R, A = int(particles), int(every), rows.shape[2] - 2
@@ -2053,39 +2094,21 @@ def particle_stream_sets(rows, logps, h_anc, h_lw, h_ess, h_res, out_lw, out_len
             e0 = int(t0) // R
             E = min(int(t1 - t0) // R, len(h_anc) - e0)
             span, own = slice(e0, e0 + E), slice(g * K, (g + 1) * K)
-            anc = np.asarray(h_anc[span, own], dtype=np.int64) - g * K
-            line = particle_lineage(anc, K)
             lens = np.asarray(out_len[s * K:(s + 1) * K], dtype=np.int64)
             longest = int(lens.max())
             if longest < 1 or longest > t1 - t0:
                 raise RuntimeError("particle stream output is inconsistent: song %d has lengths %s in %d steps"
                                    % (s, list(lens), t1 - t0))
-            songs, lps = [], []
-            for k in range(K):
-                tau = np.arange(int(lens[k]))
-                src = g * K + line[np.minimum(tau // R, E), k]
-                songs.append(np.concatenate([head[s] if per_song else head, rows[t0 + tau, src, 1:1 + A]]))
-                lps.append(np.asarray(logps[t0 + tau, src], dtype=np.float32).reshape(-1, A, 2))
-            w = np.asarray(out_lw[s * K:(s + 1) * K], dtype=np.float32).copy()
-            hit = np.nonzero(h_res[span, g])[0]
-            live = max(int(np.count_nonzero((np.arange(E) + 1) * R < longest)), int(hit.max()) + 1 if len(hit) else 0)
-            cut = slice(e0, e0 + live)
-            out[s] = ParticleSet(songs, lps, w, float(out_logz[s]) + logmeanexp(w), np.array(h_ess[cut, g]),
-                                 np.asarray(h_res[cut, g]) != 0, anc[:live], np.array(h_lw[cut, own]))
-            if W is not None:
+            if W is not None:                       # its windows closed while it held the group: no partial one here
                 w0, n_win = int(t0) // W, -(-longest // W)
                 if n_win * W > t1 - t0 or w0 + n_win > len(h_r):
                     raise RuntimeError("particle stream output is inconsistent: song %d held its group for %d steps, "
                                        "its last window of %d rows closes after %d" % (s, t1 - t0, W, n_win * W))
-                out[s].rewards = []
-                for k in range(K):
-                    j = np.arange(-(-int(lens[k]) // W))
-                    tau = (j + 1) * W - 1
-                    out[s].rewards.append(np.asarray(h_r[w0 + j, g * K + line[np.minimum(tau // R, E), k]],
-                                                     dtype=np.float32))
-                n_r = max(n_win, (int(hit.max()) + 1) * R // W if len(hit) else 0)
-                out[s].event_rewards = np.array(h_r[w0:w0 + n_r, own], dtype=np.float32)
                 beyond += int(t1 - t0) - -(-longest // R) * R
+            out[s] = _song_particle_set(head[s] if per_song else head, rows[t0:t1, own, 1:1 + A], logps[t0:t1, own], lens,
+                                        out_lw[s * K:(s + 1) * K], out_logz[s],
+                                        np.asarray(h_anc[span, own], dtype=np.int64) - g * K, h_lw[span, own],
+                                        h_ess[span, g], h_res[span, g], R, None if W is None else h_r[w0:, own], W)
             wait += int(t1 - t0) - longest
             starts[s] = int(t0)
     missing = [s for s, ps in enumerate(out) if ps is None]
@@ -2219,9 +2242,7 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
         if bank is not None:
             stats.update(loop.stats())
         if reward is not None:
-            stats.update(reward_events=len(h_r),
-                         reward_ms=[[m[i].elapsed_time(m[i + 1]) for i in range(3)]
-                                    for m in loop.reward_timed or []])
+            stats.update(reward_events=len(h_r), reward_ms=_event_ms(loop.reward_timed))
     return sets
 
 

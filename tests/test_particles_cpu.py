@@ -10,6 +10,9 @@ rows, and the three C-ABI entries' presence and refusals.  No GPU.
    disagrees with the float64 restatement only where a threshold lies within (K + 2) 2^-23 s of a prefix-sum boundary,
    and on fewer than 1 % of the entries of each K: the seeds leave the GPU comparison that room.
 3. generation.particle_lineage on a hand-written three-event ancestry with a swap and a row that dies out.
+3b. generation.particle_pool_sets on a hand-written lock-step trace: two songs, K = 3, R = 2, seven steps; two final
+   particles that share a prefix, a song whose events are cut by its last resampling, a pool without an event; the same
+   trace, one step longer, through generation.particle_stream_sets gives the same sets bit for bit.
 4. cwlt_particle_weigh / _resample / _gather are declared, bound and exported, and refuse bad arguments with 1001.
 """
 import ctypes
@@ -192,6 +195,123 @@ def test_particle_set_weights_and_draw():
     picks = [ps.draw(rng, return_index=True)[1] for _ in range(400)]
     assert 2 not in picks and 250 < picks.count(1) < 350
     assert ps.draw(np.random.default_rng(1)) is songs[ps.draw(np.random.default_rng(1), return_index=True)[1]]
+
+
+# ---- 3b. the lock-step rebuild -------------------------------------------------------------------------------------------
+POOL_K, POOL_R, POOL_W, POOL_A = 3, 2, 4, 2
+
+
+def pool_trace(T=7):
+    """A lock-step pool of two songs x 3 particles as the device leaves it after T steps, R = 2, W = 4: T // 2 events and
+    ceil(T / 4) reward events (at T = 7 the last one closes a window of 3 rows).  Song 0 (pool rows 0, 1, 2) drew 7, 5
+    and 3 rows and was resampled at event 1, ancestors [0, 0, 2]; song 1 (rows 3, 4, 5) drew 2, 2 and 1 rows and its
+    only resampling, event 0, copied row 4 over row 3.  Shared with tests/test_reward_cpu.py."""
+    K, R, W, A, N = POOL_K, POOL_R, POOL_W, POOL_A, 2 * POOL_K
+    rows = np.zeros((T, N, A), dtype=np.int64)
+    lps = np.zeros((T, N, A, 2), dtype=np.float32)
+    for t in range(T):
+        for n in range(N):
+            rows[t, n] = (100 * t + n, 7)
+            lps[t, n] = -(10 * t + n) - np.arange(A * 2).reshape(A, 2) / 8.0
+    E = T // R
+    h_anc = np.tile(np.arange(N), (E, 1))
+    h_res = np.zeros((E, 2), dtype=np.int32)
+    h_anc[1, :K], h_res[1, 0] = [0, 0, 2], 1
+    h_anc[0, K:], h_res[0, 1] = K + np.array([1, 1, 2]), 1
+    song_heads = [np.array([[0, 9]], dtype=np.int64), np.array([[1, 9], [2, 9]], dtype=np.int64)]
+    return {"heads": [h for h in song_heads for _ in range(K)], "song_heads": song_heads, "rows": rows, "logps": lps,
+            "lens": np.array([7, 5, 3, 2, 2, 1], dtype=np.int64), "lw": -np.arange(N, dtype=np.float32) / 4,
+            "log_z": np.array([-1.5, -2.5], dtype=np.float32), "h_anc": h_anc,
+            "h_lw": -np.arange(E * N, dtype=np.float32).reshape(E, N) / 16,
+            "h_ess": (np.arange(2 * E, dtype=np.float32).reshape(E, 2) + 1) / 4, "h_res": h_res,
+            "h_r": (10 * np.arange(-(-T // W))[:, None] + np.arange(N)[None, :] + 0.5).astype(np.float32)}
+
+
+def pool_sets(tr, reward):
+    return generation.particle_pool_sets(tr["heads"], tr["rows"], tr["logps"], tr["lens"], tr["lw"], tr["log_z"],
+                                         tr["h_anc"], tr["h_lw"], tr["h_ess"], tr["h_res"], POOL_K, POOL_R,
+                                         h_r=tr["h_r"] if reward else None, window=POOL_W if reward else None)
+
+
+def check_pool_sets(sets, tr):
+    """Every field of the two sets but the rewards against the values written out by hand."""
+    K = POOL_K
+    assert len(sets) == 2 and all(len(ps.songs) == K and ps.beta is None for ps in sets)
+    # (step, pool row) of every drawn row: song 0's particle 1 shares particle 0's first four rows, drawn in row 0
+    # before event 1; song 1's particles 0 and 1 are both row 4's two rows
+    want = [[[(t, 0) for t in range(7)], [(0, 0), (1, 0), (2, 0), (3, 0), (4, 1)], [(0, 2), (1, 2), (2, 2)]],
+            [[(0, 4), (1, 4)], [(0, 4), (1, 4)], [(0, 5)]]]
+    for s, ps in enumerate(sets):
+        for k in range(K):
+            toks = np.array([[100 * t + n, 7] for t, n in want[s][k]], dtype=np.int64)
+            assert np.array_equal(ps.songs[k], np.concatenate([tr["song_heads"][s], toks])), (s, k)
+            assert np.array_equal(ps.logprobs[k], np.stack([tr["logps"][t, n] for t, n in want[s][k]])), (s, k)
+            assert ps.logprobs[k].dtype == np.float32 and ps.logprobs[k].shape == (len(toks), POOL_A, 2)
+        w = tr["lw"][s * K:(s + 1) * K]
+        assert np.array_equal(ps.log_weights, w) and ps.log_weights.dtype == np.float32
+        assert ps.log_evidence == float(tr["log_z"][s]) + sampling.logmeanexp(w)
+    # song 0: its longest particle drew 7 rows: the events after rows 2, 4 and 6 are its own
+    assert sets[0].ancestors.tolist() == [[0, 1, 2], [0, 0, 2], [0, 1, 2]] and sets[0].ancestors.dtype == np.int64
+    assert sets[0].resampled.tolist() == [False, True, False] and sets[0].resampled.dtype == bool
+    assert np.array_equal(sets[0].ess, tr["h_ess"][:3, 0]) and np.array_equal(sets[0].event_log_weights,
+                                                                             tr["h_lw"][:3, :K])
+    # song 1: no event e has (e + 1) R < 2, its longest particle; event 0 is its own because it resampled the song
+    assert sets[1].ancestors.tolist() == [[1, 1, 2]] and sets[1].resampled.tolist() == [True]
+    assert np.array_equal(sets[1].ess, tr["h_ess"][:1, 1]) and np.array_equal(sets[1].event_log_weights,
+                                                                             tr["h_lw"][:1, K:])
+    assert all(ps.ess.dtype == np.float32 and ps.event_log_weights.dtype == np.float32 for ps in sets)
+
+
+def test_pool_sets_hand_trace():
+    """generation.particle_pool_sets without a reward: two songs, K = 3, R = 2, seven steps, three events."""
+    tr = pool_trace()
+    sets = pool_sets(tr, reward=False)
+    check_pool_sets(sets, tr)
+    assert all(ps.rewards is None and ps.event_rewards is None for ps in sets)
+    # h_r without a window, or a window without h_r, is the run without a reward
+    args = [tr[k] for k in ("heads", "rows", "logps", "lens", "lw", "log_z", "h_anc", "h_lw", "h_ess", "h_res")]
+    assert generation.particle_pool_sets(*args, POOL_K, POOL_R, window=POOL_W)[0].rewards is None
+    assert generation.particle_pool_sets(*args, POOL_K, POOL_R, h_r=tr["h_r"])[0].rewards is None
+    # a pool with no event at all: one step
+    tr.update(rows=tr["rows"][:1], logps=tr["logps"][:1], lens=np.ones(6, dtype=np.int64),
+              **{k: tr[k][:0] for k in ("h_anc", "h_lw", "h_ess", "h_res")})
+    sets = pool_sets(tr, reward=False)
+    assert all(ps.ancestors.shape == (0, POOL_K) and len(ps.ess) == 0 and [len(s) for s in ps.songs] == [p] * 3
+               for ps, p in zip(sets, (2, 3)))
+
+
+def stream_sets(tr, reward):
+    """The trace as a particle stream's: ring ids = the row index (group g holds song g from step 0 on), the release's
+    outputs = the pool's finals, a head per song."""
+    T, N = tr["rows"].shape[:2]
+    ring = np.concatenate([np.tile(np.arange(N)[None, :, None], (T, 1, 1)), tr["rows"],
+                           np.zeros((T, N, 1), dtype=np.int64)], axis=2)
+    return generation.particle_stream_sets(ring, tr["logps"], tr["h_anc"], tr["h_lw"], tr["h_ess"], tr["h_res"], tr["lw"],
+                                           tr["lens"], tr["log_z"], POOL_K, POOL_R, 2, tr["song_heads"],
+                                           h_r=tr["h_r"] if reward else None, window=POOL_W if reward else None)
+
+
+def same_sets(a, b):
+    """Field by field and bit for bit, dtypes and shapes included."""
+    def same(x, y):
+        if isinstance(x, list):
+            return len(x) == len(y) and all(same(p, q) for p, q in zip(x, y))
+        if x is None or y is None:
+            return x is None and y is None
+        return x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes()
+    fields = ("songs", "logprobs", "log_weights", "ess", "resampled", "ancestors", "event_log_weights", "rewards",
+              "event_rewards")
+    return a.log_evidence == b.log_evidence and a.beta == b.beta and all(same(getattr(a, f), getattr(b, f))
+                                                                         for f in fields)
+
+
+def test_pool_trace_as_a_stream_trace():
+    """Eight steps, so that every window closes: the stream's rebuild gives the pool's sets."""
+    tr = pool_trace(T=8)
+    pool = pool_sets(tr, reward=False)
+    check_pool_sets(pool, tr)                                           # the eighth step and fourth event change nothing
+    stream = stream_sets(tr, reward=False)
+    assert len(stream) == 2 and all(same_sets(a, b) for a, b in zip(stream, pool))
 
 
 # ---- 4. ABI ----------------------------------------------------------------------------------------------------------------

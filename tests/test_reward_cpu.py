@@ -4,6 +4,9 @@ C-ABI entries' presence and refusals, and the Python-level refusals.  No GPU.
 1. sampling.reward_apply_f32: the product is rounded before the sum (a case where an fma would differ is included); a
    row without a live slot keeps its weight bit for bit and records 0 whatever its reward holds (NaN, +-inf); beta = 0
    leaves every weight bit for bit; negative beta.
+1b. generation.particle_pool_sets(h_r=, window=) on the hand-written lock-step trace of tests/test_particles_cpu.py: a
+   window reward read from the ancestor's row, a run that ends inside a window, a song whose events are cut by its last
+   resampling; the same trace, one step longer, through generation.particle_stream_sets.
 2. cwlt_reward_push / _window / _apply are declared, bound and exported at ABI > 32, and refuse with 1001, before any
    launch: null pointers, W < 1, filled outside 1 .. W, n_attr outside 1 .. 8, rows < 1.
 3. generate_particles / generate / WindowReward refuse, before the model is looked at: a reward that is not callable,
@@ -18,6 +21,8 @@ import pytest
 
 import rlmg_amd  # noqa: F401
 from rlmg_amd import generation, sampling
+
+from test_particles_cpu import check_pool_sets, pool_sets, pool_trace, same_sets, stream_sets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("cwlt_reward_push", "cwlt_reward_window", "cwlt_reward_apply")
@@ -61,6 +66,44 @@ def test_apply_restatement_dead_rows_and_beta_zero():
     r = rng.normal(0, 1000, 201).astype(np.float32)
     got, rec = sampling.reward_apply_f32(lw, r, np.ones(201, np.int64), 0.0)
     assert np.array_equal(_bits(got), _bits(lw)) and np.array_equal(_bits(rec), _bits(r))
+
+
+# ---- 1b. the lock-step rebuild with rewards ------------------------------------------------------------------------------
+def test_pool_sets_rewards_hand_trace():
+    """generation.particle_pool_sets(h_r=, window=) on tests/test_particles_cpu.py's trace: W = 4 over seven steps, one
+    whole window and a last one of 3 rows, closed by the run's second reward event (h_r[i, n] = 10 i + n + 0.5)."""
+    tr = pool_trace()
+    sets = pool_sets(tr, reward=True)
+    check_pool_sets(sets, tr)
+    f = lambda *v: np.float32(v)                                        # noqa: E731
+    # song 0: window 0 closed after row 4, when final particle 1's lineage still lived in row 0 (event 1 had copied row
+    # 0 over row 1, the swap shows from row 5 on); the partial window closed after row 7, every lineage in its own row
+    want = (f(0.5, 10.5), f(0.5, 11.5), f(2.5))
+    assert [len(r) for r in sets[0].rewards] == [2, 2, 1]
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(sets[0].rewards, want)), sets[0].rewards
+    assert sets[0].event_rewards.shape == (2, 3) and np.array_equal(_bits(sets[0].event_rewards), _bits(tr["h_r"][:, :3]))
+    # song 1: 2, 2 and 1 rows, one window each, read after event 0 in the rows themselves; the run's second reward
+    # event came after the song's last particle and its last resampling: not its own
+    want = (f(3.5), f(4.5), f(5.5))
+    assert all(np.array_equal(_bits(a), _bits(b)) for a, b in zip(sets[1].rewards, want)), sets[1].rewards
+    assert sets[1].event_rewards.shape == (1, 3) and np.array_equal(_bits(sets[1].event_rewards), _bits(tr["h_r"][:1, 3:]))
+    assert all(r.dtype == np.float32 for ps in sets for r in ps.rewards)
+    assert all(ps.event_rewards.dtype == np.float32 and ps.beta is None for ps in sets)
+    # the other fields are those of the run without a reward
+    for a, b in zip(sets, pool_sets(tr, reward=False)):
+        a.rewards = a.event_rewards = None
+        assert same_sets(a, b)
+
+
+def test_pool_trace_with_rewards_as_a_stream_trace():
+    """Eight steps, so that the second window closes inside the run: the stream's rebuild gives the pool's sets, rewards
+    and event_rewards included, and both give the seven-step run's rewards."""
+    tr = pool_trace(T=8)
+    pool, stream = pool_sets(tr, reward=True), stream_sets(tr, reward=True)
+    check_pool_sets(pool, tr)
+    assert len(stream) == 2 and all(same_sets(a, b) for a, b in zip(stream, pool))
+    for a, b in zip(pool, pool_sets(pool_trace(), reward=True)):
+        assert same_sets(a, b)
 
 
 # ---- 2. ABI ----------------------------------------------------------------------------------------------------------------

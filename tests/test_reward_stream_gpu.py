@@ -12,6 +12,8 @@ fixture model (128 / 2 layers / 2 heads) against the lock-step pool.
 3. A beta per song: a constant list is the scalar run; a song with beta 0 is the song without a reward; pool equals
    stream; weights and evidence against float64 with each song's own beta.
 4. beta = 0 on the stream; WindowReward on the small discriminator at W = 50, R = 10, chunk = 100; generate().
+5. The launch sequence of both particle loops, with and without a reward, against patterns written out from the
+   loops' docstrings: 3 songs x 2 particles, (R, W, chunk) = (2, 4, 4), max_tokens 8, bar_cond 4, graphs off.
 
 bar_cond 9 and max_tokens 48 (tests/test_reward_gpu.py's): the particles draw 30 .. 39 rows at (R, W, chunk) = (4, 8, 16),
 19 .. 40 at (8, 4, 16) and 30 .. 43 at (4, 6, 24) (the test prints them), three or more windows each, and at 3 slots
@@ -390,3 +392,89 @@ def test_generate_passes_the_reward_through(world, tmp_path, monkeypatch):
         assert any(song.shape == s.shape and (song == s).all() for s in ps.songs) and ps.beta == kw["beta"][i]
     with pytest.raises(ValueError, match="reward= with slots="):        # generate's chunk is 128: W = 50 stays refused
         generation.generate(net, w2e, n_songs=5, slots=2, particles=K4, path_gendir=str(tmp_path), reward=_parity)
+
+
+# ---- 5. the launch sequence ----------------------------------------------------------------------------------------------
+@pytest.fixture
+def calls(monkeypatch):
+    """Every ops._call of the test by entry name, the call itself forwarded unchanged; graphs off."""
+    seen, real = [], ops._call
+
+    def recording(name, *args, **kw):
+        seen.append(name)
+        return real(name, *args, **kw)
+
+    monkeypatch.setattr(ops, "GRAPHS_ENABLED", False)
+    monkeypatch.setattr(ops, "_call", recording)
+    return seen
+
+
+# "all on": S and Z of the model and of the reference, then tok, bar, beat, seen, len, done, cap; a reward adds recent, live
+FAMILIES = 4 + 7
+WINDOW = ["cwlt_reward_window", "cwlt_reward_apply"]
+RELEASE = ["cwlt_particle_release", "cwlt_particle_fill", "cwlt_particle_fill"]   # the release, then beat and seen
+
+
+def _watched(names):
+    return [n for n in names if n.startswith(("cwlt_particle_", "cwlt_reward_")) or n in ("cwlt_stream_refill",
+                                                                                         "cwlt_count_bars")]
+
+
+def _lock_step_launches(T, R, W, reward):
+    """_ParticleLoop's docstring for T tokens: per token the bar count, under a reward the push, the weigh; after every
+    W-th token the reward event, ahead of the resampling event after every R-th: the resampling, then every family to
+    scratch and back; a run that ends inside a window closes it with one more reward event."""
+    gathers = ["cwlt_particle_gather"] * (2 * (FAMILIES + (2 if reward else 0)))
+    out = []
+    for t in range(1, T + 1):
+        out += ["cwlt_count_bars"] + ["cwlt_reward_push"] * reward + ["cwlt_particle_weigh"]
+        if reward and t % W == 0:
+            out += WINDOW
+        if t % R == 0:
+            out += ["cwlt_particle_resample"] + gathers
+    return out + (WINDOW if reward and T % W else [])
+
+
+def _stream_launches(T, R, W, reward):
+    """_ParticleStreamLoop's docstring for T steps: the first release; per token the refill of the model's pool and of
+    the reference's, the bar count, under a reward the push, the weigh, the advance; after every W-th token the reward
+    event, ahead of the event after every R-th: the keyed resampling, every family to scratch and back and, at
+    multiples of R -- of lcm(R, W) under a reward --, the release and its fills."""
+    gathers = ["cwlt_particle_gather"] * (2 * (FAMILIES + (2 if reward else 0)))
+    hand = R * W // int(np.gcd(R, W)) if reward else R
+    out = list(RELEASE)
+    for t in range(1, T + 1):
+        out += ["cwlt_stream_refill"] * 2 + ["cwlt_count_bars"] + ["cwlt_reward_push"] * reward
+        out += ["cwlt_particle_weigh", "cwlt_particle_advance"]
+        if reward and t % W == 0:
+            out += WINDOW
+        if t % R == 0:
+            out += ["cwlt_particle_resample_keyed"] + gathers + (RELEASE if t % hand == 0 else [])
+    return out
+
+
+def test_launch_sequences(world, calls):
+    """3 songs x 2 particles, "all on", (R, W, chunk) = (2, 4, 4), max_tokens 8 (7 drawn rows at most), bar_cond 4: the
+    lock-step pool and the 2-slot stream, each with and without a reward, launch what their docstrings say, in that
+    order; T is read off the run (the weigh launches) and must be a length the run can have."""
+    w = world
+    R, W, chunk = 2, 4, 4
+    for slots in (None, 2):
+        for reward in (None, _parity):
+            del calls[:]
+            torch.manual_seed(SEED)
+            sets = generation.generate_particles(w["net"], w["w2e"], 3, 2, bar_cond=4, max_tokens=8, chunk=chunk,
+                                                 resample_every=R, reward_window=W, ess=1.0, reward=reward, beta=BETA,
+                                                 slots=slots, **w["all on"])
+            got = _watched(calls)
+            T = got.count("cwlt_particle_weigh")
+            print("launch sequence, slots %s, reward %s: %d tokens, %d launches" % (slots, reward is not None, T, len(got)))
+            assert len(sets) == 3 and max(len(s) for ps in sets for s in ps.songs) <= 8
+            if slots is None:
+                assert T in (4, 7)                                      # one chunk, or the cap
+                want = _lock_step_launches(T, R, W, reward is not None)
+            else:
+                assert T >= 2 * chunk and T % chunk == 0               # whole chunks, one enqueued past the end
+                want = _stream_launches(T, R, W, reward is not None)
+            assert got == want, (slots, reward is not None, T)
+            assert reward is not None or not any(n.startswith("cwlt_reward_") for n in got)
