@@ -106,6 +106,38 @@ int cwlt_causal_linear_bwd_dq(const void* q, const void* k, const void* v, const
                               int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo,
                               int64_t lddq, int segments, const float* seg_ws, int dtype, void* stream);
 
+/* Packed form of the four calls above: songs of different lengths laid end to end in one (rows, H, head_dim) row buffer.
+ * cu: n_songs + 1 int32 row offsets ON THE DEVICE, cu[0] = 0, strictly increasing, cu[n_songs] = rows; song s owns rows
+ * [cu[s], cu[s + 1]) and is scanned from its own row 0 exactly as the rectangular call scans it alone (N = 1, L = its
+ * length, segments = 1): same kernels, instantiated with the offset table in place of (N, L).  One workgroup per
+ * (song, head), never segmented.  zinv and dden are (rows, H) by packed row; final_state and colsum_* are per
+ * (song, head): cwlt_scan_final_state_floats(n_songs, H) floats / (n_songs, H*64) f32.  The host does not read cu: a
+ * table that is not as described is the caller's error.  CWLT_ERR_ARG before any launch for NULL pointers, n_songs < 1,
+ * head_dim != 64 and row strides the route cannot take (as above: multiples of 4; final_state, colsum_*, dden and the
+ * sweep need bf16 with multiples of 8). */
+int cwlt_causal_linear_fwd_packed(const void* q, const void* k, const void* v, void* out, float* zinv, const int* cu,
+                                  int n_songs, int H, int head_dim,
+                                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                                  float eps, float* final_state, int dtype, void* stream);
+int cwlt_causal_linear_bwd_sweep_packed(const void* q, const void* k, const void* v, const void* out,
+                                        const float* zinv, const void* dout, const float* final_state,
+                                        void* dq, void* dk, void* dv,
+                                        float* colsum_q, float* colsum_k, float* colsum_v,
+                                        const int* cu, int n_songs, int H, int head_dim,
+                                        int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo,
+                                        int64_t lddq, int64_t lddk, int64_t lddv, int dtype, void* stream);
+int cwlt_causal_linear_bwd_dkdv_packed(const void* q, const void* k, const void* v, const void* out,
+                                       const float* zinv, const void* dout, void* dk, void* dv,
+                                       float* colsum_k, float* colsum_v, float* dden,
+                                       const int* cu, int n_songs, int H, int head_dim,
+                                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo,
+                                       int64_t lddk, int64_t lddv, int dtype, void* stream);
+int cwlt_causal_linear_bwd_dq_packed(const void* q, const void* k, const void* v, const void* out,
+                                     const float* zinv, const void* dout, void* dq, float* colsum_q, const float* dden,
+                                     const int* cu, int n_songs, int H, int head_dim,
+                                     int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo,
+                                     int64_t lddq, int dtype, void* stream);
+
 /* ---- fused residual + dropout + LayerNorm ------------------------------------------------------
  * s = x + dropout_p(a) ; y = LayerNorm(s) * gamma + beta.  Replaces, inside fast_transformers'
  * TransformerEncoderLayer.forward (built at dqn_policy/model.py:128-137, called :232):
@@ -221,6 +253,11 @@ int cwlt_gemm_bf16_tune(int variant, void* trace);
  * backward (dx = dropout with the same seed applied to dy). */
 int cwlt_posenc_dropout(const void* x, const float* pe, void* y, int64_t rows, int T, int D,
                         float p, uint64_t seed, const uint64_t* seed_base, int dtype, void* stream);
+/* Positions from a table (packed songs): y = dropout_p(x + pe[pos[r]]), pos = `rows` int32 ON THE DEVICE, each inside the
+ * pe buffer (the caller's check: the host does not read it); pe and pos must be given.  Row r keeps the dropout stream
+ * cwlt_posenc_dropout gives row r for the same seed, so the backward is still cwlt_posenc_dropout(dy, pe = NULL). */
+int cwlt_posenc_dropout_pos(const void* x, const float* pe, const int* pos, void* y, int64_t rows, int D,
+                            float p, uint64_t seed, const uint64_t* seed_base, int dtype, void* stream);
 
 /* ---- compound-word multi-embedding --------------------------------------------------------------
  * out[r, off_f : off_f+width_f] = table_f[tokens[r, f]] * sqrt(width_f), f = 0..n_attr-1.
@@ -248,6 +285,11 @@ int cwlt_cw_embed_bwd(const int64_t* tokens, const int* widths, const int* nrows
 int cwlt_cw_embed_proj_fwd(const int64_t* tokens, const void* tproj, const int* nrows, int n_attr,
                            const float* bias, const float* pe, void* out, int64_t rows, int T, int D,
                            float p, uint64_t seed, const uint64_t* seed_base, int dtype, void* stream);
+/* The same with positions from a table (packed songs): pe[pos[r], :] in place of pe[r % T, :]; pos as in
+ * cwlt_posenc_dropout_pos, pe must be given.  The backward below never reads pe and serves both. */
+int cwlt_cw_embed_proj_fwd_pos(const int64_t* tokens, const void* tproj, const int* nrows, int n_attr,
+                               const float* bias, const float* pe, const int* pos, void* out, int64_t rows, int D,
+                               float p, uint64_t seed, const uint64_t* seed_base, int dtype, void* stream);
 /* dtproj[rowofs_f + id, :] = sum of dpre[r, :] over the token rows with tokens[r, f] == id ((sum nrows, D) f32), dpre =
  * the gradient in front of the dropout (cwlt_posenc_dropout(dout, pe = NULL) with the forward's seed), row stride ldd.
  * The bias gradient is the column sum of any ONE attribute's rows of dtproj.

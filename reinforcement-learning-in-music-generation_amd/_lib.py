@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 37
+ABI_VERSION = 38
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -72,6 +72,10 @@ _SIGNATURES = {
     "cwlt_causal_linear_bwd": [_ptr] * 9 + [_c_int] * 4 + [_c_i64] * 8 + [_c_int, _ptr],
     "cwlt_causal_linear_bwd_dkdv": [_ptr] * 11 + [_c_int] * 4 + [_c_i64] * 7 + [_c_int, _ptr, _c_int, _ptr],
     "cwlt_causal_linear_bwd_dq": [_ptr] * 9 + [_c_int] * 4 + [_c_i64] * 6 + [_c_int, _ptr, _c_int, _ptr],
+    "cwlt_causal_linear_fwd_packed": [_ptr] * 6 + [_c_int] * 3 + [_c_i64] * 4 + [_c_f32, _ptr, _c_int, _ptr],
+    "cwlt_causal_linear_bwd_sweep_packed": [_ptr] * 14 + [_c_int] * 3 + [_c_i64] * 8 + [_c_int, _ptr],
+    "cwlt_causal_linear_bwd_dkdv_packed": [_ptr] * 12 + [_c_int] * 3 + [_c_i64] * 7 + [_c_int, _ptr],
+    "cwlt_causal_linear_bwd_dq_packed": [_ptr] * 10 + [_c_int] * 3 + [_c_i64] * 6 + [_c_int, _ptr],
     "cwlt_ln_blocks": [_c_i64],
     "cwlt_add_dropout_layernorm_fwd": [_ptr] * 8 + [_c_i64, _c_int, _c_f32, _c_f32, _c_u64, _ptr, _c_int, _ptr],
     "cwlt_add_dropout_layernorm_bwd": [_ptr] * 10 + [_c_i64, _c_int, _c_f32, _c_u64, _ptr, _c_int, _ptr],
@@ -99,11 +103,14 @@ _SIGNATURES = {
     "cwlt_graph_replace_memset_nodes": [_ptr, _ptr],
     "cwlt_bias_gelu_dropout_bwd": [_ptr] * 6 + [_c_i64, _c_int, _c_f32, _c_u64, _ptr, _c_int, _ptr],
     "cwlt_posenc_dropout": [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_f32, _c_u64, _ptr, _c_int, _ptr],
+    "cwlt_posenc_dropout_pos": [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_u64, _ptr, _c_int, _ptr],
     "cwlt_embed_splits": [_c_i64],
     "cwlt_cw_embed_fwd": [_ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_cw_embed_bwd": [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_cw_embed_proj_fwd": [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_f32, _c_u64, _ptr,
                                _c_int, _ptr],
+    "cwlt_cw_embed_proj_fwd_pos": [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_u64, _ptr,
+                                   _c_int, _ptr],
     "cwlt_cw_embed_proj_bwd": [_ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_i64, _c_int, _ptr],
     "cwlt_band_attn_fwd": [_ptr] * 6 + [_c_int] * 5 + [_c_i64] * 4 + [_c_f32, _c_f32, _c_u64, _ptr, _c_int, _ptr],
     "cwlt_band_attn_bwd": [_ptr] * 10 + [_c_int] * 5 + [_c_i64] * 8 + [_c_f32, _c_f32, _c_u64, _ptr, _c_int, _ptr],

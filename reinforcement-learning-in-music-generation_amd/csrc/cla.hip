@@ -118,11 +118,11 @@ __device__ __forceinline__ float4 phi4(float4 x, bool valid) {
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(128) void cla_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                       const T* __restrict__ v, T* __restrict__ o,
-                                                      float* __restrict__ zinv, int H, int L, long ldq, long ldk,
-                                                      long ldv, long ldo, float eps) {
+                                                      float* __restrict__ zinv, int H, typename SeqArg<PACKED>::type seq,
+                                                      long ldq, long ldk, long ldv, long ldo, float eps) {
     __shared__ float qs[C * LDT];
     __shared__ float ks[C * LDT];
     __shared__ float vs[C * LDT];
@@ -134,11 +134,14 @@ __global__ __launch_bounds__(128) void cla_fwd_kernel(const T* __restrict__ q, c
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hf = lane >> 5;
     const int n = blockIdx.x / H, h = blockIdx.x % H;
-    const T* qb = q + ((long)n * L) * ldq + h * D;
-    const T* kb = k + ((long)n * L) * ldk + h * D;
-    const T* vb = v + ((long)n * L) * ldv + h * D;
-    T* ob = o + ((long)n * L) * ldo + h * D;
-    float* zb = zinv + ((long)n * L) * H + h;
+    long row0;   // the stream's first row and its length (cwlt_common.h: rectangular n * L, L; packed cu[n], cu[n + 1] - cu[n])
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const T* qb = q + row0 * ldq + h * D;
+    const T* kb = k + row0 * ldk + h * D;
+    const T* vb = v + row0 * ldv + h * D;
+    T* ob = o + row0 * ldo + h * D;
+    float* zb = zinv + row0 * H + h;
 
     const int srow = tid >> 4, scol = (tid & 15) * 4;
     const int nch = (L + C - 1) / C;
@@ -226,12 +229,12 @@ __global__ __launch_bounds__(128) void cla_fwd_kernel(const T* __restrict__ q, c
 //   g_i = dout_i * z_i ; dden_i = -(dout_i . out_i) z_i ; W_ij = g_i . v_j + dden_i (j <= i)
 //   dqf_i = sum_{j<=i} W_ij kf_j  =  (W kf)_i + g_i S_prev^T + dden_i ksum_prev ;  dQ = dqf * phi'(Q)
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(128) void cla_bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                          const T* __restrict__ v, const T* __restrict__ out,
                                                          const T* __restrict__ dout, const float* __restrict__ zinv,
-                                                         T* __restrict__ dq, int H, int L, long ldq, long ldk,
-                                                         long ldv, long ldo, long lddo, long lddq) {
+                                                         T* __restrict__ dq, int H, typename SeqArg<PACKED>::type seq,
+                                                         long ldq, long ldk, long ldv, long ldo, long lddo, long lddq) {
     __shared__ float gs[C * LDT];
     __shared__ float vs[C * LDT];
     __shared__ float ks[C * LDT];
@@ -242,13 +245,16 @@ __global__ __launch_bounds__(128) void cla_bwd_dq_kernel(const T* __restrict__ q
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hf = lane >> 5;
     const int n = blockIdx.x / H, h = blockIdx.x % H;
-    const T* qb = q + ((long)n * L) * ldq + h * D;
-    const T* kb = k + ((long)n * L) * ldk + h * D;
-    const T* vb = v + ((long)n * L) * ldv + h * D;
-    const T* ob = out + ((long)n * L) * ldo + h * D;
-    const T* gb = dout + ((long)n * L) * lddo + h * D;
-    const float* zb = zinv + ((long)n * L) * H + h;
-    T* dqb = dq + ((long)n * L) * lddq + h * D;
+    long row0;   // the stream's first row and its length (cwlt_common.h: rectangular n * L, L; packed cu[n], cu[n + 1] - cu[n])
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const T* qb = q + row0 * ldq + h * D;
+    const T* kb = k + row0 * ldk + h * D;
+    const T* vb = v + row0 * ldv + h * D;
+    const T* ob = out + row0 * ldo + h * D;
+    const T* gb = dout + row0 * lddo + h * D;
+    const float* zb = zinv + row0 * H + h;
+    T* dqb = dq + row0 * lddq + h * D;
 
     const int srow = tid >> 4, scol = (tid & 15) * 4;
     const int nch = (L + C - 1) / C;
@@ -336,13 +342,13 @@ __global__ __launch_bounds__(128) void cla_bwd_dq_kernel(const T* __restrict__ q
 //   dv_j  = sum_{i>=j} A_ij g_i  = (A^T g)_j + kf_j R_next
 //   R = sum_{i later} qf_i (x) g_i,  r1 = sum_{i later} qf_i dden_i
 // ------------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool PACKED>
 __global__ __launch_bounds__(256) void cla_bwd_dkdv_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                            const T* __restrict__ v, const T* __restrict__ out,
                                                            const T* __restrict__ dout, const float* __restrict__ zinv,
-                                                           T* __restrict__ dk, T* __restrict__ dv, int H, int L,
-                                                           long ldq, long ldk, long ldv, long ldo, long lddo,
-                                                           long lddk, long lddv) {
+                                                           T* __restrict__ dk, T* __restrict__ dv, int H,
+                                                           typename SeqArg<PACKED>::type seq, long ldq, long ldk,
+                                                           long ldv, long ldo, long lddo, long lddk, long lddv) {
     __shared__ float qs[C * LDT];
     __shared__ float ks[C * LDT];
     __shared__ float vs[C * LDT];
@@ -354,14 +360,17 @@ __global__ __launch_bounds__(256) void cla_bwd_dkdv_kernel(const T* __restrict__
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hf = lane >> 5;
     const int n = blockIdx.x / H, h = blockIdx.x % H;
-    const T* qb = q + ((long)n * L) * ldq + h * D;
-    const T* kb = k + ((long)n * L) * ldk + h * D;
-    const T* vb = v + ((long)n * L) * ldv + h * D;
-    const T* ob = out + ((long)n * L) * ldo + h * D;
-    const T* gb = dout + ((long)n * L) * lddo + h * D;
-    const float* zb = zinv + ((long)n * L) * H + h;
-    T* dkb = dk + ((long)n * L) * lddk + h * D;
-    T* dvb = dv + ((long)n * L) * lddv + h * D;
+    long row0;   // the stream's first row and its length (cwlt_common.h: rectangular n * L, L; packed cu[n], cu[n + 1] - cu[n])
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const T* qb = q + row0 * ldq + h * D;
+    const T* kb = k + row0 * ldk + h * D;
+    const T* vb = v + row0 * ldv + h * D;
+    const T* ob = out + row0 * ldo + h * D;
+    const T* gb = dout + row0 * lddo + h * D;
+    const float* zb = zinv + row0 * H + h;
+    T* dkb = dk + row0 * lddk + h * D;
+    T* dvb = dv + row0 * lddv + h * D;
 
     const int srow = tid >> 4, scol = (tid & 15) * 4;  // srow 0..15
     const int nch = (L + C - 1) / C;
@@ -464,30 +473,32 @@ __global__ __launch_bounds__(256) void cla_bwd_dkdv_kernel(const T* __restrict__
 #undef CLA_KV_LOAD
 }
 
-template <typename T>
-static int launch_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H, int L,
-                      long ldq, long ldk, long ldv, long ldo, float eps, hipStream_t st) {
-    hipLaunchKernelGGL((cla_fwd_kernel<T>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                       (T*)out, zinv, H, L, ldq, ldk, ldv, ldo, eps);
+template <typename T, bool PACKED = false>
+static int launch_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H,
+                      typename SeqArg<PACKED>::type seq, long ldq, long ldk, long ldv, long ldo, float eps,
+                      hipStream_t st) {
+    hipLaunchKernelGGL((cla_fwd_kernel<T, PACKED>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k,
+                       (const T*)v, (T*)out, zinv, H, seq, ldq, ldk, ldv, ldo, eps);
     return (int)hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool PACKED = false>
 static int launch_bwd_dkdv(const void* q, const void* k, const void* v, const void* out, const float* zinv,
-                           const void* dout, void* dk, void* dv, int N, int H, int L, long ldq, long ldk, long ldv,
-                           long ldo, long lddo, long lddk, long lddv, hipStream_t st) {
-    hipLaunchKernelGGL((cla_bwd_dkdv_kernel<T>), dim3(N * H), dim3(256), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (const T*)out, (const T*)dout, zinv, (T*)dk, (T*)dv, H, L, ldq, ldk, ldv, ldo,
+                           const void* dout, void* dk, void* dv, int N, int H, typename SeqArg<PACKED>::type seq,
+                           long ldq, long ldk, long ldv, long ldo, long lddo, long lddk, long lddv, hipStream_t st) {
+    hipLaunchKernelGGL((cla_bwd_dkdv_kernel<T, PACKED>), dim3(N * H), dim3(256), 0, st, (const T*)q, (const T*)k,
+                       (const T*)v, (const T*)out, (const T*)dout, zinv, (T*)dk, (T*)dv, H, seq, ldq, ldk, ldv, ldo,
                        lddo, lddk, lddv);
     return (int)hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool PACKED = false>
 static int launch_bwd_dq(const void* q, const void* k, const void* v, const void* out, const float* zinv,
-                         const void* dout, void* dq, int N, int H, int L, long ldq, long ldk, long ldv, long ldo,
-                         long lddo, long lddq, hipStream_t st) {
-    hipLaunchKernelGGL((cla_bwd_dq_kernel<T>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                       (const T*)out, (const T*)dout, zinv, (T*)dq, H, L, ldq, ldk, ldv, ldo, lddo, lddq);
+                         const void* dout, void* dq, int N, int H, typename SeqArg<PACKED>::type seq, long ldq,
+                         long ldk, long ldv, long ldo, long lddo, long lddq, hipStream_t st) {
+    hipLaunchKernelGGL((cla_bwd_dq_kernel<T, PACKED>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k,
+                       (const T*)v, (const T*)out, (const T*)dout, zinv, (T*)dq, H, seq, ldq, ldk, ldv, ldo, lddo,
+                       lddq);
     return (int)hipGetLastError();
 }
 
@@ -539,7 +550,7 @@ int cwlt_causal_linear_fwd(const void* q, const void* k, const void* v, void* ou
     if (dtype == CWLT_BF16) {
         if (fast)
             return launch_cla_fwd_bf16(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, segments, seg_ws,
-                                       final_state, st);
+                                       final_state, nullptr, st);
         return launch_fwd<bf16_t>(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, st);
     }
     return CWLT_ERR_DTYPE;
@@ -570,7 +581,7 @@ int cwlt_causal_linear_bwd_dkdv(const void* q, const void* k, const void* v, con
     if (dtype == CWLT_BF16) {
         if (fast)
             return launch_cla_bwd_dkdv_bf16(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, N, H, L, ldq,
-                                            ldk, ldv, ldo, lddo, lddk, lddv, segments, seg_ws, st);
+                                            ldk, ldv, ldo, lddo, lddk, lddv, segments, seg_ws, nullptr, st);
         return launch_bwd_dkdv<bf16_t>(q, k, v, out, zinv, dout, dk, dv, N, H, L, ldq, ldk, ldv, ldo, lddo, lddk,
                                        lddv, st);
     }
@@ -598,7 +609,7 @@ int cwlt_causal_linear_bwd_dq(const void* q, const void* k, const void* v, const
     if (dtype == CWLT_BF16) {
         if (fast)
             return launch_cla_bwd_dq_bf16(q, k, v, out, zinv, dout, dden, dq, colsum_q, N, H, L, ldq, ldk, ldv, ldo,
-                                          lddo, lddq, segments, const_cast<float*>(seg_ws), st);
+                                          lddo, lddq, segments, const_cast<float*>(seg_ws), nullptr, st);
         return launch_bwd_dq<bf16_t>(q, k, v, out, zinv, dout, dq, N, H, L, ldq, ldk, ldv, ldo, lddo, lddq, st);
     }
     return CWLT_ERR_DTYPE;
@@ -622,7 +633,7 @@ int cwlt_causal_linear_bwd_sweep(const void* q, const void* k, const void* v, co
     if (dtype != CWLT_BF16) return CWLT_ERR_DTYPE;
     if (((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) != 0) return CWLT_ERR_ARG;
     return launch_cla_bwd_sweep_bf16(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v, N,
-                                     H, L, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, (hipStream_t)stream);
+                                     H, L, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, nullptr, (hipStream_t)stream);
 }
 
 /* both halves of the backward: the heavier reverse scan first, the dq scan back-fills its tail */
@@ -635,6 +646,108 @@ int cwlt_causal_linear_bwd(const void* q, const void* k, const void* v, const vo
     if (e) return e;
     return cwlt_causal_linear_bwd_dq(q, k, v, out, zinv, dout, dq, nullptr, nullptr, N, H, L, head_dim, ldq, ldk, ldv,
                                      ldo, lddo, lddq, 1, nullptr, dtype, stream);
+}
+
+/* ---- packed form: songs of different lengths laid end to end, song s = rows [cu[s], cu[s + 1]) ----
+ * The same kernels instantiated with the row-offset table in place of (N, L); one workgroup per (song, head), never
+ * segmented.  `cu` is read on the device only: the host cannot check it here (the Python wrapper does). */
+static int packed_head_ok(const int* cu, int n_songs, int H, int head_dim) {
+    return cu && n_songs >= 1 && H >= 1 && head_dim == cwlt::D;
+}
+
+int cwlt_causal_linear_fwd_packed(const void* q, const void* k, const void* v, void* out, float* zinv, const int* cu,
+                                  int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv,
+                                  int64_t ldo, float eps, float* final_state, int dtype, void* stream) {
+    using namespace cwlt;
+    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
+    if (!q || !k || !v || !out || !zinv) return CWLT_ERR_ARG;
+    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H)) return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo) & 7) == 0;
+    if (final_state && !fast) return CWLT_ERR_ARG;   // the bf16 whole-sequence kernel writes it
+    if (dtype == CWLT_F32)
+        return launch_fwd<float, true>(q, k, v, out, zinv, n_songs, H, cu, ldq, ldk, ldv, ldo, eps, st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_fwd_bf16(q, k, v, out, zinv, n_songs, H, 0, ldq, ldk, ldv, ldo, eps, 1, nullptr,
+                                       final_state, cu, st);
+        return launch_fwd<bf16_t, true>(q, k, v, out, zinv, n_songs, H, cu, ldq, ldk, ldv, ldo, eps, st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+/* colsum_* (n_songs, H*64) f32; dden (rows, H) f32 by packed row: as in the rectangular calls */
+int cwlt_causal_linear_bwd_dkdv_packed(const void* q, const void* k, const void* v, const void* out, const float* zinv,
+                                       const void* dout, void* dk, void* dv, float* colsum_k, float* colsum_v,
+                                       float* dden, const int* cu, int n_songs, int H, int head_dim, int64_t ldq,
+                                       int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddk, int64_t lddv,
+                                       int dtype, void* stream) {
+    using namespace cwlt;
+    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
+    if (!q || !k || !v || !out || !zinv || !dout || !dk || !dv) return CWLT_ERR_ARG;
+    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
+        bad_ld(lddk, H) || bad_ld(lddv, H))
+        return CWLT_ERR_ARG;
+    if ((colsum_k == nullptr) != (colsum_v == nullptr)) return CWLT_ERR_ARG;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddk | lddv) & 7) == 0;
+    if ((colsum_k || dden) && !fast) return CWLT_ERR_ARG;   // fused column sums and the dden hand-over: bf16 kernels only
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CWLT_F32)
+        return launch_bwd_dkdv<float, true>(q, k, v, out, zinv, dout, dk, dv, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo,
+                                            lddk, lddv, st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_bwd_dkdv_bf16(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, n_songs, H, 0,
+                                            ldq, ldk, ldv, ldo, lddo, lddk, lddv, 1, nullptr, cu, st);
+        return launch_bwd_dkdv<bf16_t, true>(q, k, v, out, zinv, dout, dk, dv, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo,
+                                             lddk, lddv, st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+int cwlt_causal_linear_bwd_dq_packed(const void* q, const void* k, const void* v, const void* out, const float* zinv,
+                                     const void* dout, void* dq, float* colsum_q, const float* dden, const int* cu,
+                                     int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv,
+                                     int64_t ldo, int64_t lddo, int64_t lddq, int dtype, void* stream) {
+    using namespace cwlt;
+    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
+    if (!q || !k || !v || (!out && !dden) || !zinv || !dout || !dq) return CWLT_ERR_ARG;
+    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) || bad_ld(lddq, H))
+        return CWLT_ERR_ARG;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddq) & 7) == 0;
+    if ((colsum_q || dden) && !fast) return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CWLT_F32)
+        return launch_bwd_dq<float, true>(q, k, v, out, zinv, dout, dq, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo, lddq,
+                                          st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_bwd_dq_bf16(q, k, v, out, zinv, dout, dden, dq, colsum_q, n_songs, H, 0, ldq, ldk, ldv,
+                                          ldo, lddo, lddq, 1, nullptr, cu, st);
+        return launch_bwd_dq<bf16_t, true>(q, k, v, out, zinv, dout, dq, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo, lddq,
+                                           st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+int cwlt_causal_linear_bwd_sweep_packed(const void* q, const void* k, const void* v, const void* out,
+                                        const float* zinv, const void* dout, const float* final_state, void* dq,
+                                        void* dk, void* dv, float* colsum_q, float* colsum_k, float* colsum_v,
+                                        const int* cu, int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk,
+                                        int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddk,
+                                        int64_t lddv, int dtype, void* stream) {
+    using namespace cwlt;
+    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
+    if (!q || !k || !v || !out || !zinv || !dout || !final_state || !dq || !dk || !dv) return CWLT_ERR_ARG;
+    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
+        bad_ld(lddq, H) || bad_ld(lddk, H) || bad_ld(lddv, H))
+        return CWLT_ERR_ARG;
+    if ((colsum_q == nullptr) != (colsum_k == nullptr) || (colsum_q == nullptr) != (colsum_v == nullptr))
+        return CWLT_ERR_ARG;
+    if (dtype != CWLT_BF16) return CWLT_ERR_DTYPE;
+    if (((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) != 0) return CWLT_ERR_ARG;
+    return launch_cla_bwd_sweep_bf16(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v,
+                                     n_songs, H, 0, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, cu, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -64,10 +64,11 @@ __device__ __forceinline__ void store_tile(float* t, int lane, const f32x16& x) 
     for (int r = 0; r < 16; ++r) t[r * 64 + lane] = x[r];
 }
 
-template <bool STATE_ONLY>
+template <bool STATE_ONLY, bool PACKED>
 __global__ __launch_bounds__(256) void cla_fwd_bf16_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                            const bf16_t* __restrict__ v, bf16_t* __restrict__ o,
-                                                           float* __restrict__ zinv, int H, int L, long ldq, long ldk,
+                                                           float* __restrict__ zinv, int H,
+                                                           typename SeqArg<PACKED>::type seq, long ldq, long ldk,
                                                            long ldv, long ldo, float eps, int P, int cps,
                                                            const float* __restrict__ pre, float* __restrict__ part,
                                                            float* __restrict__ fin) {
@@ -85,11 +86,14 @@ __global__ __launch_bounds__(256) void cla_fwd_bf16_kernel(const bf16_t* __restr
     const int seg = blockIdx.x % P;                             // segment
     const int sid = P == 1 ? stream_of_block(blockIdx.x, gridDim.x / H, H) : blockIdx.x / P;   // stream
     const int n = sid / H, h = sid % H;
-    const bf16_t* qb = q + ((long)n * L) * ldq + h * D;
-    const bf16_t* kb = k + ((long)n * L) * ldk + h * D;
-    const bf16_t* vb = v + ((long)n * L) * ldv + h * D;
-    bf16_t* ob = o + ((long)n * L) * ldo + h * D;
-    float* zb = zinv + ((long)n * L) * H + h;
+    long row0;   // the stream's first row and its length (cwlt_common.h, seq_span)
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const bf16_t* qb = q + row0 * ldq + h * D;
+    const bf16_t* kb = k + row0 * ldk + h * D;
+    const bf16_t* vb = v + row0 * ldv + h * D;
+    bf16_t* ob = o + row0 * ldo + h * D;
+    float* zb = zinv + row0 * H + h;
 
     const int srow = tid >> 3, scol = (tid & 7) * 8;
     const int nch = (L + C - 1) / C;
@@ -312,12 +316,13 @@ __device__ __forceinline__ void colsum_store(float (&bsum)[8], float* scratch, f
 // ------------------------------------------------------------------------------------------------
 // HAS_DDEN: dden (N, L, H) f32 was written by the reverse-scan kernel (launched first); the `out` stream -- needed
 // only to rebuild it -- is then not read at all (one of the six 16-byte streams of this kernel).
-template <bool HAS_DDEN>
+template <bool HAS_DDEN, bool PACKED>
 __global__ __launch_bounds__(256) void cla_bwd_dq_bf16_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout, const float* __restrict__ zinv,
-    const float* __restrict__ dden_in, bf16_t* __restrict__ dq, float* __restrict__ csum, int H, int L, long ldq,
-    long ldk, long ldv, long ldo, long lddo, long lddq, int P, int cps, const float* __restrict__ pre) {
+    const float* __restrict__ dden_in, bf16_t* __restrict__ dq, float* __restrict__ csum, int H,
+    typename SeqArg<PACKED>::type seq, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, int P, int cps,
+    const float* __restrict__ pre) {
     __shared__ __attribute__((aligned(16))) bf16_t gs[C * LD];   // g       [i][m]
     __shared__ __attribute__((aligned(16))) bf16_t vs[C * LD];   // v       [j][m]
     __shared__ __attribute__((aligned(16))) bf16_t ks[C * LD];   // phi(k)  [j][e]
@@ -331,14 +336,17 @@ __global__ __launch_bounds__(256) void cla_bwd_dq_bf16_kernel(
     const int l31 = lane & 31, hf = lane >> 5;
     const int sid = blockIdx.x / P, seg = blockIdx.x % P;      // stream, segment (P == 1: whole sequences)
     const int n = sid / H, h = sid % H;
-    const bf16_t* qb = q + ((long)n * L) * ldq + h * D;
-    const bf16_t* kb = k + ((long)n * L) * ldk + h * D;
-    const bf16_t* vb = v + ((long)n * L) * ldv + h * D;
-    const bf16_t* ob = out + ((long)n * L) * ldo + h * D;
-    const bf16_t* gb = dout + ((long)n * L) * lddo + h * D;
-    const float* zb = zinv + ((long)n * L) * H + h;
-    const float* ddb = HAS_DDEN ? dden_in + ((long)n * L) * H + h : zb;
-    bf16_t* dqb = dq + ((long)n * L) * lddq + h * D;
+    long row0;   // the stream's first row and its length (cwlt_common.h, seq_span)
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const bf16_t* qb = q + row0 * ldq + h * D;
+    const bf16_t* kb = k + row0 * ldk + h * D;
+    const bf16_t* vb = v + row0 * ldv + h * D;
+    const bf16_t* ob = out + row0 * ldo + h * D;
+    const bf16_t* gb = dout + row0 * lddo + h * D;
+    const float* zb = zinv + row0 * H + h;
+    const float* ddb = HAS_DDEN ? dden_in + row0 * H + h : zb;
+    bf16_t* dqb = dq + row0 * lddq + h * D;
 
     const int srow = tid >> 3, scol = (tid & 7) * 8;
     const int nch = (L + C - 1) / C;
@@ -479,13 +487,13 @@ __global__ __launch_bounds__(256) void cla_bwd_dq_bf16_kernel(
 // ------------------------------------------------------------------------------------------------
 // STATE_ONLY (few streams, see the forward kernel): the segment's increments of ALL backward states, 8 tiles per
 // wave -- [0..2] the dq scan's ST_0, ST_1, ones row (from k, v), [3..7] this kernel's RT_0, RT_1, RTa, R2_0, R2_1.
-template <bool STATE_ONLY>
+template <bool STATE_ONLY, bool PACKED>
 __global__ __launch_bounds__(256, 2) void cla_bwd_dkdv_bf16_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout, const float* __restrict__ zinv,
     bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, float* __restrict__ csum_k, float* __restrict__ csum_v,
-    float* __restrict__ dden_out, int H, int L, long ldq, long ldk, long ldv, long ldo, long lddo, long lddk,
-    long lddv, int P, int cps, const float* __restrict__ pre, float* __restrict__ part) {
+    float* __restrict__ dden_out, int H, typename SeqArg<PACKED>::type seq, long ldq, long ldk, long ldv, long ldo,
+    long lddo, long lddk, long lddv, int P, int cps, const float* __restrict__ pre, float* __restrict__ part) {
     __shared__ __attribute__((aligned(16))) bf16_t qs[C * LD];   // phi(q)  [i][e]
     __shared__ __attribute__((aligned(16))) bf16_t ks[C * LD];   // phi(k)  [j][e]
     __shared__ __attribute__((aligned(16))) bf16_t vs[C * LD];   // v       [j][m]
@@ -502,15 +510,18 @@ __global__ __launch_bounds__(256, 2) void cla_bwd_dkdv_bf16_kernel(
     const int l31 = lane & 31, hf = lane >> 5;
     const int sid = blockIdx.x / P, seg = blockIdx.x % P;      // stream, segment (P == 1: whole sequences)
     const int n = sid / H, h = sid % H;
-    const bf16_t* qb = q + ((long)n * L) * ldq + h * D;
-    const bf16_t* kb = k + ((long)n * L) * ldk + h * D;
-    const bf16_t* vb = v + ((long)n * L) * ldv + h * D;
-    const bf16_t* ob = out + ((long)n * L) * ldo + h * D;
-    const bf16_t* gb = dout + ((long)n * L) * lddo + h * D;
-    const float* zb = zinv + ((long)n * L) * H + h;
-    bf16_t* dkb = dk + ((long)n * L) * lddk + h * D;
-    bf16_t* dvb = dv + ((long)n * L) * lddv + h * D;
-    float* ddb = dden_out ? dden_out + ((long)n * L) * H + h : nullptr;   // dden for the dq kernel (it then skips `out`)
+    long row0;   // the stream's first row and its length (cwlt_common.h, seq_span)
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const bf16_t* qb = q + row0 * ldq + h * D;
+    const bf16_t* kb = k + row0 * ldk + h * D;
+    const bf16_t* vb = v + row0 * ldv + h * D;
+    const bf16_t* ob = out + row0 * ldo + h * D;
+    const bf16_t* gb = dout + row0 * lddo + h * D;
+    const float* zb = zinv + row0 * H + h;
+    bf16_t* dkb = dk + row0 * lddk + h * D;
+    bf16_t* dvb = dv + row0 * lddv + h * D;
+    float* ddb = dden_out ? dden_out + row0 * H + h : nullptr;   // dden for the dq kernel (it then skips `out`)
 
     const int srow = tid >> 3, scol = (tid & 7) * 8;
     const int nch = (L + C - 1) / C;
@@ -766,12 +777,14 @@ __device__ __forceinline__ bf16x8 negate8(bf16x8 x) {
     return __builtin_bit_cast(bf16x8, u);
 }
 
+template <bool PACKED>
 __global__ __launch_bounds__(512, 1) void cla_bwd_sweep_bf16_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
     const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout, const float* __restrict__ zinv,
     const float* __restrict__ fin, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk, bf16_t* __restrict__ dv,
-    float* __restrict__ csum_q, float* __restrict__ csum_k, float* __restrict__ csum_v, int H, int L, long ldq,
-    long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv) {
+    float* __restrict__ csum_q, float* __restrict__ csum_k, float* __restrict__ csum_v, int H,
+    typename SeqArg<PACKED>::type seq, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq, long lddk,
+    long lddv) {
     constexpr int TILE = C * LD;
     __shared__ __attribute__((aligned(16))) bf16_t in_[2 * 4 * TILE];   // [buffer][phi(q) | phi(k) | v | g]
     __shared__ __attribute__((aligned(16))) bf16_t er[2 * TILE];        // [buffer] R[e][m]: reverse state behind a chunk
@@ -792,15 +805,18 @@ __global__ __launch_bounds__(512, 1) void cla_bwd_sweep_bf16_kernel(
     const int l31 = lane & 31, hf = lane >> 5;
     const int sid = stream_of_block(blockIdx.x, gridDim.x / H, H);
     const int n = sid / H, h = sid % H;
-    const bf16_t* qb = q + ((long)n * L) * ldq + h * D;
-    const bf16_t* kb = k + ((long)n * L) * ldk + h * D;
-    const bf16_t* vb = v + ((long)n * L) * ldv + h * D;
-    const bf16_t* ob = out + ((long)n * L) * ldo + h * D;
-    const bf16_t* gb = dout + ((long)n * L) * lddo + h * D;
-    const float* zb = zinv + ((long)n * L) * H + h;
-    bf16_t* dqb = dq + ((long)n * L) * lddq + h * D;
-    bf16_t* dkb = dk + ((long)n * L) * lddk + h * D;
-    bf16_t* dvb = dv + ((long)n * L) * lddv + h * D;
+    long row0;   // the stream's first row and its length (cwlt_common.h, seq_span)
+    int L;
+    seq_span<PACKED>(seq, n, row0, L);
+    const bf16_t* qb = q + row0 * ldq + h * D;
+    const bf16_t* kb = k + row0 * ldk + h * D;
+    const bf16_t* vb = v + row0 * ldv + h * D;
+    const bf16_t* ob = out + row0 * ldo + h * D;
+    const bf16_t* gb = dout + row0 * lddo + h * D;
+    const float* zb = zinv + row0 * H + h;
+    bf16_t* dqb = dq + row0 * lddq + h * D;
+    bf16_t* dkb = dk + row0 * lddk + h * D;
+    bf16_t* dvb = dv + row0 * lddv + h * D;
 
     const int srow = tid >> 3, scol = (tid & 7) * 8;   // staging: one 16-byte slot of every stream per thread and chunk
     const int orow = (tid & 255) >> 3;                 // output: rows orow, orow + 32 of dK and dV (KV group) / dQ (Q group)
@@ -1069,12 +1085,22 @@ long scan_seg_floats(int N, int H, int P, int backward) {
 
 long scan_final_state_floats(int N, int H) { return (long)N * H * b16::FIN_FLOATS; }
 
+// Packed launches (cu != NULL): one workgroup per (song, head), whole songs (P = 1); a song's chunk count is its own, so the
+// chunks-per-segment argument is only an upper limit there.
+constexpr int ALL_CHUNKS = 1 << 24;
+
 int launch_cla_fwd_bf16(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H, int L,
                         long ldq, long ldk, long ldv, long ldo, float eps, int P, float* ws, float* fin,
-                        hipStream_t st) {
+                        const int* cu, hipStream_t st) {
+    if (cu) {
+        hipLaunchKernelGGL((b16::cla_fwd_bf16_kernel<false, true>), dim3(N * H), dim3(256), 0, st, (const bf16_t*)q,
+                           (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, zinv, H, cu, ldq, ldk, ldv, ldo, eps, 1,
+                           ALL_CHUNKS, (const float*)nullptr, (float*)nullptr, fin);
+        return (int)hipGetLastError();
+    }
     const int nch = (L + b16::C - 1) / b16::C;
     if (P <= 1) {
-        hipLaunchKernelGGL(b16::cla_fwd_bf16_kernel<false>, dim3(N * H), dim3(256), 0, st, (const bf16_t*)q,
+        hipLaunchKernelGGL((b16::cla_fwd_bf16_kernel<false, false>), dim3(N * H), dim3(256), 0, st, (const bf16_t*)q,
                            (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, zinv, H, L, ldq, ldk, ldv, ldo, eps, 1, nch,
                            (const float*)nullptr, (float*)nullptr, fin);
         return (int)hipGetLastError();
@@ -1083,13 +1109,13 @@ int launch_cla_fwd_bf16(const void* q, const void* k, const void* v, void* out, 
     const long NS = (long)N * H;
     float* part = ws;
     float* pre = ws + NS * P * 4 * 3 * 1024;
-    hipLaunchKernelGGL(b16::cla_fwd_bf16_kernel<true>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
+    hipLaunchKernelGGL((b16::cla_fwd_bf16_kernel<true, false>), dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
                        (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, zinv, H, L, ldq, ldk, ldv, ldo, eps, P, cps,
                        (const float*)nullptr, part, (float*)nullptr);
     const long total = NS * 2 * 3 * 1024;
     hipLaunchKernelGGL(b16::seg_prefix_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, pre, total,
                        P, 3, 3);
-    hipLaunchKernelGGL(b16::cla_fwd_bf16_kernel<false>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
+    hipLaunchKernelGGL((b16::cla_fwd_bf16_kernel<false, false>), dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
                        (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, zinv, H, L, ldq, ldk, ldv, ldo, eps, P, cps,
                        (const float*)pre, (float*)nullptr, (float*)nullptr);
     return (int)hipGetLastError();
@@ -1099,42 +1125,60 @@ int launch_cla_fwd_bf16(const void* q, const void* k, const void* v, void* out, 
 int launch_cla_bwd_sweep_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                               const void* dout, const float* fin, void* dq, void* dk, void* dv, float* csum_q,
                               float* csum_k, float* csum_v, int N, int H, int L, long ldq, long ldk, long ldv, long ldo,
-                              long lddo, long lddq, long lddk, long lddv, hipStream_t st) {
-    hipLaunchKernelGGL(b16::cla_bwd_sweep_bf16_kernel, dim3(N * H), dim3(512), 0, st, (const bf16_t*)q,
-                       (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, fin,
-                       (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, csum_q, csum_k, csum_v, H, L, ldq, ldk, ldv, ldo, lddo,
-                       lddq, lddk, lddv);
+                              long lddo, long lddq, long lddk, long lddv, const int* cu, hipStream_t st) {
+    if (cu)
+        hipLaunchKernelGGL(b16::cla_bwd_sweep_bf16_kernel<true>, dim3(N * H), dim3(512), 0, st, (const bf16_t*)q,
+                           (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, fin,
+                           (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, csum_q, csum_k, csum_v, H, cu, ldq, ldk, ldv, ldo,
+                           lddo, lddq, lddk, lddv);
+    else
+        hipLaunchKernelGGL(b16::cla_bwd_sweep_bf16_kernel<false>, dim3(N * H), dim3(512), 0, st, (const bf16_t*)q,
+                           (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, fin,
+                           (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, csum_q, csum_k, csum_v, H, L, ldq, ldk, ldv, ldo,
+                           lddo, lddq, lddk, lddv);
     return (int)hipGetLastError();
 }
 
 // P > 1: `ws` must be the workspace launch_cla_bwd_dkdv_bf16 has just filled (it computes the prefix states of both scans)
 int launch_cla_bwd_dq_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                            const void* dout, const float* dden, void* dq, float* csum, int N, int H, int L, long ldq,
-                           long ldk, long ldv, long ldo, long lddo, long lddq, int P, float* ws, hipStream_t st) {
-    const int nch = (L + b16::C - 1) / b16::C;
+                           long ldk, long ldv, long ldo, long lddo, long lddq, int P, float* ws, const int* cu,
+                           hipStream_t st) {
     const long NS = (long)N * H;
+#define CWLT_DQ(DD, PK, SEQ, PP, CPS, PRE)                                                                              \
+    hipLaunchKernelGGL((b16::cla_bwd_dq_bf16_kernel<DD, PK>), dim3(NS * (PP)), dim3(256), 0, st, (const bf16_t*)q,       \
+                       (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, dden,         \
+                       (bf16_t*)dq, csum, H, SEQ, ldq, ldk, ldv, ldo, lddo, lddq, PP, CPS, PRE)
+    if (cu) {
+        if (dden) CWLT_DQ(true, true, cu, 1, ALL_CHUNKS, (const float*)nullptr);
+        else CWLT_DQ(false, true, cu, 1, ALL_CHUNKS, (const float*)nullptr);
+        return (int)hipGetLastError();
+    }
+    const int nch = (L + b16::C - 1) / b16::C;
     const int cps = P > 1 ? seg_cps(L, P) : nch;
     const float* pre = P > 1 ? ws + NS * P * 4 * 8 * 1024 : nullptr;
     if (P < 1) P = 1;
-    if (dden)
-        hipLaunchKernelGGL(b16::cla_bwd_dq_bf16_kernel<true>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
-                           (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, dden,
-                           (bf16_t*)dq, csum, H, L, ldq, ldk, ldv, ldo, lddo, lddq, P, cps, pre);
-    else
-        hipLaunchKernelGGL(b16::cla_bwd_dq_bf16_kernel<false>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
-                           (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, dden,
-                           (bf16_t*)dq, csum, H, L, ldq, ldk, ldv, ldo, lddo, lddq, P, cps, pre);
+    if (dden) CWLT_DQ(true, false, L, P, cps, pre);
+    else CWLT_DQ(false, false, L, P, cps, pre);
+#undef CWLT_DQ
     return (int)hipGetLastError();
 }
 
 int launch_cla_bwd_dkdv_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                              const void* dout, void* dk, void* dv, float* csum_k, float* csum_v, float* dden_out,
                              int N, int H, int L, long ldq, long ldk, long ldv, long ldo, long lddo, long lddk,
-                             long lddv, int P, float* ws, hipStream_t st) {
-    const int nch = (L + b16::C - 1) / b16::C;
+                             long lddv, int P, float* ws, const int* cu, hipStream_t st) {
     const long NS = (long)N * H;
+    if (cu) {
+        hipLaunchKernelGGL((b16::cla_bwd_dkdv_bf16_kernel<false, true>), dim3(NS), dim3(256), 0, st, (const bf16_t*)q,
+                           (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv,
+                           (bf16_t*)dk, (bf16_t*)dv, csum_k, csum_v, dden_out, H, cu, ldq, ldk, ldv, ldo, lddo, lddk,
+                           lddv, 1, ALL_CHUNKS, (const float*)nullptr, (float*)nullptr);
+        return (int)hipGetLastError();
+    }
+    const int nch = (L + b16::C - 1) / b16::C;
     if (P <= 1) {
-        hipLaunchKernelGGL(b16::cla_bwd_dkdv_bf16_kernel<false>, dim3(NS), dim3(256), 0, st, (const bf16_t*)q,
+        hipLaunchKernelGGL((b16::cla_bwd_dkdv_bf16_kernel<false, false>), dim3(NS), dim3(256), 0, st, (const bf16_t*)q,
                            (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv,
                            (bf16_t*)dk, (bf16_t*)dv, csum_k, csum_v, dden_out, H, L, ldq, ldk, ldv, ldo, lddo, lddk,
                            lddv, 1, nch, (const float*)nullptr, (float*)nullptr);
@@ -1143,14 +1187,14 @@ int launch_cla_bwd_dkdv_bf16(const void* q, const void* k, const void* v, const 
     const int cps = seg_cps(L, P);
     float* part = ws;
     float* pre = ws + NS * P * 4 * 8 * 1024;
-    hipLaunchKernelGGL(b16::cla_bwd_dkdv_bf16_kernel<true>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
+    hipLaunchKernelGGL((b16::cla_bwd_dkdv_bf16_kernel<true, false>), dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
                        (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, (bf16_t*)dk,
                        (bf16_t*)dv, (float*)nullptr, (float*)nullptr, (float*)nullptr, H, L, ldq, ldk, ldv, ldo, lddo,
                        lddk, lddv, P, cps, (const float*)nullptr, part);
     const long total = NS * 2 * 8 * 1024;
     hipLaunchKernelGGL(b16::seg_prefix_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part, pre, total,
                        P, 8, 3);
-    hipLaunchKernelGGL(b16::cla_bwd_dkdv_bf16_kernel<false>, dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
+    hipLaunchKernelGGL((b16::cla_bwd_dkdv_bf16_kernel<false, false>), dim3(NS * P), dim3(256), 0, st, (const bf16_t*)q,
                        (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)out, (const bf16_t*)dout, zinv, (bf16_t*)dk,
                        (bf16_t*)dv, csum_k, csum_v, dden_out, H, L, ldq, ldk, ldv, ldo, lddo, lddk, lddv, P, cps,
                        (const float*)pre, (float*)nullptr);

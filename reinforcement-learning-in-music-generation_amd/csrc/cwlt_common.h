@@ -225,26 +225,52 @@ int launch_gemm_ffn_big(int gelu, const void* a, const void* w, const float* bia
                         uint64_t seed, const uint64_t* seed_base, hipStream_t st);
 long gemm_ffn_big_tiles(long M);
 
+// Where a scan workgroup's stream lies.  Rectangular (PACKED = false): the kernel argument is the common length L and
+// sequence n owns rows [n * L, (n + 1) * L).  Packed: the argument is `cu`, n_songs + 1 int32 row offsets on the
+// device, and song n owns rows [cu[n], cu[n + 1]).  A compile-time variant: the rectangular kernels take an int and
+// compile to what they were; the packed ones read two workgroup-uniform words (scalar loads, no VGPR).
+template <bool PACKED> struct SeqArg { typedef int type; };
+template <> struct SeqArg<true> { typedef const int* type; };
+template <bool PACKED>
+__device__ __forceinline__ void seq_span(typename SeqArg<PACKED>::type a, int n, long& row0, int& len) {
+    if constexpr (PACKED) {
+        const int b = __builtin_amdgcn_readfirstlane(a[n]), e = __builtin_amdgcn_readfirstlane(a[n + 1]);
+        row0 = b;
+        len = e - b;
+    } else {
+        row0 = (long)n * a;
+        len = a;
+    }
+}
+// Position of token row r: r % T (PACKED = false, argument T) or pos[r] (argument: `rows` int32 on the device).
+template <bool PACKED>
+__device__ __forceinline__ long row_pos(typename SeqArg<PACKED>::type a, long r) {
+    if constexpr (PACKED) return a[r];
+    else return r % a;
+}
+
 // bf16 throughput path of the causal linear attention (cla_bf16.hip); row strides must be multiples of 8.
 // P = segments per stream (scan_segments: 1 unless N * H is far below the CU count), ws = scan_seg_floats(...) floats.
 int scan_segments(int N, int H, int L);
 long scan_seg_floats(int N, int H, int P, int backward);
+// cu != NULL: the packed form (N songs, song n = rows [cu[n], cu[n + 1]); L is ignored and P must be 1).
 // fin (optional, P == 1): scan_final_state_floats(N, H) floats, the state after the last token -- what the one-sweep
 // backward (launch_cla_bwd_sweep_bf16) starts its dQ scan from.
 long scan_final_state_floats(int N, int H);
 int launch_cla_fwd_bf16(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H, int L,
                         long ldq, long ldk, long ldv, long ldo, float eps, int P, float* ws, float* fin,
-                        hipStream_t st);
+                        const int* cu, hipStream_t st);
 int launch_cla_bwd_sweep_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                               const void* dout, const float* fin, void* dq, void* dk, void* dv, float* csum_q,
                               float* csum_k, float* csum_v, int N, int H, int L, long ldq, long ldk, long ldv, long ldo,
-                              long lddo, long lddq, long lddk, long lddv, hipStream_t st);
+                              long lddo, long lddq, long lddk, long lddv, const int* cu, hipStream_t st);
 int launch_cla_bwd_dq_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                            const void* dout, const float* dden, void* dq, float* csum, int N, int H, int L, long ldq,
-                           long ldk, long ldv, long ldo, long lddo, long lddq, int P, float* ws, hipStream_t st);
+                           long ldk, long ldv, long ldo, long lddo, long lddq, int P, float* ws, const int* cu,
+                           hipStream_t st);
 int launch_cla_bwd_dkdv_bf16(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                              const void* dout, void* dk, void* dv, float* csum_k, float* csum_v, float* dden_out,
                              int N, int H, int L, long ldq, long ldk, long ldv, long ldo, long lddo, long lddk,
-                             long lddv, int P, float* ws, hipStream_t st);
+                             long lddv, int P, float* ws, const int* cu, hipStream_t st);
 
 }  // namespace cwlt

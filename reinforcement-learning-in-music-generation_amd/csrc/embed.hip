@@ -205,13 +205,14 @@ __global__ __launch_bounds__(64, 2) void cw_embed_bwd_mfma_kernel(const int64_t*
 // activations: the (rows, 1216) concatenated embeddings and the 1216 -> 512 GEMM over all token rows are gone.
 // A thread owns V = 16-byte-of-output adjacent columns of a row (the posenc kernel's shape, so that the dropout stream
 // is the one cwlt_posenc_dropout draws for the same seed: key = element offset r * D + c).  The tables are read from L2.
+// POS: the position of row r is pos[r] (a device table, packed songs) in place of r % T.
 constexpr int EP_TILE = 32;   // token rows per block iteration
-template <typename T, typename TT>
+template <typename T, typename TT, bool POS>
 __global__ __launch_bounds__(256) void cw_embed_proj_fwd_kernel(const int64_t* __restrict__ tokens, const TT* __restrict__ tp,
                                                                 EmbedArgs a, const float* __restrict__ bias,
                                                                 const float* __restrict__ pe, T* __restrict__ out,
-                                                                long rows, int Tlen, int D, uint32_t thresh,
-                                                                float keep_scale, uint64_t seed,
+                                                                long rows, typename SeqArg<POS>::type Tlen, int D,
+                                                                uint32_t thresh, float keep_scale, uint64_t seed,
                                                                 const uint64_t* __restrict__ seed_base) {
     // element offsets of the EP_TILE x n_attr table rows of a tile: the ids are read once, coalesced, and the table loads
     // of a row do not wait behind an id load of their own (two dependent memory round trips per row otherwise)
@@ -241,7 +242,7 @@ __global__ __launch_bounds__(256) void cw_embed_proj_fwd_kernel(const int64_t* _
             loadf<V>(bias + c, t);
             if (pe) {
                 float q[V];
-                loadf<V>(pe + (r % Tlen) * (long)D + c, q);
+                loadf<V>(pe + row_pos<POS>(Tlen, r) * (long)D + c, q);
 #pragma unroll
                 for (int j = 0; j < V; ++j) t[j] += q[j];
             }
@@ -536,11 +537,41 @@ int cwlt_cw_embed_proj_fwd(const int64_t* tokens, const void* tproj, const int* 
     long nb = (rows + EP_TILE - 1) / EP_TILE;
     if (nb > 256 * 32) nb = 256 * 32;
     if (dtype == CWLT_F32)
-        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<float, float>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
+        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<float, float, false>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
                            (const float*)tproj, a, bias, pe, (float*)out, (long)rows, T, D, th, ks, seed, seed_base);
     else if (dtype == CWLT_BF16)
-        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<bf16_t, bf16_t>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
+        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<bf16_t, bf16_t, false>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
                            (const bf16_t*)tproj, a, bias, pe, (bf16_t*)out, (long)rows, T, D, th, ks, seed, seed_base);
+    else
+        return CWLT_ERR_DTYPE;
+    return (int)hipGetLastError();
+}
+
+/* cwlt_cw_embed_proj_fwd for packed songs: row r takes pe[pos[r], :] (pos: `rows` int32 on the device, every entry inside
+ * the pe buffer -- the caller's check; pe must be given).  The dropout stream is unchanged: that of the row index r. */
+int cwlt_cw_embed_proj_fwd_pos(const int64_t* tokens, const void* tproj, const int* nrows, int n_attr, const float* bias,
+                               const float* pe, const int* pos, void* out, int64_t rows, int D, float p, uint64_t seed,
+                               const uint64_t* seed_base, int dtype, void* stream) {
+    using namespace cwlt;
+    EmbedArgs a;
+    int e = fill_proj_args(a, nrows, n_attr, D);
+    if (e) return e;
+    if (rows < 0 || p < 0.f || p >= 1.f) return CWLT_ERR_ARG;
+    if (rows == 0) return CWLT_OK;
+    if (!tokens || !tproj || !bias || !out || !pe || !pos ||
+        (((uintptr_t)out | (uintptr_t)tproj | (uintptr_t)bias | (uintptr_t)pe) & 15))
+        return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t th = drop_thresh(p);
+    const float ks = drop_scale(p);
+    long nb = (rows + EP_TILE - 1) / EP_TILE;
+    if (nb > 256 * 32) nb = 256 * 32;
+    if (dtype == CWLT_F32)
+        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<float, float, true>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
+                           (const float*)tproj, a, bias, pe, (float*)out, (long)rows, pos, D, th, ks, seed, seed_base);
+    else if (dtype == CWLT_BF16)
+        hipLaunchKernelGGL((cw_embed_proj_fwd_kernel<bf16_t, bf16_t, true>), dim3((unsigned)nb), dim3(256), 0, st, tokens,
+                           (const bf16_t*)tproj, a, bias, pe, (bf16_t*)out, (long)rows, pos, D, th, ks, seed, seed_base);
     else
         return CWLT_ERR_DTYPE;
     return (int)hipGetLastError();

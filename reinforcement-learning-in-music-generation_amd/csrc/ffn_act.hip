@@ -120,12 +120,14 @@ __global__ __launch_bounds__(256) void bias_gelu_dropout_bwd_kernel(const T* __r
     }
 }
 
-// y = dropout(x + pe[t]) with pe (max_len, D) f32, row r of x is position r % T   (model.py:90-92)
-template <typename T>
+// y = dropout(x + pe[t]) with pe (max_len, D) f32, row r of x is position r % T   (model.py:90-92); POS: position
+// pos[r] from a device table (packed songs) -- the dropout stream stays that of the row index r either way
+template <typename T, bool POS>
 __global__ __launch_bounds__(256) void posenc_dropout_kernel(const T* __restrict__ x, const float* __restrict__ pe,
-                                                             T* __restrict__ y, long rows, int Tlen, int D,
-                                                             uint32_t thresh, float keep_scale, uint64_t seed,
-        const uint64_t* __restrict__ seed_base) {
+                                                             T* __restrict__ y, long rows,
+                                                             typename SeqArg<POS>::type Tlen, int D, uint32_t thresh,
+                                                             float keep_scale, uint64_t seed,
+                                                             const uint64_t* __restrict__ seed_base) {
     if (seed_base) seed += *seed_base;   // device-resident offset: lets a captured hipGraph draw fresh masks per replay
     constexpr int V = VecIO<T>::N;
     const int nd = D / V;
@@ -138,7 +140,7 @@ __global__ __launch_bounds__(256) void posenc_dropout_kernel(const T* __restrict
         VecIO<T>::load(x + off, t);
         if (pe) {
             float p[V];
-            loadf<V>(pe + (r % Tlen) * (long)D + ci * V, p);
+            loadf<V>(pe + row_pos<POS>(Tlen, r) * (long)D + ci * V, p);
 #pragma unroll
             for (int j = 0; j < V; ++j) t[j] += p[j];
         }
@@ -228,11 +230,36 @@ int cwlt_posenc_dropout(const void* x, const float* pe, void* y, int64_t rows, i
     const uint32_t th = drop_thresh(p);
     const float ks = drop_scale(p);
     if (dtype == CWLT_F32)
-        hipLaunchKernelGGL((posenc_dropout_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)x, pe, (float*)y,
+        hipLaunchKernelGGL((posenc_dropout_kernel<float, false>), dim3(nb), dim3(256), 0, st, (const float*)x, pe, (float*)y,
                            (long)rows, T, D, th, ks, seed, seed_base);
     else if (dtype == CWLT_BF16)
-        hipLaunchKernelGGL((posenc_dropout_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, pe,
+        hipLaunchKernelGGL((posenc_dropout_kernel<bf16_t, false>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, pe,
                            (bf16_t*)y, (long)rows, T, D, th, ks, seed, seed_base);
+    else
+        return CWLT_ERR_DTYPE;
+    return (int)hipGetLastError();
+}
+
+/* y = dropout(x + pe[pos[r]]): cwlt_posenc_dropout for packed songs.  pos: `rows` int32 on the device, every entry inside
+ * the pe buffer (the caller's check: the host does not read it); pe must be given.  Row r draws the dropout stream
+ * cwlt_posenc_dropout gives row r for the same seed. */
+int cwlt_posenc_dropout_pos(const void* x, const float* pe, const int* pos, void* y, int64_t rows, int D, float p,
+                            uint64_t seed, const uint64_t* seed_base, int dtype, void* stream) {
+    using namespace cwlt;
+    if (!x || !y || !pe || !pos || rows < 0 || D <= 0 || (D & 7) || p < 0.f || p >= 1.f) return CWLT_ERR_ARG;
+    if (rows == 0) return CWLT_OK;
+    const long n4 = rows * (long)(D / (dtype == CWLT_BF16 ? 8 : 4));
+    long nb = (n4 + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t th = drop_thresh(p);
+    const float ks = drop_scale(p);
+    if (dtype == CWLT_F32)
+        hipLaunchKernelGGL((posenc_dropout_kernel<float, true>), dim3(nb), dim3(256), 0, st, (const float*)x, pe,
+                           (float*)y, (long)rows, pos, D, th, ks, seed, seed_base);
+    else if (dtype == CWLT_BF16)
+        hipLaunchKernelGGL((posenc_dropout_kernel<bf16_t, true>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, pe,
+                           (bf16_t*)y, (long)rows, pos, D, th, ks, seed, seed_base);
     else
         return CWLT_ERR_DTYPE;
     return (int)hipGetLastError();

@@ -244,6 +244,55 @@ class CWTrunk(nn.Module):
             return self.transformer_encoder.prefill(x.view(N, L, D), memory, lengths, kernel="gemm", last=last,
                                                     heads=(hw, hb), rows=rows, all_rows=all_rows)
 
+    def forward_hidden_packed(self, x, cu_seqlens, pos=None):
+        """Songs of different lengths laid end to end: x (R, 6) int64, cu_seqlens an ops.SeqOffsets (or n_songs + 1 row
+        offsets; song s = rows [cu[s], cu[s + 1])).  -> (R, d_model): every song's rows are what forward_hidden gives that
+        song alone, up to where the dropout stream (keyed by the packed row) differs.
+        pos (R) int32, optional: the position of every row inside its song.  The kernels read pe[pos[r]] unchecked, so
+        the table is built here from the offsets' host copy when it is not given, and compared with that table (one
+        device comparison, a host sync) when it is: a pos that does not belong to cu_seqlens is refused."""
+        if not x.is_cuda:
+            raise RuntimeError("rlmg_amd models run on the GPU only (no CPU fallback): move inputs to cuda")
+        if x.dim() != 2:
+            raise ValueError("packed tokens are (R, n_attr), got %s" % (tuple(x.shape),))
+        cu = ops._seq_offsets(cu_seqlens, x.device).check_rows(x.shape[0])
+        want = cu.positions()
+        if pos is None:
+            pos = want
+        elif pos.dtype != torch.int32 or pos.shape != want.shape or not torch.equal(pos, want):
+            raise ValueError("pos is not the position table of cu_seqlens (row r of song s is position r - cu[s])")
+        return self._forward_hidden_packed(x, cu, pos)
+
+    def _forward_hidden_packed(self, x, cu_seqlens, pos):
+        """forward_hidden_packed with a position table the caller vouches for (data.pack_songs builds it with the
+        offsets)."""
+        if self._recurrent:
+            raise RuntimeError("model was built with is_training=False (recurrent encoder)")
+        if not x.is_cuda:
+            raise RuntimeError("rlmg_amd models run on the GPU only (no CPU fallback): move inputs to cuda")
+        if x.dim() != 2:
+            raise ValueError("packed tokens are (R, n_attr), got %s" % (tuple(x.shape),))
+        R = x.shape[0]
+        cu = ops._seq_offsets(cu_seqlens, x.device).check_rows(R)
+        pe = self.pos_emb
+        p = pe.dropout.p if pe.training else 0.0
+        seed = ops.next_seed() if p > 0 else 0
+        if ops.EMBED_PROJ and R >= ops.EMBED_PROJ_MIN_ROWS:
+            h = ops.embed_proj(x.unsqueeze(0), self._tables(), self.in_linear.weight, self.in_linear.bias, pe.pe, p, seed,
+                               self.compute_dtype, pos=pos, max_len=cu.max_len)
+        else:
+            h = ops.PosEncDropoutPosFn.apply(self.embed(x), pe.pe, pos, cu.max_len, p, seed).unsqueeze(0)
+        attn_mask = TriangularCausalMask(cu.max_len, device=x.device)
+        return self.transformer_encoder(h, attn_mask, cu_seqlens=cu).squeeze(0)
+
+    def train_step_packed(self, batch):
+        """train_step on a data.PackedBatch: the six masked means sum(mask * nll) / sum(mask) over the packed rows -- the
+        loss the padded batch of the same songs defines, without the padded rows' work."""
+        cu = ops.SeqOffsets(batch.cu, host=batch.cu_host)
+        h = self._forward_hidden_packed(batch.tokens, cu, batch.pos)
+        losses = self._losses(h, batch.target, batch.mask)
+        return tuple(losses[i] for i in range(len(self.n_token)))
+
     def _losses(self, h, target, loss_mask):
         logits = self.fused_logits(h)
         return ops.heads_ce(logits, target, loss_mask, self.n_token)

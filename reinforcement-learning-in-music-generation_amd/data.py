@@ -87,3 +87,124 @@ def load_ppo(path_dictionary, path_train_data, n_seq=8, T=1200, seed=1234):
     x, y, mask = _synth(n_seq, T, PPO_N, seed)
     return (e2w, w2e), {"train_x": x, "train_y": y, "mask": mask}
 
+
+# ----------------------------------------------------------------------------------------------------------------------
+# packed variable-length batches: songs laid end to end in one row buffer (CWTrunk.train_step_packed)
+# ----------------------------------------------------------------------------------------------------------------------
+class PackedBatch:
+    """Songs of different lengths end to end.  tokens, target (R, A) int64, mask (R) f32, pos (R) int32 (the position of
+    a row inside its song), cu (n_songs + 1) int32 row offsets -- all on `device` -- with cu_host, the same offsets as a
+    tuple of ints, and songs, the dataset indices in packed order (-1: the filler song of pad_rows_to)."""
+
+    def __init__(self, tokens, target, mask, cu, cu_host, pos, songs):
+        self.tokens, self.target, self.mask, self.cu, self.cu_host, self.pos, self.songs = (tokens, target, mask, cu,
+                                                                                            cu_host, pos, songs)
+
+    @property
+    def rows(self):
+        return self.cu_host[-1]
+
+    @property
+    def max_len(self):
+        return max(b - a for a, b in zip(self.cu_host, self.cu_host[1:]))
+
+
+def song_lengths(mask):
+    """(N, T) loss mask -> (N) int64: a song's length is its last live row plus 1 (0: no live row at all)."""
+    m = np.asarray(mask) != 0
+    T = m.shape[1]
+    return np.where(m.any(1), T - np.argmax(m[:, ::-1], axis=1), 0).astype(np.int64)
+
+
+def pack_songs(x, y, mask, indices, pad_rows_to=None, device=None, lengths=None):
+    """The songs `indices` of x, y (N, T, A), mask (N, T) as one PackedBatch, longest first (ties in the order given) so
+    the scan launch's tail is short.  Rows past a song's last live mask row are dropped; holes inside it stay, with their
+    mask 0.  pad_rows_to = k: one filler song (tokens 0, mask 0) is appended so that R % k == 0.  A song with no live
+    row is refused: the scan has no empty streams."""
+    import torch
+    indices = [int(i) for i in indices]
+    if not indices:
+        raise ValueError("pack_songs needs at least one song")
+    if lengths is None:
+        lengths = song_lengths(np.asarray(mask)[indices])
+    else:
+        lengths = np.asarray(lengths, dtype=np.int64)[indices]
+    if (lengths <= 0).any():
+        raise ValueError("song %d has no live mask row: an empty song cannot be packed"
+                         % indices[int(np.argmax(lengths <= 0))])
+    order = np.argsort(-lengths, kind="stable")
+    songs = [indices[i] for i in order]
+    lens = [int(lengths[i]) for i in order]
+    A = x.shape[2]
+    R = sum(lens)
+    fill = (-R) % int(pad_rows_to) if pad_rows_to else 0
+    tok = np.zeros((R + fill, A), dtype=np.int64)
+    tgt = np.zeros((R + fill, A), dtype=np.int64)
+    msk = np.zeros(R + fill, dtype=np.float32)
+    pos = np.zeros(R + fill, dtype=np.int32)
+    cu = [0]
+    for s, n in zip(songs, lens):
+        a = cu[-1]
+        tok[a:a + n], tgt[a:a + n], msk[a:a + n] = x[s, :n], y[s, :n], mask[s, :n]
+        pos[a:a + n] = np.arange(n)
+        cu.append(a + n)
+    if fill:
+        pos[R:] = np.arange(fill)
+        cu.append(R + fill)
+        songs = songs + [-1]
+    if device is None:
+        device = "cuda"
+    t = lambda a: torch.from_numpy(a).to(device)
+    return PackedBatch(t(tok), t(tgt), t(msk), torch.tensor(cu, dtype=torch.int32, device=device), tuple(cu), t(pos),
+                       songs)
+
+
+def _packed_groups(all_len, indices, rows_per_step, seed, max_len):
+    """The epoch's batches as lists of song indices: `indices` in the order of a permutation drawn from `seed`, cut
+    greedily (a batch closes when the next song does not fit).  Host arithmetic on the lengths only."""
+    for i in indices:
+        n = int(all_len[i])
+        if n <= 0:
+            raise ValueError("song %d has no live mask row: an empty song cannot be packed" % i)
+        if n > rows_per_step:
+            raise ValueError("song %d has %d rows, more than rows_per_step = %d" % (i, n, rows_per_step))
+        if max_len is not None and n > max_len:
+            raise ValueError("song %d has %d rows, more than the positional table (%d)" % (i, n, max_len))
+    groups, cur, rows = [], [], 0
+    for j in np.random.default_rng(seed).permutation(len(indices)):
+        i = indices[j]
+        n = int(all_len[i])
+        if cur and rows + n > rows_per_step:
+            groups.append(cur)
+            cur, rows = [], 0
+        cur.append(i)
+        rows += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def packed_groups(mask, rows_per_step, seed, max_len=None, indices=None, rank=0, world=1):
+    """The song indices of every batch packed_batches yields for the same arguments (a list of lists), from the lengths
+    alone: nothing is packed or uploaded.  len() of it is the epoch's step count."""
+    rows_per_step = int(rows_per_step)
+    indices = list(range(len(mask))) if indices is None else [int(i) for i in indices]
+    all_len = song_lengths(mask)
+    per_rank = [_packed_groups(all_len, indices[r::world], rows_per_step, seed, max_len) for r in range(world)]
+    return per_rank[rank][:min(len(g) for g in per_rank)]
+
+
+def packed_batches(x, y, mask, rows_per_step, seed, max_len=None, indices=None, pad_rows_to=None, device=None,
+                   rank=0, world=1):
+    """One epoch of PackedBatches of at most rows_per_step rows (filler included): the songs (`indices`, default all) in
+    the order of a permutation drawn from `seed`, cut greedily -- a batch closes when the next song does not fit -- so
+    every song appears exactly once and the same seed gives the same batches.  max_len: the positional table's length.
+    A song longer than rows_per_step or max_len is refused before anything is yielded.
+    world > 1 (data parallelism): rank r packs its own stride indices[r::world]; every rank yields the batch count of
+    the rank with the fewest (each works it out from the lengths alone), so that the ranks take the same number of
+    steps -- the songs of the surplus batches sit out that epoch."""
+    if pad_rows_to and int(rows_per_step) % int(pad_rows_to):
+        raise ValueError("rows_per_step must be a multiple of pad_rows_to")
+    groups = packed_groups(mask, rows_per_step, seed, max_len, indices, rank, world)
+    all_len = song_lengths(mask)
+    return (pack_songs(x, y, mask, g, pad_rows_to, device, lengths=all_len) for g in groups)      # one batch at a time

@@ -38,10 +38,14 @@ class TransformerModel(LinearTransformer):
     """agent_pretrain.py:213 re-declares model.LinearTransformer under this name."""
 
 
-def train(n_epoch=None, compute_dtype=torch.float32, log=print):
+def train(n_epoch=None, compute_dtype=torch.float32, log=print, packed_rows=None):
     """agent_pretrain.py:485-632: sequential batches of 4, loss = mean of the 6 CE losses, zero_grad / backward /
-    clip_grad_norm_(3) / Adam(1e-4); loss-banded checkpoints under ./ckpt."""
+    clip_grad_norm_(3) / Adam(1e-4); loss-banded checkpoints under ./ckpt.
+    packed_rows (or CWLT_PACKED_ROWS; default off): instead of rectangular batches of 4, every step takes songs cut at
+    their last live mask row and laid end to end, at most that many rows (data.packed_batches, a fresh permutation per
+    epoch; net.train_step_packed) -- the same loss per song set without the padded rows' work."""
     n_epoch = int(os.environ.get("CWLT_N_EPOCH", 4000)) if n_epoch is None else n_epoch
+    packed_rows = int(os.environ.get("CWLT_PACKED_ROWS", 0) or 0) if packed_rows is None else int(packed_rows)
     max_grad_norm = 3
     rank, local, world = rdist.init_from_env()
     torch.cuda.set_device(local)
@@ -67,14 +71,27 @@ def train(n_epoch=None, compute_dtype=torch.float32, log=print):
     epoch_loss = float("nan")
     for epoch in range(n_epoch):
         acc_loss, acc_losses = 0.0, np.zeros(6)
-        for bidx in range(num_batch):
+        if packed_rows:
+            # the step count from the lengths alone; the batches themselves are packed and uploaded one at a time
+            num_batch = len(cwdata.packed_groups(train_mask, packed_rows, seed=epoch, max_len=net.pos_emb.pe.shape[-2],
+                                                 rank=rank, world=world))
+            if num_batch == 0:
+                raise ValueError("packed_rows: a rank has no batch (fewer songs than ranks)")
+            steps = cwdata.packed_batches(train_x, train_y, train_mask, packed_rows, seed=epoch,
+                                          max_len=net.pos_emb.pe.shape[-2], device="cuda", rank=rank, world=world)
+        else:
+            steps = range(num_batch)
+        for bidx, step in enumerate(steps):
             if saver_agent:
                 saver_agent.global_step_increment()
-            st = batch_size * (bidx * world + rank)              # rank-strided batches under data parallelism
-            batch_x = torch.from_numpy(train_x[st:st + batch_size]).long().cuda()
-            batch_y = torch.from_numpy(train_y[st:st + batch_size]).long().cuda()
-            batch_mask = torch.from_numpy(train_mask[st:st + batch_size]).float().cuda()
-            losses = net.train_step(batch_x, batch_y, batch_mask)
+            if packed_rows:
+                losses = net.train_step_packed(step)
+            else:
+                st = batch_size * (bidx * world + rank)              # rank-strided batches under data parallelism
+                batch_x = torch.from_numpy(train_x[st:st + batch_size]).long().cuda()
+                batch_y = torch.from_numpy(train_y[st:st + batch_size]).long().cuda()
+                batch_mask = torch.from_numpy(train_mask[st:st + batch_size]).float().cuda()
+                losses = net.train_step(batch_x, batch_y, batch_mask)
             loss = (losses[0] + losses[1] + losses[2] + losses[3] + losses[4] + losses[5]) / 6
             sync.zero_grad()
             loss.backward()

@@ -47,7 +47,10 @@ class _EncoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wq, bq, wk, bk, wv, bv, wo, bo, w1, b1, w2, b2, g1, be1, g2, be2, H, p, seeds, layer,
-                shadow=None, grad_mode=True):
+                shadow=None, grad_mode=True, cu=None):
+        # cu (ops.SeqOffsets): x is (1, R, D), songs of different lengths laid end to end; only the scan knows where a
+        # song starts, everything else in the layer is row-wise.  The one-call layer path is not taken (the encoder
+        # passes no cache for packed input).
         # `grad_mode`: torch.is_grad_enabled() at the call site.  Inside forward() autograd has switched it off, and
         # ctx.needs_input_grad is true for the parameters even under torch.no_grad() -- without the flag every inference
         # and rollout pass would pay for what only a backward needs (the gd output, the scan's final state).
@@ -70,6 +73,9 @@ class _EncoderLayerFn(torch.autograd.Function):
         g1f, be1f, g2f, be2f, b1f = (ops._f32(t) for t in (g1, be1, g2, be2, b1))
 
         ctx.wt = shadow[10] if shadow is not None and len(shadow) > 10 else None
+        ctx.cu = cu
+        if cu is not None and (N != 1 or (shadow is not None and len(shadow) > 8 and shadow[8] is not None)):
+            raise RuntimeError("packed input is one (1, R, D) row buffer on the per-op layer path")
         if shadow is not None and len(shadow) > 8 and shadow[8] is not None:
             # steps of a few thousand token rows: the whole layer is ONE host call (csrc/layer.hip) -- the same kernels,
             # enqueued from C; what the backward needs stays in one `saved` buffer
@@ -107,8 +113,12 @@ class _EncoderLayerFn(torch.autograd.Function):
             qkv = torch.addmm(bqkv, x2, wqkv.t())
         qkv5 = qkv.view(N, L, 3, H, D // H)
         # with a backward to follow, the bf16 scan also hands over its final state: the backward is then one sweep
-        _, _, _, a, zinv, fin = ops.cla_fwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2],
-                                            final_state=will_backward)
+        if cu is not None:
+            _, _, _, a, zinv, fin = ops.cla_fwd_packed(qkv5[0, :, 0], qkv5[0, :, 1], qkv5[0, :, 2], cu,
+                                                       final_state=will_backward)
+        else:
+            _, _, _, a, zinv, fin = ops.cla_fwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2],
+                                                final_state=will_backward)
         ctx.fin = fin
         a2 = a.view(R, D)
         if ops.linear_ln_supported(a2, wo_a, x2):
@@ -242,8 +252,12 @@ class _EncoderLayerFn(torch.autograd.Function):
         da = dgrad(do, wo_a, 1)                                               # (R, D)
         dwo = wgrad(do, a.view(R, D))
         qkv5 = qkv.view(N, L, 3, H, D // H)
-        dqkv, dbqkv = ops.cla_bwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], a, zinv, da.view(N, L, H, D // H),
-                                  want_colsum=True, final_state=ctx.fin)
+        if ctx.cu is not None:
+            dqkv, dbqkv = ops.cla_bwd_packed(qkv5[0, :, 0], qkv5[0, :, 1], qkv5[0, :, 2], a.view(R, H, D // H), zinv,
+                                             da.view(R, H, D // H), ctx.cu, want_colsum=True, final_state=ctx.fin)
+        else:
+            dqkv, dbqkv = ops.cla_bwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], a, zinv, da.view(N, L, H, D // H),
+                                      want_colsum=True, final_state=ctx.fin)
         ctx.fin = None
         dqkv2 = dqkv.view(R, 3 * D)
         if small:
@@ -255,8 +269,9 @@ class _EncoderLayerFn(torch.autograd.Function):
                                                                            # (NN is hipBLASLt's faster form for this shape)
                                                                            # (out-of-place addmm first copies ds1: 268 MB)
         dwqkv = wgrad(dqkv2, x2)                                           # (3D, D)
-        return _EncoderLayerFn._hand_over(ctx.layer, dx.view(N, L, D), D, dwqkv, dbqkv, dwo, dbo, dw1, db1, dw2, db2, dg1,
-                                          dbe1, dg2, dbe2)
+        res = _EncoderLayerFn._hand_over(ctx.layer, dx.view(N, L, D), D, dwqkv, dbqkv, dwo, dbo, dw1, db1, dw2, db2, dg1,
+                                         dbe1, dg2, dbe2)
+        return res if ctx.cu is None else res + (None,)       # one slot per forward input: packed calls pass `cu` too
 
     @staticmethod
     def _hand_over(layer, dx, D, dwqkv, dbqkv, dwo, dbo, dw1, db1, dw2, db2, dg1, dbe1, dg2, dbe2):
@@ -400,12 +415,15 @@ class TransformerEncoderLayer(nn.Module):
                 (at.out_projection.weight,), (at.out_projection.bias,), (self.linear1.weight,), (self.linear2.weight,),
                 (self.linear2.bias,)]
 
-    def forward(self, x, attn_mask=None, shadow=None):
+    def forward(self, x, attn_mask=None, shadow=None, cu=None):
         if attn_mask is not None and not getattr(attn_mask, "lower_triangular", False):
             raise RuntimeError("CausalLinearAttention only supports full lower triangular masks")
         p = self.dropout.p if self.training else 0.0
         seeds = tuple(ops.next_seed() for _ in range(3)) if p > 0 else (0, 0, 0)
         at = self.attention
+        if cu is not None:
+            return _EncoderLayerFn.apply(
+                x, *_layer_params(self), at.n_heads, p, seeds, self, shadow, torch.is_grad_enabled(), cu)
         return _EncoderLayerFn.apply(
             x, at.query_projection.weight, at.query_projection.bias, at.key_projection.weight, at.key_projection.bias,
             at.value_projection.weight, at.value_projection.bias, at.out_projection.weight, at.out_projection.bias,
@@ -441,11 +459,19 @@ class TransformerEncoder(nn.Module):
             self._layer_c_params = ok
         return ok
 
-    def forward(self, x, attn_mask=None, length_mask=None):
+    def forward(self, x, attn_mask=None, length_mask=None, cu_seqlens=None):
+        """cu_seqlens (ops.SeqOffsets, or n_songs + 1 row offsets): x is (1, R, D), songs of different lengths laid end
+        to end; attention stays inside each song.  Packed calls run the per-op layers (R and the offsets change every
+        step, so the one-call layer path and captured graphs do not apply)."""
         if length_mask is not None:
             raise NotImplementedError("the reference never passes a length mask (dqn_policy/model.py:232)")
         if not x.is_cuda:
             raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
+        cu = None
+        if cu_seqlens is not None:
+            if x.dim() != 3 or x.shape[0] != 1:
+                raise ValueError("packed input is one (1, R, D) row buffer, got %s" % (tuple(x.shape),))
+            cu = ops._seq_offsets(cu_seqlens, x.device).check_rows(x.shape[1])
         per = 7                                             # buffers per layer (TransformerEncoderLayer.shadow_groups)
         sh = self._shadow
         if sh is None or not sh.matches(x.dtype, x.device):
@@ -453,7 +479,7 @@ class TransformerEncoder(nn.Module):
         bufs = sh.refresh()
         bufs32 = None
         cache = None
-        if self._layer_c_ok(x):
+        if cu is None and self._layer_c_ok(x):
             # few token rows: one host call per layer (csrc/layer.hip); with a backward to come, the transposed weight
             # copies of all layers are refreshed by one launch
             cache = self._cache
@@ -495,7 +521,7 @@ class TransformerEncoder(nn.Module):
                     sh_i = sh_i + (bufs32[i] if bufs32 is not None else None, None, i, tuple(tcache.views[4 * i:4 * i + 4]))
                 elif bufs32 is not None:
                     sh_i = sh_i + (bufs32[i],)
-                x = layer(x, attn_mask, sh_i)
+                x = layer(x, attn_mask, sh_i) if cu is None else layer(x, attn_mask, sh_i, cu)
         if self.norm is not None:
             x = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return x

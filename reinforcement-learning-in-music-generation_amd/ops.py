@@ -647,6 +647,168 @@ def causal_linear_attention(q, k, v, eps=CLA_EPS):
     return CausalLinearAttentionFn.apply(q, k, v, eps, torch.is_grad_enabled())
 
 
+# ---- packed form: songs of different lengths end to end in one (R, H, 64) row buffer --------------------------------
+class SeqOffsets:
+    """Row offsets of packed songs: `dev` (n_songs + 1) int32 on the GPU for the kernels, `host` the same numbers as a
+    tuple for every check (the kernels trust the table).  Song s owns rows [host[s], host[s + 1])."""
+
+    def __init__(self, cu, device=None, host=None):
+        if host is None:
+            host = cu.tolist() if torch.is_tensor(cu) else list(cu)
+        self.host = tuple(int(x) for x in host)
+        h = self.host
+        if len(h) < 2 or h[0] != 0:
+            raise ValueError("cu_seqlens must hold n_songs + 1 >= 2 row offsets starting at 0")
+        if any(b <= a for a, b in zip(h, h[1:])):
+            raise ValueError("cu_seqlens must be strictly increasing: an empty song has no rows to scan")
+        if h[-1] >= 2 ** 31:
+            raise ValueError("packed row offsets are int32")
+        if torch.is_tensor(cu) and cu.is_cuda and cu.dtype == torch.int32 and cu.is_contiguous():
+            if tuple(cu.shape) != (len(h),):
+                raise ValueError("device cu_seqlens and its host copy differ in length")
+            self.dev = cu
+        else:
+            if device is None:
+                raise RuntimeError("cu_seqlens must be an int32 GPU tensor (or name the device to put it on)")
+            self.dev = torch.tensor(h, dtype=torch.int32, device=device)
+        self.n_songs = len(h) - 1
+        self.rows = h[-1]
+        self.max_len = max(b - a for a, b in zip(h, h[1:]))
+
+    def positions(self):
+        """(rows) int32 on the offsets' device: the position of every packed row inside its song (built once)."""
+        if getattr(self, "_pos", None) is None:
+            h = self.host
+            self._pos = torch.cat([torch.arange(b - a, dtype=torch.int32) for a, b in zip(h, h[1:])]).to(self.dev.device)
+        return self._pos
+
+    def check_rows(self, rows):
+        if rows != self.rows:
+            raise ValueError("cu_seqlens ends at row %d, the packed buffer has %d rows" % (self.rows, rows))
+        return self
+
+
+def _seq_offsets(cu, device):
+    return cu if isinstance(cu, SeqOffsets) else SeqOffsets(cu, device=device)
+
+
+def _packed_stride(t):
+    """(R, H, 64) view of a row buffer: last two dims dense -> row stride, or None."""
+    R, H, D = t.shape
+    if t.stride(2) != 1 or t.stride(1) != D or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
+        return None
+    return t.stride(0)
+
+
+def _as_packed_rows(t):
+    ld = _packed_stride(t)
+    if ld is None:
+        t = t.contiguous()
+        ld = _packed_stride(t)
+    return t, ld
+
+
+def cla_fwd_packed(q, k, v, cu, eps=CLA_EPS, final_state=None):
+    """q, k, v: (R, H, 64) views (row-strided ok) of songs laid end to end, cu: SeqOffsets (or n_songs + 1 offsets) ->
+    q, k, v, out (R, H, 64) dense, zinv (R, H) f32 [, fin as `cla_fwd`: per (song, head)].  Every song is scanned from its
+    own row 0, one workgroup per (song, head); never segmented."""
+    lib = _lib.load()
+    R, H, D = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("causal linear attention needs q, k, v of one shape (R, H, D)")
+    if q.dtype != k.dtype or q.dtype != v.dtype:
+        raise TypeError("q, k, v dtypes differ")
+    _lib.dev(q, "q")
+    cu = _seq_offsets(cu, q.device).check_rows(R)
+    q, ldq = _as_packed_rows(q)
+    k, ldk = _as_packed_rows(k)
+    v, ldv = _as_packed_rows(v)
+    out = torch.empty((R, H, D), dtype=q.dtype, device=q.device)
+    zinv = torch.empty((R, H), dtype=torch.float32, device=q.device)
+    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv))
+    fin = None
+    if final_state and SCAN_SWEEP and fast:
+        fin = torch.empty(int(lib.cwlt_scan_final_state_floats(cu.n_songs, H)), dtype=torch.float32, device=q.device)
+    _call("cwlt_causal_linear_fwd_packed", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
+          _lib.dev(zinv), _lib.dev(cu.dev), cu.n_songs, H, D, ldq, ldk, ldv, H * D, float(eps), _lib.opt(fin),
+          _lib.dtype_code(q.dtype), _lib.stream_ptr())
+    if final_state is not None:
+        return q, k, v, out, zinv, fin
+    return q, k, v, out, zinv
+
+
+def cla_bwd_packed(q, k, v, out, zinv, dout, cu, want_colsum=False, final_state=None, per_song=False):
+    """-> dqkv (R, 3, H, 64) [, dbias (3*H*64) f32]: `cla_bwd` for packed songs, same routes.
+    per_song (bf16 kernels' fused column sums only): dbias as the kernels wrote it, (3, n_songs, H*64), not summed."""
+    R, H, D = q.shape
+    cu = _seq_offsets(cu, q.device).check_rows(R)
+    S = cu.n_songs
+    dout, lddo = _as_packed_rows(dout)
+    q, ldq = _as_packed_rows(q)
+    k, ldk = _as_packed_rows(k)
+    v, ldv = _as_packed_rows(v)
+    dqkv = torch.empty((R, 3, H, D), dtype=q.dtype, device=q.device)
+    ld = 3 * H * D
+    common = (_lib.dev(q), _lib.dev(k), _lib.dev(v), _lib.dev(out), _lib.dev(zinv), _lib.dev(dout, "dout"))
+    tail = (_lib.dev(cu.dev), S, H, D)
+    code, st = _lib.dtype_code(q.dtype), _lib.stream_ptr()
+    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv, lddo))
+    fused = want_colsum and fast
+    if final_state is not None and not fast:
+        final_state = None          # as in cla_bwd: a dout view the bf16 kernels cannot take goes through the pair
+    if final_state is not None:
+        cs = torch.empty((3, S, H * D), dtype=torch.float32, device=q.device) if want_colsum else None
+        _call("cwlt_causal_linear_bwd_sweep_packed", *common, _lib.dev(final_state), _lib.dev(dqkv[:, 0]),
+              _lib.dev(dqkv[:, 1]), _lib.dev(dqkv[:, 2]), *([_lib.dev(cs[i]) for i in range(3)] if want_colsum
+                                                            else [None] * 3),
+              *tail, ldq, ldk, ldv, H * D, lddo, ld, ld, ld, code, st)
+        if not want_colsum:
+            return dqkv
+        if per_song:
+            return dqkv, cs
+        return dqkv, (cs.sum(1).reshape(3 * H * D) if S > 1 else cs.reshape(3 * H * D))
+    if per_song and not fused:
+        raise ValueError("per-song column sums come from the bf16 kernels (row strides % 8 == 0) only")
+    cs = torch.empty((3, S, H * D), dtype=torch.float32, device=q.device) if fused else None
+    dden = torch.empty((R, H), dtype=torch.float32, device=q.device) if fast else None
+    _call("cwlt_causal_linear_bwd_dkdv_packed", *common, _lib.dev(dqkv[:, 1]), _lib.dev(dqkv[:, 2]),
+          _lib.dev(cs[1]) if fused else None, _lib.dev(cs[2]) if fused else None, _lib.opt(dden), *tail,
+          ldq, ldk, ldv, H * D, lddo, ld, ld, code, st)
+    _call("cwlt_causal_linear_bwd_dq_packed", *common, _lib.dev(dqkv[:, 0]), _lib.dev(cs[0]) if fused else None,
+          _lib.opt(dden), *tail, ldq, ldk, ldv, H * D, lddo, ld, code, st)
+    if not want_colsum:
+        return dqkv
+    if fused:
+        dbias = cs if per_song else cs.sum(1).reshape(3 * H * D) if S > 1 else cs.reshape(3 * H * D)
+    else:
+        dbias = colsum(dqkv.view(R, 3 * H * D))
+    return dqkv, dbias
+
+
+class CausalLinearAttentionPackedFn(torch.autograd.Function):
+    """CausalLinearAttentionFn over packed songs: q, k, v (R, H, 64), cu a SeqOffsets."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu, eps=CLA_EPS, grad_mode=True):
+        q, k, v, out, zinv, fin = cla_fwd_packed(q, k, v, cu, eps,
+                                                 final_state=bool(grad_mode) and any(ctx.needs_input_grad))
+        ctx.save_for_backward(q, k, v, out, zinv)
+        ctx.fin, ctx.cu = fin, cu
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, zinv = ctx.saved_tensors
+        dqkv = cla_bwd_packed(q, k, v, out, zinv, dout, ctx.cu, final_state=ctx.fin)
+        return dqkv[:, 0], dqkv[:, 1], dqkv[:, 2], None, None, None
+
+
+def causal_linear_attention_packed(q, k, v, cu, eps=CLA_EPS):
+    """Causal linear attention within each song of a packed (R, H, 64) buffer; cu: SeqOffsets or n_songs + 1 offsets."""
+    _lib.dev(q, "q")
+    return CausalLinearAttentionPackedFn.apply(q, k, v, _seq_offsets(cu, q.device), eps, torch.is_grad_enabled())
+
+
 # --------------------------------------------------------------------------------------------------
 # residual + dropout + LayerNorm
 # --------------------------------------------------------------------------------------------------
@@ -1127,12 +1289,30 @@ def colsum(x):
     return out
 
 
-def posenc_dropout(x, pe, T, p=0.0, seed=0):
-    """x (rows, D) dense; pe (max_len, D) f32 or None -> dropout(x + pe[r % T])."""
+def _check_pos(pos, rows, T, pe):
+    """pos: (rows) int32 on the GPU, positions of packed rows; T: the longest song (a host number: the kernels trust the
+    table, so what is checked is that the caller's bound fits the positional buffer)."""
+    if pe is None:
+        raise ValueError("pos= needs the positional table")
+    if pos.dtype != torch.int32 or tuple(pos.shape) != (rows,) or not pos.is_contiguous():
+        raise ValueError("pos must be a dense int32 tensor with one entry per row")
+    if int(T) < 1 or int(T) > pe.shape[0]:
+        raise RuntimeError("longest song %d exceeds the positional table (%d)" % (int(T), pe.shape[0]))
+
+
+def posenc_dropout(x, pe, T, p=0.0, seed=0, pos=None):
+    """x (rows, D) dense; pe (max_len, D) f32 or None -> dropout(x + pe[r % T]).
+    pos (rows) int32, optional: dropout(x + pe[pos[r]]) for packed songs, T then the longest song (every pos < T); the
+    dropout stream of row r is the same either way."""
     lib = _lib.load()
     rows, D = x.shape
     x = x.contiguous()
     y = torch.empty_like(x)
+    if pos is not None:
+        _check_pos(pos, rows, T, pe)
+        _call("cwlt_posenc_dropout_pos", _lib.dev(x, "x"), _lib.dev(pe), _lib.dev(pos, "pos"), _lib.dev(y), rows, D,
+              float(p), int(seed), _seed_base(), _lib.dtype_code(x.dtype), _lib.stream_ptr())
+        return y
     _call("cwlt_posenc_dropout", _lib.dev(x, "x"), _lib.opt(pe), _lib.dev(y), rows, int(T), D, float(p),
                                        int(seed), _seed_base(), _lib.dtype_code(x.dtype), _lib.stream_ptr())
     return y
@@ -1156,6 +1336,23 @@ class PosEncDropoutFn(torch.autograd.Function):
             return dy, None, None, None
         N, T, D = dy.shape
         return posenc_dropout(dy.reshape(N * T, D), None, T, ctx.p, ctx.seed).view(N, T, D), None, None, None
+
+
+class PosEncDropoutPosFn(torch.autograd.Function):
+    """PosEncDropoutFn for packed songs: x (R, D), row r at position pos[r] (int32 on the GPU), max_len the longest
+    song.  The backward never reads pe, so it is the rectangular one."""
+
+    @staticmethod
+    def forward(ctx, x, pe, pos, max_len, p, seed):
+        R, D = x.shape
+        ctx.p, ctx.seed, ctx.T = p, seed, int(max_len)
+        return posenc_dropout(x, pe.reshape(-1, D), max_len, p, seed, pos=pos)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if ctx.p == 0:
+            return dy, None, None, None, None, None
+        return posenc_dropout(dy, None, ctx.T, ctx.p, ctx.seed), None, None, None, None, None
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1227,7 +1424,7 @@ class EmbedProjFn(torch.autograd.Function):
     one-hot MFMA GEMM of cwlt_cw_embed_bwd), db = the column sum of one attribute's rows of dP."""
 
     @staticmethod
-    def forward(ctx, tokens, tproj, bias, pe, nrows, p, seed, out_dtype):
+    def forward(ctx, tokens, tproj, bias, pe, nrows, p, seed, out_dtype, pos=None, max_len=None):
         if tokens.dtype != torch.int64:
             raise TypeError("tokens must be int64 (the reference indexes nn.Embedding with .long())")
         N, T, A = tokens.shape
@@ -1238,17 +1435,24 @@ class EmbedProjFn(torch.autograd.Function):
             raise ValueError("projected tables / bias do not match the vocabularies")
         if pe is not None:
             pe = pe.reshape(-1, D)
-            if T > pe.shape[0]:
+            if pos is None and T > pe.shape[0]:
                 raise RuntimeError("sequence length %d exceeds the positional table (%d)" % (T, pe.shape[0]))
         tok = tokens.reshape(-1, A).contiguous()
         rows = tok.shape[0]
         tp = tproj.detach().to(out_dtype).contiguous()
         out = torch.empty((rows, D), dtype=out_dtype, device=tok.device)
-        _call("cwlt_cw_embed_proj_fwd", _lib.dev(tok, "tokens"), _lib.dev(tp), _lib.int_array(nrows), A,
-              _lib.dev(_f32(bias)), _lib.opt(None if pe is None else _f32(pe)), _lib.dev(out), rows, int(T), D, float(p),
-              int(seed), _seed_base(), _lib.dtype_code(out_dtype), _lib.stream_ptr())
+        if pos is not None:
+            _check_pos(pos, rows, max_len, pe)
+            _call("cwlt_cw_embed_proj_fwd_pos", _lib.dev(tok, "tokens"), _lib.dev(tp), _lib.int_array(nrows), A,
+                  _lib.dev(_f32(bias)), _lib.dev(_f32(pe)), _lib.dev(pos, "pos"), _lib.dev(out), rows, D, float(p),
+                  int(seed), _seed_base(), _lib.dtype_code(out_dtype), _lib.stream_ptr())
+        else:
+            _call("cwlt_cw_embed_proj_fwd", _lib.dev(tok, "tokens"), _lib.dev(tp), _lib.int_array(nrows), A,
+                  _lib.dev(_f32(bias)), _lib.opt(None if pe is None else _f32(pe)), _lib.dev(out), rows, int(T), D,
+                  float(p), int(seed), _seed_base(), _lib.dtype_code(out_dtype), _lib.stream_ptr())
         ctx.save_for_backward(tok)
         ctx.cfg = (list(nrows), T, D, p, seed)
+        ctx.pos_form = pos is not None
         return out.view(N, T, D)
 
     @staticmethod
@@ -1266,18 +1470,21 @@ class EmbedProjFn(torch.autograd.Function):
         _call("cwlt_cw_embed_proj_bwd", _lib.dev(tok), _lib.int_array(nrows), A, D, _lib.dev(dpre, "dpre"), _lib.dev(part),
               _lib.dev(dtp), rows, D, _lib.dtype_code(dpre.dtype), _lib.stream_ptr())
         dbias = dtp[:nrows[0]].sum(0)             # every token row has exactly one id of attribute 0
-        return None, dtp, dbias, None, None, None, None, None
+        return (None, dtp, dbias) + (None,) * (5 if ctx.pos_form is False else 7)
 
 
-def embed_proj(tokens, tables, w_in, b_in, pe, p, seed, out_dtype):
-    """tokens (N, T, A); tables: A embedding weights (n_f, d_f) f32; w_in (D, sum d_f), b_in (D); pe (.., max_len, D)."""
+def embed_proj(tokens, tables, w_in, b_in, pe, p, seed, out_dtype, pos=None, max_len=None):
+    """tokens (N, T, A); tables: A embedding weights (n_f, d_f) f32; w_in (D, sum d_f), b_in (D); pe (.., max_len, D).
+    pos (N * T) int32 with max_len = the longest song: packed songs, row r at position pos[r] in place of r % T."""
     cols, parts = 0, []
     for t in tables:
         d = t.shape[1]
         parts.append(torch.nn.functional.linear(t * math.sqrt(d), w_in[:, cols:cols + d]))
         cols += d
     tproj = torch.cat(parts, 0)
-    return EmbedProjFn.apply(tokens, tproj, b_in, pe, tuple(t.shape[0] for t in tables), p, seed, out_dtype)
+    if pos is None:
+        return EmbedProjFn.apply(tokens, tproj, b_in, pe, tuple(t.shape[0] for t in tables), p, seed, out_dtype)
+    return EmbedProjFn.apply(tokens, tproj, b_in, pe, tuple(t.shape[0] for t in tables), p, seed, out_dtype, pos, max_len)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -54,9 +54,15 @@ def write_config_log(logfile_path, purpose, len_train_x, len_train_y, epochs, ba
 
 
 def pretrain(model, my_dataset, optimizer, scheduler, flag, config_path, ckpt_path, num_epoch=None, sync=None,
-             log=print):
-    """my_pretrain.py:34-135.  -> list of the last batch's loss per epoch (the reference's `record_loss`)."""
+             log=print, packed_rows=None):
+    """my_pretrain.py:34-135.  -> list of the last batch's loss per epoch (the reference's `record_loss`).
+    packed_rows (or CWLT_PACKED_ROWS; default off; agent pretraining only): every step takes songs cut at their last
+    live mask row and laid end to end, at most that many rows (data.packed_batches, a fresh permutation per epoch;
+    model.train_step_packed) in place of rectangular batches of 12."""
     num_epoch = NUM_EPOCH if num_epoch is None else num_epoch
+    packed_rows = int(os.environ.get("CWLT_PACKED_ROWS", 0) or 0) if packed_rows is None else int(packed_rows)
+    if packed_rows and flag:
+        raise ValueError("packed batches are for the agent's pretraining: the reward model attends across a band")
     rank = torch.distributed.get_rank() if (sync is not None and sync.world > 1) else 0
     world = sync.world if sync is not None else 1
     train_x, train_y, mask = my_dataset["train_x"], my_dataset["train_y"], my_dataset["mask"]
@@ -75,12 +81,25 @@ def pretrain(model, my_dataset, optimizer, scheduler, flag, config_path, ckpt_pa
     for epoch in range(num_epoch):
         acc_loss, arr_losses = 0.0, np.zeros(6)
         CELoss = None
-        for bidx in range(num_batch):
-            st = BATCH_SIZE * (bidx * world + rank)
-            batch_x = torch.from_numpy(train_x[st:st + BATCH_SIZE]).long().to(device)
-            batch_y = torch.from_numpy(train_y[st:st + BATCH_SIZE]).long().to(device)
-            batch_mask = torch.from_numpy(mask[st:st + BATCH_SIZE]).float().to(device)
-            losses = model.train_step(batch_x, batch_y, batch_mask)
+        if packed_rows:
+            # the step count from the lengths alone; the batches themselves are packed and uploaded one at a time
+            num_batch = len(cwdata.packed_groups(mask, packed_rows, seed=epoch, max_len=model.pos_emb.pe.shape[-2],
+                                                 rank=rank, world=world))
+            if num_batch == 0:
+                raise ValueError("packed_rows: a rank has no batch (fewer songs than ranks)")
+            steps = cwdata.packed_batches(train_x, train_y, mask, packed_rows, seed=epoch,
+                                          max_len=model.pos_emb.pe.shape[-2], device=device, rank=rank, world=world)
+        else:
+            steps = range(num_batch)
+        for bidx, step in enumerate(steps):
+            if packed_rows:
+                losses = model.train_step_packed(step)
+            else:
+                st = BATCH_SIZE * (bidx * world + rank)
+                batch_x = torch.from_numpy(train_x[st:st + BATCH_SIZE]).long().to(device)
+                batch_y = torch.from_numpy(train_y[st:st + BATCH_SIZE]).long().to(device)
+                batch_mask = torch.from_numpy(mask[st:st + BATCH_SIZE]).float().to(device)
+                losses = model.train_step(batch_x, batch_y, batch_mask)
             CELoss = (losses[0] + losses[1] + losses[2] + losses[3] + losses[4] + losses[5]) / 6
             sync.zero_grad()
             CELoss.backward()
