@@ -433,6 +433,16 @@ int cwlt_causal_linear_fwd_state(const void* q, const void* k, const void* v, vo
                                  const int* lengths, int N, int H, int L, int head_dim, int64_t ldq, int64_t ldk,
                                  int64_t ldv, int64_t ldo, float eps, int segments, float* seg_ws, int dtype,
                                  void* stream);
+/* Packed form: songs of different lengths laid end to end in (rows, H, 64) row buffers, as the packed scans above.  cu:
+ * n_songs + 1 int32 row offsets ON THE DEVICE (cu[0] = 0, strictly increasing; the host does not read it); song s owns
+ * rows [cu[s], cu[s + 1]), starts from S[s], Z[s] ((n_songs, H, 64, 64) / (n_songs, H, 64)) and leaves there the state
+ * after its last row.  The same kernel with the offset table in place of (lengths, L): one workgroup per (song, head)
+ * runs ceil(len / 32) chunks from the song's own row 0, never segmented, so out rows, S and Z of a song are bitwise
+ * those of cwlt_causal_linear_fwd_state on that song alone (N = 1, L = len, segments = 1) and no row outside
+ * [0, cu[n_songs]) is read or written.  Refusals as above, plus a NULL cu; n_songs = 0 launches nothing. */
+int cwlt_causal_linear_fwd_state_packed(const void* q, const void* k, const void* v, void* out, float* S, float* Z,
+                                        const int* cu, int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk,
+                                        int64_t ldv, int64_t ldo, float eps, int dtype, void* stream);
 
 /* ---- generation: one CW token through the whole recurrent-form model (f32) --------------------------
  * Replaces the per-token body of the reference's generation loop: `forward_hidden(input_, memory,
@@ -673,7 +683,11 @@ int cwlt_blend_logits(const float* logits, int64_t ld, const float* ref_logits, 
  * seen_rows (nb * Lb x ld f32), row t of a song the state after its rows 0 .. t from a zero state -- what the logits
  * of row t, which predict row t + 1, are penalised by.  The song's decay is that of k = key[i Lb] (DEVICE int64 x nb *
  * Lb, the per-row key of cwlt_prefer_logits; NULL: i); k outside [0, n_songs): decay 0.  One thread per (song, column)
- * walks the rows in order with the step of cwlt_prefer_track.  nb * Lb <= 2^20. */
+ * walks the rows in order with the step of cwlt_prefer_track.  nb * Lb <= 2^20.
+ *
+ * cwlt_prefer_scan_packed: the same for n_block songs laid end to end, song i in rows [cu[i], cu[i + 1]) (cu: DEVICE
+ * int32 x n_block + 1, as cwlt_causal_linear_fwd_state_packed; not read by the host); its decay is that of k =
+ * key[cu[i]] (NULL: i).  The rows of a song are bitwise those of cwlt_prefer_scan.  n_block <= 2^20. */
 int cwlt_prefer_logits(const float* logits, int64_t ld, const int* n_class, int n_attr, const int64_t* key,
                        const int64_t* bar, const int64_t* sched, int64_t n_songs, const float* bias,
                        int64_t bias_rows, int64_t ld_bias, const float* pen, const float* seen, int64_t ld_seen,
@@ -683,6 +697,9 @@ int cwlt_prefer_track(const int64_t* tokens, int64_t rows, const int* n_class, i
                       int64_t ld_seen, void* stream);
 int cwlt_prefer_scan(const int64_t* tokens, int64_t nb, int64_t Lb, const int* n_class, int n_attr, const float* pen,
                      int64_t n_songs, const int64_t* key, float* seen_rows, int64_t ld, void* stream);
+int cwlt_prefer_scan_packed(const int64_t* tokens, const int* cu, int64_t n_block, const int* n_class, int n_attr,
+                            const float* pen, int64_t n_songs, const int64_t* key, float* seen_rows, int64_t ld,
+                            void* stream);
 
 /* ---- continuous batching (csrc/stream.hip) ------------------------------------------------------------------------------
  * A pool of `slots` rows of cwlt_decode_step_rows runs many songs; per token the stream enqueues the decode step,

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_PKG, "libcwlt.so")
 
 CWLT_F32 = 0
 CWLT_BF16 = 1
-ABI_VERSION = 38
+ABI_VERSION = 39
 
 _c_int = ctypes.c_int
 _c_i64 = ctypes.c_int64
@@ -121,6 +121,7 @@ _SIGNATURES = {
     "cwlt_prefill_segments": [_c_int, _c_int, _c_int],
     "cwlt_prefill_seg_floats": [_c_int, _c_int, _c_int],
     "cwlt_causal_linear_fwd_state": [_ptr] * 7 + [_c_int] * 4 + [_c_i64] * 4 + [_c_f32, _c_int, _ptr, _c_int, _ptr],
+    "cwlt_causal_linear_fwd_state_packed": [_ptr] * 7 + [_c_int] * 3 + [_c_i64] * 4 + [_c_f32, _c_int, _ptr],
     "cwlt_decode_workspace_floats": [ctypes.POINTER(DecodeModel)],
     "cwlt_decode_step": [ctypes.POINTER(DecodeModel), _ptr, _ptr, _ptr, _ptr, _c_int, _ptr],
     "cwlt_decode_gemv": [_ptr] * 7 + [_c_f32] + [_ptr] * 3 + [_c_int] * 4 + [_c_i64] * 4 + [_ptr],
@@ -149,6 +150,7 @@ _SIGNATURES = {
                            _ptr, _c_i64, _c_i64, _ptr],
     "cwlt_prefer_track": [_ptr, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _c_i64, _ptr],
     "cwlt_prefer_scan": [_ptr, _c_i64, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr],
+    "cwlt_prefer_scan_packed": [_ptr, _ptr, _c_i64, _ptr, _c_int, _ptr, _c_i64, _ptr, _ptr, _c_i64, _ptr],
     "cwlt_grammar_track": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _ptr, _ptr],
     "cwlt_count_bars": [_ptr, _c_i64, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr],
     "cwlt_stream_refill": [_ptr, _ptr, _c_int, _c_i64, _c_i64, _ptr, _ptr, _c_i64, _c_i64, _ptr, _c_i64, _ptr],

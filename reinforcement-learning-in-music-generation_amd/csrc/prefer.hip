@@ -5,7 +5,8 @@
 // b the song's bias row for the row's bar count, s = seen[n][c], f / p the song's frequency / presence penalty for
 // the attribute of c (0 for the attribute's class 0, the neutral class, and without `seen`).  `seen` is one f32 per
 // class and song, moved after every row by seen = seen * decay + hit: cwlt_prefer_track (one row per slot, after a
-// draw) and cwlt_prefer_scan (every row of given songs, for the scorers) share seen_step.
+// draw) and cwlt_prefer_scan / cwlt_prefer_scan_packed (every row of given songs, padded to one length or laid end to
+// end, for the scorers) share seen_step.
 // Every product and sum is rounded on its own in f32 (fp contract off in prefer_one and seen_step: v_mul_f32 +
 // v_add_f32, no v_fmac_f32), so the device is bitwise the numpy float32 restatement (sampling.prefer_logits_f32,
 // Preference.seen_states) and generation and scoring see the same state.
@@ -141,22 +142,34 @@ __global__ __launch_bounds__(256) void prefer_track_kernel(const int64_t* __rest
 // One thread per (song, column) walks the song's rows in order from a zero state and writes the state after rows
 // 0 .. t into row t: threads of one song are neighbours in c, so every load and store is coalesced across columns.
 // A song outside [0, n_songs) has decay 0: its rows hold the hit of their own token alone.
-__global__ __launch_bounds__(256) void prefer_scan_kernel(const int64_t* __restrict__ tokens, unsigned nb, long Lb,
-                                                          PreferAttr at, int width, const float* __restrict__ pen,
-                                                          long n_songs, const int64_t* __restrict__ key,
+// PACKED: `seq` is the int32 offset table cu in place of Lb, song sg owns rows [cu[sg], cu[sg + 1]) (a thread's own
+// two words: the songs of one wave differ).
+template <bool PACKED>
+__global__ __launch_bounds__(256) void prefer_scan_kernel(const int64_t* __restrict__ tokens, unsigned nb,
+                                                          typename SeqArg<PACKED>::type seq, PreferAttr at, int width,
+                                                          const float* __restrict__ pen, long n_songs,
+                                                          const int64_t* __restrict__ key,
                                                           float* __restrict__ seen_rows, long ld) {
     const unsigned total = nb * (unsigned)width, stride = gridDim.x * blockDim.x;
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const unsigned sg = i / (unsigned)width;
         const int c = (int)(i - sg * (unsigned)width);
-        const long k = key ? key[(long)sg * Lb] : (long)sg;
+        long row0, Lb;
+        if constexpr (PACKED) {
+            row0 = seq[sg];
+            Lb = seq[sg + 1] - row0;
+        } else {
+            row0 = (long)sg * seq;
+            Lb = seq;
+        }
+        const long k = key ? key[row0] : (long)sg;
         const float d = k < 0 || k >= n_songs ? 0.0f : pen[k * (2 * at.n_attr + 1) + 2 * at.n_attr];
         int first;
         const int a = attr_of(at, c, &first);
         const int64_t mine = (int64_t)(c - first);
         float s = 0.0f;
         for (long t = 0; t < Lb; ++t) {
-            const long row = (long)sg * Lb + t;
+            const long row = row0 + t;
             s = seen_step(s, d, tokens[row * at.n_attr + a] == mine ? 1.0f : 0.0f);
             seen_rows[row * ld + c] = s;
         }
@@ -238,7 +251,21 @@ extern "C" int cwlt_prefer_scan(const int64_t* tokens, int64_t nb, int64_t Lb, c
     if (width < 0 || n_songs < 1 || nb < 1 || Lb < 1 || nb > (1L << 20) || Lb > (1L << 20) || nb * Lb > (1L << 20) ||
         ld < width)
         return CWLT_ERR_ARG;
-    hipLaunchKernelGGL(prefer_scan_kernel, dim3(prefer_blocks(nb * width)), dim3(256), 0, (hipStream_t)stream, tokens,
-                       (unsigned)nb, (long)Lb, at, width, pen, (long)n_songs, key, seen_rows, (long)ld);
+    hipLaunchKernelGGL(prefer_scan_kernel<false>, dim3(prefer_blocks(nb * width)), dim3(256), 0, (hipStream_t)stream,
+                       tokens, (unsigned)nb, (int)Lb, at, width, pen, (long)n_songs, key, seen_rows, (long)ld);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cwlt_prefer_scan_packed(const int64_t* tokens, const int* cu, int64_t n_block, const int* n_class,
+                                       int n_attr, const float* pen, int64_t n_songs, const int64_t* key,
+                                       float* seen_rows, int64_t ld, void* stream) {
+    using namespace cwlt;
+    if (!tokens || !cu || !pen || !seen_rows) return CWLT_ERR_ARG;
+    PreferAttr at;
+    const int width = prefer_attr(n_class, n_attr, &at);
+    if (width < 0 || n_songs < 1 || n_block < 1 || n_block > (1L << 20) || ld < width) return CWLT_ERR_ARG;
+    hipLaunchKernelGGL(prefer_scan_kernel<true>, dim3(prefer_blocks(n_block * width)), dim3(256), 0,
+                       (hipStream_t)stream, tokens, (unsigned)n_block, cu, at, width, pen, (long)n_songs, key,
+                       seen_rows, (long)ld);
     return (int)hipGetLastError();
 }

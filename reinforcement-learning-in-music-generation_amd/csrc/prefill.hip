@@ -19,6 +19,10 @@
 // Few streams (one song at the repo dims is 8 workgroups on 256 CUs): the segmented form cuts every sequence into runs
 // of whole chunks, one workgroup each -- pass 1 reduces each run to its state increment, pass 2 turns the increments
 // into starting states (S0, Z0 added), pass 3 is the scan above from each run's own start.
+//
+// Packed form (cwlt_causal_linear_fwd_state_packed): prompts of different lengths laid end to end in
+// (R, H, 64) row buffers with a device table of song starts; the same scan kernel instantiated with the table in place
+// of (lengths, L), one workgroup per (song, head), never segmented -- every song bit for bit the rectangular scan of it.
 #include "cwlt_common.h"
 
 namespace cwlt {
@@ -165,12 +169,16 @@ __global__ __launch_bounds__(256) void cla_state_prefix_kernel(const float* __re
 // The scan proper.  G == 1: one workgroup per (n, h) starts from (S, Z) and writes the final state back.  G > 1:
 // workgroup (n, h, g) runs segment g's chunks from the starting state pass 2 left in ws; the segment holding the
 // sequence's last chunk writes the final state (no workgroup reads S or Z then, so in place is safe).
+// PACKED: `seq` is the offset table cu (cwlt_common.h, seq_span) in place of L; workgroup (s, h) owns rows [cu[s],
+// cu[s + 1]) of (R, H, 64) row buffers and runs all of the song's chunks from its row 0, never segmented (ws and
+// lengths are NULL, G is 1) -- the rectangular scan of that song alone, chunk for chunk.
+template <bool PACKED>
 __global__ __launch_bounds__(128) void cla_fwd_state_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                             const float* __restrict__ v, float* __restrict__ o,
                                                             float* __restrict__ S, float* __restrict__ Z,
                                                             const float* __restrict__ ws, const int* __restrict__ lengths,
-                                                            int H, int L, int G, int cps, long ldq, long ldk, long ldv,
-                                                            long ldo, float eps) {
+                                                            int H, typename SeqArg<PACKED>::type seq, int G_, int cps,
+                                                            long ldq, long ldk, long ldv, long ldo, float eps) {
     __shared__ float qs[C * LDT];
     __shared__ float ks[C * LDT];
     __shared__ float vs[C * LDT];
@@ -178,18 +186,28 @@ __global__ __launch_bounds__(128) void cla_fwd_state_kernel(const float* __restr
     __shared__ float ksum[2][D];
     __shared__ float zs[2][C];
 
+    const int G = PACKED ? 1 : G_;
     const int nh = blockIdx.x / G, g = blockIdx.x % G, n = nh / H, h = nh % H;
     int len, nch, c0, c1;
-    seg_range(lengths, n, L, g, cps, len, nch, c0, c1);
+    long row0;  // the stream's first row
+    if constexpr (PACKED) {
+        seq_span<true>(seq, n, row0, len);
+        nch = (len + C - 1) / C;
+        c0 = 0;
+        c1 = nch;
+    } else {
+        row0 = (long)n * seq;
+        seg_range(lengths, n, seq, g, cps, len, nch, c0, c1);
+    }
     if (c0 >= c1) return;  // nothing to add (a length of 0 leaves S and Z bit-for-bit as they are)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hf = lane >> 5;
-    const float* qb = q + ((long)n * L) * ldq + h * D;
-    const float* kb = k + ((long)n * L) * ldk + h * D;
-    const float* vb = v + ((long)n * L) * ldv + h * D;
-    float* ob = o + ((long)n * L) * ldo + h * D;
+    const float* qb = q + row0 * ldq + h * D;
+    const float* kb = k + row0 * ldk + h * D;
+    const float* vb = v + row0 * ldv + h * D;
+    float* ob = o + row0 * ldo + h * D;
     float* Sb = S + (long)nh * (D * D) + 32 * w + l31;  // this lane's value column m = 32w + l31
     float* Zb = Z + (long)nh * D;
     const float* Sin = G == 1 ? Sb : ws + (long)blockIdx.x * (D * D + D) + 32 * w + l31;
@@ -328,9 +346,27 @@ int cwlt_causal_linear_fwd_state(const void* q, const void* k, const void* v, vo
         hipLaunchKernelGGL(cla_state_prefix_kernel, dim3(N * H), dim3(256), 0, st, (const float*)S, (const float*)Z,
                            seg_ws, segments);
     }
-    hipLaunchKernelGGL(cla_fwd_state_kernel, dim3(N * H * segments), dim3(128), 0, st, (const float*)q,
+    hipLaunchKernelGGL(cla_fwd_state_kernel<false>, dim3(N * H * segments), dim3(128), 0, st, (const float*)q,
                        (const float*)k, (const float*)v, (float*)out, S, Z, (const float*)seg_ws, lengths, H, L,
                        segments, cps, (long)ldq, (long)ldk, (long)ldv, (long)ldo, eps);
+    return (int)hipGetLastError();
+}
+
+int cwlt_causal_linear_fwd_state_packed(const void* q, const void* k, const void* v, void* out, float* S, float* Z,
+                                        const int* cu, int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk,
+                                        int64_t ldv, int64_t ldo, float eps, int dtype, void* stream) {
+    using namespace cwlt;
+    using namespace cwlt::prefill;
+    if (!q || !k || !v || !out || !S || !Z || !cu || n_songs < 0 || H <= 0 || head_dim != 64) return CWLT_ERR_ARG;
+    if (dtype != CWLT_F32) return CWLT_ERR_DTYPE;
+    if (ldq % 4 || ldk % 4 || ldv % 4 || ldq < H * 64 || ldk < H * 64 || ldv < H * 64 || ldo < H * 64 ||
+        ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16)
+        return CWLT_ERR_ARG;
+    if ((int64_t)n_songs * H > 0x7fffffffLL) return CWLT_ERR_ARG;
+    if (n_songs == 0) return CWLT_OK;
+    hipLaunchKernelGGL(cla_fwd_state_kernel<true>, dim3(n_songs * H), dim3(128), 0, (hipStream_t)stream,
+                       (const float*)q, (const float*)k, (const float*)v, (float*)out, S, Z, (const float*)nullptr,
+                       (const int*)nullptr, H, cu, 1, 0, (long)ldq, (long)ldk, (long)ldv, (long)ldo, eps);
     return (int)hipGetLastError();
 }
 

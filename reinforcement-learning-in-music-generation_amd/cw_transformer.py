@@ -225,24 +225,60 @@ class CWTrunk(nn.Module):
         between the replays of a running stream): tokens (N, L, 6) int64, lengths (N) int32 or None, last (N) int64 =
         lengths - 1, all on the GPU.  -> (hidden (N, D), logits (N, sum n_token)); all_rows=True: (None, logits (N, L,
         sum n_token)), the heads on every row (prefill_hidden(logits="all"))."""
+        N, L, _ = tokens.shape
+        x, heads, rows = self._prefill_front(tokens.reshape(N * L, -1), rows)
+        return self.transformer_encoder.prefill(x.view(N, L, -1), memory, lengths, kernel="gemm", last=last,
+                                                heads=heads, rows=rows, all_rows=all_rows)
+
+    def _prefill_front(self, tokens, rows):
+        """The gemm prefill's row-wise front: tokens (M, 6) -> (x (M, D) = in_linear(embedding) + pe[0] by
+        cwlt_decode_gemm in calls of at most `rows` rows, the stacked f32 heads (w, b), rows)."""
         rows = 4096 if rows is None else int(rows)
         if not 1 <= rows <= 4096:
             raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
-        N, L, _ = tokens.shape
+        M = tokens.shape[0]
         D = self.d_model
         with torch.no_grad():
-            emb = ops.cw_embed(tokens, self._tables(), torch.float32).reshape(N * L, -1)
-            x = torch.empty((N * L, D), dtype=torch.float32, device=tokens.device)
-            pe = self.pos_emb.pe.reshape(-1, D)[0].float().expand(min(rows, N * L), D).contiguous()   # pe[0] rows
+            emb = ops.cw_embed(tokens, self._tables(), torch.float32).reshape(M, -1)
+            x = torch.empty((M, D), dtype=torch.float32, device=tokens.device)
+            pe = self.pos_emb.pe.reshape(-1, D)[0].float().expand(min(rows, M), D).contiguous()   # pe[0] rows
             w, b = ops._f32(self.in_linear.weight), ops._f32(self.in_linear.bias)
-            for a in range(0, N * L, rows):
-                z = min(N * L, a + rows)
+            for a in range(0, M, rows):
+                z = min(M, a + rows)
                 ops.decode_gemm(w, b, emb[a:z], res=pe[:z - a], out=x[a:z])
             heads = self._heads()
             hw = torch.cat([ops._f32(m.weight) for m in heads], 0)
             hb = torch.cat([ops._f32(m.bias) for m in heads], 0)
-            return self.transformer_encoder.prefill(x.view(N, L, D), memory, lengths, kernel="gemm", last=last,
-                                                    heads=(hw, hb), rows=rows, all_rows=all_rows)
+        return x, (hw, hb), rows
+
+    def prefill_hidden_packed(self, tokens, cu_seqlens, memory, logits=True, rows=None):
+        """prefill_hidden(kernel="gemm") for prompts laid end to end, no padded rows: tokens (R, 6) int64 on the GPU,
+        cu_seqlens an ops.SeqOffsets (or n_songs + 1 row offsets; song s = rows [cu[s], cu[s + 1])), memory the per-layer
+        [S (n_songs, ...), Zs] state, advanced IN PLACE.  Every song's state, hidden row and logits are bitwise those of
+        prefill_hidden(kernel="gemm", lengths=...) whatever the padding there.  logits=True -> (hidden (n_songs, D),
+        logits (n_songs, sum n_token)) of each song's last row; logits="all" -> (R, sum n_token), row cu[s] + t the
+        next-token logits after song s's rows 0 .. t.  The offsets are checked on their host copy; the kernels trust
+        the table."""
+        if logits not in (True, "all"):
+            raise ValueError("logits must be True or 'all', got %r" % (logits,))
+        if not tokens.is_cuda:
+            raise RuntimeError("rlmg_amd models run on the GPU only (no CPU fallback): move inputs to cuda")
+        if tokens.dim() != 2:
+            raise ValueError("packed tokens are (R, n_attr), got %s" % (tuple(tokens.shape),))
+        cu = ops._seq_offsets(cu_seqlens, tokens.device).check_rows(tokens.shape[0])
+        h, lg = self._prefill_gemm_packed(tokens, cu, memory, rows, all_rows=logits == "all")
+        return lg if logits == "all" else (h, lg)
+
+    def _prefill_gemm_packed(self, tokens, cu, memory, rows=None, all_rows=False):
+        """prefill_hidden_packed on device arguments only (cu an ops.SeqOffsets the caller vouches for; no host sync, so
+        it can be enqueued between the replays of a running stream).  -> (hidden, logits) or (None, logits (R, W))."""
+        if not self._recurrent:
+            raise RuntimeError("the packed prefill needs a model built with is_training=False (recurrent encoder)")
+        if self.compute_dtype != torch.float32:
+            raise RuntimeError("the packed prefill computes in f32; this model's activations are %s"
+                               % self.compute_dtype)
+        x, heads, rows = self._prefill_front(tokens, rows)
+        return self.transformer_encoder.prefill_packed(x, memory, cu, heads, rows=rows, all_rows=all_rows)
 
     def forward_hidden_packed(self, x, cu_seqlens, pos=None):
         """Songs of different lengths laid end to end: x (R, 6) int64, cu_seqlens an ops.SeqOffsets (or n_songs + 1 row

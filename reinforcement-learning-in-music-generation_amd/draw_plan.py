@@ -571,8 +571,9 @@ def check_entry(model, what, sampler=None, like=None, **kernel):
     if sampler is not None:
         sampler_settings(sampler)
     for name, value in kernel.items():
-        if value not in ("blas", "gemm"):
-            raise ValueError("%s must be 'blas' or 'gemm', got %r" % (name, value))
+        if value not in ("blas", "gemm", "packed"):
+            raise ValueError("%s must be 'blas' or 'gemm' (or 'packed', gemm's bits without padded rows), got %r"
+                             % (name, value))
     if not getattr(model, "_recurrent", False):
         raise RuntimeError("%s needs a model built with is_training=False (recurrent encoder)" % what)
     if model.training:

@@ -96,6 +96,35 @@ def stream_bank_plan(prompt_lengths, slots, prefill_rows=None, bank=None, entry_
     return B, min(nb, blocks) * B
 
 
+def packed_blocks(lengths, prefill_rows=None, max_songs=None):
+    """Blocks of the packed prefill -> [(a, z), ...]: consecutive whole songs [a, z), taken greedily while the block's
+    summed rows stay within prefill_rows (default PREFILL_ROWS) and it holds at most max_songs songs (None: no cap); a
+    song longer than the budget is a block of its own."""
+    rows = PREFILL_ROWS if prefill_rows is None else int(prefill_rows)
+    if rows < 1:
+        raise ValueError("prefill_rows must be >= 1, got %d" % rows)
+    if max_songs is not None and int(max_songs) < 1:
+        raise ValueError("max_songs must be >= 1, got %d" % max_songs)
+    lens = [int(n) for n in lengths]
+    out, a, used = [], 0, 0
+    for i, n in enumerate(lens):
+        if n < 1:
+            raise ValueError("song %d is empty: a packed block holds songs of at least one row" % i)
+        if i > a and (used + n > rows or (max_songs is not None and i - a >= int(max_songs))):
+            out.append((a, i))
+            a, used = i, 0
+        used += n
+    if lens:
+        out.append((a, len(lens)))
+    return out
+
+
+def _pack_rows(arrays, dev=None):
+    """Songs laid end to end: a list of (L_i, A) int64 arrays -> ((R, A) array, its ops.SeqOffsets on `dev`)."""
+    cu = np.concatenate([[0], np.cumsum([len(x) for x in arrays])])
+    return np.concatenate(arrays), ops.SeqOffsets(cu.tolist(), device=dev)
+
+
 def bank_may_prefill(j, B, bank, assigned):
     """Reuse rule of the bank: block j (songs [j B, (j + 1) B), entries [(j % nb) B, ...) with nb = bank // B) may be
     written once the block that held those entries before it, j - nb, has all its songs assigned to slots (`assigned`:
@@ -331,13 +360,23 @@ class DecodeSession:
 
     def _prefill(self, tokens, lengths=None, kernel="blas", prefill_rows=None):
         """prefill() without the host copy: -> (n_songs, sum n_token) f32 device logits."""
-        if kernel not in ("blas", "gemm"):
-            raise ValueError("kernel must be 'blas' or 'gemm', got %r" % (kernel,))
+        if kernel not in ("blas", "gemm", "packed"):
+            raise ValueError("kernel must be 'blas' or 'gemm' (or 'packed'), got %r" % (kernel,))
         if self.model.training:
             raise RuntimeError("generation runs in eval() mode (agent_pretrain.py:657)")
         if self.model.compute_dtype != torch.float32:
             raise RuntimeError("prefill computes in f32: this session's model runs %s activations (step() one token "
                                "at a time instead)" % self.model.compute_dtype)
+        if kernel == "packed" and lengths is None and isinstance(tokens, (list, tuple)) and \
+                len(tokens) > 0 and all(np.ndim(t) == 2 for t in tokens):
+            # the packed form's own input: one (P_i, A) array per song
+            arrays = [np.asarray(t, dtype=np.int64).reshape(-1, len(self.n_token)) for t in tokens]
+            if any(len(t) == 0 for t in arrays):
+                raise ValueError("the packed prefill takes prompts of at least one row each")
+            lengths = [len(t) for t in arrays]
+            tokens = np.zeros((len(arrays), max(lengths), len(self.n_token)), dtype=np.int64)
+            for i, t in enumerate(arrays):
+                tokens[i, :len(t)] = t
         toks = np.asarray(tokens, dtype=np.int64)
         if toks.ndim == 2:
             toks = toks[None]
@@ -368,6 +407,14 @@ class DecodeSession:
                     h[a:z], logits[a:z] = self.model.prefill_hidden(
                         torch.as_tensor(toks[a:z, :Pb]).to(self.dev), [[S[a:z], Z[a:z]] for S, Z in self.memory],
                         lens[a:z], kernel="gemm", logits=True)
+            elif kernel == "packed":
+                # the same bits without the padded rows: blocks of whole songs by their summed rows
+                h = torch.empty((self.n_songs, self.model.d_model), dtype=torch.float32, device=self.dev)
+                logits = torch.empty((self.n_songs, self.width), dtype=torch.float32, device=self.dev)
+                for a, z in packed_blocks(lens, prefill_rows):
+                    rows, cu = _pack_rows([toks[i, :lens[i]] for i in range(a, z)], self.dev)
+                    h[a:z], logits[a:z] = self.model.prefill_hidden_packed(
+                        torch.as_tensor(rows).to(self.dev), cu, [[S[a:z], Z[a:z]] for S, Z in self.memory])
             else:
                 h = self.model.prefill_hidden(torch.as_tensor(toks).to(self.dev), self.memory,
                                               None if lengths is None else lens)
@@ -398,7 +445,10 @@ class DecodeSession:
         kernel="blas" (default): the projections on hipBLASLt.  kernel="gemm": the batch-invariant prefill
         (CWTrunk.prefill_hidden(kernel="gemm"), every projection a cwlt_decode_gemm): song i's state, hidden row and
         logits are bitwise the same whatever the other prompts, their lengths and order; songs go through in blocks of
-        at most prefill_rows // P (default PREFILL_ROWS) prompts, which changes no bits."""
+        at most prefill_rows // P (default PREFILL_ROWS) prompts, which changes no bits.  kernel="packed": the same
+        bits without the padded rows (CWTrunk.prefill_hidden_packed): the prompts are laid end to end, in blocks of whole
+        songs of at most prefill_rows summed rows (packed_blocks); tokens may then also be a list of n_songs (P_i, 6)
+        arrays in place of a padded array with lengths."""
         out = self._prefill(tokens, lengths, kernel, prefill_rows)
         self._host_logits.copy_(out, non_blocking=True)
         torch.cuda.current_stream(self.dev).synchronize()
@@ -1152,8 +1202,10 @@ class _PromptBank:
                 state[i * per + self.bank * sf:(i + 1) * per].view(self.bank, H, d)] for i in range(n_layer)]
         return state, mem, torch.zeros((self.bank, sess.width), dtype=torch.float32, device=sess.dev)
 
-    def _init_bank(self, heads, bar0s, caps, B, bank, prefill_rows=None, ref=None):
-        """heads, bar0s, caps: one entry per song."""
+    def _init_bank(self, heads, bar0s, caps, B, bank, prefill_rows=None, ref=None, packed=False):
+        """heads, bar0s, caps: one entry per song.  packed: the blocks go through the packed prefill
+        (CWTrunk._prefill_gemm_packed, the same bits): the prompts lie end to end on the device, without padding, and
+        every block has its own offset table, all built here."""
         sess, dev = self.sess, self.sess.dev
         self.song_cap = int(max(caps))
         self.B, self.bank = int(B), int(bank)
@@ -1164,10 +1216,20 @@ class _PromptBank:
         # every prompt on the device once, padded to the longest: no host copy (and no sync) inside the stream
         lens = np.array([len(h) for h in heads], dtype=np.int64)
         self.lens = lens
-        toks = np.zeros((self.n_songs, int(lens.max()), self.A), dtype=np.int64)
-        for i, h in enumerate(heads):
-            toks[i, :len(h)] = h
-        self.toks = torch.as_tensor(toks).to(dev)
+        self.packed = bool(packed)
+        if self.packed:
+            # ... or end to end: block j is rows [row0[j], row0[j + 1]), its offsets (from 0) a view of one table
+            self.toks = torch.as_tensor(np.concatenate(heads)).to(dev)
+            cu = [np.concatenate([[0], np.cumsum(lens[j * self.B:(j + 1) * self.B])]) for j in range(self.n_blocks)]
+            table = torch.as_tensor(np.concatenate(cu).astype(np.int32)).to(dev)
+            at = np.concatenate([[0], np.cumsum([len(c) for c in cu])])
+            self.block_cu = [ops.SeqOffsets(table[at[j]:at[j + 1]], host=c.tolist()) for j, c in enumerate(cu)]
+            self.block_row0 = np.concatenate([[0], np.cumsum([c[-1] for c in cu])])
+        else:
+            toks = np.zeros((self.n_songs, int(lens.max()), self.A), dtype=np.int64)
+            for i, h in enumerate(heads):
+                toks[i, :len(h)] = h
+            self.toks = torch.as_tensor(toks).to(dev)
         self.dev_len = torch.as_tensor(lens.astype(np.int32)).to(dev)
         self.bar0_all = torch.as_tensor(np.asarray(bar0s, dtype=np.int64)).to(dev)
         self.cap_all = torch.as_tensor(np.asarray(caps, dtype=np.int64)).to(dev)
@@ -1182,9 +1244,14 @@ class _PromptBank:
         for S, Z in mem:
             S.zero_()
             Z.zero_()
-        P = int(self.lens[a:z].max())
-        dl = self.dev_len[a:z]
-        _, logits = model._prefill_gemm(self.toks[a:z, :P].contiguous(), mem, dl, dl.to(torch.int64) - 1)
+        if self.packed:
+            j = a // self.B
+            _, logits = model._prefill_gemm_packed(self.toks[self.block_row0[j]:self.block_row0[j + 1]],
+                                                   self.block_cu[j], mem)
+        else:
+            P = int(self.lens[a:z].max())
+            dl = self.dev_len[a:z]
+            _, logits = model._prefill_gemm(self.toks[a:z, :P].contiguous(), mem, dl, dl.to(torch.int64) - 1)
         bank_logits[e0:e1].copy_(logits)
 
     def _block_written(self, a, z, e0, e1):
@@ -1234,10 +1301,10 @@ class _BankStreamLoop(_PromptBank, _StreamLoop):
     it waits (song -2), and keeps its song's cap in `cap`."""
 
     def __init__(self, sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk, prefill_rows=None,
-                 **kw):
+                 packed=False, **kw):
         super().__init__(sess, n_songs, seed, bar_mask, bar_cond, chunk, **kw)
         self.cap = torch.ones(self.S, dtype=torch.int64, device=sess.dev)
-        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows)
+        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows, packed=packed)
         self.bank_bar0 = torch.zeros(self.bank, dtype=torch.int64, device=sess.dev)
         self.bank_cap = torch.ones(self.bank, dtype=torch.int64, device=sess.dev)
 
@@ -1277,10 +1344,10 @@ class _ParticleBankStreamLoop(_PromptBank, _ParticleStreamLoop):
     k's counters and enqueues the next block's prefill behind it."""
 
     def __init__(self, sess, heads, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0s, caps, B, bank,
-                 chunk, prefill_rows=None, **kw):
+                 chunk, prefill_rows=None, packed=False, **kw):
         super().__init__(sess, None, None, n_songs, particles, every, ess, seed, bar_mask, bar_cond, bar0s[0],
                          max(caps), chunk, **kw)                 # cap0, the step limit's: the largest cap
-        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows, ref=self.plan.ref)
+        self._init_bank(heads, bar0s, caps, B, bank, prefill_rows, ref=self.plan.ref, packed=packed)
 
     def _hand_out_songs(self):
         ops.particle_release_bank(self.K, self.n_songs, self.bar0_all, self.cap_all, self.gsong, self.song, self.pos,
@@ -1346,7 +1413,7 @@ def _check_prompts(prompts, n_songs, word2event, n_token, bar_cond, max_tokens):
 def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                      chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
                      return_logprobs=False, grammar=None, reference=None, alpha=None, where="generate_stream",
-                     preferences=None):
+                     preferences=None, packed_prefill=False):
     """generate_stream -> (songs, stats): steps run, tokens (prompts included) and drawn, slot-steps (steps x slots),
     wall seconds, host seconds spent waiting on the device, and whether the token ran as a captured graph.  With
     prompts: also the block size, bank entries, blocks prefilled, their GPU seconds and the gated chunks.
@@ -1370,6 +1437,9 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
     else:
         if bank is not None or prefill_rows is not None:
             raise ValueError("bank and prefill_rows belong to per-song prompts (prompts=[...])")
+        if packed_prefill:
+            raise ValueError("packed_prefill belongs to per-song prompts (prompts=[...]): a shared prompt is one "
+                             "prefill with nothing to pad")
         heads, bar0s, caps = ([v[0]] * n_songs for v in _check_prompts(
             [INIT_CW[0] if prompt is None else prompt], 1, word2event, None, bar_cond, max_tokens))
     plan = DrawPlan(model, word2event, n_songs, where, sampler, constraints, grammar, reference, alpha, return_logprobs,
@@ -1392,7 +1462,7 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
         B, bank = stream_bank_plan([len(h) for h in heads], slots, prefill_rows, bank, per_entry,
                                    torch.cuda.mem_get_info(sess.dev)[0])
         loop = _BankStreamLoop(sess, heads, n_songs, seed, bar_mask, bar_cond, bar0s, caps, B, bank, chunk,
-                               prefill_rows=prefill_rows, **kw)
+                               prefill_rows=prefill_rows, packed=bool(packed_prefill), **kw)
     else:
         head = None if prompt is None else heads[0]
         snap_state, snap_logits = _stream_snapshot(model, head, A)
@@ -1424,7 +1494,8 @@ def _generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tok
 
 def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_tokens=None, prompt=None, sampler="dqn",
                     chunk=128, log=None, prompts=None, bank=None, prefill_rows=None, constraints=None,
-                    return_logprobs=False, grammar=None, reference=None, alpha=None, preferences=None):
+                    return_logprobs=False, grammar=None, reference=None, alpha=None, preferences=None,
+                    packed_prefill=False):
     """Generate `n_songs` songs by continuous batching: a pool of `slots` GEMM-step decode slots (_StreamLoop) in which
     a slot starts the next song on the token after its song ends, and the device decides when a song ends.
     -> list of n_songs (L_i, 6) int64 arrays, in song order.
@@ -1445,6 +1516,9 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     about 0.8 GB of prefill activations at d_model 512); bank = the smallest multiple of B with max(2 B, 2 slots)
     entries, capped by the songs and a quarter of free device memory (one entry at d_model 512 / 12 layers / 8 heads
     is 12 x 8 x 64 x 65 x 4 B = 1.6 MB).  `bank` (a multiple of B) overrides the bank size.
+    packed_prefill=True: the same blocks go through the packed prefill (CWTrunk.prefill_hidden_packed): a block's
+    prompts lie end to end and no padded row is computed; B, the bank, the blocks and the songs are unchanged, bit for
+    bit.  Refused without a prompt list.
 
     constraints, return_logprobs, grammar, reference / alpha: as in generate_batch, from the same plan (DrawPlan), and
     song k -- its (L_k - P_k, 6, 2) log-probs too -- is bitwise song k of generate_batch with the same options.  Each
@@ -1459,7 +1533,8 @@ def generate_stream(model, word2event, n_songs, slots=256, bar_cond=17, max_toke
     return _generate_stream(model, word2event, n_songs, slots=slots, bar_cond=bar_cond, max_tokens=max_tokens,
                             prompt=prompt, sampler=sampler, chunk=chunk, log=log, prompts=prompts, bank=bank,
                             prefill_rows=prefill_rows, constraints=constraints, return_logprobs=return_logprobs,
-                            grammar=grammar, reference=reference, alpha=alpha, preferences=preferences)[0]
+                            grammar=grammar, reference=reference, alpha=alpha, preferences=preferences,
+                            packed_prefill=packed_prefill)[0]
 
 
 def _refuse_logprobs(return_logprobs, where):
@@ -1894,15 +1969,16 @@ def _particle_setup(where, model, word2event, n_songs, particles, resample_every
                         preferences=_repeat_per_song(preferences, n, K))
 
 
-def _shared_prefill(sess, toks, lengths, K):
+def _shared_prefill(sess, toks, lengths, K, kernel="gemm"):
     """The lock-step pool's prefill, once a song: row g K of toks (N, P, A) -- every song's K rows hold
     the same prompt -- goes through the batch-invariant prefill on a scratch session of N / K songs, whose state is a
     bank of N / K entries, and cwlt_particle_refill_bank broadcasts entry g to rows g K .. g K + K - 1 of `sess` (ids
-    arange(N), every row fresh) -> (N, width) logits, bitwise sess._prefill(toks, lengths, "gemm")'s, as is the state."""
+    arange(N), every row fresh) -> (N, width) logits, bitwise sess._prefill(toks, lengths, "gemm")'s, as is the state.
+    kernel: "gemm" or "packed", the two batch-invariant prefills."""
     N = sess.n_songs
     scratch = DecodeSession(sess.model, n_songs=N // K, kernel="gemm", graph=False)
     scratch.reset()
-    bank_logits = scratch._prefill(toks[::K], None if lengths is None else lengths[::K], kernel="gemm")
+    bank_logits = scratch._prefill(toks[::K], None if lengths is None else lengths[::K], kernel=kernel)
     logits = torch.empty((N, sess.width), dtype=torch.float32, device=sess.dev)
     ops.particle_refill_bank(sess._state, scratch._state, sess.n_layer, sess.s_floats, sess.z_floats, logits,
                              bank_logits, torch.ones(N, dtype=torch.int64, device=sess.dev),
@@ -1918,7 +1994,8 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
     copies per phase; a stats that comes with {"timed": True} also gets the HIP-event times of every event's resampling
     and two gather phases (and of every reward event's window kernel, callable and apply kernel).
     reward: a _reward_spec; a run that ends inside a window closes it with one partial reward event.
-    share_prefill: every song's K rows hold one prompt and prefill is "gemm": prefill it once (_shared_prefill);
+    share_prefill: every song's K rows hold one prompt and prefill is "gemm" or "packed": prefill it once
+    (_shared_prefill);
     stats' prefilled_prompts is then the songs, not the rows."""
     N, K, R, A = plan.n_songs, int(particles), int(resample_every), len(word2event)
     cap = max(caps)
@@ -1938,8 +2015,8 @@ def _run_particles(model, word2event, heads, caps, plan, particles, resample_eve
             toks[i, :len(p)] = p
         lengths = None if all(len(p) == P for p in heads) else [len(p) for p in heads]
         if share_prefill:
-            loop.start(_shared_prefill(sess, toks, lengths, K),
-                       None if ref is None else _shared_prefill(ref, toks, lengths, K))
+            loop.start(_shared_prefill(sess, toks, lengths, K, prefill),
+                       None if ref is None else _shared_prefill(ref, toks, lengths, K, prefill))
         else:
             loop.start(sess._prefill(toks, lengths, kernel=prefill),
                        None if ref is None else ref._prefill(toks, lengths, kernel=prefill))
@@ -2183,7 +2260,8 @@ def _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, 
 
 
 def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particles, slots, resample_every, ess, bar_cond,
-                         chunk, log, prompt, stats=None, reward=None, bank=None, prefill_rows=None):
+                         chunk, log, prompt, stats=None, reward=None, bank=None, prefill_rows=None,
+                         packed_prefill=False):
     """generate_particles(slots=) after its refusals: the rows of `plan` (particles consecutive rows per song), S =
     min(slots, n_songs) songs in flight -> n_songs ParticleSets.  stats (a dict, optional): steps, events, seconds (all
     of it) and run_seconds (up to the last chunk read, before the host rebuilds the sets), graph, drawn, the pool rows
@@ -2210,7 +2288,7 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
                                       torch.cuda.mem_get_info(sess.dev)[0])
         loop = _ParticleBankStreamLoop(sess, song_heads, n_songs, K, R, ess, seed, bar_mask, bar_cond,
                                        list(plan.bar0s[::K]), caps[::K], B, entries, chunk, prefill_rows=prefill_rows,
-                                       **kw)
+                                       packed=packed_prefill, **kw)
     else:
         song_heads = heads[0]
         snap = _stream_snapshot(model, prompt, A, "gemm")
@@ -2249,7 +2327,7 @@ def _run_particle_stream(model, word2event, heads, caps, plan, n_songs, particle
 def generate_particles(model, word2event, n_songs, particles, resample_every=16, ess=0.5, bar_cond=17, max_tokens=None,
                        prompts=None, sampler="dqn", chunk=128, log=None, prefill="blas", constraints=None,
                        grammar=None, reference=None, alpha=None, preferences=None, reward=None, reward_window=50,
-                       beta=1.0, slots=None, bank=None, prefill_rows=None, share_prefill=None):
+                       beta=1.0, slots=None, bank=None, prefill_rows=None, share_prefill=None, packed_prefill=False):
     """Generate `n_songs` songs with `particles` = K weighted particles each, by sequential Monte Carlo with the device
     sampler as the proposal.  -> list of n_songs ParticleSet.
 
@@ -2283,7 +2361,8 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     particles exactly when prefill="gemm" -- each prompt is prefilled once into a scratch bank of n_songs entries (a
     second one for a reference) and cwlt_particle_refill_bank broadcasts every entry to its song's K rows; the gemm
     prefill is batch invariant, so the sets are bitwise those of the K-fold prefill.  False: every row is prefilled, K
-    times a prompt.  True with prefill="blas" is refused: that prefill is not batch invariant.
+    times a prompt.  True with prefill="blas" is refused: that prefill is not batch invariant.  prefill="packed" (the
+    gemm prefill without its padded rows, DecodeSession.prefill) is batch invariant too and is shared in the same way.
 
     slots=S (None, the default: the lock-step pool above, unchanged): the particle stream.  S songs are in
     flight on S K rows of one session and n_songs may be far larger than S: a group of K consecutive rows takes the next
@@ -2309,7 +2388,8 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     song's ParticleSet -- rewards, event_rewards and beta included -- is bit for bit the lock-step pool's with
     prefill="gemm" after the same torch.manual_seed, whatever slots, bank, prefill_rows and the other songs.  bank or
     prefill_rows without slots= and a prompt list are refused, and what stream_bank_plan and the prompts' own checks
-    refuse, before the model is looked at.
+    refuse, before the model is looked at.  packed_prefill=True: the bank's blocks go through the packed prefill (as in
+    generate_stream), same sets bit for bit; refused without a prompt bank.
 
     reward, reward_window = W, beta: reward terms in the weights.  Each particle's drawn rows (not its
     prompt) are cut into consecutive windows of W rows, the last one possibly partial; after the last row of each
@@ -2341,13 +2421,16 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
     outside 2 .. 1024, n_songs x particles > 4096 (the step's row limit), resample_every < 1, ess outside [0, 1], then
     everything generate_batch refuses."""
     spec = _reward_spec(reward, reward_window, beta, n_songs)
-    if share_prefill and prefill != "gemm":
-        raise ValueError("share_prefill=True needs prefill=\"gemm\": the %r prefill is not batch invariant, so one "
-                         "prefill a song would not give the bits of one a particle" % (prefill,))
+    if share_prefill and prefill not in ("gemm", "packed"):
+        raise ValueError("share_prefill=True needs prefill=\"gemm\" (or \"packed\"): the %r prefill is not batch "
+                         "invariant, so one prefill a song would not give the bits of one a particle" % (prefill,))
     if slots is not None:
         _particle_stream_refusals(n_songs, particles, slots, resample_every, chunk, prompts, reward, reward_window,
                                   bank=bank)
     banked = _particle_bank_refusals(n_songs, slots, prompts, bank, prefill_rows, word2event, bar_cond, max_tokens)
+    if packed_prefill and not banked:
+        raise ValueError("packed_prefill belongs to the prompt bank: slots= with per-song prompts (prompts=[...]) and "
+                         "bank=")
     if slots is not None:
         heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                             ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
@@ -2355,11 +2438,13 @@ def generate_particles(model, word2event, n_songs, particles, resample_every=16,
                                             pool=min(int(slots), max(int(n_songs), 1)))
         return _run_particle_stream(model, word2event, heads, caps, plan, int(n_songs), particles, slots, resample_every,
                                     ess, bar_cond, int(chunk), log, None if prompts is None else heads[0], reward=spec,
-                                    bank=bank if banked else None, prefill_rows=prefill_rows)
+                                    bank=bank if banked else None, prefill_rows=prefill_rows,
+                                    packed_prefill=bool(packed_prefill))
     heads, caps, plan = _particle_setup("generate_particles", model, word2event, n_songs, particles, resample_every,
                                         ess, bar_cond, max_tokens, prompts, sampler, chunk, prefill, constraints,
                                         grammar, reference, alpha, preferences)
-    share = isinstance(prompts, (list, tuple)) and prefill == "gemm" and (share_prefill is None or bool(share_prefill))
+    share = isinstance(prompts, (list, tuple)) and prefill in ("gemm", "packed") and \
+        (share_prefill is None or bool(share_prefill))
     return _run_particles(model, word2event, heads, caps, plan, particles, resample_every, ess, bar_cond, int(chunk),
                           log, None if prompts is None else prefill, reward=spec, share_prefill=share)
 
@@ -2422,8 +2507,11 @@ def _score_setup(where, model, word2event, songs, mask, sampler, kernel, **draw)
 def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
     """What score_songs and policy_stats share after _score_setup: the songs in blocks of whole songs under prefill_rows
     token rows (at most SCORE_BLOCK_SONGS songs), each prefilled on a fresh scratch state with the heads on every row --
-    by `model`, and by plan.reference (a second model over the same tokens) when there is one.  Yields per block (songs
-    of the block, Lb, [logits (nb * Lb, n_logits) per model], targets (nb * Lb, A) int64 on the device: row t of a song
+    by `model`, and by plan.reference (a second model over the same tokens) when there is one.  A block is R rows: nb
+    songs padded to the block's longest, Lb (R = nb * Lb, song i from row i * Lb), or with kernel="packed" laid end to
+    end (packed_blocks: the SUMMED rows stay under prefill_rows; R = their sum, song i from row cu[i]) -- the two differ
+    in where a song's rows lie, not in what is done with them.  Yields per block (songs of the block, the first row of
+    each, [logits (R, n_logits) per model], targets (R, A) int64 on the device: row t of a song
     holds song[t + 1], -1 on its last row and on padding, the plan on the device (DeviceDraw), and what each row adds
     to it: its song index `key` (under constraints or a blend), bar count `bar` (under constraints) and position `beat`
     (under a grammar), else None).  Under plan.alpha the model's logits are replaced by the blend's, alpha x +
@@ -2442,24 +2530,37 @@ def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
     draw = DeviceDraw(plan, dev)
     if draw.order is not None:
         beats = [plan.grammar.beat_states(x)[0] for x in songs]
-    per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
-    for a0 in range(0, n, per):
-        blk = songs[a0:a0 + per]
+    packed = kernel == "packed"
+    if packed:
+        blocks = packed_blocks([len(x) for x in songs], rows_budget, SCORE_BLOCK_SONGS)
+    else:
+        per = max(1, min(SCORE_BLOCK_SONGS, rows_budget // max(len(x) for x in songs)))
+        blocks = [(a0, min(n, a0 + per)) for a0 in range(0, n, per)]
+    for a0, z0 in blocks:
+        blk = songs[a0:z0]
         nb, Lb = len(blk), max(len(x) for x in blk)
-        toks = np.zeros((nb, Lb, A), dtype=np.int64)
-        tgt = np.full((nb, Lb, A), -1, dtype=np.int64)          # the last row of a song and padding: not scored
-        bar = np.ones((nb, Lb), dtype=np.int64)
-        beat = np.full((nb, Lb), -1, dtype=np.int64)
+        lens = [len(x) for x in blk]
+        span = lens if packed else [Lb] * nb                    # rows each song takes in the block
+        starts = np.concatenate([[0], np.cumsum(span)])
+        R = int(starts[-1])
+        toks = np.zeros((R, A), dtype=np.int64)
+        tgt = np.full((R, A), -1, dtype=np.int64)               # the last row of a song and padding: not scored
+        bar = np.ones(R, dtype=np.int64)
+        beat = np.full(R, -1, dtype=np.int64)
         for i, x in enumerate(blk):
-            toks[i, :len(x)] = x
-            tgt[i, :len(x) - 1] = x[1:]
-            bar[i, :len(x) - 1] = bars[a0 + i]
+            r = int(starts[i])
+            toks[r:r + len(x)] = x
+            tgt[r:r + len(x) - 1] = x[1:]
+            bar[r:r + len(x) - 1] = bars[a0 + i]
             if draw.order is not None:
-                beat[i, :len(x) - 1] = beats[a0 + i][1:]
+                beat[r:r + len(x) - 1] = beats[a0 + i][1:]
         lgs, key = [], None
         if draw.sched is not None or draw.alpha is not None or draw.pen is not None:
-            key = torch.arange(a0, a0 + nb, device=dev).repeat_interleave(Lb)
-        dbar = None if draw.sched is None and draw.bias is None else torch.as_tensor(bar.reshape(-1)).to(dev)
+            key = torch.arange(a0, a0 + nb, device=dev).repeat_interleave(torch.as_tensor(span, device=dev),
+                                                                          output_size=R)
+        dbar = None if draw.sched is None and draw.bias is None else torch.as_tensor(bar).to(dev)
+        dtoks = torch.as_tensor(toks).to(dev)
+        cu = ops.SeqOffsets(starts.tolist(), device=dev) if packed else None
         with torch.no_grad():
             for net in models:
                 enc = net.transformer_encoder
@@ -2467,17 +2568,21 @@ def _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
                 d = net.d_model // H
                 memory = [[torch.zeros((nb, H, d, d), dtype=torch.float32, device=dev),
                            torch.zeros((nb, H, d), dtype=torch.float32, device=dev)] for _ in enc.layers]
-                lg = net.prefill_hidden(torch.as_tensor(toks).to(dev), memory, [len(x) for x in blk], kernel=kernel,
-                                        logits="all")
-                lgs.append(lg.reshape(nb * Lb, -1))
+                if packed:
+                    lg = net.prefill_hidden_packed(dtoks, cu, memory, logits="all")
+                else:
+                    lg = net.prefill_hidden(dtoks.view(nb, Lb, A), memory, lens, kernel=kernel, logits="all")
+                lgs.append(lg.reshape(R, -1))
             if draw.alpha is not None:
                 lgs[0] = ops.blend_logits(lgs[0], lgs[1], n_token, draw.alpha, out=lgs[0], key=key)
             if draw.pen is not None:
-                seen = ops.prefer_scan(torch.as_tensor(toks.reshape(-1, A)).to(dev), nb, n_token, draw.pen, key) \
-                    if draw.penalised else None
+                seen = None
+                if draw.penalised:
+                    seen = ops.prefer_scan_packed(dtoks, cu, n_token, draw.pen, key) if packed else \
+                        ops.prefer_scan(dtoks, nb, n_token, draw.pen, key)
                 lgs[0] = _prefer_token(draw, lgs[0], n_token, seen=seen, key=key, bar=dbar)
-        dbeat = None if draw.order is None else torch.as_tensor(beat.reshape(-1)).to(dev)
-        yield blk, Lb, lgs, torch.as_tensor(tgt.reshape(-1, A)).to(dev), draw, key, dbar, dbeat
+        dbeat = None if draw.order is None else torch.as_tensor(beat).to(dev)
+        yield blk, starts, lgs, torch.as_tensor(tgt).to(dev), draw, key, dbar, dbeat
 
 
 def score_songs(model, word2event, songs, sampler="categorical", constraints=None, kernel="gemm", mask=None,
@@ -2499,8 +2604,10 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
     scores are bitwise the same whatever the other songs, their order and lengths, and prefill_rows.  "blas": the
     hipBLASLt prefill, faster and not batch invariant.  Songs go in blocks of whole songs under prefill_rows token rows
     (default PREFILL_ROWS; at most SCORE_BLOCK_SONGS songs), each block on a fresh scratch state: no session is
-    touched.  The logits are scored by cwlt_score_categorical, the sampler's own kernel body, so the logits a draw came
-    from, scored at the class it drew, give the sampler's pair bitwise.
+    touched.  kernel="packed": the bits of "gemm" without the padded rows -- a block's songs lie end to end
+    (CWTrunk.prefill_hidden_packed, cwlt_prefer_scan_packed), its SUMMED rows stay under prefill_rows (packed_blocks),
+    and every per-row table is built per packed row.  The logits are scored by cwlt_score_categorical, the sampler's
+    own kernel body, so the logits a draw came from, scored at the class it drew, give the sampler's pair bitwise.
     grammar: a Grammar: row t + 1 is scored under the row grammar (cwlt_score_categorical_grammar), its kind that of
     song[t + 1]'s own bar-beat class and its position Grammar.beat_states(song)[0][t + 1]; an ill-formed row gets -inf
     in the sampler column of the offending attribute and a finite model column.
@@ -2519,14 +2626,14 @@ def score_songs(model, word2event, songs, sampler="categorical", constraints=Non
                                      constraints=constraints, grammar=grammar, reference=reference, alpha=alpha,
                                      preferences=preferences)
     out = []
-    for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
+    for blk, starts, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
         kw = d.keywords(bar, key=key)
         if d.order is not None:
             lp = ops.score_categorical_grammar(lgs[0], plan.n_token, tgt, *d.grammar(beat), **kw)
         else:
             lp = ops.score_categorical(lgs[0], plan.n_token, tgt, **kw)
-        lp = lp.view(len(blk), Lb, -1, 2).cpu().numpy()
-        out.extend(lp[i, :len(x) - 1].copy() for i, x in enumerate(blk))
+        lp = lp.view(len(tgt), -1, 2).cpu().numpy()
+        out.extend(lp[r:r + len(x) - 1].copy() for r, x in zip(starts, blk))
     return out
 
 
@@ -2559,12 +2666,12 @@ def policy_stats(model, word2event, songs, reference=None, sampler="categorical"
                                      constraints=constraints, grammar=grammar, reference=reference, alpha=alpha,
                                      lone_reference=True, preferences=preferences)
     out = []
-    for blk, Lb, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
+    for blk, starts, lgs, tgt, d, key, bar, beat in _song_blocks(model, songs, bars, plan, kernel, prefill_rows):
         st = ops.policy_stats(lgs[0], plan.n_token, None if reference is None else lgs[1], grammar=d.grammar(beat),
                               bar_class=tgt[:, d.bar_attr or 0].contiguous(),     # no grammar: only the sign is read
                               **d.keywords(bar, key=key))
-        st = st.view(len(blk), Lb, *st.shape[1:]).cpu().numpy()
-        out.extend(st[i, :len(x) - 1].copy() for i, x in enumerate(blk))
+        st = st.cpu().numpy()
+        out.extend(st[r:r + len(x) - 1].copy() for r, x in zip(starts, blk))
     return out
 
 

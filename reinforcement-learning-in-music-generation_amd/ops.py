@@ -1707,6 +1707,42 @@ def cla_fwd_state(q, k, v, S, Z, lengths=None, eps=CLA_EPS, out=None, segments=N
     return out
 
 
+def cla_fwd_state_packed(q, k, v, S, Z, cu, eps=CLA_EPS, out=None):
+    """cla_fwd_state for songs laid end to end: q, k, v (R, H, 64) f32 views (row-strided ok, so the three column blocks
+    of a qkv buffer go in as they are), cu: SeqOffsets (or n_songs + 1 offsets); S (n_songs, H, 64, 64), Z (n_songs, H,
+    64) f32, song s's starting state, updated IN PLACE to the state after its last row.  One workgroup per (song,
+    head) from the song's own row 0, never segmented: a song's out rows, S and Z are bitwise those of cla_fwd_state on
+    it alone (N = 1, segments = 1).  out: an (R, H, 64) f32 view with dense rows to write into (None: a fresh one)."""
+    R, H, D = q.shape
+    if k.shape != q.shape or v.shape != q.shape:
+        raise ValueError("cla_fwd_state_packed needs q, k, v of one shape (R, H, D)")
+    if q.dtype != k.dtype or q.dtype != v.dtype:
+        raise TypeError("q, k, v dtypes differ")
+    _lib.dev(q, "q")
+    cu = _seq_offsets(cu, q.device).check_rows(R)
+    n = cu.n_songs
+    if S.shape != (n, H, D, D) or Z.shape != (n, H, D):
+        raise ValueError("state shapes %s / %s do not match (n_songs, H, D, D) / (n_songs, H, D) = %s"
+                         % (tuple(S.shape), tuple(Z.shape), (n, H, D, D)))
+    if S.dtype != torch.float32 or Z.dtype != torch.float32 or not S.is_contiguous() or not Z.is_contiguous():
+        raise TypeError("the recurrent state is dense f32 (it is updated in place)")
+    for name, t in (("k", k), ("v", v), ("S", S), ("Z", Z), ("cu_seqlens", cu.dev)):
+        if t.device != q.device:
+            raise ValueError("%s is on %s, q on %s" % (name, t.device, q.device))
+    q, ldq = _as_packed_rows(q)
+    k, ldk = _as_packed_rows(k)
+    v, ldv = _as_packed_rows(v)
+    if out is None:
+        out = torch.empty((R, H, D), dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1 or \
+            out.stride(1) != D or out.stride(0) < H * D:
+        raise ValueError("out must be an (R, H, D) tensor of q's dtype and device with dense rows")
+    _call("cwlt_causal_linear_fwd_state_packed", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
+          _lib.dev(S, "S"), _lib.dev(Z, "Z"), _lib.dev(cu.dev), n, H, D, ldq, ldk, ldv, out.stride(0), float(eps),
+          _lib.dtype_code(q.dtype), _lib.stream_ptr())
+    return out
+
+
 def sqrt_width(w):
     return math.sqrt(w)
 
@@ -2197,6 +2233,32 @@ def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None):
         _call("cwlt_prefer_scan", _lib.dev(tokens[a * Lb:z * Lb], "tokens"), z - a, Lb, _lib.int_array(n_class), A,
               _lib.dev(pn, "pen"), pn.shape[0], _lib.opt(_rows(key, a * Lb, z * Lb)),
               _lib.dev(out[a * Lb:z * Lb], "seen_rows"), out.stride(0), _lib.stream_ptr())
+    return out
+
+
+def prefer_scan_packed(tokens, cu, n_class, pen, key=None, out=None):
+    """prefer_scan for songs laid end to end (cwlt_prefer_scan_packed): tokens (R, A) int64, cu: SeqOffsets (or n + 1
+    offsets), song i in rows [cu[i], cu[i + 1]) with the decay of song key[cu[i]] (key (R,) int64; None: song i) ->
+    seen_rows (R, sum n_class) f32, every song's rows bitwise prefer_scan's."""
+    fn, W, A = "prefer_scan_packed", sum(n_class), len(n_class)
+    if tokens.dtype != torch.int64 or not tokens.is_contiguous() or tokens.dim() != 2 or tokens.shape[1] != A:
+        raise TypeError("%s takes contiguous int64 tokens (rows, %d)" % (fn, A))
+    total = tokens.shape[0]
+    _lib.dev(tokens, "tokens")
+    cu = _seq_offsets(cu, tokens.device).check_rows(total)
+    if cu.n_songs > 1 << 20:
+        raise ValueError("%s: %d songs are past the 2^20 songs of one launch" % (fn, cu.n_songs))
+    n_songs = _prefer_pen(fn, pen, A)
+    if key is not None and (key.dtype != torch.int64 or key.numel() != total or not key.is_contiguous()):
+        raise ValueError("%s: key must be a contiguous (rows,) int64 tensor" % fn)
+    if key is None and cu.n_songs > n_songs:
+        raise ValueError("%s: without a key song i reads row i of pen: %d songs, %d rows" % (fn, cu.n_songs, n_songs))
+    if out is None:
+        out = torch.empty((total, W), dtype=torch.float32, device=tokens.device)
+    else:
+        _prefer_seen(fn, out, total, W, "out")
+    _call("cwlt_prefer_scan_packed", _lib.dev(tokens, "tokens"), _lib.dev(cu.dev), cu.n_songs, _lib.int_array(n_class),
+          A, _lib.dev(pen, "pen"), n_songs, _lib.opt(key), _lib.dev(out, "seen_rows"), out.stride(0), _lib.stream_ptr())
     return out
 
 

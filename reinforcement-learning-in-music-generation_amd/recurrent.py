@@ -162,11 +162,41 @@ class RecurrentTransformerEncoder(nn.Module):
             if len(S) != x.shape[0] or len(Zs) != x.shape[0]:
                 raise ValueError("state holds %d sequences, the prompt batch %d" % (len(S), x.shape[0]))
 
-    def _prefill_gemm(self, x, state, lengths, last, heads, rows, all_rows=False):
+    def prefill_packed(self, x, state, cu, heads, rows=None, all_rows=False):
+        """prefill(kernel="gemm") without padded rows: x (R, D) the embedded rows of songs laid end to end, cu an
+        ops.SeqOffsets (song s = rows [cu[s], cu[s + 1])), `state` one [S (n_songs, H, 64, 64), Zs (n_songs, H, 64)] per
+        layer, advanced IN PLACE.  Every launch but the scan is row-wise and the scan (ops.cla_fwd_state_packed) runs
+        each song from its own row 0, so a song's state, hidden row and logits are bitwise those of kernel="gemm".
+        -> (hidden (n_songs, D), logits (n_songs, n_out)) of every song's last row, or with all_rows=True (None, logits
+        (R, n_out)).  No host sync: the last rows are gathered at cu.dev[1:] - 1 on the device."""
+        if not isinstance(cu, ops.SeqOffsets):
+            raise TypeError("prefill_packed takes the songs' offsets as an ops.SeqOffsets")
+        if x.dim() != 2:
+            raise ValueError("prefill_packed takes packed rows (R, D), got %s" % (tuple(x.shape),))
+        cu.check_rows(x.shape[0])
+        if not x.is_cuda:
+            raise RuntimeError("rlmg_amd encoder runs on the GPU only (no CPU fallback)")
+        if x.dtype != torch.float32:
+            raise RuntimeError("prefill computes in f32 (got %s activations)" % x.dtype)
+        if state is None or len(state) != len(self.layers) or any(s is None for s in state):
+            raise ValueError("prefill needs one [S, Zs] state per layer, updated in place")
+        for S, Zs in state:
+            if len(S) != cu.n_songs or len(Zs) != cu.n_songs:
+                raise ValueError("state holds %d sequences, the packed rows %d songs" % (len(S), cu.n_songs))
+        if heads is None:
+            raise ValueError("the packed prefill ends in the heads GEMM: pass heads=(weight, bias)")
+        return self._prefill_gemm(x, state, None, None, heads, 4096 if rows is None else int(rows), all_rows, cu=cu)
+
+    def _prefill_gemm(self, x, state, lengths, last, heads, rows, all_rows=False, cu=None):
+        """cu (ops.SeqOffsets): the packed form -- x is (R, D), the scan takes the offsets and `lengths`, `last` are
+        unused; everything else is the same row-wise chain over M = R rows."""
         if not 1 <= rows <= 4096:
             raise ValueError("rows must be in [1, 4096] (cwlt_decode_gemm's rows per call), got %d" % rows)
-        N, L, D = x.shape
-        M = N * L
+        if cu is not None:
+            (M, D), N, L = x.shape, cu.n_songs, None
+        else:
+            N, L, D = x.shape
+            M = N * L
         H = self.layers[0].attention.n_heads
         d = D // H
         F = self.layers[0].linear1.out_features
@@ -187,7 +217,10 @@ class RecurrentTransformerEncoder(nn.Module):
         new = lambda n: torch.empty((M, n), dtype=torch.float32, device=dev)
         x0 = x.reshape(M, D).contiguous()
         xn, qkv, s1, x1, hh, s2 = new(D), new(3 * D), new(D), new(D), new(F), new(D)
-        a = torch.zeros((N, L, H, d), dtype=torch.float32, device=dev)    # padded rows stay zero: never written
+        if cu is not None:
+            a = torch.empty((M, H, d), dtype=torch.float32, device=dev)   # every row is live
+        else:
+            a = torch.zeros((N, L, H, d), dtype=torch.float32, device=dev)    # padded rows stay zero: never written
         with torch.no_grad():
             for i, (layer, (S, Zs)) in enumerate(zip(self.layers, state)):
                 at = layer.attention
@@ -197,8 +230,12 @@ class RecurrentTransformerEncoder(nn.Module):
                 prev = self.layers[i - 1] if i else None
                 gemm(wqkv, bqkv, s2 if prev else x0, qkv, ln=pair(prev.norm2) if prev else None,
                      normed=xn if prev else None)
-                q = qkv.view(N, L, 3, H, d)
-                ops.cla_fwd_state(q[:, :, 0], q[:, :, 1], q[:, :, 2], S, Zs, lengths, out=a, segments=1)
+                if cu is not None:
+                    q = qkv.view(M, 3, H, d)
+                    ops.cla_fwd_state_packed(q[:, 0], q[:, 1], q[:, 2], S, Zs, cu, out=a)
+                else:
+                    q = qkv.view(N, L, 3, H, d)
+                    ops.cla_fwd_state(q[:, :, 0], q[:, :, 1], q[:, :, 2], S, Zs, lengths, out=a, segments=1)
                 gemm(f(at.out_projection.weight), f(at.out_projection.bias), a.view(M, D), s1,
                      res=xn if prev else x0)
                 gemm(f(layer.linear1.weight), f(layer.linear1.bias), s1, hh, ln=pair(layer.norm1), act="gelu",
@@ -209,10 +246,13 @@ class RecurrentTransformerEncoder(nn.Module):
                 logits = torch.empty((M, w.shape[0]), dtype=torch.float32, device=dev)
                 gemm(w, b, s2, logits, ln=pair(self.layers[-1].norm2),
                      ln2=pair(self.norm) if self.norm is not None else None)
-                return None, logits.view(N, L, w.shape[0])
-            if last is None:
-                last = torch.full((N,), L - 1, dtype=torch.int64, device=dev)
-            top = s2.view(N, L, D)[torch.arange(N, device=dev), last]          # (N, D): a gather, exact
+                return None, logits if cu is not None else logits.view(N, L, w.shape[0])
+            if cu is not None:
+                top = s2[cu.dev[1:].long() - 1]                                    # every song's last row
+            else:
+                if last is None:
+                    last = torch.full((N,), L - 1, dtype=torch.int64, device=dev)
+                top = s2.view(N, L, D)[torch.arange(N, device=dev), last]      # (N, D): a gather, exact
             ln2 = pair(self.norm) if self.norm is not None else None
             w, b = f(heads[0]), f(heads[1])
             logits = torch.empty((N, w.shape[0]), dtype=torch.float32, device=dev)
