@@ -473,50 +473,171 @@ __global__ __launch_bounds__(256) void cla_bwd_dkdv_kernel(const T* __restrict__
 #undef CLA_KV_LOAD
 }
 
-template <typename T, bool PACKED = false>
-static int launch_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H,
-                      typename SeqArg<PACKED>::type seq, long ldq, long ldk, long ldv, long ldo, float eps,
-                      hipStream_t st) {
-    hipLaunchKernelGGL((cla_fwd_kernel<T, PACKED>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (T*)out, zinv, H, seq, ldq, ldk, ldv, ldo, eps);
+// The launchers take both forms, as the bf16 ones do (cwlt_common.h): cu != nullptr is the packed one -- N songs, song n
+// = rows [cu[n], cu[n + 1]), L ignored.  `go` holds the one argument list; `seq` is L or cu.
+template <typename T>
+static int launch_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H, int L,
+                      const int* cu, long ldq, long ldk, long ldv, long ldo, float eps, hipStream_t st) {
+    auto go = [&](auto kernel, auto seq) {
+        hipLaunchKernelGGL(kernel, dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k, (const T*)v, (T*)out, zinv,
+                           H, seq, ldq, ldk, ldv, ldo, eps);
+    };
+    cu ? go(cla_fwd_kernel<T, true>, cu) : go(cla_fwd_kernel<T, false>, L);
     return (int)hipGetLastError();
 }
 
-template <typename T, bool PACKED = false>
+template <typename T>
 static int launch_bwd_dkdv(const void* q, const void* k, const void* v, const void* out, const float* zinv,
-                           const void* dout, void* dk, void* dv, int N, int H, typename SeqArg<PACKED>::type seq,
-                           long ldq, long ldk, long ldv, long ldo, long lddo, long lddk, long lddv, hipStream_t st) {
-    hipLaunchKernelGGL((cla_bwd_dkdv_kernel<T, PACKED>), dim3(N * H), dim3(256), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (const T*)out, (const T*)dout, zinv, (T*)dk, (T*)dv, H, seq, ldq, ldk, ldv, ldo,
-                       lddo, lddk, lddv);
+                           const void* dout, void* dk, void* dv, int N, int H, int L, const int* cu, long ldq,
+                           long ldk, long ldv, long ldo, long lddo, long lddk, long lddv, hipStream_t st) {
+    auto go = [&](auto kernel, auto seq) {
+        hipLaunchKernelGGL(kernel, dim3(N * H), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)out,
+                           (const T*)dout, zinv, (T*)dk, (T*)dv, H, seq, ldq, ldk, ldv, ldo, lddo, lddk, lddv);
+    };
+    cu ? go(cla_bwd_dkdv_kernel<T, true>, cu) : go(cla_bwd_dkdv_kernel<T, false>, L);
     return (int)hipGetLastError();
 }
 
-template <typename T, bool PACKED = false>
+template <typename T>
 static int launch_bwd_dq(const void* q, const void* k, const void* v, const void* out, const float* zinv,
-                         const void* dout, void* dq, int N, int H, typename SeqArg<PACKED>::type seq, long ldq,
-                         long ldk, long ldv, long ldo, long lddo, long lddq, hipStream_t st) {
-    hipLaunchKernelGGL((cla_bwd_dq_kernel<T, PACKED>), dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k,
-                       (const T*)v, (const T*)out, (const T*)dout, zinv, (T*)dq, H, seq, ldq, ldk, ldv, ldo, lddo,
-                       lddq);
+                         const void* dout, void* dq, int N, int H, int L, const int* cu, long ldq, long ldk, long ldv,
+                         long ldo, long lddo, long lddq, hipStream_t st) {
+    auto go = [&](auto kernel, auto seq) {
+        hipLaunchKernelGGL(kernel, dim3(N * H), dim3(128), 0, st, (const T*)q, (const T*)k, (const T*)v, (const T*)out,
+                           (const T*)dout, zinv, (T*)dq, H, seq, ldq, ldk, ldv, ldo, lddo, lddq);
+    };
+    cu ? go(cla_bwd_dq_kernel<T, true>, cu) : go(cla_bwd_dq_kernel<T, false>, L);
     return (int)hipGetLastError();
 }
 
-static bool bad_ld(long ld, int H) { return ld < (long)H * D || (ld & 3) != 0; }
-
-}  // namespace cwlt
-
-extern "C" {
+// a row stride (elements) must hold the H heads and be a multiple of 4
+template <typename... Ld>
+static bool bad_ld(int H, Ld... ld) { return ((ld < (long)H * D || (ld & 3) != 0) || ...); }
 
 /* A sequence of nch = ceil(L / 64) chunks cut into `segments` pieces of cps = ceil(nch / segments) whole chunks: every
  * piece must own at least one chunk.  A count such as 4 for 9 chunks (cps 3: the fourth piece is empty) would leave that
  * piece's state increment unwritten and the prefix / suffix pass would add workspace garbage to its neighbours. */
-static int cwlt_segments_ok(int L, int segments) {
+static bool segments_ok(int L, int segments) {
     const int nch = (L + 63) / 64;
-    if (segments < 1 || segments > nch) return 0;
+    if (segments < 1 || segments > nch) return false;
     const int cps = (nch + segments - 1) / segments;
     return (long)(segments - 1) * cps < nch;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The four scan entries, once each for both forms.  cu == nullptr: N sequences of L rows.  cu != nullptr: the packed
+// form -- N = n_songs, L ignored, one segment and no workspace (the extern "C" forwards below pass 1 / nullptr); `cu` is
+// read on the device only, the host cannot check it here (the Python wrapper does).
+// ------------------------------------------------------------------------------------------------
+/* The shape rules.  Rectangular: an empty batch or sequence is nothing to do -- *empty is set and the caller returns
+ * CWLT_OK before it looks at any pointer.  Packed: at least one song. */
+static int scan_shape(int N, int H, int L, const int* cu, int head_dim, bool* empty) {
+    *empty = !cu && (N == 0 || L == 0);
+    if (H <= 0 || head_dim != D || (cu ? N < 1 : (N < 0 || L < 0))) return CWLT_ERR_ARG;
+    return CWLT_OK;
+}
+
+/* segments > 1: the bf16 kernels on whole rectangular sequences only, with their workspace */
+static bool bad_segments(int L, const int* cu, int segments, const float* seg_ws, bool fast) {
+    return segments < 1 || (segments > 1 && (cu || !fast || !seg_ws || !segments_ok(L, segments)));
+}
+
+static int scan_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H, int L,
+                    const int* cu, int head_dim, long ldq, long ldk, long ldv, long ldo, float eps, int segments,
+                    float* seg_ws, float* final_state, int dtype, void* stream) {
+    bool empty;
+    if (scan_shape(N, H, L, cu, head_dim, &empty)) return CWLT_ERR_ARG;
+    if (empty) return CWLT_OK;
+    if (!q || !k || !v || !out || !zinv) return CWLT_ERR_ARG;
+    if (bad_ld(H, ldq, ldk, ldv, ldo)) return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo) & 7) == 0;
+    if (bad_segments(L, cu, segments, seg_ws, fast)) return CWLT_ERR_ARG;
+    if (final_state && (!fast || segments != 1)) return CWLT_ERR_ARG;   // the bf16 whole-sequence kernel writes it
+    if (dtype == CWLT_F32) return launch_fwd<float>(q, k, v, out, zinv, N, H, L, cu, ldq, ldk, ldv, ldo, eps, st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_fwd_bf16(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, segments, seg_ws,
+                                       final_state, cu, st);
+        return launch_fwd<bf16_t>(q, k, v, out, zinv, N, H, L, cu, ldq, ldk, ldv, ldo, eps, st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+/* colsum_* (N * segments, H*64) f32; dden (rows, H) f32 by row */
+static int scan_bwd_dkdv(const void* q, const void* k, const void* v, const void* out, const float* zinv,
+                         const void* dout, void* dk, void* dv, float* colsum_k, float* colsum_v, float* dden, int N,
+                         int H, int L, const int* cu, int head_dim, long ldq, long ldk, long ldv, long ldo, long lddo,
+                         long lddk, long lddv, int segments, float* seg_ws, int dtype, void* stream) {
+    bool empty;
+    if (scan_shape(N, H, L, cu, head_dim, &empty)) return CWLT_ERR_ARG;
+    if (empty) return CWLT_OK;
+    if (!q || !k || !v || !out || !zinv || !dout || !dk || !dv) return CWLT_ERR_ARG;
+    if (bad_ld(H, ldq, ldk, ldv, ldo, lddo, lddk, lddv)) return CWLT_ERR_ARG;
+    if ((colsum_k == nullptr) != (colsum_v == nullptr)) return CWLT_ERR_ARG;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddk | lddv) & 7) == 0;
+    if ((colsum_k || dden) && !fast) return CWLT_ERR_ARG;   // fused column sums and the dden hand-over: bf16 kernels only
+    if (bad_segments(L, cu, segments, seg_ws, fast)) return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CWLT_F32)
+        return launch_bwd_dkdv<float>(q, k, v, out, zinv, dout, dk, dv, N, H, L, cu, ldq, ldk, ldv, ldo, lddo, lddk,
+                                      lddv, st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_bwd_dkdv_bf16(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, N, H, L, ldq,
+                                            ldk, ldv, ldo, lddo, lddk, lddv, segments, seg_ws, cu, st);
+        return launch_bwd_dkdv<bf16_t>(q, k, v, out, zinv, dout, dk, dv, N, H, L, cu, ldq, ldk, ldv, ldo, lddo, lddk,
+                                       lddv, st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+static int scan_bwd_dq(const void* q, const void* k, const void* v, const void* out, const float* zinv,
+                       const void* dout, void* dq, float* colsum_q, const float* dden, int N, int H, int L,
+                       const int* cu, int head_dim, long ldq, long ldk, long ldv, long ldo, long lddo, long lddq,
+                       int segments, const float* seg_ws, int dtype, void* stream) {
+    bool empty;
+    if (scan_shape(N, H, L, cu, head_dim, &empty)) return CWLT_ERR_ARG;
+    if (empty) return CWLT_OK;
+    if (!q || !k || !v || (!out && !dden) || !zinv || !dout || !dq) return CWLT_ERR_ARG;
+    if (bad_ld(H, ldq, ldk, ldv, ldo, lddo, lddq)) return CWLT_ERR_ARG;
+    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddq) & 7) == 0;
+    if ((colsum_q || dden) && !fast) return CWLT_ERR_ARG;   // as in the dkdv scan
+    if (bad_segments(L, cu, segments, seg_ws, fast)) return CWLT_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == CWLT_F32)
+        return launch_bwd_dq<float>(q, k, v, out, zinv, dout, dq, N, H, L, cu, ldq, ldk, ldv, ldo, lddo, lddq, st);
+    if (dtype == CWLT_BF16) {
+        if (fast)
+            return launch_cla_bwd_dq_bf16(q, k, v, out, zinv, dout, dden, dq, colsum_q, N, H, L, ldq, ldk, ldv, ldo,
+                                          lddo, lddq, segments, const_cast<float*>(seg_ws), cu, st);
+        return launch_bwd_dq<bf16_t>(q, k, v, out, zinv, dout, dq, N, H, L, cu, ldq, ldk, ldv, ldo, lddo, lddq, st);
+    }
+    return CWLT_ERR_DTYPE;
+}
+
+/* the whole backward in one reverse sweep (bf16, whole sequences): every input stream is read once */
+static int scan_bwd_sweep(const void* q, const void* k, const void* v, const void* out, const float* zinv,
+                          const void* dout, const float* final_state, void* dq, void* dk, void* dv, float* colsum_q,
+                          float* colsum_k, float* colsum_v, int N, int H, int L, const int* cu, int head_dim, long ldq,
+                          long ldk, long ldv, long ldo, long lddo, long lddq, long lddk, long lddv, int dtype,
+                          void* stream) {
+    bool empty;
+    if (scan_shape(N, H, L, cu, head_dim, &empty)) return CWLT_ERR_ARG;
+    if (empty) return CWLT_OK;
+    if (!q || !k || !v || !out || !zinv || !dout || !final_state || !dq || !dk || !dv) return CWLT_ERR_ARG;
+    if (bad_ld(H, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv)) return CWLT_ERR_ARG;
+    if ((colsum_q == nullptr) != (colsum_k == nullptr) || (colsum_q == nullptr) != (colsum_v == nullptr))
+        return CWLT_ERR_ARG;
+    if (dtype != CWLT_BF16) return CWLT_ERR_DTYPE;
+    if (((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) != 0) return CWLT_ERR_ARG;
+    return launch_cla_bwd_sweep_bf16(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v, N,
+                                     H, L, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, cu, (hipStream_t)stream);
+}
+
+}  // namespace cwlt
+
+extern "C" {
 
 int cwlt_scan_segments(int N, int H, int L, int dtype) {
     if (dtype != CWLT_BF16 || N <= 0 || H <= 0 || L <= 0) return 1;
@@ -536,24 +657,8 @@ int64_t cwlt_scan_final_state_floats(int N, int H) {
 int cwlt_causal_linear_fwd(const void* q, const void* k, const void* v, void* out, float* zinv, int N, int H,
                            int L, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float eps,
                            int segments, float* seg_ws, float* final_state, int dtype, void* stream) {
-    using namespace cwlt;
-    if (N < 0 || H <= 0 || L < 0 || head_dim != D) return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;                     // empty batch / sequence: nothing to do
-    if (!q || !k || !v || !out || !zinv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H)) return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo) & 7) == 0;
-    if (segments < 1 || (segments > 1 && (!fast || !seg_ws || !cwlt_segments_ok(L, segments)))) return CWLT_ERR_ARG;
-    if (final_state && (!fast || segments != 1)) return CWLT_ERR_ARG;   // the bf16 whole-sequence kernel writes it
-    if (dtype == CWLT_F32) return launch_fwd<float>(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_fwd_bf16(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, segments, seg_ws,
-                                       final_state, nullptr, st);
-        return launch_fwd<bf16_t>(q, k, v, out, zinv, N, H, L, ldq, ldk, ldv, ldo, eps, st);
-    }
-    return CWLT_ERR_DTYPE;
+    return cwlt::scan_fwd(q, k, v, out, zinv, N, H, L, nullptr, head_dim, ldq, ldk, ldv, ldo, eps, segments, seg_ws,
+                          final_state, dtype, stream);
 }
 
 int cwlt_causal_linear_bwd_dkdv(const void* q, const void* k, const void* v, const void* out, const float* zinv,
@@ -561,79 +666,25 @@ int cwlt_causal_linear_bwd_dkdv(const void* q, const void* k, const void* v, con
                                 int N, int H, int L, int head_dim,
                                 int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddk,
                                 int64_t lddv, int segments, float* seg_ws, int dtype, void* stream) {
-    using namespace cwlt;
-    if (N < 0 || H <= 0 || L < 0 || head_dim != D) return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    if (!q || !k || !v || !out || !zinv || !dout || !dk || !dv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
-        bad_ld(lddk, H) || bad_ld(lddv, H))
-        return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    if ((colsum_k == nullptr) != (colsum_v == nullptr)) return CWLT_ERR_ARG;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddk | lddv) & 7) == 0;
-    if (colsum_k && !fast) return CWLT_ERR_ARG;      // fused column sums exist in the bf16 kernels only
-    if (dden && !fast) return CWLT_ERR_ARG;          // the dden hand-over too
-    if (segments < 1 || (segments > 1 && (!fast || !seg_ws || !cwlt_segments_ok(L, segments)))) return CWLT_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CWLT_F32)
-        return launch_bwd_dkdv<float>(q, k, v, out, zinv, dout, dk, dv, N, H, L, ldq, ldk, ldv, ldo, lddo, lddk, lddv,
-                                      st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_bwd_dkdv_bf16(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, N, H, L, ldq,
-                                            ldk, ldv, ldo, lddo, lddk, lddv, segments, seg_ws, nullptr, st);
-        return launch_bwd_dkdv<bf16_t>(q, k, v, out, zinv, dout, dk, dv, N, H, L, ldq, ldk, ldv, ldo, lddo, lddk,
-                                       lddv, st);
-    }
-    return CWLT_ERR_DTYPE;
+    return cwlt::scan_bwd_dkdv(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, N, H, L, nullptr, head_dim,
+                               ldq, ldk, ldv, ldo, lddo, lddk, lddv, segments, seg_ws, dtype, stream);
 }
 
 int cwlt_causal_linear_bwd_dq(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                               const void* dout, void* dq, float* colsum_q, const float* dden, int N, int H, int L,
                               int head_dim, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo,
                               int64_t lddq, int segments, const float* seg_ws, int dtype, void* stream) {
-    using namespace cwlt;
-    if (N < 0 || H <= 0 || L < 0 || head_dim != D) return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    if (!q || !k || !v || (!out && !dden) || !zinv || !dout || !dq) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) || bad_ld(lddq, H))
-        return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddq) & 7) == 0;
-    if (colsum_q && !fast) return CWLT_ERR_ARG;      // fused column sums exist in the bf16 kernels only
-    if (dden && !fast) return CWLT_ERR_ARG;
-    if (segments < 1 || (segments > 1 && (!fast || !seg_ws || !cwlt_segments_ok(L, segments)))) return CWLT_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CWLT_F32)
-        return launch_bwd_dq<float>(q, k, v, out, zinv, dout, dq, N, H, L, ldq, ldk, ldv, ldo, lddo, lddq, st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_bwd_dq_bf16(q, k, v, out, zinv, dout, dden, dq, colsum_q, N, H, L, ldq, ldk, ldv, ldo,
-                                          lddo, lddq, segments, const_cast<float*>(seg_ws), nullptr, st);
-        return launch_bwd_dq<bf16_t>(q, k, v, out, zinv, dout, dq, N, H, L, ldq, ldk, ldv, ldo, lddo, lddq, st);
-    }
-    return CWLT_ERR_DTYPE;
+    return cwlt::scan_bwd_dq(q, k, v, out, zinv, dout, dq, colsum_q, dden, N, H, L, nullptr, head_dim, ldq, ldk, ldv,
+                             ldo, lddo, lddq, segments, seg_ws, dtype, stream);
 }
 
-/* the whole backward in one reverse sweep (bf16, whole sequences): every input stream is read once */
 int cwlt_causal_linear_bwd_sweep(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                                  const void* dout, const float* final_state, void* dq, void* dk, void* dv,
                                  float* colsum_q, float* colsum_k, float* colsum_v, int N, int H, int L, int head_dim,
                                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                                  int64_t lddk, int64_t lddv, int dtype, void* stream) {
-    using namespace cwlt;
-    if (N < 0 || H <= 0 || L < 0 || head_dim != D) return CWLT_ERR_ARG;
-    if (N == 0 || L == 0) return CWLT_OK;
-    if (!q || !k || !v || !out || !zinv || !dout || !final_state || !dq || !dk || !dv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
-        bad_ld(lddq, H) || bad_ld(lddk, H) || bad_ld(lddv, H))
-        return CWLT_ERR_ARG;
-    if ((colsum_q == nullptr) != (colsum_k == nullptr) || (colsum_q == nullptr) != (colsum_v == nullptr))
-        return CWLT_ERR_ARG;
-    if (dtype != CWLT_BF16) return CWLT_ERR_DTYPE;
-    if (((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) != 0) return CWLT_ERR_ARG;
-    return launch_cla_bwd_sweep_bf16(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v, N,
-                                     H, L, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, nullptr, (hipStream_t)stream);
+    return cwlt::scan_bwd_sweep(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v, N, H, L,
+                                nullptr, head_dim, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, dtype, stream);
 }
 
 /* both halves of the backward: the heavier reverse scan first, the dq scan back-fills its tail */
@@ -649,85 +700,34 @@ int cwlt_causal_linear_bwd(const void* q, const void* k, const void* v, const vo
 }
 
 /* ---- packed form: songs of different lengths laid end to end, song s = rows [cu[s], cu[s + 1]) ----
- * The same kernels instantiated with the row-offset table in place of (N, L); one workgroup per (song, head), never
- * segmented.  `cu` is read on the device only: the host cannot check it here (the Python wrapper does). */
-static int packed_head_ok(const int* cu, int n_songs, int H, int head_dim) {
-    return cu && n_songs >= 1 && H >= 1 && head_dim == cwlt::D;
-}
-
+ * The same entries with the row-offset table in place of (N, L); one workgroup per (song, head), never segmented.
+ * colsum_* (n_songs, H*64) f32; dden (rows, H) f32 by packed row.  A null table is refused here: to the shared entries
+ * it would mean the rectangular form. */
 int cwlt_causal_linear_fwd_packed(const void* q, const void* k, const void* v, void* out, float* zinv, const int* cu,
                                   int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv,
                                   int64_t ldo, float eps, float* final_state, int dtype, void* stream) {
-    using namespace cwlt;
-    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
-    if (!q || !k || !v || !out || !zinv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H)) return CWLT_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo) & 7) == 0;
-    if (final_state && !fast) return CWLT_ERR_ARG;   // the bf16 whole-sequence kernel writes it
-    if (dtype == CWLT_F32)
-        return launch_fwd<float, true>(q, k, v, out, zinv, n_songs, H, cu, ldq, ldk, ldv, ldo, eps, st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_fwd_bf16(q, k, v, out, zinv, n_songs, H, 0, ldq, ldk, ldv, ldo, eps, 1, nullptr,
-                                       final_state, cu, st);
-        return launch_fwd<bf16_t, true>(q, k, v, out, zinv, n_songs, H, cu, ldq, ldk, ldv, ldo, eps, st);
-    }
-    return CWLT_ERR_DTYPE;
+    if (!cu) return CWLT_ERR_ARG;
+    return cwlt::scan_fwd(q, k, v, out, zinv, n_songs, H, 0, cu, head_dim, ldq, ldk, ldv, ldo, eps, 1, nullptr,
+                          final_state, dtype, stream);
 }
 
-/* colsum_* (n_songs, H*64) f32; dden (rows, H) f32 by packed row: as in the rectangular calls */
 int cwlt_causal_linear_bwd_dkdv_packed(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                                        const void* dout, void* dk, void* dv, float* colsum_k, float* colsum_v,
                                        float* dden, const int* cu, int n_songs, int H, int head_dim, int64_t ldq,
                                        int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddk, int64_t lddv,
                                        int dtype, void* stream) {
-    using namespace cwlt;
-    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
-    if (!q || !k || !v || !out || !zinv || !dout || !dk || !dv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
-        bad_ld(lddk, H) || bad_ld(lddv, H))
-        return CWLT_ERR_ARG;
-    if ((colsum_k == nullptr) != (colsum_v == nullptr)) return CWLT_ERR_ARG;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddk | lddv) & 7) == 0;
-    if ((colsum_k || dden) && !fast) return CWLT_ERR_ARG;   // fused column sums and the dden hand-over: bf16 kernels only
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CWLT_F32)
-        return launch_bwd_dkdv<float, true>(q, k, v, out, zinv, dout, dk, dv, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo,
-                                            lddk, lddv, st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_bwd_dkdv_bf16(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, n_songs, H, 0,
-                                            ldq, ldk, ldv, ldo, lddo, lddk, lddv, 1, nullptr, cu, st);
-        return launch_bwd_dkdv<bf16_t, true>(q, k, v, out, zinv, dout, dk, dv, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo,
-                                             lddk, lddv, st);
-    }
-    return CWLT_ERR_DTYPE;
+    if (!cu) return CWLT_ERR_ARG;
+    return cwlt::scan_bwd_dkdv(q, k, v, out, zinv, dout, dk, dv, colsum_k, colsum_v, dden, n_songs, H, 0, cu, head_dim,
+                               ldq, ldk, ldv, ldo, lddo, lddk, lddv, 1, nullptr, dtype, stream);
 }
 
 int cwlt_causal_linear_bwd_dq_packed(const void* q, const void* k, const void* v, const void* out, const float* zinv,
                                      const void* dout, void* dq, float* colsum_q, const float* dden, const int* cu,
                                      int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk, int64_t ldv,
                                      int64_t ldo, int64_t lddo, int64_t lddq, int dtype, void* stream) {
-    using namespace cwlt;
-    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
-    if (!q || !k || !v || (!out && !dden) || !zinv || !dout || !dq) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) || bad_ld(lddq, H))
-        return CWLT_ERR_ARG;
-    const bool fast = dtype == CWLT_BF16 && ((ldq | ldk | ldv | ldo | lddo | lddq) & 7) == 0;
-    if ((colsum_q || dden) && !fast) return CWLT_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == CWLT_F32)
-        return launch_bwd_dq<float, true>(q, k, v, out, zinv, dout, dq, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo, lddq,
-                                          st);
-    if (dtype == CWLT_BF16) {
-        if (fast)
-            return launch_cla_bwd_dq_bf16(q, k, v, out, zinv, dout, dden, dq, colsum_q, n_songs, H, 0, ldq, ldk, ldv,
-                                          ldo, lddo, lddq, 1, nullptr, cu, st);
-        return launch_bwd_dq<bf16_t, true>(q, k, v, out, zinv, dout, dq, n_songs, H, cu, ldq, ldk, ldv, ldo, lddo, lddq,
-                                           st);
-    }
-    return CWLT_ERR_DTYPE;
+    if (!cu) return CWLT_ERR_ARG;
+    return cwlt::scan_bwd_dq(q, k, v, out, zinv, dout, dq, colsum_q, dden, n_songs, H, 0, cu, head_dim, ldq, ldk, ldv,
+                             ldo, lddo, lddq, 1, nullptr, dtype, stream);
 }
 
 int cwlt_causal_linear_bwd_sweep_packed(const void* q, const void* k, const void* v, const void* out,
@@ -736,18 +736,9 @@ int cwlt_causal_linear_bwd_sweep_packed(const void* q, const void* k, const void
                                         const int* cu, int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk,
                                         int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq, int64_t lddk,
                                         int64_t lddv, int dtype, void* stream) {
-    using namespace cwlt;
-    if (!packed_head_ok(cu, n_songs, H, head_dim)) return CWLT_ERR_ARG;
-    if (!q || !k || !v || !out || !zinv || !dout || !final_state || !dq || !dk || !dv) return CWLT_ERR_ARG;
-    if (bad_ld(ldq, H) || bad_ld(ldk, H) || bad_ld(ldv, H) || bad_ld(ldo, H) || bad_ld(lddo, H) ||
-        bad_ld(lddq, H) || bad_ld(lddk, H) || bad_ld(lddv, H))
-        return CWLT_ERR_ARG;
-    if ((colsum_q == nullptr) != (colsum_k == nullptr) || (colsum_q == nullptr) != (colsum_v == nullptr))
-        return CWLT_ERR_ARG;
-    if (dtype != CWLT_BF16) return CWLT_ERR_DTYPE;
-    if (((ldq | ldk | ldv | ldo | lddo | lddq | lddk | lddv) & 7) != 0) return CWLT_ERR_ARG;
-    return launch_cla_bwd_sweep_bf16(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v,
-                                     n_songs, H, 0, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, cu, (hipStream_t)stream);
+    if (!cu) return CWLT_ERR_ARG;
+    return cwlt::scan_bwd_sweep(q, k, v, out, zinv, dout, final_state, dq, dk, dv, colsum_q, colsum_k, colsum_v, n_songs,
+                                H, 0, cu, head_dim, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv, dtype, stream);
 }
 
 }  // extern "C"

@@ -322,52 +322,51 @@ int64_t cwlt_prefill_seg_floats(int N, int H, int segments) {
     return segments > 1 ? (int64_t)N * H * segments * (64 * 64 + 64) : 0;
 }
 
+/* Both forms.  cu == nullptr: N sequences of L rows.  cu != nullptr: the packed one -- N = n_songs, and the forward below
+ * passes no lengths, L = 0, one segment and no workspace. */
+static int fwd_state(const void* q, const void* k, const void* v, void* out, float* S, float* Z, const int* lengths,
+                     int N, int H, int L, const int* cu, int head_dim, long ldq, long ldk, long ldv, long ldo, float eps,
+                     int segments, float* seg_ws, int dtype, hipStream_t st) {
+    using namespace cwlt::prefill;
+    if (!q || !k || !v || !out || !S || !Z || N < 0 || H <= 0 || L < 0 || head_dim != 64) return CWLT_ERR_ARG;
+    if (dtype != CWLT_F32) return CWLT_ERR_DTYPE;
+    if (ldq % 4 || ldk % 4 || ldv % 4 || ldq < H * 64 || ldk < H * 64 || ldv < H * 64 || ldo < H * 64 ||
+        ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16)   // 16-byte row loads of q, k, v
+        return CWLT_ERR_ARG;
+    if (cu && (int64_t)N * H > 0x7fffffffLL) return CWLT_ERR_ARG;
+    if (segments < 1 || (segments > 1 && !seg_ws)) return CWLT_ERR_ARG;
+    const int chunks = (L + C - 1) / C, cps = (chunks + segments - 1) / segments;
+    if (chunks > 0 && (segments - 1) * cps >= chunks) return CWLT_ERR_ARG;  // every segment must own a chunk
+    if (N == 0 || (!cu && L == 0)) return CWLT_OK;
+    if (segments > 1) {
+        hipLaunchKernelGGL(cla_state_delta_kernel, dim3(N * H * segments), dim3(128), 0, st, (const float*)k,
+                           (const float*)v, seg_ws, lengths, H, L, segments, cps, ldk, ldv);
+        hipLaunchKernelGGL(cla_state_prefix_kernel, dim3(N * H), dim3(256), 0, st, (const float*)S, (const float*)Z,
+                           seg_ws, segments);
+    }
+    auto go = [&](auto kernel, auto seq) {   // seq: L or cu
+        hipLaunchKernelGGL(kernel, dim3(N * H * segments), dim3(128), 0, st, (const float*)q, (const float*)k,
+                           (const float*)v, (float*)out, S, Z, (const float*)seg_ws, lengths, H, seq, segments, cps,
+                           ldq, ldk, ldv, ldo, eps);
+    };
+    cu ? go(cla_fwd_state_kernel<true>, cu) : go(cla_fwd_state_kernel<false>, L);
+    return (int)hipGetLastError();
+}
+
 int cwlt_causal_linear_fwd_state(const void* q, const void* k, const void* v, void* out, float* S, float* Z,
                                  const int* lengths, int N, int H, int L, int head_dim, int64_t ldq, int64_t ldk,
                                  int64_t ldv, int64_t ldo, float eps, int segments, float* seg_ws, int dtype,
                                  void* stream) {
-    using namespace cwlt;
-    using namespace cwlt::prefill;
-    if (!q || !k || !v || !out || !S || !Z || N < 0 || H <= 0 || L < 0 || head_dim != 64) return CWLT_ERR_ARG;
-    if (dtype != CWLT_F32) return CWLT_ERR_DTYPE;
-    // 16-byte row loads of q, k, v
-    if (ldq % 4 || ldk % 4 || ldv % 4 || ldq < H * 64 || ldk < H * 64 || ldv < H * 64 || ldo < H * 64 ||
-        ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16)
-        return CWLT_ERR_ARG;
-    const int chunks = (L + C - 1) / C;
-    if (segments < 1 || (segments > 1 && !seg_ws)) return CWLT_ERR_ARG;
-    const int cps = (chunks + segments - 1) / (segments > 0 ? segments : 1);
-    if (chunks > 0 && (segments - 1) * cps >= chunks) return CWLT_ERR_ARG;  // every segment must own a chunk
-    if (N == 0 || L == 0) return CWLT_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (segments > 1) {
-        hipLaunchKernelGGL(cla_state_delta_kernel, dim3(N * H * segments), dim3(128), 0, st, (const float*)k,
-                           (const float*)v, seg_ws, lengths, H, L, segments, cps, (long)ldk, (long)ldv);
-        hipLaunchKernelGGL(cla_state_prefix_kernel, dim3(N * H), dim3(256), 0, st, (const float*)S, (const float*)Z,
-                           seg_ws, segments);
-    }
-    hipLaunchKernelGGL(cla_fwd_state_kernel<false>, dim3(N * H * segments), dim3(128), 0, st, (const float*)q,
-                       (const float*)k, (const float*)v, (float*)out, S, Z, (const float*)seg_ws, lengths, H, L,
-                       segments, cps, (long)ldq, (long)ldk, (long)ldv, (long)ldo, eps);
-    return (int)hipGetLastError();
+    return fwd_state(q, k, v, out, S, Z, lengths, N, H, L, nullptr, head_dim, ldq, ldk, ldv, ldo, eps, segments, seg_ws,
+                     dtype, (hipStream_t)stream);
 }
 
 int cwlt_causal_linear_fwd_state_packed(const void* q, const void* k, const void* v, void* out, float* S, float* Z,
                                         const int* cu, int n_songs, int H, int head_dim, int64_t ldq, int64_t ldk,
                                         int64_t ldv, int64_t ldo, float eps, int dtype, void* stream) {
-    using namespace cwlt;
-    using namespace cwlt::prefill;
-    if (!q || !k || !v || !out || !S || !Z || !cu || n_songs < 0 || H <= 0 || head_dim != 64) return CWLT_ERR_ARG;
-    if (dtype != CWLT_F32) return CWLT_ERR_DTYPE;
-    if (ldq % 4 || ldk % 4 || ldv % 4 || ldq < H * 64 || ldk < H * 64 || ldv < H * 64 || ldo < H * 64 ||
-        ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16)
-        return CWLT_ERR_ARG;
-    if ((int64_t)n_songs * H > 0x7fffffffLL) return CWLT_ERR_ARG;
-    if (n_songs == 0) return CWLT_OK;
-    hipLaunchKernelGGL(cla_fwd_state_kernel<true>, dim3(n_songs * H), dim3(128), 0, (hipStream_t)stream,
-                       (const float*)q, (const float*)k, (const float*)v, (float*)out, S, Z, (const float*)nullptr,
-                       (const int*)nullptr, H, cu, 1, 0, (long)ldq, (long)ldk, (long)ldv, (long)ldo, eps);
-    return (int)hipGetLastError();
+    if (!cu) return CWLT_ERR_ARG;   // to fwd_state a null table would mean the rectangular form
+    return fwd_state(q, k, v, out, S, Z, nullptr, n_songs, H, 0, cu, head_dim, ldq, ldk, ldv, ldo, eps, 1, nullptr,
+                     dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

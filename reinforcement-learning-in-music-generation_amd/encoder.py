@@ -113,12 +113,8 @@ class _EncoderLayerFn(torch.autograd.Function):
             qkv = torch.addmm(bqkv, x2, wqkv.t())
         qkv5 = qkv.view(N, L, 3, H, D // H)
         # with a backward to follow, the bf16 scan also hands over its final state: the backward is then one sweep
-        if cu is not None:
-            _, _, _, a, zinv, fin = ops.cla_fwd_packed(qkv5[0, :, 0], qkv5[0, :, 1], qkv5[0, :, 2], cu,
-                                                       final_state=will_backward)
-        else:
-            _, _, _, a, zinv, fin = ops.cla_fwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2],
-                                                final_state=will_backward)
+        _, _, _, a, zinv, fin = ops.cla_fwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], final_state=will_backward,
+                                            cu=cu)
         ctx.fin = fin
         a2 = a.view(R, D)
         if ops.linear_ln_supported(a2, wo_a, x2):
@@ -252,12 +248,8 @@ class _EncoderLayerFn(torch.autograd.Function):
         da = dgrad(do, wo_a, 1)                                               # (R, D)
         dwo = wgrad(do, a.view(R, D))
         qkv5 = qkv.view(N, L, 3, H, D // H)
-        if ctx.cu is not None:
-            dqkv, dbqkv = ops.cla_bwd_packed(qkv5[0, :, 0], qkv5[0, :, 1], qkv5[0, :, 2], a.view(R, H, D // H), zinv,
-                                             da.view(R, H, D // H), ctx.cu, want_colsum=True, final_state=ctx.fin)
-        else:
-            dqkv, dbqkv = ops.cla_bwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], a, zinv, da.view(N, L, H, D // H),
-                                      want_colsum=True, final_state=ctx.fin)
+        dqkv, dbqkv = ops.cla_bwd(qkv5[:, :, 0], qkv5[:, :, 1], qkv5[:, :, 2], a, zinv, da.view(N, L, H, D // H),
+                                  want_colsum=True, final_state=ctx.fin, cu=ctx.cu)
         ctx.fin = None
         dqkv2 = dqkv.view(R, 3 * D)
         if small:

@@ -18,14 +18,15 @@ LN_EPS = 1e-5   # nn.LayerNorm default, used by fast_transformers' encoder layer
 # helpers
 # --------------------------------------------------------------------------------------------------
 def _row_stride(t):
-    """(N, L, H, D) view whose last two dims are dense and whose batch stride is L*row_stride."""
-    N, L, H, D = t.shape
+    """Row stride of an (N, L, H, D) or (R, H, D) view of a row buffer whose last two dims are dense and (4-D) whose batch
+    stride is L*row_stride; None where the kernels cannot take the view as it is."""
+    H, D = t.shape[-2:]
     if t.numel() == 0:
         return H * D                 # empty batch / sequence: strides are irrelevant
-    if t.stride(3) != 1 or t.stride(2) != D:
+    if t.stride(-1) != 1 or t.stride(-2) != D:
         return None
-    ld = t.stride(1)
-    if N > 1 and t.stride(0) != L * ld:
+    ld = t.stride(-3)
+    if t.dim() == 4 and t.shape[0] > 1 and t.stride(0) != t.shape[1] * ld:
         return None
     if ld % 4 != 0 or t.data_ptr() % 16 != 0:
         return None
@@ -543,108 +544,142 @@ def _seg_ws(N, H, P, backward, device):
 SCAN_SWEEP = os.environ.get("CWLT_SCAN_SWEEP", "1") != "0"
 
 
-def cla_fwd(q, k, v, eps=CLA_EPS, final_state=None):
-    """q, k, v: (N, L, H, 64) views (row-strided ok) -> out (N, L, H, 64) dense, zinv (N, L, H) f32
-    [, fin: the scan's final state for `cla_bwd(final_state=fin)`, or None where the one-sweep backward does not apply
-    (f32, odd row strides, segmented few-stream launches) or final_state is False -- a sixth element whenever
-    final_state is given (True / False) at all]."""
-    lib = _lib.load()
-    N, L, H, D = q.shape
+def _scan_fast(dtype, *lds):
+    """Whether a scan call takes the bf16 MFMA kernels (the library decides the same way; its own buffers are dense)."""
+    return dtype == torch.bfloat16 and all(x % 8 == 0 for x in lds)
+
+
+def _check_qkv(fn, q, k, v, cu):
+    """q, k, v of one shape and dtype, in either form of the scans -> cu, N, L, H, D.  cu None: (N, L, H, D) sequences.
+    Else the packed form, songs laid end to end in ONE row buffer (R, H, D) or (1, R, H, D): cu comes back as the
+    SeqOffsets of its R rows, N = n_songs, L = None."""
     if k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("causal linear attention needs q, k, v of one shape (N, L, H, D)")
+        raise ValueError("%s needs q, k, v of one shape %s" % (fn, "(N, L, H, D)" if cu is None else "(R, H, D)"))
     if q.dtype != k.dtype or q.dtype != v.dtype:
         raise TypeError("q, k, v dtypes differ")
+    if cu is None:
+        return (None,) + tuple(q.shape)
+    _lib.dev(q, "q")
+    if q.dim() != 3 and (q.dim() != 4 or q.shape[0] != 1):
+        raise ValueError("%s: packed songs are one row buffer, (R, H, D) or (1, R, H, D)" % fn)
+    R, H, D = q.shape[-3:]
+    cu = _seq_offsets(cu, q.device).check_rows(R)
+    return cu, cu.n_songs, None, H, D
+
+
+def cla_fwd(q, k, v, eps=CLA_EPS, final_state=None, cu=None):
+    """q, k, v: (N, L, H, 64) views (row-strided ok) -> q, k, v, out (N, L, H, 64) dense, zinv (N, L, H) f32
+    [, fin: the scan's final state for `cla_bwd(final_state=fin)`, or None where the one-sweep backward does not apply
+    (f32, odd row strides, segmented few-stream launches) or final_state is False -- a sixth element whenever
+    final_state is given (True / False) at all].
+    cu (SeqOffsets or n_songs + 1 offsets): the packed form (_check_qkv) -- every song is scanned from its own row 0,
+    one workgroup per (song, head), never segmented; out and zinv take q's leading dims, fin is per (song, head)."""
+    lib = _lib.load()
+    cu, N, L, H, D = _check_qkv("causal linear attention", q, k, v, cu)
     q, ldq = _as_rows(q)
     k, ldk = _as_rows(k)
     v, ldv = _as_rows(v)
-    out = torch.empty((N, L, H, D), dtype=q.dtype, device=q.device)
-    zinv = torch.empty((N, L, H), dtype=torch.float32, device=q.device)
-    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv))
-    P = scan_segments(N, H, L, q.dtype, fast)
+    out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    zinv = torch.empty(q.shape[:-1], dtype=torch.float32, device=q.device)
+    fast = _scan_fast(q.dtype, ldq, ldk, ldv)
+    P = scan_segments(N, H, L, q.dtype, fast) if cu is None else 1
     ws = _seg_ws(N, H, P, False, q.device)
     fin = None
-    if final_state and SCAN_SWEEP and fast and P == 1 and N * L > 0:
+    if final_state and SCAN_SWEEP and fast and P == 1 and q.numel() > 0:
         fin = torch.empty(int(lib.cwlt_scan_final_state_floats(N, H)), dtype=torch.float32, device=q.device)
-    _call("cwlt_causal_linear_fwd", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out), _lib.dev(zinv),
-        N, H, L, D, ldq, ldk, ldv, H * D, float(eps), P, _lib.opt(ws), _lib.opt(fin), _lib.dtype_code(q.dtype),
-        _lib.stream_ptr())
+    # the two entry points differ in their name and in how they say where the sequences are
+    name, where, seg = (("", (N, H, L, D), (P, _lib.opt(ws))) if cu is None
+                        else ("_packed", (_lib.dev(cu.dev), N, H, D), ()))
+    _call("cwlt_causal_linear_fwd" + name, _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
+          _lib.dev(zinv), *where, ldq, ldk, ldv, H * D, float(eps), *seg, _lib.opt(fin), _lib.dtype_code(q.dtype),
+          _lib.stream_ptr())
     if final_state is not None:
         return q, k, v, out, zinv, fin
     return q, k, v, out, zinv
 
 
-def cla_bwd(q, k, v, out, zinv, dout, want_colsum=False, final_state=None):
+def cla_bwd(q, k, v, out, zinv, dout, want_colsum=False, final_state=None, cu=None, per_song=False):
     """-> dqkv (N, L, 3, H, 64): dq | dk | dv side by side (= gradient of a fused QKV projection)
     [, dbias (3*H*64) f32 = its column sums, fused into the kernels on the bf16 path].
-    final_state: what `cla_fwd(final_state=True)` returned for these q, k, v -- the backward then runs as one sweep."""
-    lib = _lib.load()
-    N, L, H, D = q.shape
+    final_state: what `cla_fwd(final_state=True)` returned for these q, k, v -- the backward then runs as one sweep.
+    cu: the packed form as in `cla_fwd`, same routes; dqkv takes q's leading dims.  per_song (packed, the bf16 kernels'
+    fused column sums only): dbias as the kernels wrote it, (3, n_songs, H*64), not summed."""
+    cu, N, L, H, D = _check_qkv("causal linear attention", q, k, v, cu)
+    if per_song and cu is None:
+        raise ValueError("per-song column sums belong to the packed form")
     dout, lddo = _as_rows(dout)
     q, ldq = _as_rows(q)
     k, ldk = _as_rows(k)
     v, ldv = _as_rows(v)
-    dqkv = torch.empty((N, L, 3, H, D), dtype=q.dtype, device=q.device)
+    lead, R = tuple(q.shape[:-2]), q.numel() // (H * D)
+    dqkv = torch.empty(lead + (3, H, D), dtype=q.dtype, device=q.device)
+    dq, dk, dv = (_lib.dev(dqkv.select(-3, i)) for i in range(3))
     ld = 3 * H * D
     common = (_lib.dev(q), _lib.dev(k), _lib.dev(v), _lib.dev(out), _lib.dev(zinv), _lib.dev(dout, "dout"))
     code, st = _lib.dtype_code(q.dtype), _lib.stream_ptr()
-    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv, lddo))
+    name, where = ("", (N, H, L, D)) if cu is None else ("_packed", (_lib.dev(cu.dev), N, H, D))
+    fast = _scan_fast(q.dtype, ldq, ldk, ldv, lddo)
     fused = want_colsum and fast
     if final_state is not None and not fast:
         # dout arrived as a view whose row stride the bf16 kernels cannot take (a legal autograd input of the public
         # causal_linear_attention): the final state is simply not used -- the dkdv + dq pair below handles any stride
         final_state = None
     if final_state is not None:
-        cs = torch.empty((3, N, H * D), dtype=torch.float32, device=q.device) if want_colsum else None
-        _call("cwlt_causal_linear_bwd_sweep", *common, _lib.dev(final_state), _lib.dev(dqkv[:, :, 0]),
-              _lib.dev(dqkv[:, :, 1]), _lib.dev(dqkv[:, :, 2]), *([_lib.dev(cs[i]) for i in range(3)] if want_colsum
-                                                                  else [None] * 3),
-              N, H, L, D, ldq, ldk, ldv, H * D, lddo, ld, ld, ld, code, st)
-        if not want_colsum:
-            return dqkv
-        return dqkv, (cs.sum(1).reshape(3 * H * D) if N > 1 else cs.reshape(3 * H * D))
-    P = scan_segments(N, H, L, q.dtype, fast)
-    ws = _seg_ws(N, H, P, True, q.device)          # shared by the two calls: dkdv fills it, dq reads it
-    cs = torch.empty((3, N * P, H * D), dtype=torch.float32, device=q.device) if fused else None
-    # dden = -(dout . out) * zinv: written by the reverse scan, read by the dq scan instead of the whole `out` stream
-    dden = torch.empty((N, L, H), dtype=torch.float32, device=q.device) if fast else None
-    _call("cwlt_causal_linear_bwd_dkdv", *common, _lib.dev(dqkv[:, :, 1]), _lib.dev(dqkv[:, :, 2]),
-          _lib.dev(cs[1]) if fused else None, _lib.dev(cs[2]) if fused else None, _lib.opt(dden), N, H, L, D,
-          ldq, ldk, ldv, H * D, lddo, ld, ld, P, _lib.opt(ws), code, st)
-    _call("cwlt_causal_linear_bwd_dq", *common, _lib.dev(dqkv[:, :, 0]), _lib.dev(cs[0]) if fused else None,
-          _lib.opt(dden), N, H, L, D, ldq, ldk, ldv, H * D, lddo, ld, P, _lib.opt(ws), code, st)
+        P, cs = 1, torch.empty((3, N, H * D), dtype=torch.float32, device=q.device) if want_colsum else None
+        _call("cwlt_causal_linear_bwd_sweep" + name, *common, _lib.dev(final_state), dq, dk, dv,
+              *([_lib.dev(cs[i]) for i in range(3)] if want_colsum else [None] * 3),
+              *where, ldq, ldk, ldv, H * D, lddo, ld, ld, ld, code, st)
+    else:
+        if per_song and not fused:
+            raise ValueError("per-song column sums come from the bf16 kernels (row strides % 8 == 0) only")
+        P = scan_segments(N, H, L, q.dtype, fast) if cu is None else 1
+        ws = _seg_ws(N, H, P, True, q.device)          # shared by the two calls: dkdv fills it, dq reads it
+        seg = (P, _lib.opt(ws)) if cu is None else ()
+        cs = torch.empty((3, N * P, H * D), dtype=torch.float32, device=q.device) if fused else None
+        # dden = -(dout . out) * zinv: written by the reverse scan, read by the dq scan instead of the whole `out` stream
+        dden = torch.empty(lead + (H,), dtype=torch.float32, device=q.device) if fast else None
+        _call("cwlt_causal_linear_bwd_dkdv" + name, *common, dk, dv, _lib.dev(cs[1]) if fused else None,
+              _lib.dev(cs[2]) if fused else None, _lib.opt(dden), *where, ldq, ldk, ldv, H * D, lddo, ld, ld, *seg,
+              code, st)
+        _call("cwlt_causal_linear_bwd_dq" + name, *common, dq, _lib.dev(cs[0]) if fused else None, _lib.opt(dden),
+              *where, ldq, ldk, ldv, H * D, lddo, ld, *seg, code, st)
     if not want_colsum:
         return dqkv
-    if fused:
-        dbias = cs.sum(1).reshape(3 * H * D) if N * P > 1 else cs.reshape(3 * H * D)
-    else:
-        dbias = colsum(dqkv.view(N * L, 3 * H * D))
-    return dqkv, dbias
+    if cs is None:
+        return dqkv, colsum(dqkv.view(R, 3 * H * D))
+    if per_song:
+        return dqkv, cs
+    return dqkv, (cs.sum(1).reshape(3 * H * D) if N * P > 1 else cs.reshape(3 * H * D))
 
 
 class CausalLinearAttentionFn(torch.autograd.Function):
-    """out = CLA(q, k, v): q, k, v (N, L, H, 64) raw projections, elu+1 applied inside the kernel.
+    """out = CLA(q, k, v): q, k, v (N, L, H, 64) raw projections, elu+1 applied inside the kernel; with cu (a
+    SeqOffsets), packed songs as in `cla_fwd`.
 
     Replaces fast_transformers CausalLinearAttention.forward + causal_dot_product
     (reference call sites: dqn_policy/model.py:128-137,231-232).
     """
 
     @staticmethod
-    def forward(ctx, q, k, v, eps=CLA_EPS, grad_mode=True):
+    def forward(ctx, q, k, v, eps=CLA_EPS, grad_mode=True, cu=None):
         # grad_mode = torch.is_grad_enabled() at the call site (inside forward() it is off; see encoder._EncoderLayerFn)
-        q, k, v, out, zinv, fin = cla_fwd(q, k, v, eps, final_state=bool(grad_mode) and any(ctx.needs_input_grad))
+        q, k, v, out, zinv, fin = cla_fwd(q, k, v, eps, final_state=bool(grad_mode) and any(ctx.needs_input_grad), cu=cu)
         ctx.save_for_backward(q, k, v, out, zinv)
-        ctx.fin = fin
+        ctx.fin, ctx.cu = fin, cu
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, zinv = ctx.saved_tensors
-        dqkv = cla_bwd(q, k, v, out, zinv, dout, final_state=ctx.fin)
-        return dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], None, None
+        dqkv = cla_bwd(q, k, v, out, zinv, dout, final_state=ctx.fin, cu=ctx.cu)
+        return dqkv.select(-3, 0), dqkv.select(-3, 1), dqkv.select(-3, 2), None, None, None
 
 
-def causal_linear_attention(q, k, v, eps=CLA_EPS):
-    return CausalLinearAttentionFn.apply(q, k, v, eps, torch.is_grad_enabled())
+def causal_linear_attention(q, k, v, eps=CLA_EPS, cu=None):
+    if cu is not None:
+        _lib.dev(q, "q")
+        cu = _seq_offsets(cu, q.device)      # built once: forward and backward both read it
+    return CausalLinearAttentionFn.apply(q, k, v, eps, torch.is_grad_enabled(), cu)
 
 
 # ---- packed form: songs of different lengths end to end in one (R, H, 64) row buffer --------------------------------
@@ -692,121 +727,19 @@ def _seq_offsets(cu, device):
     return cu if isinstance(cu, SeqOffsets) else SeqOffsets(cu, device=device)
 
 
-def _packed_stride(t):
-    """(R, H, 64) view of a row buffer: last two dims dense -> row stride, or None."""
-    R, H, D = t.shape
-    if t.stride(2) != 1 or t.stride(1) != D or t.stride(0) % 4 != 0 or t.data_ptr() % 16 != 0:
-        return None
-    return t.stride(0)
-
-
-def _as_packed_rows(t):
-    ld = _packed_stride(t)
-    if ld is None:
-        t = t.contiguous()
-        ld = _packed_stride(t)
-    return t, ld
-
-
 def cla_fwd_packed(q, k, v, cu, eps=CLA_EPS, final_state=None):
-    """q, k, v: (R, H, 64) views (row-strided ok) of songs laid end to end, cu: SeqOffsets (or n_songs + 1 offsets) ->
-    q, k, v, out (R, H, 64) dense, zinv (R, H) f32 [, fin as `cla_fwd`: per (song, head)].  Every song is scanned from its
-    own row 0, one workgroup per (song, head); never segmented."""
-    lib = _lib.load()
-    R, H, D = q.shape
-    if k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("causal linear attention needs q, k, v of one shape (R, H, D)")
-    if q.dtype != k.dtype or q.dtype != v.dtype:
-        raise TypeError("q, k, v dtypes differ")
-    _lib.dev(q, "q")
-    cu = _seq_offsets(cu, q.device).check_rows(R)
-    q, ldq = _as_packed_rows(q)
-    k, ldk = _as_packed_rows(k)
-    v, ldv = _as_packed_rows(v)
-    out = torch.empty((R, H, D), dtype=q.dtype, device=q.device)
-    zinv = torch.empty((R, H), dtype=torch.float32, device=q.device)
-    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv))
-    fin = None
-    if final_state and SCAN_SWEEP and fast:
-        fin = torch.empty(int(lib.cwlt_scan_final_state_floats(cu.n_songs, H)), dtype=torch.float32, device=q.device)
-    _call("cwlt_causal_linear_fwd_packed", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
-          _lib.dev(zinv), _lib.dev(cu.dev), cu.n_songs, H, D, ldq, ldk, ldv, H * D, float(eps), _lib.opt(fin),
-          _lib.dtype_code(q.dtype), _lib.stream_ptr())
-    if final_state is not None:
-        return q, k, v, out, zinv, fin
-    return q, k, v, out, zinv
+    """`cla_fwd(cu=cu)`: q, k, v (R, H, 64) -> q, k, v, out (R, H, 64) dense, zinv (R, H) f32 [, fin]."""
+    return cla_fwd(q, k, v, eps, final_state, cu=cu)
 
 
 def cla_bwd_packed(q, k, v, out, zinv, dout, cu, want_colsum=False, final_state=None, per_song=False):
-    """-> dqkv (R, 3, H, 64) [, dbias (3*H*64) f32]: `cla_bwd` for packed songs, same routes.
-    per_song (bf16 kernels' fused column sums only): dbias as the kernels wrote it, (3, n_songs, H*64), not summed."""
-    R, H, D = q.shape
-    cu = _seq_offsets(cu, q.device).check_rows(R)
-    S = cu.n_songs
-    dout, lddo = _as_packed_rows(dout)
-    q, ldq = _as_packed_rows(q)
-    k, ldk = _as_packed_rows(k)
-    v, ldv = _as_packed_rows(v)
-    dqkv = torch.empty((R, 3, H, D), dtype=q.dtype, device=q.device)
-    ld = 3 * H * D
-    common = (_lib.dev(q), _lib.dev(k), _lib.dev(v), _lib.dev(out), _lib.dev(zinv), _lib.dev(dout, "dout"))
-    tail = (_lib.dev(cu.dev), S, H, D)
-    code, st = _lib.dtype_code(q.dtype), _lib.stream_ptr()
-    fast = q.dtype == torch.bfloat16 and all(x % 8 == 0 for x in (ldq, ldk, ldv, lddo))
-    fused = want_colsum and fast
-    if final_state is not None and not fast:
-        final_state = None          # as in cla_bwd: a dout view the bf16 kernels cannot take goes through the pair
-    if final_state is not None:
-        cs = torch.empty((3, S, H * D), dtype=torch.float32, device=q.device) if want_colsum else None
-        _call("cwlt_causal_linear_bwd_sweep_packed", *common, _lib.dev(final_state), _lib.dev(dqkv[:, 0]),
-              _lib.dev(dqkv[:, 1]), _lib.dev(dqkv[:, 2]), *([_lib.dev(cs[i]) for i in range(3)] if want_colsum
-                                                            else [None] * 3),
-              *tail, ldq, ldk, ldv, H * D, lddo, ld, ld, ld, code, st)
-        if not want_colsum:
-            return dqkv
-        if per_song:
-            return dqkv, cs
-        return dqkv, (cs.sum(1).reshape(3 * H * D) if S > 1 else cs.reshape(3 * H * D))
-    if per_song and not fused:
-        raise ValueError("per-song column sums come from the bf16 kernels (row strides % 8 == 0) only")
-    cs = torch.empty((3, S, H * D), dtype=torch.float32, device=q.device) if fused else None
-    dden = torch.empty((R, H), dtype=torch.float32, device=q.device) if fast else None
-    _call("cwlt_causal_linear_bwd_dkdv_packed", *common, _lib.dev(dqkv[:, 1]), _lib.dev(dqkv[:, 2]),
-          _lib.dev(cs[1]) if fused else None, _lib.dev(cs[2]) if fused else None, _lib.opt(dden), *tail,
-          ldq, ldk, ldv, H * D, lddo, ld, ld, code, st)
-    _call("cwlt_causal_linear_bwd_dq_packed", *common, _lib.dev(dqkv[:, 0]), _lib.dev(cs[0]) if fused else None,
-          _lib.opt(dden), *tail, ldq, ldk, ldv, H * D, lddo, ld, code, st)
-    if not want_colsum:
-        return dqkv
-    if fused:
-        dbias = cs if per_song else cs.sum(1).reshape(3 * H * D) if S > 1 else cs.reshape(3 * H * D)
-    else:
-        dbias = colsum(dqkv.view(R, 3 * H * D))
-    return dqkv, dbias
-
-
-class CausalLinearAttentionPackedFn(torch.autograd.Function):
-    """CausalLinearAttentionFn over packed songs: q, k, v (R, H, 64), cu a SeqOffsets."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, cu, eps=CLA_EPS, grad_mode=True):
-        q, k, v, out, zinv, fin = cla_fwd_packed(q, k, v, cu, eps,
-                                                 final_state=bool(grad_mode) and any(ctx.needs_input_grad))
-        ctx.save_for_backward(q, k, v, out, zinv)
-        ctx.fin, ctx.cu = fin, cu
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, k, v, out, zinv = ctx.saved_tensors
-        dqkv = cla_bwd_packed(q, k, v, out, zinv, dout, ctx.cu, final_state=ctx.fin)
-        return dqkv[:, 0], dqkv[:, 1], dqkv[:, 2], None, None, None
+    """`cla_bwd(cu=cu)` -> dqkv (R, 3, H, 64) [, dbias (3*H*64) f32, or (3, n_songs, H*64) with per_song]."""
+    return cla_bwd(q, k, v, out, zinv, dout, want_colsum, final_state, cu=cu, per_song=per_song)
 
 
 def causal_linear_attention_packed(q, k, v, cu, eps=CLA_EPS):
     """Causal linear attention within each song of a packed (R, H, 64) buffer; cu: SeqOffsets or n_songs + 1 offsets."""
-    _lib.dev(q, "q")
-    return CausalLinearAttentionPackedFn.apply(q, k, v, _seq_offsets(cu, q.device), eps, torch.is_grad_enabled())
+    return causal_linear_attention(q, k, v, eps, cu=cu)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1668,79 +1601,57 @@ def recurrent_cla_step(qkv, S, Z, H, eps=CLA_EPS):
     return out
 
 
-def cla_fwd_state(q, k, v, S, Z, lengths=None, eps=CLA_EPS, out=None, segments=None):
+def cla_fwd_state(q, k, v, S, Z, lengths=None, eps=CLA_EPS, out=None, segments=None, cu=None):
     """The prompt form of recurrent_cla_step (csrc/prefill.hip): q, k, v (N, L, H, 64) views (row-strided ok) of a
     whole prompt per sequence; S (N, H, 64, 64), Z (N, H, 64) f32 recurrent states, read as the starting state and
     updated IN PLACE to the state after each sequence's last token; lengths: (N) int32 device tensor (or None = all
     L) -- rows t >= lengths[n] add nothing and stay unwritten in `out` (a dense (N, L, H, 64) buffer to write into,
     or None for a fresh one).  segments: runs per sequence of the few-stream form (None = the library's choice,
-    cwlt_prefill_segments; 1 = one workgroup per (sequence, head)).  -> out."""
-    N, L, H, D = q.shape
-    if k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("cla_fwd_state needs q, k, v of one shape (N, L, H, D)")
-    if q.dtype != k.dtype or q.dtype != v.dtype:
-        raise TypeError("q, k, v dtypes differ")
+    cwlt_prefill_segments; 1 = one workgroup per (sequence, head)).  -> out.
+    cu (SeqOffsets or n_songs + 1 offsets): songs laid end to end (_check_qkv; f32 views, so the three column blocks of a
+    qkv buffer go in as they are), S and Z one state per song.  One workgroup per (song, head) from the song's own row 0,
+    never segmented and without lengths: a song's out rows, S and Z are bitwise those of this call on it alone (N = 1,
+    segments = 1).  `out` may then be a view with dense rows."""
+    packed, n = ("", "N") if cu is None else ("_packed", "n_songs")
+    cu, N, L, H, D = _check_qkv("cla_fwd_state" + packed, q, k, v, cu)
     if S.shape != (N, H, D, D) or Z.shape != (N, H, D):
-        raise ValueError("state shapes %s / %s do not match (N, H, D, D) / (N, H, D) = %s"
-                         % (tuple(S.shape), tuple(Z.shape), (N, H, D, D)))
+        raise ValueError("state shapes %s / %s do not match (%s, H, D, D) / (%s, H, D) = %s"
+                         % (tuple(S.shape), tuple(Z.shape), n, n, (N, H, D, D)))
     if S.dtype != torch.float32 or Z.dtype != torch.float32 or not S.is_contiguous() or not Z.is_contiguous():
         raise TypeError("the recurrent state is dense f32 (it is updated in place)")
     if lengths is not None:
-        if lengths.shape != (N,) or lengths.dtype != torch.int32 or not lengths.is_contiguous():
-            raise ValueError("lengths must be a dense (N,) int32 tensor")
-    for name, t in (("k", k), ("v", v), ("S", S), ("Z", Z), ("lengths", lengths)):
+        if cu is not None or lengths.shape != (N,) or lengths.dtype != torch.int32 or not lengths.is_contiguous():
+            raise ValueError("lengths must be a dense (N,) int32 tensor (and the packed form takes none)")
+    table = ("lengths", lengths) if cu is None else ("cu_seqlens", cu.dev)
+    for name, t in (("k", k), ("v", v), ("S", S), ("Z", Z), table):
         if t is not None and t.device != q.device:
             raise ValueError("%s is on %s, q on %s" % (name, t.device, q.device))
     q, ldq = _as_rows(q)
     k, ldk = _as_rows(k)
     v, ldv = _as_rows(v)
     if out is None:
-        out = torch.empty((N, L, H, D), dtype=q.dtype, device=q.device)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or not out.is_contiguous():
-        raise ValueError("out must be a dense (N, L, H, D) tensor of q's dtype and device")
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device:
+        raise ValueError("out must be a tensor of q's shape, dtype and device")
+    elif cu is None and not out.is_contiguous():
+        raise ValueError("out must be a dense (N, L, H, D) tensor")
+    elif cu is not None and (out.stride(-1) != 1 or out.stride(-2) != D or out.stride(-3) < H * D):
+        raise ValueError("out must be an (R, H, D) tensor with dense rows")
     lib = _lib.load()
-    P = lib.cwlt_prefill_segments(N, H, L) if segments is None else int(segments)
+    P = 1 if cu is not None else lib.cwlt_prefill_segments(N, H, L) if segments is None else int(segments)
     ws = torch.empty(int(lib.cwlt_prefill_seg_floats(N, H, P)), dtype=torch.float32, device=q.device) if P > 1 else None
-    _call("cwlt_causal_linear_fwd_state", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
-          _lib.dev(S, "S"), _lib.dev(Z, "Z"), _lib.opt(lengths), N, H, L, D, ldq, ldk, ldv, H * D, float(eps), P,
-          _lib.opt(ws), _lib.dtype_code(q.dtype), _lib.stream_ptr())
+    # the two entry points differ in their name, in how they say where the sequences are, and in out's row stride
+    where, ldo, seg = (((_lib.opt(lengths), N, H, L, D), H * D, (P, _lib.opt(ws))) if cu is None
+                       else ((_lib.dev(cu.dev), N, H, D), out.stride(-3), ()))
+    _call("cwlt_causal_linear_fwd_state" + packed, _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
+          _lib.dev(S, "S"), _lib.dev(Z, "Z"), *where, ldq, ldk, ldv, ldo, float(eps), *seg, _lib.dtype_code(q.dtype),
+          _lib.stream_ptr())
     return out
 
 
 def cla_fwd_state_packed(q, k, v, S, Z, cu, eps=CLA_EPS, out=None):
-    """cla_fwd_state for songs laid end to end: q, k, v (R, H, 64) f32 views (row-strided ok, so the three column blocks
-    of a qkv buffer go in as they are), cu: SeqOffsets (or n_songs + 1 offsets); S (n_songs, H, 64, 64), Z (n_songs, H,
-    64) f32, song s's starting state, updated IN PLACE to the state after its last row.  One workgroup per (song,
-    head) from the song's own row 0, never segmented: a song's out rows, S and Z are bitwise those of cla_fwd_state on
-    it alone (N = 1, segments = 1).  out: an (R, H, 64) f32 view with dense rows to write into (None: a fresh one)."""
-    R, H, D = q.shape
-    if k.shape != q.shape or v.shape != q.shape:
-        raise ValueError("cla_fwd_state_packed needs q, k, v of one shape (R, H, D)")
-    if q.dtype != k.dtype or q.dtype != v.dtype:
-        raise TypeError("q, k, v dtypes differ")
-    _lib.dev(q, "q")
-    cu = _seq_offsets(cu, q.device).check_rows(R)
-    n = cu.n_songs
-    if S.shape != (n, H, D, D) or Z.shape != (n, H, D):
-        raise ValueError("state shapes %s / %s do not match (n_songs, H, D, D) / (n_songs, H, D) = %s"
-                         % (tuple(S.shape), tuple(Z.shape), (n, H, D, D)))
-    if S.dtype != torch.float32 or Z.dtype != torch.float32 or not S.is_contiguous() or not Z.is_contiguous():
-        raise TypeError("the recurrent state is dense f32 (it is updated in place)")
-    for name, t in (("k", k), ("v", v), ("S", S), ("Z", Z), ("cu_seqlens", cu.dev)):
-        if t.device != q.device:
-            raise ValueError("%s is on %s, q on %s" % (name, t.device, q.device))
-    q, ldq = _as_packed_rows(q)
-    k, ldk = _as_packed_rows(k)
-    v, ldv = _as_packed_rows(v)
-    if out is None:
-        out = torch.empty((R, H, D), dtype=q.dtype, device=q.device)
-    elif out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1 or \
-            out.stride(1) != D or out.stride(0) < H * D:
-        raise ValueError("out must be an (R, H, D) tensor of q's dtype and device with dense rows")
-    _call("cwlt_causal_linear_fwd_state_packed", _lib.dev(q, "q"), _lib.dev(k, "k"), _lib.dev(v, "v"), _lib.dev(out),
-          _lib.dev(S, "S"), _lib.dev(Z, "Z"), _lib.dev(cu.dev), n, H, D, ldq, ldk, ldv, out.stride(0), float(eps),
-          _lib.dtype_code(q.dtype), _lib.stream_ptr())
-    return out
+    """`cla_fwd_state(cu=cu)`: q, k, v, out (R, H, 64), S (n_songs, H, 64, 64), Z (n_songs, H, 64)."""
+    return cla_fwd_state(q, k, v, S, Z, None, eps, out, cu=cu)
 
 
 def sqrt_width(w):
@@ -2203,20 +2114,30 @@ def prefer_track(tokens, n_class, pen, seen, fresh=None, song=None, seen0=None):
     return seen
 
 
-def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None):
+def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None, cu=None):
     """The repetition state along given songs (cwlt_prefer_scan): tokens (nb * Lb, A) int64, song i in rows [i Lb,
     (i + 1) Lb) -> seen_rows (nb * Lb, sum n_class) f32, row t of a song the state after its rows 0 .. t from zero, by
     prefer_track's step with the decay of song key[i Lb] (key (nb * Lb,) int64, the per-row key of prefer_logits; None:
-    song i) in pen (n_songs, 2 A + 1) f32.  Songs go through in launches of at most 2^20 rows."""
-    fn, W, A, nb = "prefer_scan", sum(n_class), len(n_class), int(n_songs_block)
+    song i) in pen (n_songs, 2 A + 1) f32.  Songs go through in launches of at most 2^20 rows.
+    cu (SeqOffsets or n + 1 offsets; n_songs_block is then unused): songs laid end to end (cwlt_prefer_scan_packed),
+    song i in rows [cu[i], cu[i + 1]) with the decay of song key[cu[i]], every song's rows bitwise the above."""
+    fn, W, A = "prefer_scan" if cu is None else "prefer_scan_packed", sum(n_class), len(n_class)
     if tokens.dtype != torch.int64 or not tokens.is_contiguous() or tokens.dim() != 2 or tokens.shape[1] != A:
-        raise TypeError("%s takes contiguous int64 tokens (nb * Lb, %d)" % (fn, A))
+        raise TypeError("%s takes contiguous int64 tokens (rows, %d)" % (fn, A))
     total = tokens.shape[0]
-    if nb < 1 or total < nb or total % nb:
-        raise ValueError("%s: %d token rows are no whole number of rows for each of %d songs" % (fn, total, nb))
-    Lb = total // nb
-    if Lb > 1 << 20:
-        raise ValueError("%s: a song of %d rows is past the 2^20 rows of one launch" % (fn, Lb))
+    if cu is None:
+        nb = int(n_songs_block)
+        if nb < 1 or total < nb or total % nb:
+            raise ValueError("%s: %d token rows are no whole number of rows for each of %d songs" % (fn, total, nb))
+        Lb = total // nb
+        if Lb > 1 << 20:
+            raise ValueError("%s: a song of %d rows is past the 2^20 rows of one launch" % (fn, Lb))
+    else:
+        _lib.dev(tokens, "tokens")
+        cu = _seq_offsets(cu, tokens.device).check_rows(total)
+        nb = cu.n_songs
+        if nb > 1 << 20:
+            raise ValueError("%s: %d songs are past the 2^20 songs of one launch" % (fn, nb))
     n_songs = _prefer_pen(fn, pen, A)
     if key is not None and (key.dtype != torch.int64 or key.numel() != total or not key.is_contiguous()):
         raise ValueError("%s: key must be a contiguous (rows,) int64 tensor" % fn)
@@ -2226,6 +2147,10 @@ def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None):
         out = torch.empty((total, W), dtype=torch.float32, device=tokens.device)
     else:
         _prefer_seen(fn, out, total, W, "out")
+    if cu is not None:
+        _call("cwlt_prefer_scan_packed", _lib.dev(tokens, "tokens"), _lib.dev(cu.dev), nb, _lib.int_array(n_class), A,
+              _lib.dev(pen, "pen"), n_songs, _lib.opt(key), _lib.dev(out, "seen_rows"), out.stride(0), _lib.stream_ptr())
+        return out
     per = max(1, (1 << 20) // Lb)
     for a in range(0, nb, per):
         z = min(nb, a + per)
@@ -2237,29 +2162,8 @@ def prefer_scan(tokens, n_songs_block, n_class, pen, key=None, out=None):
 
 
 def prefer_scan_packed(tokens, cu, n_class, pen, key=None, out=None):
-    """prefer_scan for songs laid end to end (cwlt_prefer_scan_packed): tokens (R, A) int64, cu: SeqOffsets (or n + 1
-    offsets), song i in rows [cu[i], cu[i + 1]) with the decay of song key[cu[i]] (key (R,) int64; None: song i) ->
-    seen_rows (R, sum n_class) f32, every song's rows bitwise prefer_scan's."""
-    fn, W, A = "prefer_scan_packed", sum(n_class), len(n_class)
-    if tokens.dtype != torch.int64 or not tokens.is_contiguous() or tokens.dim() != 2 or tokens.shape[1] != A:
-        raise TypeError("%s takes contiguous int64 tokens (rows, %d)" % (fn, A))
-    total = tokens.shape[0]
-    _lib.dev(tokens, "tokens")
-    cu = _seq_offsets(cu, tokens.device).check_rows(total)
-    if cu.n_songs > 1 << 20:
-        raise ValueError("%s: %d songs are past the 2^20 songs of one launch" % (fn, cu.n_songs))
-    n_songs = _prefer_pen(fn, pen, A)
-    if key is not None and (key.dtype != torch.int64 or key.numel() != total or not key.is_contiguous()):
-        raise ValueError("%s: key must be a contiguous (rows,) int64 tensor" % fn)
-    if key is None and cu.n_songs > n_songs:
-        raise ValueError("%s: without a key song i reads row i of pen: %d songs, %d rows" % (fn, cu.n_songs, n_songs))
-    if out is None:
-        out = torch.empty((total, W), dtype=torch.float32, device=tokens.device)
-    else:
-        _prefer_seen(fn, out, total, W, "out")
-    _call("cwlt_prefer_scan_packed", _lib.dev(tokens, "tokens"), _lib.dev(cu.dev), cu.n_songs, _lib.int_array(n_class),
-          A, _lib.dev(pen, "pen"), n_songs, _lib.opt(key), _lib.dev(out, "seen_rows"), out.stride(0), _lib.stream_ptr())
-    return out
+    """`prefer_scan(cu=cu)`: tokens (R, A) int64 -> seen_rows (R, sum n_class) f32."""
+    return prefer_scan(tokens, None, n_class, pen, key, out, cu=cu)
 
 
 def grammar_track(tokens, bar_attr, order, beat, fresh=None, song=None, beat0=None):

@@ -230,12 +230,9 @@ class RecurrentTransformerEncoder(nn.Module):
                 prev = self.layers[i - 1] if i else None
                 gemm(wqkv, bqkv, s2 if prev else x0, qkv, ln=pair(prev.norm2) if prev else None,
                      normed=xn if prev else None)
-                if cu is not None:
-                    q = qkv.view(M, 3, H, d)
-                    ops.cla_fwd_state_packed(q[:, 0], q[:, 1], q[:, 2], S, Zs, cu, out=a)
-                else:
-                    q = qkv.view(N, L, 3, H, d)
-                    ops.cla_fwd_state(q[:, :, 0], q[:, :, 1], q[:, :, 2], S, Zs, lengths, out=a, segments=1)
+                q = qkv.view(a.shape[:-2] + (3, H, d))
+                ops.cla_fwd_state(q.select(-3, 0), q.select(-3, 1), q.select(-3, 2), S, Zs, lengths, out=a, segments=1,
+                                  cu=cu)
                 gemm(f(at.out_projection.weight), f(at.out_projection.bias), a.view(M, D), s1,
                      res=xn if prev else x0)
                 gemm(f(layer.linear1.weight), f(layer.linear1.bias), s1, hh, ln=pair(layer.norm1), act="gelu",

@@ -109,6 +109,92 @@ def test_argument_validation_without_gpu(built):
     assert lib.cwlt_gemm_bf16_tune(-1, None) == 0
 
 
+# Argument names of the attention-scan entry points in call order; `ld*` are row strides in elements.
+_SCAN_ARGS = {
+    "fwd": "q k v out zinv N H L head_dim ldq ldk ldv ldo eps segments seg_ws final_state dtype stream",
+    "bwd_dkdv": "q k v out zinv dout dk dv colsum_k colsum_v dden N H L head_dim ldq ldk ldv ldo lddo lddk lddv "
+                "segments seg_ws dtype stream",
+    "bwd_dq": "q k v out zinv dout dq colsum_q dden N H L head_dim ldq ldk ldv ldo lddo lddq segments seg_ws dtype "
+              "stream",
+    "bwd_sweep": "q k v out zinv dout final_state dq dk dv colsum_q colsum_k colsum_v N H L head_dim ldq ldk ldv ldo "
+                 "lddo lddq lddk lddv dtype stream",
+    "fwd_packed": "q k v out zinv cu N H head_dim ldq ldk ldv ldo eps final_state dtype stream",
+    "bwd_dkdv_packed": "q k v out zinv dout dk dv colsum_k colsum_v dden cu N H head_dim ldq ldk ldv ldo lddo lddk "
+                       "lddv dtype stream",
+    "bwd_dq_packed": "q k v out zinv dout dq colsum_q dden cu N H head_dim ldq ldk ldv ldo lddo lddq dtype stream",
+    "bwd_sweep_packed": "q k v out zinv dout final_state dq dk dv colsum_q colsum_k colsum_v cu N H head_dim ldq ldk "
+                        "ldv ldo lddo lddq lddk lddv dtype stream",
+    "fwd_state": "q k v out S Z lengths N H L head_dim ldq ldk ldv ldo eps segments seg_ws dtype stream",
+    "fwd_state_packed": "q k v out S Z cu N H head_dim ldq ldk ldv ldo eps dtype stream",
+}
+_SCAN_OPTIONAL = ("colsum_q", "colsum_k", "colsum_v", "dden", "seg_ws", "lengths", "stream")
+_F32, _BF16, _ARG, _DTYPE = 0, 1, 1001, 1002
+_SCAN_POINTERS = set("q k v out zinv dout dq dk dv final_state S Z cu".split()) | set(_SCAN_OPTIONAL)
+# (entry, arguments that differ from the valid call, status).  The valid call: every required pointer the non-null
+# dummy 16, optional ones null, H = 8, head_dim 64, every row stride 512, bf16 (fwd_state*: f32), one segment; rectangular
+# N = 1, L = 128; packed N = n_songs = 2.  Every row is refused, or is empty input, before any launch.
+_SCAN_REFUSALS = [
+    ("fwd", dict(N=0, q=None, k=None, v=None, out=None, zinv=None), 0),
+    ("fwd", dict(L=0, q=None, k=None, v=None, out=None, zinv=None), 0),
+    ("fwd", dict(N=-1), _ARG), ("fwd", dict(q=None), _ARG), ("fwd", dict(head_dim=32), _ARG),
+    ("fwd", dict(ldq=508), _ARG), ("fwd", dict(ldq=514), _ARG),
+    ("fwd", dict(dtype=_F32, final_state=16), _ARG), ("fwd", dict(ldq=516, final_state=16), _ARG),
+    ("fwd", dict(segments=0), _ARG), ("fwd", dict(segments=2), _ARG),
+    ("fwd", dict(dtype=_F32, segments=2, seg_ws=16), _ARG), ("fwd", dict(dtype=2), _DTYPE),
+    ("bwd_dkdv", dict(N=0), 0), ("bwd_dkdv", dict(colsum_k=16), _ARG),
+    ("bwd_dkdv", dict(dtype=_F32, colsum_k=16, colsum_v=16), _ARG), ("bwd_dkdv", dict(dtype=_F32, dden=16), _ARG),
+    ("bwd_dkdv", dict(ldq=508), _ARG), ("bwd_dkdv", dict(dtype=2), _DTYPE),
+    ("bwd_dq", dict(out=None), _ARG), ("bwd_dq", dict(dtype=_F32, colsum_q=16), _ARG),
+    ("bwd_dq", dict(ldq=516, dden=16), _ARG), ("bwd_dq", dict(dtype=2), _DTYPE),
+    ("bwd_sweep", dict(N=0), 0), ("bwd_sweep", dict(ldq=516), _ARG), ("bwd_sweep", dict(final_state=None), _ARG),
+    ("bwd_sweep", dict(colsum_q=16), _ARG), ("bwd_sweep", dict(dtype=_F32), _DTYPE),
+    ("fwd_packed", dict(cu=None), _ARG), ("fwd_packed", dict(N=0), _ARG), ("fwd_packed", dict(head_dim=32), _ARG),
+    ("fwd_packed", dict(q=None), _ARG), ("fwd_packed", dict(ldq=508), _ARG),
+    ("fwd_packed", dict(dtype=_F32, final_state=16), _ARG), ("fwd_packed", dict(ldq=516, final_state=16), _ARG),
+    ("fwd_packed", dict(dtype=2), _DTYPE),
+    ("bwd_dkdv_packed", dict(cu=None), _ARG), ("bwd_dkdv_packed", dict(N=0), _ARG),
+    ("bwd_dkdv_packed", dict(colsum_k=16), _ARG), ("bwd_dkdv_packed", dict(dtype=_F32, dden=16), _ARG),
+    ("bwd_dkdv_packed", dict(dtype=2), _DTYPE),
+    ("bwd_dq_packed", dict(out=None), _ARG), ("bwd_dq_packed", dict(dtype=_F32, colsum_q=16), _ARG),
+    ("bwd_dq_packed", dict(N=0), _ARG), ("bwd_dq_packed", dict(dtype=2), _DTYPE),
+    ("bwd_sweep_packed", dict(ldq=516), _ARG), ("bwd_sweep_packed", dict(final_state=None), _ARG),
+    ("bwd_sweep_packed", dict(colsum_k=16), _ARG), ("bwd_sweep_packed", dict(cu=None), _ARG),
+    ("bwd_sweep_packed", dict(dtype=_F32), _DTYPE),
+    # (no segment-count case here: this scan's chunk is not 64 tokens, and a count that looks refusable may launch)
+    ("fwd_state", dict(N=0), 0), ("fwd_state", dict(L=0), 0), ("fwd_state", dict(S=None), _ARG),
+    ("fwd_state", dict(ldq=510), _ARG), ("fwd_state", dict(q=24), _ARG), ("fwd_state", dict(segments=0), _ARG),
+    ("fwd_state", dict(segments=2, L=256), _ARG), ("fwd_state", dict(dtype=_BF16), _DTYPE),
+    ("fwd_state_packed", dict(N=0), 0), ("fwd_state_packed", dict(cu=None), _ARG),
+    ("fwd_state_packed", dict(N=-1), _ARG), ("fwd_state_packed", dict(ldq=508), _ARG),
+    ("fwd_state_packed", dict(q=24), _ARG), ("fwd_state_packed", dict(dtype=_BF16), _DTYPE),
+]
+
+
+def test_scan_entry_points_refuse_bad_arguments_without_gpu(built):
+    """The padded and the packed attention-scan entry points return the same codes for the same mistakes, and every
+    one of them before any launch (there is no GPU here)."""
+    lib = built.load()
+    for entry, change, want in _SCAN_REFUSALS:
+        names = _SCAN_ARGS[entry].split()
+        assert not set(change) - set(names), (entry, change)
+        packed, state = entry.endswith("_packed"), entry.startswith("fwd_state")
+        args = dict(N=2 if packed else 1, H=8, L=128, head_dim=64, eps=1e-6, segments=1,
+                    dtype=_F32 if state else _BF16)
+        if "final_state" in names and "bwd" not in entry:
+            args["final_state"] = None
+        for n in names:
+            if n.startswith("ld"):
+                args[n] = 512
+            elif n in _SCAN_OPTIONAL:
+                args[n] = None
+            elif n not in args:
+                args[n] = 16
+        args.update(change)
+        call = [ctypes.c_void_p(args[n]) if n in _SCAN_POINTERS else args[n] for n in names]
+        got = getattr(lib, "cwlt_causal_linear_" + entry)(*call)
+        assert got == want, (entry, change, got, want)
+
+
 def test_product_has_no_cpu_fallback(built):
     """CPU tensors are refused loudly instead of being routed to a fallback."""
     import torch
